@@ -1,26 +1,36 @@
 #!/usr/bin/env python
 """Denoising steps/sec of the HIP sampler on MI355X (BASELINE.json metric).
 
-    python bench.py --gpus 1 --steps 100 --warmup 5
+    python bench.py --gpus 1 --steps 100 --warmup 5                    # the headline alone
+    python bench.py --gpus 1 --steps 100 --warmup 5 --full             # ... and everything else this file measures
+    python bench.py --gpus 1 --steps 100 --warmup 5 --dump-outputs DIR # ... and the outputs of the last timed step as DIR/<name>.npy
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
+
+A plain run sets up, warms up, captures the loop, times exactly K steps once and prints the line (metric, value, unit, ms_per_step, ...).
+--full adds what takes runs of its own: the median of 7 repeats of the timed region (min / max alongside), the roofline passes below, the
+whole 100-step loop, the box figures, the CPU baseline with its first-step oracle check, and the secondary configs.
+--dump-outputs DIR writes the state the last timed step produced -- v (rotation vectors), p (positions, Angstrom) and s (residue types) of
+every sample, the arrays the sampling loop hands its caller -- as float32 .npy files (rank r > 0 of a multi-rank run: <name>_rank<r>.npy).
+The inputs are seeded: the same arguments give the same inputs in every run.
 
 One "step" = one iteration of the sampling loop (EpsilonNet forward + rotation/position/sequence transitions,
 device RNG included) over one batch of synthetic complexes.  Workload at every N: BASELINE.json configs[1]
 (AbDesign codesign_single model block, L=256, 6 CDR segments, batch 32 per GPU, T=100); the K timed steps are
-steps T..T-K+1 of that sampler.  Inputs (res_feat, pair_feat, initial state) are resident in HBM before the timed
+steps T..T-K+1 of that sampler; K > T runs the whole loop K // T times from the same initial state and then
+K % T steps of it.  Inputs (res_feat, pair_feat, initial state) are resident in HBM before the timed
 region; encode() and PDB I/O are outside the metric.  value = samples*K / max-over-ranks time.
 Samples are independent, so ranks share nothing during the loop (weak scaling, 32 samples per GPU); the only
 exchange is the candidate all_gather of the batched-sampling reduction after the last step, which is inside the
 timed region at N>1.
 
-Roofline accounting: the dominant kernel is the IPA core -- since round 4 with the block's
+Roofline accounting (--full): the dominant kernel is the IPA core -- since round 4 with the block's
 tail (out_transform + LayerNorm + MLP + LayerNorm) fused into it; its ALGORITHMIC bytes per launch are N*(256*L^2 + 1076*L) (pair
 features once + node features in/out + frames/mask: the survey's figure for the whole block), its duration is measured live with HIP
 events recorded on the launch stream around every launch (DESIGN.md section 5 says where they sit when the loop is replayed from a
 hipGraph).  `roofline.two_launch_form` times the core alone (ABOPT_FUSE_TAIL=0) in one extra pass; `box` carries the device-to-device
-copy rate and the clock the dominant kernel sustained, so a reader can tell a slow box from a slow kernel.  The timed region is run
-`--repeats` times and the median is reported (min / max alongside).
+copy rate and the clock the dominant kernel sustained, so a reader can tell a slow box from a slow kernel.  With --full the timed
+region is run `--repeats` times (default 7) and the median is reported (min / max alongside).
 """
 import argparse
 import json
@@ -342,7 +352,7 @@ def main():
     ap.add_argument('--gpus', type=int, default=1)
     ap.add_argument('--steps', type=int, default=100)
     ap.add_argument('--warmup', type=int, default=5)
-    ap.add_argument('--repeats', type=int, default=7, help='the K-step timed region is run this many times; the median is reported')
+    ap.add_argument('--repeats', type=int, default=None, help='the K-step timed region is run this many times; the median is reported (default 1, with --full 7)')
     ap.add_argument('--batch', type=int, default=32, help='samples per GPU')
     ap.add_argument('--length', type=int, default=256)
     ap.add_argument('--graph', choices=('on', 'off'), default='on', help='replay the K-step loop from a hipGraph captured before the timed region')
@@ -351,6 +361,10 @@ def main():
     ap.add_argument('--replay-only', action='store_true', help='skip the eager_events and two_launch_form passes: under rocprofv3 every dominant-kernel launch is then a replayed one (profiles/*_kernel_stats_replay_only.txt)')
     ap.add_argument('--no-cpu-baseline', action='store_true')
     ap.add_argument('--no-secondary', action='store_true', help='skip train_step_ms / sample_e2e_ms / config3 / poses1000 (N=1 only)')
+    ap.add_argument('--full', action='store_true', help='besides the headline: 7 repeats, roofline passes, the 100-step loop, box figures, CPU baseline and '
+                                                         'secondary configs (--graph-events / --no-prof / --replay-only / --no-cpu-baseline / --no-secondary '
+                                                         'shape this part)')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None, help='write the outputs of the last timed step as DIR/<name>.npy (float32)')
     args = ap.parse_args()
 
     if args.gpus > 1 and 'WORLD_SIZE' not in os.environ:
@@ -385,33 +399,45 @@ def main():
     from ab_opt_amd import hip
     from ab_opt_amd.sampler import all_gather_candidates
     hip.lib()
-    N, L, T, K, W, R = args.batch, args.length, 100, args.steps, args.warmup, max(1, args.repeats)
-    assert 1 <= K <= T and W <= T
+    N, L, T, K, W = args.batch, args.length, 100, args.steps, args.warmup
+    R = max(1, args.repeats if args.repeats is not None else (7 if args.full else 1))
+    assert K >= 1 and W >= 0
     use_graph = args.graph == 'on'
+    prof = args.full and not args.no_prof           # the measurement hooks (events, spans) belong to --full
+    # K steps = K // T whole loops (t = T .. 1) from the same initial state, then K % T steps (t = T .. T - K % T + 1)
+    chunks = lambda n: [T] * (n // T) + ([n % T] if n % T else [])
     log('building workload', dict(N=N, L=L, T=T, K=K, W=W, repeats=R, graph=use_graph), hip.device_info())
     dpm, state, res_feat, pair_feat, gen, mres = build_workload(dev, N, L, T, seed=2022 + rank)
     log('workload ready')
     run = lambda n, graph=False: dpm._run(state, T, res_feat, pair_feat, gen, mres, True, True, True, None, 1234 + rank, rank * N * L, False,
                                           stop_after=n, graph=graph)
 
+    def run_steps(n, graph=False):
+        """n steps as chunks of at most T; returns the trajectory buffers of the last chunk and the index of its last step's output."""
+        for c in chunks(n):
+            out = run(c, graph)
+        return out, T - c
+
     # the network outputs of the first step (same launch geometry as the timed steps), kept for the oracle check below
     first = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         beta = dpm.trans_pos.var_sched.betas[T].expand([N]).contiguous()
         first = hip.eps_net_forward(dpm.eps_net.packed(), state[0], state[1] / 10.0, state[2], res_feat, pair_feat, beta, gen, mres, False, 0, False,
                                     pair_bias_cache=hip.pair_bias_cache(dpm.eps_net.encoder.packed_array(), NUM_LAYERS, pair_feat),
                                     pair_terms=hip.pair_terms(pair_feat) if dpm._pair_terms_wanted(N, L, N, dev) else None)     # (what the timed loop runs)
         first = {k: (v.clone() if v is not None else None) for k, v in first.items()}
     if W > 0:
-        run(W)
+        run_steps(W)
     torch.cuda.synchronize()
     graph_events = False
     if use_graph:
         # capture (outside the timed region, like the warmup): K steps of the loop, the one-off pair-bias cache build included
         t_cap = time.perf_counter()
-        hip.GRAPH_CAPTURE_EVENTS = bool(args.graph_events and not args.no_prof)
-        hip.GRAPH_CAPTURE_SPANS = not args.no_prof            # in-kernel launch spans: the dominant kernel timed inside the replayed graph
-        run(K, graph=True)
+        hip.GRAPH_CAPTURE_EVENTS = bool(args.graph_events and prof)
+        # in-kernel launch spans: the dominant kernel timed inside the replayed graph (one replay of one graph per timed region: K <= T)
+        hip.GRAPH_CAPTURE_SPANS = prof and K <= T
+        for c in sorted(set(chunks(K))):
+            run(c, graph=True)
         hip.GRAPH_CAPTURE_SPANS = False
         torch.cuda.synchronize()
         graph_events = hip.GRAPH_CAPTURE_EVENTS
@@ -430,16 +456,17 @@ def main():
         if not graph:
             hip.prof_enable(events)
         t0 = time.perf_counter()
-        tv, tp, ts, _, _ = run(K, graph=graph)
+        (tv, tp, ts, _, _), i = run_steps(K, graph=graph)
         if dist is not None:
             # batched-sampling reduction: gather generated-residue CA candidates of every rank (design_for_pdb.py:326-336)
-            cand = tp[T - K][gen].reshape(N, -1, 3).contiguous()
+            cand = tp[i][gen].reshape(N, -1, 3).contiguous()
             all_gather_candidates(cand)
         torch.cuda.synchronize()
         barrier()
         torch.cuda.synchronize()
         dt = time.perf_counter() - t0
-        assert torch.isfinite(tp[T - K]).all()
+        assert torch.isfinite(tp[i]).all()
+        last_out[:] = [('v', tv[i]), ('p', tp[i]), ('s', ts[i])]
         local_times.append(dt)                 # this rank's own clock (the reported time is the MAX over ranks)
         if dist is not None:
             tmax = torch.tensor([dt], dtype=torch.float64, device=dev if backend == 'nccl' else 'cpu')
@@ -450,10 +477,10 @@ def main():
     # ---- the timed region, R times.  Eager mode: HIP events around every IPA-core launch inside it.  Graph mode: host-recorded
     # event pairs cannot live in a replayed graph, so the kernel is timed in ONE extra eager pass of the same K steps right after
     # the repeats (same process, same box, same clocks), unless --graph-events put the records into the graph itself.
-    times, launches, ipa_ms, local_times = [], 0, 0.0, []
+    times, launches, ipa_ms, local_times, last_out = [], 0, 0.0, [], []
     for r in range(R):
-        times.append(timed_pass(use_graph, events=not args.no_prof))
-        if not use_graph and not args.no_prof:
+        times.append(timed_pass(use_graph, events=prof))
+        if not use_graph and prof:
             n_, ms_ = hip.prof_collect()
             launches, ipa_ms = launches + n_, ipa_ms + ms_
         elif graph_events:
@@ -461,6 +488,13 @@ def main():
             launches, ipa_ms = launches + n_, ipa_ms + ms_
     hip.prof_enable(False)
     log('timed region x%d: %s ms per step' % (R, ', '.join('%.4f' % (t / K * 1e3) for t in times)))
+    if args.dump_outputs:
+        # what the last timed step computed (the graph's buffers are written again by the passes below): float32, 0.2 MB at N=32, L=256
+        import numpy as np
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        for name, a in last_out:
+            np.save(os.path.join(args.dump_outputs, name + ('_rank%d' % rank if rank else '') + '.npy'), a.float().cpu().numpy())
+        log('outputs of the last timed step written to', args.dump_outputs)
     # who took part: every rank's device and its OWN median step time, gathered through the process group the timing used -- a SCALE line
     # can be checked at a glance (all ranks present, one device each, nobody far off the others)
     ranks_seen = None
@@ -471,7 +505,7 @@ def main():
         ranks_seen = [None] * dist.get_world_size()
         dist.all_gather_object(ranks_seen, mine)
     instrumented, eager_events = None, None
-    if use_graph and not graph_events and not args.no_prof:
+    if use_graph and not graph_events and prof:
         # (i) one more replay of the SAME graph, its dominant-kernel launches timed by their in-kernel wall-clock spans (first workgroup in,
         #     last workgroup out: what rocprofv3 reports) -- host-recorded events cannot sit in a replayed graph, and an eager pass is not the
         #     same thing: its launch gaps let the chip clock up (kernels 5-10 % faster than in the back-to-back replay on a power-limited box)
@@ -489,11 +523,11 @@ def main():
             eager_events = dict(ms_per_step=round(dt_e / K * 1e3, 4), avg_launch_ms=round(ms_e / max(n_e, 1), 4), launches=n_e)
         if launches == 0:                                   # (a shape that does not take the 32-row kernels: events are all there is)
             launches, ipa_ms, instrumented = n_e, ms_e, eager_events['ms_per_step']
-    clock = hip.prof_clock()                                    # the clock wave 0 / workgroup 0 of the last dominant-kernel launch ran at
+    clock = hip.prof_clock() if args.full else None             # the clock wave 0 / workgroup 0 of the last dominant-kernel launch ran at
     # the WHOLE loop the metric names (all T steps from noise to t = 1, one graph replay each), next to the K-step headline: the headline's K
     # steps are t = T .. T-K+1 and carry the one-off pair-bias cache build, so a reader can tell how the 20-step line relates to a full call
     loop_full = None
-    if rank == 0 and world == 1 and use_graph and K < T and not args.no_prof:
+    if rank == 0 and world == 1 and use_graph and K < T and prof:
         run(T, graph=True)                                      # capture + first replay
         torch.cuda.synchronize()
         lt = []
@@ -507,7 +541,7 @@ def main():
     # the two-launch form of a block (32-row core, then the tail kernel) in one more eager pass: the IPA core ALONE, for continuity with
     # the rounds before the tail was fused into it (bit-identical results; not part of the timed region)
     two_launch = None
-    if rank == 0 and world == 1 and not args.no_prof and not args.replay_only and os.environ.get('ABOPT_FUSE_TAIL') is None:
+    if rank == 0 and world == 1 and prof and not args.replay_only and os.environ.get('ABOPT_FUSE_TAIL') is None:
         os.environ['ABOPT_FUSE_TAIL'] = '0'
         try:
             run(2)
@@ -519,7 +553,7 @@ def main():
             del os.environ['ABOPT_FUSE_TAIL']
     # what this box gives: device-to-device copy rate (read + write bytes) and the one-off cost of a sample() call that the K steps share
     box = None
-    if rank == 0:
+    if rank == 0 and args.full:
         a = torch.empty(1 << 28, dtype=torch.float32, device=dev)           # 1 GiB
         b = torch.empty_like(a)
         b.copy_(a); torch.cuda.synchronize()
@@ -564,7 +598,8 @@ def main():
             'unit': 'sample-steps/s', 'n_gpus': world, 'steps': K, 'warmup': W, 'ms_per_step': round(step_s * 1e3, 4),
             'repeats': R, 'ms_per_step_min': round(ts_sorted[0] / K * 1e3, 4), 'ms_per_step_max': round(ts_sorted[-1] / K * 1e3, 4),
             'value_min': round(world * N * K / ts_sorted[-1], 2), 'value_max': round(world * N * K / ts_sorted[0], 2),
-            'aggregate': 'median of the repeats; each repeat times exactly K steps (barrier + synchronize on both sides, max over ranks)',
+            'aggregate': 'median of the repeats (1 unless --repeats or --full); each repeat times exactly K steps (barrier + synchronize on both sides, max over ranks)',
+            'full': args.full,
             'higher_is_better': True, 'scaling': 'weak', 'vs_baseline': None, 'dtype': 'f32', 'data': 'synthetic',
             'config': {'workload': f'AbDesign codesign_single model block (F=128, C=64, 6 IPA layers, T=100), L={L}, 6 CDR segments, '
                                    f'batch {N} per GPU, distinct pair features per sample, device Philox RNG',
@@ -596,7 +631,7 @@ def main():
         if loop_full is not None:
             line['loop100_ms_per_step'] = loop_full['loop100_ms_per_step']
             line['loop100'] = loop_full
-        elif K == T:
+        elif K % T == 0:
             line['loop100_ms_per_step'] = round(step_s * 1e3, 4)
         if two_launch:
             u = two_launch['ipa_core_avg_launch_ms']
@@ -604,11 +639,13 @@ def main():
                               note='ABOPT_FUSE_TAIL=0: the 32-row IPA core as its own kernel (HIP events, one eager pass of the same K steps); '
                                    'same arithmetic, bit-identical results -- the timed region above runs the fused form')
             line['roofline']['two_launch_form'] = two_launch
-        if world == 1 and not args.no_cpu_baseline:
+        if not args.full:
+            del line['roofline'], line['box']                  # figures of the --full passes
+        if args.full and world == 1 and not args.no_cpu_baseline:
             log('cpu baseline on', os.cpu_count(), 'cores ...')
             check = (dpm, T, state, res_feat, pair_feat, gen, mres, first, [0, N // 2 + 1] if N > 2 else [0]) if first is not None else None
             line['cpu_baseline'] = cpu_baseline(L, T, check=check)
-        if world == 1 and not args.no_secondary:
+        if args.full and world == 1 and not args.no_secondary:
             log('secondary configs ...')
             dpm.clear_graphs()
             torch.cuda.empty_cache()

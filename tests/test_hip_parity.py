@@ -2172,7 +2172,7 @@ def test_bench_two_ranks_on_one_gpu():
     import sys
     from conftest import ROOT
     sk = socket.socket(); sk.bind(('127.0.0.1', 0)); port = sk.getsockname()[1]; sk.close()
-    common = ['--steps', '6', '--warmup', '2', '--repeats', '3', '--batch', '8', '--no-cpu-baseline', '--no-secondary']
+    common = ['--steps', '6', '--warmup', '2', '--repeats', '3', '--batch', '8', '--full', '--no-cpu-baseline', '--no-secondary']
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY='0')
     one = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '1'] + common, capture_output=True, text=True, env=env, timeout=900)
     assert one.returncode == 0, one.stderr[-2000:]
@@ -2231,7 +2231,7 @@ def test_two_devices_rccl_bench_sampling_and_graphed_ddp(tmp_path):
     sk = socket.socket(); sk.bind(('127.0.0.1', 0)); port = sk.getsockname()[1]; sk.close()
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY='0')
     two = subprocess.run([sys.executable, '-m', 'torch.distributed.run', '--nnodes=1', '--nproc-per-node', '2', '--master-addr', '127.0.0.1',
-                          '--master-port', str(port), os.path.join(ROOT, 'bench.py'), '--gpus', '2', '--steps', '6', '--warmup', '2', '--repeats', '3'],
+                          '--master-port', str(port), os.path.join(ROOT, 'bench.py'), '--gpus', '2', '--steps', '6', '--warmup', '2', '--repeats', '3', '--full'],
                          capture_output=True, text=True, env=env, timeout=1800)
     assert two.returncode == 0, two.stderr[-3000:]
     line = json.loads([l for l in two.stdout.strip().splitlines() if l.startswith('{')][-1])
@@ -2355,6 +2355,31 @@ def test_bench_nccl_branch_single_rank():
     assert r.returncode == 0, r.stderr[-3000:]
     line = json.loads([l for l in r.stdout.strip().splitlines() if l.startswith('{')][-1])
     assert line['config']['backend'] == 'nccl' and line['n_gpus'] == 1 and line['value'] > 0
+
+
+@pytest.mark.gpu
+def test_bench_plain_run_times_k_steps_and_dumps_the_last_one(tmp_path):
+    """A plain `bench.py` run times exactly --steps steps once and prints the headline alone (the --full figures are absent); K > T runs
+    K // T whole loops and then K % T steps from the same seeded state, so the outputs --dump-outputs writes for K = 105 are those of K = 5."""
+    import json
+    import subprocess
+    import sys
+    import numpy as np
+    from conftest import ROOT
+    got = {}
+    for k in (105, 5):
+        out = tmp_path / f'k{k}'
+        r = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '1', '--steps', str(k), '--warmup', '2', '--batch', '8', '--length', '128',
+                            '--dump-outputs', str(out)], capture_output=True, text=True, timeout=900)
+        assert r.returncode == 0, r.stderr[-3000:]
+        line = json.loads([l for l in r.stdout.strip().splitlines() if l.startswith('{')][-1])
+        assert line['steps'] == k and line['repeats'] == 1 and line['ms_per_step'] > 0 and line['value'] > 0 and not line['full']
+        assert not {'roofline', 'box', 'cpu_baseline', 'secondary', 'loop100'} & set(line)
+        got[k] = {n: np.load(out / f'{n}.npy') for n in ('v', 'p', 's')}
+        assert got[k]['v'].shape == got[k]['p'].shape == (8, 128, 3) and got[k]['s'].shape == (8, 128)
+        assert all(a.dtype == np.float32 and np.isfinite(a).all() for a in got[k].values())
+    for n in ('v', 'p', 's'):
+        assert np.array_equal(got[105][n], got[5][n]), n
 
 
 @pytest.mark.gpu

@@ -8,9 +8,9 @@ ROOT=$(pwd)
 OUT=$ROOT/${1:-gpurun_out/prof}; mkdir -p $OUT
 TAG=$(basename $OUT)
 export TMPDIR=/tmp
-python bench.py > $OUT/bench_full.log 2> $OUT/bench_full.err
+python bench.py --full > $OUT/bench_full.log 2> $OUT/bench_full.err
 cd /tmp
-rocprofv3 --kernel-trace --stats -d $OUT/stats -- python $ROOT/bench.py --no-cpu-baseline --no-secondary > $OUT/bench_profiled.log 2>&1
+rocprofv3 --kernel-trace --stats -d $OUT/stats -- python $ROOT/bench.py --full --no-cpu-baseline --no-secondary > $OUT/bench_profiled.log 2>&1
 python $ROOT/tools/rocprof_summary.py $OUT/stats > $OUT/kernel_stats.txt
 CMD="python $ROOT/bench.py --steps 4 --warmup 1 --repeats 1 --graph off --no-prof --no-cpu-baseline --no-secondary"
 i=0

@@ -3,7 +3,7 @@
 # without events, hipGraph with the event records captured inside.  Usage (GPU box): bash tools/r03_ab_graph.sh
 cd "$(dirname "$0")/.." && mkdir -p gpurun_out
 export TMPDIR=/tmp
-C="--no-cpu-baseline --no-secondary --repeats 5"
+C="--full --no-cpu-baseline --no-secondary --repeats 5"
 for v in "--graph off" "--graph off --no-prof" "--graph on" "--graph on --graph-events" "--graph off" "--graph on"; do
   echo "=== bench.py $v" >> gpurun_out/ab_graph.log
   timeout 600 python bench.py $C $v >> gpurun_out/ab_graph.log 2>> gpurun_out/ab_graph.err

@@ -7,9 +7,9 @@ ROOT=$(pwd)
 OUT=$ROOT/${1:-gpurun_out/r04_a}; mkdir -p $OUT
 TAG=$(basename $OUT)
 export TMPDIR=/tmp
-python bench.py --steps 20 --warmup 5 > $OUT/bench_full.log 2> $OUT/bench_full.err
+python bench.py --steps 20 --warmup 5 --full > $OUT/bench_full.log 2> $OUT/bench_full.err
 cd /tmp
-rocprofv3 --kernel-trace --stats -d $OUT/stats -- python $ROOT/bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-secondary > $OUT/bench_profiled.log 2>&1
+rocprofv3 --kernel-trace --stats -d $OUT/stats -- python $ROOT/bench.py --steps 20 --warmup 5 --full --no-cpu-baseline --no-secondary > $OUT/bench_profiled.log 2>&1
 python $ROOT/tools/rocprof_summary.py $OUT/stats > $OUT/kernel_stats.txt
 rm -rf $OUT/stats
 CMD="python $ROOT/bench.py --steps 4 --warmup 1 --repeats 1 --graph off --no-prof --no-cpu-baseline --no-secondary"

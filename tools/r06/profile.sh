@@ -5,13 +5,13 @@
 # passes of developer builds with one stream removed: W_out terms / key-value fragments / z + bias cache)   5. steady-state training step   6. other shapes
 cd "$(dirname "$0")/../.." && ROOT=$(pwd) && OUT=$ROOT/${1:-gpurun_out/r06_j} && mkdir -p $OUT && TAG=$(basename $OUT)
 export TMPDIR=/tmp
-python bench.py --steps 20 --warmup 5 > $OUT/bench_full.log 2> $OUT/bench_full.err
+python bench.py --steps 20 --warmup 5 --full > $OUT/bench_full.log 2> $OUT/bench_full.err
 cd /tmp
-rocprofv3 --kernel-trace --stats -d $OUT/stats -- python $ROOT/bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-secondary > $OUT/bench_profiled.log 2>&1
+rocprofv3 --kernel-trace --stats -d $OUT/stats -- python $ROOT/bench.py --steps 20 --warmup 5 --full --no-cpu-baseline --no-secondary > $OUT/bench_profiled.log 2>&1
 python $ROOT/tools/rocprof_summary.py $OUT/stats > $OUT/kernel_stats.txt
 rm -rf $OUT/stats
 # the same with replayed launches only (no eager_events / two-launch passes): the average that roofline.avg_launch_ms must agree with
-rocprofv3 --kernel-trace --stats -d $OUT/stats_r -- python $ROOT/bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-secondary --replay-only > $OUT/bench_profiled_replay_only.log 2>&1
+rocprofv3 --kernel-trace --stats -d $OUT/stats_r -- python $ROOT/bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-secondary --replay-only --full > $OUT/bench_profiled_replay_only.log 2>&1
 python $ROOT/tools/rocprof_summary.py $OUT/stats_r > $OUT/kernel_stats_replay_only.txt
 rm -rf $OUT/stats_r
 CMD="python $ROOT/bench.py --steps 4 --warmup 1 --repeats 1 --graph off --no-prof --no-cpu-baseline --no-secondary"
