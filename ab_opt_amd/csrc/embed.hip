@@ -290,10 +290,7 @@ constexpr int PMT = 4;        // 16-pair tiles per wave
     }
 #define SEL4(ARR, I) ((I) == 0 ? ARR[0] : (I) == 1 ? ARR[1] : (I) == 2 ? ARR[2] : ARR[3])
 
-#ifndef PE_LB
-#define PE_LB 2
-#endif
-__global__ __launch_bounds__(256, PE_LB) void pair_embed_kernel(PairArgs a) {
+__global__ __launch_bounds__(256, 2) void pair_embed_kernel(PairArgs a) {
     const int lane = threadIdx.x & 63, fm = lane & 15, kq = lane >> 4;
     const int L = a.L, A = a.A;
     const int jblocks = (L + 16 * PMT - 1) / (16 * PMT);
@@ -440,12 +437,8 @@ __global__ __launch_bounds__(256, PE_LB) void pair_embed_kernel(PairArgs a) {
             const unsigned jr = (unsigned)min(j0 + mt * 16 + fm_late, L - 1);
             const float psm = SEL4(ps, mt);
             const V3 nj = xyz(atoms_b[jr * 16u + 0u]), caj = xyz(atoms_b[jr * 16u + 1u]), cj = xyz(atoms_b[jr * 16u + 2u]);
-#if defined(PE_ABL) && (PE_ABL & 1)      // developer build: no dihedral geometry
-            const float x0 = nj.x, x1 = caj.y;
-#else
             const float x0 = dihedral_from_four_points(ci, nj, caj, cj);
             const float x1 = dihedral_from_four_points(ni, cai, ci, nj);
-#endif
             f32x4 d0, d1;
 #pragma unroll
             for (int blk = 0; blk < 2; ++blk)
@@ -455,11 +448,7 @@ __global__ __launch_bounds__(256, PE_LB) void pair_embed_kernel(PairArgs a) {
                     const int ang = k >= 13, m = k - 13 * ang;
                     const float x = ang ? x1 : x0;
                     float v = 0.f;
-#if defined(PE_ABL) && (PE_ABL & 2)      // developer build: no sin / cos
-                    if (k < 26) v = (m == 0) ? x : x * a.freq[m <= 6 ? m - 1 : m - 7];
-#else
                     if (k < 26) v = (m == 0) ? x : ((m <= 6) ? sinf(x * a.freq[m - 1]) : cosf(x * a.freq[m - 7]));
-#endif
                     if (blk == 0) d0[q] = v * psm; else d1[q] = v * psm;
                 }
             // register-array write with a loop-variant index would go to scratch: select per tile

@@ -26,30 +26,8 @@
 #include "tail_common.h"
 #include "kernels.h"
 
-// Developer ablations (never in the shipped build): make CXXEXTRA=-DCORE_ABL=<bits>.  bit 0: pair waves load z only once;
-// bit 1: A/C waves load their fragments only once; bit 2: pair waves skip the aggregation MFMAs; bit 3: A waves skip their MFMAs;
-// bit 4: C waves skip their MFMAs; bit 5: pair waves skip the softmax arithmetic.  Results are wrong by construction.
-#ifndef CORE_ABL
-#define CORE_ABL 0
-#endif
-
-#ifdef CORE_TIMING   // developer build (make CXXEXTRA=-DCORE_TIMING): s_memtime section timers of one workgroup, printed by the launcher
-#include <cstdio>
-#define TSTAMP(k) { const long long now_ = clock64(); tacc[k] += now_ - tprev; tprev = now_; }
-#define TSYNC(kw, kb) { TSTAMP(kw) __syncthreads(); TSTAMP(kb) }
-__device__ long long g_core_timing[3][8];
-#else
-#define TSTAMP(k)
-#define TSYNC(kw, kb) __syncthreads();
-#if defined(PERSIST_TIMING) || defined(C32_TIMING) || defined(C32_COUNT)   // developer builds: per-role clocks of one workgroup
-#include <cstdio>
-__device__ long long g_core_timing[3][8];
-#endif
-#endif
-
-#ifndef PBC_CHUNK_MAJOR
-#define PBC_CHUNK_MAJOR 1 // layout of a layer's slab of the pair-bias cache: 1 [chunk][row of the batch][12 x 16] (the same argument as ZT_CHUNK_MAJOR below) | 0 [row][chunk][12 x 16]
-#endif
+// Layout of a layer's slab of the pair-bias cache: chunk-major, [chunk][row of the batch][12 x 16].  The workgroups of a launch read the same
+// chunk of their rows at the same time, so its live set is one dense plane (the same argument as for the pair terms, at the 32-row kernel).
 namespace abopt {
 
 constexpr int NPW = 8, RPW = BI / NPW;          // pair waves, query rows per pair wave
@@ -138,11 +116,8 @@ __global__ __launch_bounds__(NTH) void ipa_core_kernel(const float* __restrict__
     const int slice = SPLIT ? blockIdx.x % nsplit : 0;
     const int c_lo = SPLIT ? slice * nchunk / nsplit : 0, c_hi = SPLIT ? (slice + 1) * nchunk / nsplit : nchunk;
     const int ncl = c_hi - c_lo;                                        // key chunks of this workgroup (all of them unless SPLIT)
-    const int c0 = SPLIT ? c_lo : ((CORE_ABL & 512) ? ib % nchunk : 0);
+    const int c0 = SPLIT ? c_lo : 0;
     auto chunk_of = [&](int it) { const int c = it + c0; return c < nchunk ? c : c - nchunk; };      // iteration -> key chunk
-#ifdef CORE_TIMING
-    long long tacc[8] = {0, 0, 0, 0, 0, 0, 0, 0}, tprev = clock64();   // 0 prologue | 1 work | 2 barrier wait | 3 epilogue own | 4 F1/F2 waits | 5 common epilogue
-#endif
 
     // ---------------------------------------------------------------- prologue (every role first puts its own global loads in flight)
     auto fill_lds = [&]() {
@@ -175,8 +150,8 @@ __global__ __launch_bounds__(NTH) void ipa_core_kernel(const float* __restrict__
         const char* pbrow[RPW];                                          // wave-uniform row bases (SGPRs) + one per-lane byte offset
 #pragma unroll
         for (int ii = 0; ii < RPW; ++ii)
-            pbrow[ii] = CACHED ? reinterpret_cast<const char*>(pbc + ((zbase + min(i0 + il0 + ii, L - 1)) * (int64_t)(PBC_CHUNK_MAJOR ? 1 : nchunk)) * (H * JC)) : nullptr;
-        const unsigned pb_chunk = PBC_CHUNK_MAJOR ? (unsigned)((N / (z_shared ? z_shared : 1)) * L) * (unsigned)(H * JC * 4) : (unsigned)(H * JC * 4);      // bytes from a row's chunk to its next one
+            pbrow[ii] = CACHED ? reinterpret_cast<const char*>(pbc + (zbase + min(i0 + il0 + ii, L - 1)) * (H * JC)) : nullptr;
+        const unsigned pb_chunk = (unsigned)((N / (z_shared ? z_shared : 1)) * L) * (unsigned)(H * JC * 4);      // bytes from a row's chunk to its next one
         const unsigned pb_lane = (unsigned)(min(fm, H - 1) * JC + kq * 4) * 4u;
         // the dump goes out through a buffer descriptor: base = this sample's [12,L,L] slab (SGPRs), one lane-constant byte offset
         // (head, key group) and a wave-uniform row/chunk offset -- no 64-bit per-lane addresses in the hot loop
@@ -190,14 +165,10 @@ __global__ __launch_bounds__(NTH) void ipa_core_kernel(const float* __restrict__
         const int ch_ = chunk_of(min((CH), ncl - 1));                          /* past the end: harmless re-read */      \
         _Pragma("unroll") for (int r_ = 0; r_ < 4; ++r_)                                                                \
             ring[SLOT][r_] = ZLOAD(reinterpret_cast<const f32x4*>(zrow[II] + ((unsigned)min(ch_ * JC + kq * 4 + r_, L - 1) * (unsigned)(C * 4) + lane_b))); \
-        if (CACHED && !(CORE_ABL & 64)) ringb[SLOT] = ZLOAD(reinterpret_cast<const f32x4*>(pbrow[II] + ((unsigned)ch_ * pb_chunk + pb_lane))); \
+        if (CACHED) ringb[SLOT] = ZLOAD(reinterpret_cast<const f32x4*>(pbrow[II] + ((unsigned)ch_ * pb_chunk + pb_lane))); \
     }
 // z and its bias cache are read once per launch: non-temporal loads (measured 182 -> 174 us per launch at N=32, L=256)
-#ifdef CORE_NO_NT
-#define ZLOAD(p) (*(p))
-#else
 #define ZLOAD(p) __builtin_nontemporal_load(p)
-#endif
         PW_ISSUE(0, 0, 0) PW_ISSUE(1, 1, 0)
         fill_lds();
         float m_run[RPW], l_run[RPW];
@@ -214,12 +185,11 @@ __global__ __launch_bounds__(NTH) void ipa_core_kernel(const float* __restrict__
 #pragma unroll
         for (int ii = 0; ii < RPW; ++ii) mi_b[ii] = (i0 + il0 + ii < L) && sm.mk[min(i0 + il0 + ii, L - 1)] != 0;
         __syncthreads();                                                    // barrier #0: S(0) ready
-        TSTAMP(0)
 
         // one (query row, chunk) position: ring slot SLOT holds its z; BUF = chunk % 3
 #define PW_POS(SLOT, II, CH, BUF)                                                                                        \
     {                                                                                                                    \
-        if (!(CORE_ABL & 1)) PW_ISSUE(((SLOT) + 2) % 3, II, (CH) + 1)       /* two positions ahead = same row, next chunk */ \
+        PW_ISSUE(((SLOT) + 2) % 3, II, (CH) + 1)                            /* two positions ahead = same row, next chunk */ \
         const int il_ = il0 + (II);                                                                                      \
         float* spp_ = sm.sp + ((BUF) * BI + il_) * SROW + spo;                                                           \
         f32x4 sv_ = *reinterpret_cast<const f32x4*>(spp_);                                                               \
@@ -254,8 +224,6 @@ __global__ __launch_bounds__(NTH) void ipa_core_kernel(const float* __restrict__
             l2_[r_] = ((mk4_ >> (8 * r_)) & 0xffu) ? x_ : x_ - kMask2;      /* ga.py:20-23 (masked QUERY rows are zeroed at the end instead) */ \
         }                                                                                                                \
         f32x4 pv_; float sc_;                                                                                            \
-        if (CORE_ABL & 32) { sc_ = 1.f; pv_ = (f32x4){l2_[0], l2_[1], l2_[2], l2_[3]}; l_run[II] += l2_[0]; }           \
-        else {                                                                                                           \
         const float mx_ = rows_max(fmaxf(fmaxf(l2_[0], l2_[1]), fmaxf(l2_[2], l2_[3])));                                 \
         const float mn_ = fmaxf(m_run[II], mx_);                                                                         \
         sc_ = __builtin_amdgcn_exp2f(m_run[II] - mn_);                                                                   \
@@ -264,9 +232,6 @@ __global__ __launch_bounds__(NTH) void ipa_core_kernel(const float* __restrict__
         l_run[II] = l_run[II] * sc_ + ps_;                                                                               \
         m_run[II] = mn_;                                                                                                 \
         _Pragma("unroll") for (int mt_ = 0; mt_ < 4; ++mt_) accP[II][mt_] *= sc_;                                        \
-        }                                                                                                                \
-        if (CORE_ABL & 4) { _Pragma("unroll") for (int r_ = 0; r_ < 4; ++r_) accP[II][r_] += ring[SLOT][r_] * pv_[r_]; } \
-        else                                                                                                             \
         _Pragma("unroll") for (int r_ = 0; r_ < 4; ++r_)                                                                 \
             _Pragma("unroll") for (int mt_ = 0; mt_ < 4; ++mt_) accP[II][mt_] = mfma4(ring[SLOT][r_][mt_], pv_[r_], accP[II][mt_]); \
         *reinterpret_cast<f32x4*>(spp_) = pv_;                                                                           \
@@ -278,7 +243,7 @@ __global__ __launch_bounds__(NTH) void ipa_core_kernel(const float* __restrict__
         const uint32_t mk4_ = *reinterpret_cast<const uint32_t*>(&sm.mk[chunk_of(CH) * JC + kq * 4]);                    \
         PW_POS((2 * (K)) % 3, 0, CH, K)                                                                                  \
         PW_POS((2 * (K) + 1) % 3, 1, CH, K)                                                                              \
-        TSYNC(1, 2)                                                         /* barrier #(CH + 1) */                       \
+        __syncthreads();                                                    /* barrier #(CH + 1) */                       \
     }
         int ch = 0;
         for (; ch + 3 <= ncl; ch += 3) { PW_CHUNK(0, ch) PW_CHUNK(1, ch + 1) PW_CHUNK(2, ch + 2) }
@@ -303,8 +268,8 @@ __global__ __launch_bounds__(NTH) void ipa_core_kernel(const float* __restrict__
                     reinterpret_cast<f32x4*>(fo)[r] = (f32x4){accP[ii][0][r] * inv, accP[ii][1][r] * inv, accP[ii][2][r] * inv, accP[ii][3][r] * inv};
             }
         }
-        TSYNC(3, 4)                                                         // F1: lsum visible, C waves done with the last chunk
-        TSYNC(3, 4)                                                         // F2: aggregated points in LDS
+        __syncthreads();                                                    // F1: lsum visible, C waves done with the last chunk
+        __syncthreads();                                                    // F2: aggregated points in LDS
     } else if (wave < NPW + 4) {
         // =========================================================================================== A waves: S(t + 1)
         const int h0 = (wave - NPW) * 3;
@@ -316,7 +281,7 @@ __global__ __launch_bounds__(NTH) void ipa_core_kernel(const float* __restrict__
     {                                                                                                                    \
         const int c_ = chunk_of(min((CH), ncl - 1));                                                                     \
         const f32x4* fr_ = kvn + ((int64_t)c_ * H + h0 + (HH)) * 512 + lane;                                             \
-        if (!(CORE_ABL & 128)) { _Pragma("unroll") for (int s_ = 0; s_ < 4; ++s_) kf[HH][s_] = fr_[s_ * 64]; }           \
+        _Pragma("unroll") for (int s_ = 0; s_ < 4; ++s_) kf[HH][s_] = fr_[s_ * 64];                                      \
     }
 #define AW_ISSUE0(HH) { const f32x4* fr_ = kvn + ((int64_t)chunk_of(0) * H + h0 + (HH)) * 512 + lane;                   \
         _Pragma("unroll") for (int s_ = 0; s_ < 4; ++s_) kf[HH][s_] = fr_[s_ * 64]; }
@@ -328,15 +293,12 @@ __global__ __launch_bounds__(NTH) void ipa_core_kernel(const float* __restrict__
                 const f32x4 q0 = qh[0], q1 = qh[64], q2 = qh[128], q3 = qh[192];
                 // rows = keys (A operand k'), columns = queries (B operand q'); two chains hide the 40-cycle dependent-MFMA latency
                 f32x4 acc0 = (f32x4){0.f, 0.f, 0.f, 0.f}, acc1 = acc0;
-                if (CORE_ABL & 8) { acc0 = kf[hh][0] * q0 + kf[hh][1] * q1; acc1 = kf[hh][2] * q2 + kf[hh][3] * q3; }
-                else {
 #pragma unroll
                 for (int s = 0; s < 4; ++s) { acc0 = mfma4(kf[hh][0][s], q0[s], acc0); acc1 = mfma4(kf[hh][2][s], q2[s], acc1); }
 #pragma unroll
                 for (int s = 0; s < 4; ++s) { acc0 = mfma4(kf[hh][1][s], q1[s], acc0); if (s < 3) acc1 = mfma4(kf[hh][3][s], q3[s], acc1); }
-                }
                 const f32x4 sres = acc0 + acc1;
-                if (!(CORE_ABL & 2) && (!(CORE_ABL & 1024) || (c & 1))) { if (hh == 0) AW_ISSUE(0, c + 1) else if (hh == 1) AW_ISSUE(1, c + 1) else AW_ISSUE(2, c + 1) }
+                if (hh == 0) AW_ISSUE(0, c + 1) else if (hh == 1) AW_ISSUE(1, c + 1) else AW_ISSUE(2, c + 1)
                 *reinterpret_cast<f32x4*>(sm.sp + (buf * BI + fm) * SROW + sp_off(h, kq)) = sres;      // accumulator row 4 kq + r = key, column fm = query
                 __builtin_amdgcn_sched_barrier(0);                          // keep the per-head order: hipcc otherwise sinks all reloads to the end of the iteration
             }
@@ -346,16 +308,15 @@ __global__ __launch_bounds__(NTH) void ipa_core_kernel(const float* __restrict__
         __syncthreads();
         produce(0, 0);
         __syncthreads();                                                    // barrier #0
-        TSTAMP(0)
         int buf = 1;
         for (int c = 1; c < ncl; ++c) {
             produce(c, buf);
             buf = (buf == 2) ? 0 : buf + 1;
-            TSYNC(1, 2)                                                     // barrier #c
+            __syncthreads();                                                // barrier #c
         }
-        TSYNC(1, 2)                                                         // barrier #nchunk
-        TSYNC(3, 4)                                                         // F1
-        TSYNC(3, 4)                                                         // F2
+        __syncthreads();                                                    // barrier #nchunk
+        __syncthreads();                                                    // F1
+        __syncthreads();                                                    // F2
     } else {
         // =========================================================================================== C waves: node / point aggregation of chunk t - 1
         const int h0 = (wave - NPW - 4) * 3;
@@ -369,7 +330,7 @@ __global__ __launch_bounds__(NTH) void ipa_core_kernel(const float* __restrict__
 #define CW_ISSUE(HH, CH)                                                                                                 \
     {                                                                                                                    \
         const f32x4* fr_ = kvn + ((int64_t)chunk_of(min((CH), ncl - 1)) * H + h0 + (HH)) * 512 + 4 * 64 + lane;          \
-        if (!(CORE_ABL & 256)) { _Pragma("unroll") for (int s_ = 0; s_ < 4; ++s_) vf[HH][s_] = fr_[s_ * 64]; }           \
+        _Pragma("unroll") for (int s_ = 0; s_ < 4; ++s_) vf[HH][s_] = fr_[s_ * 64];                                      \
     }
 #define CW_ISSUE0(HH) { const f32x4* fr_ = kvn + ((int64_t)chunk_of(0) * H + h0 + (HH)) * 512 + 4 * 64 + lane;          \
         _Pragma("unroll") for (int s_ = 0; s_ < 4; ++s_) vf[HH][s_] = fr_[s_ * 64]; }
@@ -381,8 +342,6 @@ __global__ __launch_bounds__(NTH) void ipa_core_kernel(const float* __restrict__
                 const float sc = sm.scl[(par * BI + fm) * SCLD + h];                                   // rescale of (query fm, head h)
                 const f32x4 pa = *reinterpret_cast<const f32x4*>(sm.sp + (buf * BI + fm) * SROW + sp_off(h, kq));   // B: column = query fm, step s <-> key 4 kq + s
                 accV[hh][0] *= sc; accV[hh][1] *= sc; accT[hh][0] *= sc; accT[hh][1] *= sc;
-                if (CORE_ABL & 16) { accV[hh][0] += vf[hh][0] * pa; accV[hh][1] += vf[hh][1] * pa; accT[hh][0] += vf[hh][2] * pa; accT[hh][1] += vf[hh][3] * pa; }
-                else
 #pragma unroll
                 for (int s = 0; s < 4; ++s) {                                                          // A: row fm <-> value channels 2 fm (+1) / point coordinates 2 fm (+1)
                     accV[hh][0] = mfma4(vf[hh][s][0], pa[s], accV[hh][0]);
@@ -390,7 +349,7 @@ __global__ __launch_bounds__(NTH) void ipa_core_kernel(const float* __restrict__
                     accT[hh][0] = mfma4(vf[hh][s][2], pa[s], accT[hh][0]);
                     accT[hh][1] = mfma4(vf[hh][s][3], pa[s], accT[hh][1]);
                 }
-                if (!(CORE_ABL & 2) && (!(CORE_ABL & 1024) || (c & 1))) { if (hh == 0) CW_ISSUE(0, c + 1) else if (hh == 1) CW_ISSUE(1, c + 1) else CW_ISSUE(2, c + 1) }
+                if (hh == 0) CW_ISSUE(0, c + 1) else if (hh == 1) CW_ISSUE(1, c + 1) else CW_ISSUE(2, c + 1)
                 __builtin_amdgcn_sched_barrier(0);                          // keep the per-head order (see the A waves)
             }
         };
@@ -399,16 +358,15 @@ __global__ __launch_bounds__(NTH) void ipa_core_kernel(const float* __restrict__
         __syncthreads();
         const bool mi_c = (i0 + fm < L) && sm.mk[min(i0 + fm, L - 1)] != 0;
         __syncthreads();                                                    // barrier #0
-        TSTAMP(0)
-        TSYNC(1, 2)                                                         // barrier #1: P(0) ready
+        __syncthreads();                                                    // barrier #1: P(0) ready
         int buf = 0;                                                        // buffer of the chunk being consumed
         for (int c = 1; c < ncl; ++c) {
             consume(c - 1, buf);
             buf = (buf == 2) ? 0 : buf + 1;
-            TSYNC(1, 2)                                                     // barrier #(c + 1)
+            __syncthreads();                                                // barrier #(c + 1)
         }
         consume(ncl - 1, buf);
-        TSYNC(3, 4)                                                         // F1
+        __syncthreads();                                                    // F1
         float* pts = sm.sp;                                                 // [BI][H][24] aggregated global-frame points; the S/P tile is free now
         const int i = i0 + fm;
 #pragma unroll
@@ -427,7 +385,7 @@ __global__ __launch_bounds__(NTH) void ipa_core_kernel(const float* __restrict__
 #pragma unroll
             for (int r = 0; r < 3; ++r) { po[r] = accT[hh][0][r] * inv; po[12 + r] = accT[hh][1][r] * inv; }
         }
-        TSYNC(3, 4)                                                         // F2
+        __syncthreads();                                                    // F2
     }
 
     if (SPLIT) return;                                                      // the merge kernel finishes the rows
@@ -463,11 +421,6 @@ __global__ __launch_bounds__(NTH) void ipa_core_kernel(const float* __restrict__
         }
         *reinterpret_cast<f32x4*>(fpnt + H * P * 3 + 4 * g) = dist;
     }
-#ifdef CORE_TIMING
-    TSTAMP(5)
-    if (blockIdx.x == 17 && lane == 0 && (wave == 0 || wave == NPW || wave == NPW + 4))
-        for (int k = 0; k < 8; ++k) g_core_timing[wave == 0 ? 0 : (wave == NPW ? 1 : 2)][k] = tacc[k];
-#endif
 }
 
 // =====================================================================================================================
@@ -527,7 +480,7 @@ __device__ __attribute__((noinline)) void persist_point_epilogue(const float* __
 }
 
 // Short crops (L <= 64, the reference's CDR + 20 antigen residues: a block is over after 2..4 positions and the per-block pieces set the
-// pace -- at L = 48, by -DPERSIST_TIMING barrier waits per interval class: the A waves' point epilogue ~10k cycles, their q' swap ~6k,
+// pace -- at L = 48, by barrier waits per interval class: the A waves' point epilogue ~10k cycles, their q' swap ~6k,
 // the C waves' block epilogue ~7k on top of 3 x 9k of positions, the pair waves waiting at 60 % of the barriers) were tried in a
 // specialised form in round 3: point epilogue on the pair waves (208 bytes of scratch per lane: 4.36 -> 4.87 ms per 1000-pose step)
 // and z requests after the position's MFMAs instead of before (neutral).  Neither is kept.
@@ -547,15 +500,6 @@ __global__ __launch_bounds__(NTH) void ipa_core_persist_kernel(const float* __re
     const int tid = threadIdx.x, lane = tid & 63, fm = lane & 15, kq = lane >> 4;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int G = gridDim.x;
-#ifdef PERSIST_TIMING
-    long long pt_wait = 0, pt_mem = 0, pt_lds = 0, pt_mf = 0, pt_start = clock64(), pt_wk[3] = {0, 0, 0};
-    int pt_cls = 0;                                                     // class of the current interval: 0 first chunk of a block, 2 last, 1 between
-#define PSYNC() { const long long a_ = clock64(); __syncthreads(); const long long d_ = clock64() - a_; pt_wait += d_; pt_wk[pt_cls] += d_; }
-#define PCLS(G) { const int c_ = (G) % nchunk; pt_cls = c_ == 0 ? 0 : (c_ == nchunk - 1 ? 2 : 1); }
-#else
-#define PSYNC() __syncthreads();
-#define PCLS(G)
-#endif
     const int nb = (total_blocks - (int)blockIdx.x + G - 1) / G;        // blocks of this workgroup (>= 1)
     const int gtot = nb * nchunk;                                       // positions
     auto blk = [&](int j) { return pblk_of((int)blockIdx.x + min(j, nb - 1) * G, nib, L, xcd_remap, z_shared); };
@@ -574,13 +518,13 @@ __global__ __launch_bounds__(NTH) void ipa_core_persist_kernel(const float* __re
         const unsigned lane_b = (unsigned)fm * 16u;
         const unsigned pb_lane = (unsigned)(min(fm, H - 1) * JC + kq * 4) * 4u;
         const char *zrow[RPW], *pbrow[RPW], *zrow_n[RPW], *pbrow_n[RPW];     // wave-uniform row bases of the current and the next block
-        const unsigned pb_chunk = PBC_CHUNK_MAJOR ? (unsigned)(((total_blocks / nib) / (z_shared ? z_shared : 1)) * L) * (unsigned)(H * JC * 4) : (unsigned)(H * JC * 4);
+        const unsigned pb_chunk = (unsigned)(((total_blocks / nib) / (z_shared ? z_shared : 1)) * L) * (unsigned)(H * JC * 4);
         auto rows_of = [&](const PBlk& b, const char** zr, const char** pr) {
 #pragma unroll
             for (int ii = 0; ii < RPW; ++ii) {
                 const int64_t row = b.zbase + min(b.i0 + il0 + ii, L - 1);
                 zr[ii] = reinterpret_cast<const char*>(z + (row * (int64_t)L) * C);
-                pr[ii] = reinterpret_cast<const char*>(pbc + (row * (int64_t)(PBC_CHUNK_MAJOR ? 1 : nchunk)) * (H * JC));
+                pr[ii] = reinterpret_cast<const char*>(pbc + row * (H * JC));
             }
         };
         f32x4 ring[3][4], ringb[3];
@@ -604,8 +548,8 @@ __global__ __launch_bounds__(NTH) void ipa_core_persist_kernel(const float* __re
         float m_run[RPW], l_run[RPW];
         f32x4 accP[RPW][4];
         const int spo = sp_off(fm, kq);
-        PSYNC()                                                    // LDS tile visible
-        PSYNC()                                                    // S(0) ready
+        __syncthreads();                                           // LDS tile visible
+        __syncthreads();                                           // S(0) ready
         // one (query row, position): ring slot SLOT holds its z; BUF = position % 3; PAR = position parity
 #define PP_POS(SLOT, II, CH, BUF, PAR)                                                                                   \
     {                                                                                                                    \
@@ -679,11 +623,10 @@ __global__ __launch_bounds__(NTH) void ipa_core_persist_kernel(const float* __re
         };
 #define PP_STEP(K, G)                                                                                                    \
     {                                                                                                                    \
-        PCLS(G)                                                                                                          \
         if (c == 0) block_begin();                                                                                       \
         PP_CHUNK(K, c, (G) & 1)                                                                                          \
         if (c == nchunk - 1) { block_end(); c = 0; ++j; } else ++c;                                                      \
-        PSYNC()                                                    /* B_g */                                     \
+        __syncthreads();                                           /* B_g */                                     \
     }
         int g = 0;
         for (; g + 3 <= gtot; g += 3) { PP_STEP(0, g) PP_STEP(1, g + 1) PP_STEP(2, g + 2) }
@@ -692,7 +635,7 @@ __global__ __launch_bounds__(NTH) void ipa_core_persist_kernel(const float* __re
             if (g + 1 < gtot) PP_STEP(1, g + 1)
         }
 #undef PP_STEP
-        PSYNC()                                                    // T1: the C waves finished the last block
+        __syncthreads();                                           // T1: the C waves finished the last block
     } else if (wave < NPW + 4) {
         // =========================================================================================== A waves: S(g + 1) in interval g
         const int h0 = (wave - NPW) * 3;
@@ -703,9 +646,6 @@ __global__ __launch_bounds__(NTH) void ipa_core_persist_kernel(const float* __re
         _Pragma("unroll") for (int s_ = 0; s_ < 4; ++s_) kf[HH][s_] = fr_[s_ * 64]; }
         // S(position) -> sp[buf]; after each head's MFMAs its registers are refilled with the NEXT position's key fragments
         auto produce = [&](int buf, const f32x4* kv_next, int ch_next) {
-#ifdef PERSIST_TIMING
-            { const long long a_ = clock64(); asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); pt_mem += clock64() - a_; }
-#endif
 #pragma unroll
             for (int hh = 0; hh < 3; ++hh) {
                 const int h = h0 + hh;
@@ -734,12 +674,11 @@ __global__ __launch_bounds__(NTH) void ipa_core_persist_kernel(const float* __re
             PA_ISSUE(0, kv0, ch0) PA_ISSUE(1, kv0, ch0) PA_ISSUE(2, kv0, ch0)
         }
         fill_first();
-        PSYNC()
+        __syncthreads();
         { const f32x4* kv1; int ch1; kv_pos(1, kv1, ch1); produce(0, kv1, ch1); }
-        PSYNC()                                                    // S(0) ready
+        __syncthreads();                                           // S(0) ready
         int bufn = 1;                                                       // buffer of position g + 1
         for (int g = 0; g < gtot; ++g) {
-            PCLS(g)
             const int gn = g + 1;
             if (gn < gtot) {
                 if (gn % nchunk == 0) {
@@ -768,9 +707,9 @@ __global__ __launch_bounds__(NTH) void ipa_core_persist_kernel(const float* __re
                 const PBlk bp = blk(g / nchunk - 1);
                 persist_point_epilogue(ptsb, R, t, feat, bp.rowbase, bp.i0, L, atid, 4 * 64);
             }
-            PSYNC()                                                // B_g
+            __syncthreads();                                       // B_g
         }
-        PSYNC()                                                    // T1: the C waves finished the last block
+        __syncthreads();                                           // T1: the C waves finished the last block
         { const PBlk bl = blk(nb - 1); persist_point_epilogue(ptsb, R, t, feat, bl.rowbase, bl.i0, L, atid, 4 * 64); }
     } else {
         // =========================================================================================== C waves: position g - 1 in interval g
@@ -790,21 +729,11 @@ __global__ __launch_bounds__(NTH) void ipa_core_persist_kernel(const float* __re
             kv = kv_of(b); ch = pc % nchunk;
         };
         auto consume = [&](int buf, int par, const f32x4* kv_next, int ch_next) {
-#ifdef PERSIST_TIMING
-            { const long long a_ = clock64(); asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); pt_mem += clock64() - a_; }
-#endif
 #pragma unroll
             for (int hh = 0; hh < 3; ++hh) {
                 const int h = h0 + hh;
-#ifdef PERSIST_TIMING
-                const long long ta_ = clock64();
-#endif
                 const float sc = scl[(par * BI + fm) * SCLD + h];
                 const f32x4 pa = *reinterpret_cast<const f32x4*>(sp + (buf * BI + fm) * SROW + sp_off(h, kq));
-#ifdef PERSIST_TIMING
-                asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-                const long long tb_ = clock64();
-#endif
                 accV[hh][0] *= sc; accV[hh][1] *= sc; accT[hh][0] *= sc; accT[hh][1] *= sc;
 #pragma unroll
                 for (int s = 0; s < 4; ++s) {
@@ -813,10 +742,6 @@ __global__ __launch_bounds__(NTH) void ipa_core_persist_kernel(const float* __re
                     accT[hh][0] = mfma4(vf[hh][s][2], pa[s], accT[hh][0]);
                     accT[hh][1] = mfma4(vf[hh][s][3], pa[s], accT[hh][1]);
                 }
-#ifdef PERSIST_TIMING
-                __builtin_amdgcn_sched_barrier(0);
-                { const long long tc_ = clock64(); pt_lds += tb_ - ta_; pt_mf += tc_ - tb_; }
-#endif
                 if (hh == 0) PC_ISSUE(0, kv_next, ch_next) else if (hh == 1) PC_ISSUE(1, kv_next, ch_next) else PC_ISSUE(2, kv_next, ch_next)
                 __builtin_amdgcn_sched_barrier(0);
             }
@@ -849,33 +774,24 @@ __global__ __launch_bounds__(NTH) void ipa_core_persist_kernel(const float* __re
             PC_ISSUE(0, kv0, ch0) PC_ISSUE(1, kv0, ch0) PC_ISSUE(2, kv0, ch0)
         }
         fill_first();
-        PSYNC()
-        PSYNC()                                                    // S(0) ready
-        PSYNC()                                                    // B_0: P(0) ready
+        __syncthreads();
+        __syncthreads();                                           // S(0) ready
+        __syncthreads();                                           // B_0: P(0) ready
         int buf = 0;                                                        // buffer of position g - 1
         for (int g = 1; g <= gtot; ++g) {
-            PCLS(g)
             const int p = g - 1;
             const f32x4* kvx; int chx;
             kv_pos(g, kvx, chx);
             consume(buf, p & 1, kvx, chx);
             buf = (buf == 2) ? 0 : buf + 1;
             if (p % nchunk == nchunk - 1) block_epilogue(p / nchunk);
-            PSYNC()                                                // B_g (g < gtot), T1 (g == gtot)
+            __syncthreads();                                       // B_g (g < gtot), T1 (g == gtot)
         }
     }
 #undef PP_ISSUE
 #undef PP_POS
 #undef PP_CHUNK
 #undef PA_ISSUE
-#ifdef PERSIST_TIMING
-    if (blockIdx.x == 17 && lane == 0 && (wave == 0 || wave == NPW || wave == NPW + 4)) {
-        long long* o = g_core_timing[wave == 0 ? 0 : (wave == NPW ? 1 : 2)];
-        o[0] = clock64() - pt_start; o[1] = pt_wait; o[2] = pt_mem; o[3] = pt_lds; o[4] = pt_mf; o[5] = pt_wk[0]; o[6] = pt_wk[1]; o[7] = pt_wk[2];
-    }
-#endif
-#undef PSYNC
-#undef PCLS
 #undef PC_ISSUE
 }
 
@@ -892,42 +808,16 @@ __global__ __launch_bounds__(NTH) void ipa_core_persist_kernel(const float* __re
 // Wave w and w + 4 share a SIMD: every SIMD hosts one pair wave and one A or C wave (308 / 320 MFMAs per chunk).  Same per-row
 // arithmetic in the same order as the 16-row kernels: results are bit-identical to them (test_persistent_core_is_bit_identical runs this
 // kernel for its large batches).  One block per workgroup; the sampler's bench shape (N = 32, L = 256) is exactly 256 blocks.
-#ifndef C32_RING
-#define C32_RING 3       // slots of the pair waves' z ring (3 or 4)
-#endif
-#ifndef C32_CPIPE
-#define C32_CPIPE 0
-#endif
-#ifndef C32_LAZY
-#define C32_LAZY 2       // exact lazy rescale: skip the accumulator rescale where every factor is exactly 1 (wave-uniform branch; bit-identical).  bit 1 = pair waves (a row),
-                         // bit 2 = C waves (a (head, row tile)), in the fused kernel only.  79 % of the rescales qualify at the bench shape.  Round 5, same-box A/Bs of the fused
-                         // kernel on five boxes: C waves -4.5, -0.4 / -2.6, -1.4 / -0.7, -1.5 / -0.2 % (and +4 % once with an earlier build); pair waves too: 0 on average; the
-                         // two-launch core +4.5 % (hence FUSE only).  Shipped for the C waves: a per cent on average, never a different bit.
-#endif
-#ifdef C32_COUNT      // developer build: how often a lazy rescale could skip (printed by the launcher): {pair row-chunks, of them unchanged, C (head, tile, chunk), unchanged, C chunks (6 heads x 32 rows), unchanged}
-__device__ unsigned long long g_c32_count[8];
-#define C32_CNT(k, v) if (lane == 0) atomicAdd(&g_c32_count[k], (unsigned long long)(v));
-#else
-#define C32_CNT(k, v)
-#endif
-#ifndef C32_ABL
-#define C32_ABL 0        // developer ablations (timing only, results wrong): 1 no z / bias loads in the loop | 32 z / bias loads all from one L1-resident address | 64 no softmax arithmetic in rows 1..7 (P = S) | 128 no pair MFMAs | 256 / 512 no A / C MFMAs (nothing instead) | 2 no fragment loads in the loop | 4 / 8 / 16 pair / A / C MFMAs off | 1024 no accumulator rescale (pair and C waves) | 2048 no v_exp_f32 in rows 1..7
-#endif
-#ifndef ZT_CHUNK_MAJOR
-#define ZT_CHUNK_MAJOR 2  // layout of the pair terms: 2 [chunk][row of the batch][4 KB] -- every workgroup of a launch reads the SAME chunk of its rows at the same time, so the live
-                          // set of a chunk interval is ONE dense plane (33 MB at the bench shape) instead of 4 KB out of every 64 KB row | 1 chunk-major inside a sample's slab | 0 [row][chunk][4 KB]
-#endif
-#ifndef C32_ZAUX
-#define C32_ZAUX 2       // cache policy bits of the z / bias stream's buffer loads (2 = nt)
-#endif
+// z / bias stream: a 3-slot ring of z row chunks for the pair waves; buffer loads with cache policy nt (aux 2).
+// Lazy rescale (exact: skip the accumulator rescale where every factor is exactly 1, a wave-uniform branch; bit-identical) runs on the C waves of
+// the fused kernel only.  79 % of the rescales qualify at the bench shape.  Round 5, same-box A/Bs of the fused kernel on five boxes: C waves
+// -4.5, -0.4 / -2.6, -1.4 / -0.7, -1.5 / -0.2 % (and +4 % once with an earlier build); on the pair waves too: 0 on average; in the two-launch
+// core: +4.5 %.
+// Pair terms (ZT) are chunk-major, [chunk][row of the batch][4 KB]: every workgroup of a launch reads the SAME chunk of its rows at the same time,
+// so the live set of a chunk interval is ONE dense plane (33 MB at the bench shape) instead of 4 KB out of every 64 KB row.
 constexpr int BI2 = 32, NPW2 = 4, RPW2 = BI2 / NPW2, NTH2 = 512, HPW = 6;
 
-#define C32_EXP2(x) ((C32_ABL & 2048) ? (x) : __builtin_amdgcn_exp2f(x))      // (ablation 2048: no v_exp_f32 in rows 1..7)
-#ifdef C32_OLDMASK
-#define C32_L2(x, r) (((mk4_ >> (8 * (r))) & 0xffu) ? (x) * kScale2 : (x) * kScale2 - kMask2)
-#else
 #define C32_L2(x, r) __builtin_fmaf((x), kScale2, mterm_[r])
-#endif
 // FUSE (round 4): the block's tail -- out_transform, mask, residual, LayerNorm, mlp_transition, LayerNorm (ga.py:174-177) -- runs as the
 // EPILOGUE of this kernel on the 32 rows the workgroup owns; `feat` (7.3 KB per row: 60 MB written here and read back by the tail kernel
 // at the bench shape) never leaves the chip and the block is two launches instead of three.  After the key loop:
@@ -956,15 +846,6 @@ __global__ void prof_span_reset_kernel() {
     const int i = blockIdx.x * 256 + threadIdx.x;
     if (i < PROF_SLOTS) { g_prof_span[i][0] = ~0ull; g_prof_span[i][1] = 0ull; }
 }
-#ifndef C32F_ABL
-#define C32F_ABL 0       // developer ablations of the fused epilogue (timing only, results wrong): 1 no W_out refills | 2 no MFMAs | 4 producers write nothing | 8 / 16 C waves: no node-feature staging / no point writes
-#endif
-#ifdef C32F_TIMING   // developer build: clock stamps of every wave of workgroup 17 through the fused epilogue, printed by the launcher
-__device__ long long g_c32f_timing[8][16];
-#define C32F_STAMP(k) if (blockIdx.x == 17 && lane == 0) g_c32f_timing[wave][k] = clock64() - t32f_begin;
-#else
-#define C32F_STAMP(k)
-#endif
 struct TailArgs {
     const float *wot, *wmf, *x, *ubias, *g1, *be1, *b0, *b1, *b2, *g2, *be2;
     float* out;
@@ -1032,20 +913,6 @@ __global__ __launch_bounds__(NTH2) void ipa_core32_kernel(const float* __restric
     const int nchunk = (L + JC - 1) / JC, nib16 = (L + BI - 1) / BI;
     const long long probe_c0 = clock64(), probe_w0 = wall_clock64();
     if (prof_slot >= 0 && threadIdx.x == 0) atomicMin(&g_prof_span[prof_slot][0], (unsigned long long)probe_w0);
-#ifdef C32F_TIMING
-    const long long t32f_begin = clock64();
-#endif
-#ifdef C32_TIMING   // developer build: per-role clocks of workgroup 17: total | barrier waits in the chunk loop | wall clock (100 MHz ticks)
-    const long long t_begin = clock64(), w_begin = wall_clock64();
-    long long t_wait = 0;
-    if (blockIdx.x == 17 && lane == 0) g_core_timing[2][7 - 0] = 0;
-    if (blockIdx.x == 17 && lane == 0) atomicAdd(reinterpret_cast<unsigned long long*>(&g_core_timing[0][4 + (wave >> 2)]) + 0, (unsigned long long)__builtin_amdgcn_s_getreg(2308) << (8 * (wave & 3)));   // SIMD of every wave
-#define C32_SYNC() { const long long t0_ = clock64(); __syncthreads(); t_wait += clock64() - t0_; }
-#define C32_REPORT(ROLE) if (blockIdx.x == 17 && lane == 0 && (wave == 0 || wave == NPW2 || wave == NPW2 + 2)) { g_core_timing[ROLE][0] = clock64() - t_begin; g_core_timing[ROLE][1] = t_wait; g_core_timing[ROLE][2] = wall_clock64() - w_begin; }
-#else
-#define C32_SYNC() __syncthreads();
-#define C32_REPORT(ROLE) {}
-#endif
     const int i0 = ib * BI2;
     const int64_t rowbase = (int64_t)n * L;
     const int64_t zbase = z_shared ? (int64_t)(n / z_shared) * L : rowbase;
@@ -1055,10 +922,7 @@ __global__ __launch_bounds__(NTH2) void ipa_core32_kernel(const float* __restric
     float* const ptsf = reinterpret_cast<float*>(smem_raw + C32F_PTS_OFF);      // [32][H][24]
     const int64_t row0f = rowbase + i0, row_endf = rowbase + L;               // the 32 rows of this block in the flattened [N L] order
     TailP2Pre<NTH2 / 64> pre;                                                   // what phase 2 needs from global memory: requested while phase 1 finishes
-#ifndef C32F_RD
-#define C32F_RD 12
-#endif
-    constexpr int RD = C32F_RD;                                                 // W_out k-steps in flight per consumer wave: 12 x 2 KB of terms, 96 KB per CU
+    constexpr int RD = 12;                                                      // W_out k-steps in flight per consumer wave: 12 x 2 KB of terms, 96 KB per CU
     // W_out arrives PRE-SPLIT (ta.wot: the scaled fp16 terms pack_tail_weights_kernel makes once per weight version; out_ln_mlp_kernel streams
     // the same layout): one consumer wave per SIMD has nobody to hide a split's VALU operations behind -- with fp32 fragments split in
     // registers (round 4, first version) the phase was bound by that wave's instruction issue (466 cycles per k-step, 64k cycles in all).
@@ -1070,9 +934,7 @@ __global__ __launch_bounds__(NTH2) void ipa_core32_kernel(const float* __restric
         f32x16 acc[4];                                                          // one chain per K group (ot_kstep3)
 #pragma unroll
         for (int g = 0; g < 4; ++g) acc_zero(acc[g]);
-        C32F_STAMP(1)
         __syncthreads();                                                        // E0: staging buffers 0 / 1 and the aggregated points are in LDS
-        C32F_STAMP(2)
         const char* xrd = stage + (lane & 31) * OT_SROW + (lane >> 5) * 16;
         // One k-step: the three products of ot_kstep3 on operands already in registers; the feat terms of the next k-step are requested from
         // LDS before the first product (this wave is alone on its SIMD's matrix pipe: nobody else hides an LDS round trip) and the ring
@@ -1086,9 +948,8 @@ __global__ __launch_bounds__(NTH2) void ipa_core32_kernel(const float* __restric
             if ((KK) + 1 < (NK)) {                                                                                       \
                 xnh = *reinterpret_cast<const u32x4*>(xb + ((KK) % OT_SPC + 1) * 32); xnl = *reinterpret_cast<const u32x4*>(xb + ((KK) % OT_SPC + 1) * 32 + OT_PLANE); \
             }                                                                                                            \
-            if (C32F_ABL & 2) acc[((KK) % OT_SPC) / OT_SPW][0] += __uint_as_float((wH[0] ^ xh[0]) + (wL[2] ^ xl[2]));    \
-            else ot_kstep3(wH, wL, xh, xl, acc[((KK) % OT_SPC) / OT_SPW]);                                               \
-            if (!(C32F_ABL & 1) && i_ + RD < OT_ST) { const u32x4* nf_ = wfr + (int64_t)kstep(i_ + RD) * OT_WVEC; wt[(KK) % RD].h = nf_[0]; wt[(KK) % RD].l = nf_[64]; } \
+            ot_kstep3(wH, wL, xh, xl, acc[((KK) % OT_SPC) / OT_SPW]);                                                    \
+            if (i_ + RD < OT_ST) { const u32x4* nf_ = wfr + (int64_t)kstep(i_ + RD) * OT_WVEC; wt[(KK) % RD].h = nf_[0]; wt[(KK) % RD].l = nf_[64]; } \
         }
 #define C32F_XFIRST() { xnh = *reinterpret_cast<const u32x4*>(xb); xnl = *reinterpret_cast<const u32x4*>(xb + OT_PLANE); }
         u32x4 xnh, xnl;
@@ -1100,7 +961,6 @@ __global__ __launch_bounds__(NTH2) void ipa_core32_kernel(const float* __restric
                 C32F_XFIRST()
                 C32F_KSTEP(p, 0, 12) C32F_KSTEP(p, 1, 12) C32F_KSTEP(p, 2, 12) C32F_KSTEP(p, 3, 12) C32F_KSTEP(p, 4, 12) C32F_KSTEP(p, 5, 12)
                 C32F_KSTEP(p, 6, 12) C32F_KSTEP(p, 7, 12) C32F_KSTEP(p, 8, 12) C32F_KSTEP(p, 9, 12) C32F_KSTEP(p, 10, 12) C32F_KSTEP(p, 11, 12)
-                C32F_STAMP(3 + p)
                 __syncthreads();                                                // E(p + 1)
             }
             {
@@ -1108,7 +968,6 @@ __global__ __launch_bounds__(NTH2) void ipa_core32_kernel(const float* __restric
                 C32F_XFIRST()
                 C32F_KSTEP(p, 12, 24) C32F_KSTEP(p, 13, 24) C32F_KSTEP(p, 14, 24) C32F_KSTEP(p, 15, 24) C32F_KSTEP(p, 16, 24) C32F_KSTEP(p, 17, 24)
                 C32F_KSTEP(p, 18, 24) C32F_KSTEP(p, 19, 24) C32F_KSTEP(p, 20, 24) C32F_KSTEP(p, 21, 24) C32F_KSTEP(p, 22, 24) C32F_KSTEP(p, 23, 24)
-                C32F_STAMP(4 + p)
                 __syncthreads();                                                // E(p + 2)
             }
         }
@@ -1117,7 +976,6 @@ __global__ __launch_bounds__(NTH2) void ipa_core32_kernel(const float* __restric
             C32F_XFIRST()
             C32F_KSTEP(8, 0, 12) C32F_KSTEP(8, 1, 12) C32F_KSTEP(8, 2, 12) C32F_KSTEP(8, 3, 12) C32F_KSTEP(8, 4, 12) C32F_KSTEP(8, 5, 12)
             C32F_KSTEP(8, 6, 12) C32F_KSTEP(8, 7, 12) C32F_KSTEP(8, 8, 12) C32F_KSTEP(8, 9, 12) C32F_KSTEP(8, 10, 12) C32F_KSTEP(8, 11, 12)
-            C32F_STAMP(3 + 8)
             __syncthreads();                                                    // E9
         }
         {
@@ -1125,12 +983,10 @@ __global__ __launch_bounds__(NTH2) void ipa_core32_kernel(const float* __restric
             C32F_XFIRST()
 
             C32F_KSTEP(8, 12, 18) C32F_KSTEP(8, 13, 18) C32F_KSTEP(8, 14, 18) C32F_KSTEP(8, 15, 18) C32F_KSTEP(8, 16, 18) C32F_KSTEP(8, 17, 18)
-            C32F_STAMP(3 + 9)
             __syncthreads();                                                    // E10
         }
 #undef C32F_KSTEP
 #undef C32F_XFIRST
-        C32F_STAMP(13)
         // S_out u (without the bias) = ((p0 + p1) + (p2 + p3)): what out_ln_mlp_kernel forms from its four K-group slabs
         float (*us)[XLD] = reinterpret_cast<float (*)[XLD]>(smem_raw + C32F_U_OFF);
 #pragma unroll
@@ -1157,47 +1013,35 @@ __global__ __launch_bounds__(NTH2) void ipa_core32_kernel(const float* __restric
         // z and the bias cache are read through buffer descriptors of this sample's slabs: a request is ONE instruction -- descriptor (SGPRs),
         // the row's byte offset (an SGPR, added by the hardware) and the lane's offset inside a row (a VGPR that lives for a whole chunk)
         // (ZT: the same bytes per row-chunk, 4 KB, in the term layout [chunk][channel tile][lane]: every request is 1 KB contiguous, chunks past L are zero-padded)
-        const int rows_tot_ = ((int)gridDim.x / nib2 / (z_shared ? z_shared : 1)) * L;          // rows of the terms buffer (distinct samples x L): ZT_CHUNK_MAJOR == 2
-        const __amdgpu_buffer_rsrc_t zrs = ZT ? (ZT_CHUNK_MAJOR == 2 ? __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(zt), 0, (unsigned)rows_tot_ * (unsigned)nchunk * (JC * C * 4), 0x00020000)
-                                                                     : __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(zt + zbase * (int64_t)nchunk * (JC * C)), 0, L * nchunk * (JC * C * 4), 0x00020000))
+        const int rows_tot_ = ((int)gridDim.x / nib2 / (z_shared ? z_shared : 1)) * L;          // rows of the terms buffer (distinct samples x L)
+        const __amdgpu_buffer_rsrc_t zrs = ZT ? __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(zt), 0, (unsigned)rows_tot_ * (unsigned)nchunk * (JC * C * 4), 0x00020000)
                                               : __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(z + zbase * (int64_t)L * C), 0, L * L * C * 4, 0x00020000);
-        const __amdgpu_buffer_rsrc_t brs = PBC_CHUNK_MAJOR ? __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(pbc), 0, (unsigned)rows_tot_ * (unsigned)nchunk * (H * JC * 4), 0x00020000)
-                                                           : __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(pbc + zbase * (int64_t)nchunk * (H * JC)), 0, L * nchunk * (H * JC) * 4, 0x00020000);
+        const __amdgpu_buffer_rsrc_t brs = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(pbc), 0, (unsigned)rows_tot_ * (unsigned)nchunk * (H * JC * 4), 0x00020000);
         int zrow[RPW2], pbrow[RPW2];
 #pragma unroll
         for (int ii = 0; ii < RPW2; ++ii) {
             const int row = min(i0 + il0 + ii, L - 1);
-            zrow[ii] = ZT ? (ZT_CHUNK_MAJOR == 2 ? ((int)zbase + row) * (JC * C * 4) : (ZT_CHUNK_MAJOR ? row * (JC * C * 4) : row * nchunk * (JC * C * 4))) : row * L * (C * 4);
-            pbrow[ii] = PBC_CHUNK_MAJOR ? ((int)zbase + row) * (H * JC * 4) : row * nchunk * (H * JC * 4);
+            zrow[ii] = ZT ? ((int)zbase + row) * (JC * C * 4) : row * L * (C * 4);
+            pbrow[ii] = ((int)zbase + row) * (H * JC * 4);
         }
         const unsigned lane_b = (unsigned)fm * 16u;
         const unsigned pb_lane = (unsigned)(min(fm, H - 1) * JC + kq * 4) * 4u;
-        f32x4 ring[C32_RING][4], ringb[4];                                  // z ring: requests run C32_RING - 1 positions ahead; the bias (needed one position earlier, see below) 3 ahead
+        f32x4 ring[3][4], ringb[4];                                         // z ring: requests run 2 positions ahead; the bias (needed one position earlier, see below) 3 ahead
         // byte offsets of the lane's four key rows / of its bias quad inside a row, for the chunk the requests currently go to: computed once
         // per chunk, so a request is one instruction (SGPR row base + VGPR offset) and no address arithmetic rides in the hot loop
         unsigned koff_[4], boff_;
 #define P2_KOFF(CH)                                                                                                      \
     {                                                                                                                    \
-        const int ch_ = (C32_ABL & 32) ? 0 : min((CH), nchunk - 1);             /* past the end: harmless re-read */      \
-        _Pragma("unroll") for (int r_ = 0; r_ < 4; ++r_) koff_[r_] = ZT ? ((unsigned)ch_ * (unsigned)(ZT_CHUNK_MAJOR == 2 ? rows_tot_ * (JC * C * 4) : (ZT_CHUNK_MAJOR ? L * (JC * C * 4) : (JC * C * 4))) + (unsigned)(r_ * 1024 + lane * 16)) : (unsigned)min(ch_ * JC + kq * 4 + r_, L - 1) * (unsigned)(C * 4) + lane_b; \
+        const int ch_ = min((CH), nchunk - 1);                                  /* past the end: harmless re-read */      \
+        _Pragma("unroll") for (int r_ = 0; r_ < 4; ++r_) koff_[r_] = ZT ? ((unsigned)ch_ * (unsigned)(rows_tot_ * (JC * C * 4)) + (unsigned)(r_ * 1024 + lane * 16)) : (unsigned)min(ch_ * JC + kq * 4 + r_, L - 1) * (unsigned)(C * 4) + lane_b; \
     }
-#define P2_BOFF(CH) boff_ = (unsigned)((C32_ABL & 32) ? 0 : min((CH), nchunk - 1)) * (PBC_CHUNK_MAJOR ? (unsigned)rows_tot_ * (unsigned)(H * JC * 4) : (unsigned)(H * JC * 4)) + pb_lane;
-#ifdef C32_OLDLOAD
-        const char* zslab = reinterpret_cast<const char*>(z + zbase * (int64_t)L * C);
-        const char* bslab = reinterpret_cast<const char*>(pbc + (PBC_CHUNK_MAJOR ? 0 : zbase * (int64_t)nchunk * (H * JC)));
+#define P2_BOFF(CH) boff_ = (unsigned)min((CH), nchunk - 1) * ((unsigned)rows_tot_ * (unsigned)(H * JC * 4)) + pb_lane;
 #define P2_ISSUE_Z(SLOT, II)                                                                                            \
         _Pragma("unroll") for (int r_ = 0; r_ < 4; ++r_)                                                                \
-            ring[SLOT][r_] = ZLOAD(reinterpret_cast<const f32x4*>(zslab + zrow[II] + koff_[r_]));
-#define P2_ISSUE_B(SLOT, II) ringb[SLOT] = ZLOAD(reinterpret_cast<const f32x4*>(bslab + pbrow[II] + boff_));
-#else
-#define P2_ISSUE_Z(SLOT, II)                                                                                            \
-        _Pragma("unroll") for (int r_ = 0; r_ < 4; ++r_)                                                                \
-            ring[SLOT][r_] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(zrs, koff_[r_], zrow[(C32_ABL & 32) ? 0 : II], C32_ZAUX));   /* aux 2 = nt, as ZLOAD */
-#define P2_ISSUE_B(SLOT, II) ringb[SLOT] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(brs, boff_, pbrow[(C32_ABL & 32) ? 0 : II], C32_ZAUX));
-#endif
+            ring[SLOT][r_] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(zrs, koff_[r_], zrow[II], 2));   /* aux 2 = nt, as ZLOAD */
+#define P2_ISSUE_B(SLOT, II) ringb[SLOT] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(brs, boff_, pbrow[II], 2));
         P2_KOFF(0) P2_BOFF(0)
         P2_ISSUE_B(0, 0) P2_ISSUE_Z(0, 0) P2_ISSUE_B(1, 1) P2_ISSUE_Z(1, 1) P2_ISSUE_B(2, 2)
-        if (C32_RING == 4) P2_ISSUE_Z(2, 2)
         fill_mask();
         f32x4 accP[RPW2][4];
         float* mlw = mlr + (il0 * 16 + fm) * 2;                             // this wave's rows; all four key groups of a lane column keep the same value
@@ -1210,7 +1054,7 @@ __global__ __launch_bounds__(NTH2) void ipa_core32_kernel(const float* __restric
         const int spo = sp_off(fm, kq);
         __syncthreads();                                                    // key mask visible
         __syncthreads();                                                    // barrier #0: S(0) ready
-        // Position (chunk CH, row II) is number 8 CH + II; its z sits in ring slot (8 CH + II) % C32_RING, its bias in slot II % 4.
+        // Position (chunk CH, row II) is number 8 CH + II; its z sits in ring slot (8 CH + II) % 3, its bias in slot II % 4.
         // With two waves on a SIMD nobody else fills the ~40 dependent VALU / LDS steps of a row's softmax, so a row's softmax runs
         // in the shadow of the PREVIOUS row's 16 MFMAs (software pipeline inside a chunk; a chunk's first row waits for its barrier).
         // softmax of row II of the chunk in sp[BUF] -> pvn_, scn_ (P, the rescale factor and the running maximum / sum go to LDS)
@@ -1234,8 +1078,7 @@ __global__ __launch_bounds__(NTH2) void ipa_core32_kernel(const float* __restric
     }
         // one MFMA of row II (k-step K_ >> 2, channel tile K_ & 3) and a fence: the source order below IS the issue order
 #define P2_MF(SLOT, II, K_)                                                                                              \
-        if (C32_ABL & 4096) accP[II][(K_) & 3][(K_) >> 2] += ring[SLOT][(K_) >> 2][(K_) & 3] * pvc_[(K_) >> 2]; else     /* (ablation 4096: one VALU fma per operand instead of the MFMA: the loads stay alive) */ \
-        if (!(C32_ABL & 128)) accP[II][(K_) & 3] = mfma4(ring[SLOT][(K_) >> 2][(K_) & 3], pvc_[(K_) >> 2], accP[II][(K_) & 3]);                \
+        accP[II][(K_) & 3] = mfma4(ring[SLOT][(K_) >> 2][(K_) & 3], pvc_[(K_) >> 2], accP[II][(K_) & 3]);                \
         __builtin_amdgcn_sched_barrier(0);
         // rows 0..6 of a chunk: the 16 MFMAs of row II, each followed by a piece of row II + 1's softmax and accumulator rescale
         // (an MFMA holds the pipe for 32 cycles; 3..8 dependent VALU steps ride in its shadow)
@@ -1243,20 +1086,15 @@ __global__ __launch_bounds__(NTH2) void ipa_core32_kernel(const float* __restric
     {                                                                                                                    \
         const f32x4 pvc_ = pvn_;                                                                                         \
         if ((II) + 3 == 8) P2_BOFF((CH) + 1)                                /* the requests move on to the next chunk */ \
-        if ((II) + C32_RING - 1 == 8) P2_KOFF((CH) + 1)                                                                  \
-        if (!(C32_ABL & 1)) {                                                                                            \
-            P2_ISSUE_B(((II) + 3) & 3, ((II) + 3) & 7)                                                                   \
-            P2_ISSUE_Z(((SLOT) + C32_RING - 1) % C32_RING, ((II) + C32_RING - 1) & 7)                                    \
-        }                                                                                                                \
+        if ((II) + 2 == 8) P2_KOFF((CH) + 1)                                                                             \
+        P2_ISSUE_B(((II) + 3) & 3, ((II) + 3) & 7)                                                                       \
+        P2_ISSUE_Z(((SLOT) + 2) % 3, ((II) + 2) & 7)                                                                     \
         const int il_ = il0 + (II) + 1;                                                                                  \
         float* spp_ = sp + ((BUF) * BI2 + il_) * SROW + spo;                                                             \
         f32x4 sv_ = *reinterpret_cast<const f32x4*>(spp_);                                                               \
         const float2 ml_ = *reinterpret_cast<const float2*>(mlw + ((II) + 1) * 32);                                      \
         __builtin_amdgcn_sched_barrier(0);                                                                               \
         P2_MF(SLOT, II, 0) P2_MF(SLOT, II, 1)                                                                            \
-        if (C32_ABL & 64) { pvn_ = sv_; scn_ = 1.f; *reinterpret_cast<f32x4*>(spp_) = pvn_;                              \
-            P2_MF(SLOT, II, 2) P2_MF(SLOT, II, 3) P2_MF(SLOT, II, 4) P2_MF(SLOT, II, 5) P2_MF(SLOT, II, 6) P2_MF(SLOT, II, 7) P2_MF(SLOT, II, 8) P2_MF(SLOT, II, 9) \
-            P2_MF(SLOT, II, 10) P2_MF(SLOT, II, 11) P2_MF(SLOT, II, 12) P2_MF(SLOT, II, 13) P2_MF(SLOT, II, 14) P2_MF(SLOT, II, 15) } else {   \
         sv_ += ringb[((II) + 1) & 3];                                                                                    \
         P2_MF(SLOT, II, 2)                                                                                               \
         float l2_[4];                                                                                                    \
@@ -1271,9 +1109,9 @@ __global__ __launch_bounds__(NTH2) void ipa_core32_kernel(const float* __restric
         const float mn_ = fmaxf(ml_.x, mx_);                                                                             \
         scn_ = __builtin_amdgcn_exp2f(ml_.x - mn_);                                                                      \
         P2_MF(SLOT, II, 5)                                                                                               \
-        pvn_[0] = C32_EXP2(l2_[0] - mn_); pvn_[1] = C32_EXP2(l2_[1] - mn_);                                              \
+        pvn_[0] = __builtin_amdgcn_exp2f(l2_[0] - mn_); pvn_[1] = __builtin_amdgcn_exp2f(l2_[1] - mn_); \
         P2_MF(SLOT, II, 6)                                                                                               \
-        pvn_[2] = C32_EXP2(l2_[2] - mn_); pvn_[3] = C32_EXP2(l2_[3] - mn_);                                              \
+        pvn_[2] = __builtin_amdgcn_exp2f(l2_[2] - mn_); pvn_[3] = __builtin_amdgcn_exp2f(l2_[3] - mn_); \
         float ps_ = (pvn_[0] + pvn_[1]) + (pvn_[2] + pvn_[3]);                                                           \
         P2_MF(SLOT, II, 7)                                                                                               \
         { auto a_ = __builtin_amdgcn_permlane16_swap(__float_as_uint(ps_), __float_as_uint(ps_), false, false);          \
@@ -1287,35 +1125,26 @@ __global__ __launch_bounds__(NTH2) void ipa_core32_kernel(const float* __restric
         P2_MF(SLOT, II, 10)                                                                                              \
         if (kq == 0) { scl[((CHPAR) * BI2 + il_) * SCLD + fm] = scn_; *reinterpret_cast<float2*>(mlw + ((II) + 1) * 32) = make_float2(mn_, ln_); } \
         __builtin_amdgcn_sched_barrier(0);                                                                               \
-        /* C32_LAZY & 1: no running maximum of this row moved in this chunk (every factor exactly 1) -> the 16 multiplications change */ \
-        /* nothing and are skipped (wave-uniform); they then run as one group behind the row's last MFMAs instead of between them     */ \
-        if (C32_LAZY & 1) {                                                                                              \
-        P2_MF(SLOT, II, 11) P2_MF(SLOT, II, 12) P2_MF(SLOT, II, 13) P2_MF(SLOT, II, 14) P2_MF(SLOT, II, 15)              \
-        if ((__builtin_amdgcn_ballot_w64(scn_ != 1.f) & 0x0fff0fff0fff0fffull) != 0ull) {                                \
-            accP[(II) + 1][0] *= scn_; accP[(II) + 1][1] *= scn_; accP[(II) + 1][2] *= scn_; accP[(II) + 1][3] *= scn_; } \
-        } else {                                                                                                         \
         P2_MF(SLOT, II, 11)                                                                                              \
-        if (!(C32_ABL & 1024)) accP[(II) + 1][0] *= scn_;                                                                \
+        accP[(II) + 1][0] *= scn_;                                                                                       \
         P2_MF(SLOT, II, 12)                                                                                              \
-        if (!(C32_ABL & 1024)) accP[(II) + 1][1] *= scn_;                                                                \
+        accP[(II) + 1][1] *= scn_;                                                                                       \
         P2_MF(SLOT, II, 13)                                                                                              \
-        if (!(C32_ABL & 1024)) accP[(II) + 1][2] *= scn_;                                                                \
+        accP[(II) + 1][2] *= scn_;                                                                                       \
         P2_MF(SLOT, II, 14)                                                                                              \
-        if (!(C32_ABL & 1024)) accP[(II) + 1][3] *= scn_;                                                                \
-        P2_MF(SLOT, II, 15) } }                                                                                          \
+        accP[(II) + 1][3] *= scn_;                                                                                       \
+        P2_MF(SLOT, II, 15)                                                                                              \
     }
         // the last row of a chunk: nothing to overlap with (the next chunk's logits are behind the barrier)
 #define P2_POS_LAST(SLOT, II, CH)                                                                                        \
     {                                                                                                                    \
         const f32x4 pvc_ = pvn_;                                                                                         \
         if ((II) + 3 == 8) P2_BOFF((CH) + 1)                                /* the requests move on to the next chunk */ \
-        if ((II) + C32_RING - 1 == 8) P2_KOFF((CH) + 1)                                                                  \
-        if (!(C32_ABL & 1)) {                                                                                            \
-            P2_ISSUE_B(((II) + 3) & 3, ((II) + 3) & 7)                                                                   \
-            P2_ISSUE_Z(((SLOT) + C32_RING - 1) % C32_RING, ((II) + C32_RING - 1) & 7)                                    \
-        }                                                                                                                \
+        if ((II) + 2 == 8) P2_KOFF((CH) + 1)                                                                             \
+        P2_ISSUE_B(((II) + 3) & 3, ((II) + 3) & 7)                                                                       \
+        P2_ISSUE_Z(((SLOT) + 2) % 3, ((II) + 2) & 7)                                                                     \
         _Pragma("unroll") for (int r_ = 0; r_ < 4; ++r_)                                                                 \
-            _Pragma("unroll") for (int mt_ = 0; mt_ < 4; ++mt_) { if (C32_ABL & 4096) accP[II][mt_][r_] += ring[SLOT][r_][mt_] * pvc_[r_]; else accP[II][mt_] = mfma4(ring[SLOT][r_][mt_], pvc_[r_], accP[II][mt_]); } \
+            _Pragma("unroll") for (int mt_ = 0; mt_ < 4; ++mt_) accP[II][mt_] = mfma4(ring[SLOT][r_][mt_], pvc_[r_], accP[II][mt_]); \
         __builtin_amdgcn_sched_barrier(0);                                                                               \
     }
         // ---- ZT (round 6): z arrives as K-packed two-term fp16 (pair_terms_kernel): the ring slot r of a row IS the A operand of channel tile r -- 8 halves {z_h(keys 4 kq .. + 3), z_l(same keys)} of
@@ -1355,11 +1184,9 @@ __global__ __launch_bounds__(NTH2) void ipa_core32_kernel(const float* __restric
     {                                                                                                                    \
         const u32x4 bh_ = (u32x4){pkn_[0], pkn_[1], pkn_[0], pkn_[1]}; const u32x2 bl_ = (u32x2){pkn_[2], pkn_[3]};          \
         if ((II) + 3 == 8) P2_BOFF((CH) + 1)                                /* the requests move on to the next chunk */ \
-        if ((II) + C32_RING - 1 == 8) P2_KOFF((CH) + 1)                                                                  \
-        if (!(C32_ABL & 1)) {                                                                                            \
-            P2_ISSUE_B(((II) + 3) & 3, ((II) + 3) & 7)                                                                   \
-            P2_ISSUE_Z(((SLOT) + C32_RING - 1) % C32_RING, ((II) + C32_RING - 1) & 7)                                    \
-        }                                                                                                                \
+        if ((II) + 2 == 8) P2_KOFF((CH) + 1)                                                                             \
+        P2_ISSUE_B(((II) + 3) & 3, ((II) + 3) & 7)                                                                       \
+        P2_ISSUE_Z(((SLOT) + 2) % 3, ((II) + 2) & 7)                                                                     \
         const int il_ = il0 + (II) + 1;                                                                                  \
         float* spp_ = sp + ((BUF) * BI2 + il_) * SROW + spo;                                                             \
         f32x4 sv_ = *reinterpret_cast<const f32x4*>(spp_);                                                               \
@@ -1380,8 +1207,8 @@ __global__ __launch_bounds__(NTH2) void ipa_core32_kernel(const float* __restric
         scn_ = __builtin_amdgcn_exp2f(ml_.x - mn_);                                                                      \
         P2H_MF(SLOT, II, 4)                                                                                               \
         f32x4 pvn_;                                                                                                      \
-        pvn_[0] = C32_EXP2(l2_[0] - mn_); pvn_[1] = C32_EXP2(l2_[1] - mn_);                                              \
-        pvn_[2] = C32_EXP2(l2_[2] - mn_); pvn_[3] = C32_EXP2(l2_[3] - mn_);                                              \
+        pvn_[0] = __builtin_amdgcn_exp2f(l2_[0] - mn_); pvn_[1] = __builtin_amdgcn_exp2f(l2_[1] - mn_); \
+        pvn_[2] = __builtin_amdgcn_exp2f(l2_[2] - mn_); pvn_[3] = __builtin_amdgcn_exp2f(l2_[3] - mn_); \
         P2H_MF(SLOT, II, 5)                                                                                               \
         float ps_ = (pvn_[0] + pvn_[1]) + (pvn_[2] + pvn_[3]);                                                           \
         { auto a_ = __builtin_amdgcn_permlane16_swap(__float_as_uint(ps_), __float_as_uint(ps_), false, false);          \
@@ -1402,14 +1229,12 @@ __global__ __launch_bounds__(NTH2) void ipa_core32_kernel(const float* __restric
     {                                                                                                                    \
         const u32x4 bh_ = (u32x4){pkn_[0], pkn_[1], pkn_[0], pkn_[1]}; const u32x2 bl_ = (u32x2){pkn_[2], pkn_[3]};          \
         if ((II) + 3 == 8) P2_BOFF((CH) + 1)                                                                             \
-        if ((II) + C32_RING - 1 == 8) P2_KOFF((CH) + 1)                                                                  \
-        if (!(C32_ABL & 1)) {                                                                                            \
-            P2_ISSUE_B(((II) + 3) & 3, ((II) + 3) & 7)                                                                   \
-            P2_ISSUE_Z(((SLOT) + C32_RING - 1) % C32_RING, ((II) + C32_RING - 1) & 7)                                    \
-        }                                                                                                                \
+        if ((II) + 2 == 8) P2_KOFF((CH) + 1)                                                                             \
+        P2_ISSUE_B(((II) + 3) & 3, ((II) + 3) & 7)                                                                       \
+        P2_ISSUE_Z(((SLOT) + 2) % 3, ((II) + 2) & 7)                                                                     \
         P2H_MF(SLOT, II, 0) P2H_MF(SLOT, II, 1) P2H_MF(SLOT, II, 2) P2H_MF(SLOT, II, 3) P2H_MF(SLOT, II, 4) P2H_MF(SLOT, II, 5) P2H_MF(SLOT, II, 6) P2H_MF(SLOT, II, 7) \
     }
-#define P2_SLOT(K, II) ((8 * (K) + (II)) % C32_RING)
+#define P2_SLOT(K, II) ((8 * (K) + (II)) % 3)
 #define P2_CHUNK(K, CH)                                                                                                  \
     {                                                                                                                    \
         const uint32_t mk4_ = *reinterpret_cast<const uint32_t*>(&mk[(CH) * JC + kq * 4]);                               \
@@ -1418,11 +1243,11 @@ __global__ __launch_bounds__(NTH2) void ipa_core32_kernel(const float* __restric
         const int CHPAR = (CH) & 1;                                                                                      \
         f32x4 pvn_; float scn_;                                                                                                  \
         P2_SM(0, K)                                                                                                      \
-        if (!(C32_ABL & 1024) && !((C32_LAZY & 1) && (__builtin_amdgcn_ballot_w64(scn_ != 1.f) & 0x0fff0fff0fff0fffull) == 0ull)) { _Pragma("unroll") for (int mt_ = 0; mt_ < 4; ++mt_) accP[0][mt_] *= scn_; } \
+        _Pragma("unroll") for (int mt_ = 0; mt_ < 4; ++mt_) accP[0][mt_] *= scn_;                                         \
         __builtin_amdgcn_sched_barrier(0);                                                                               \
         P2_POS(P2_SLOT(K, 0), 0, CH, K) P2_POS(P2_SLOT(K, 1), 1, CH, K) P2_POS(P2_SLOT(K, 2), 2, CH, K) P2_POS(P2_SLOT(K, 3), 3, CH, K) \
         P2_POS(P2_SLOT(K, 4), 4, CH, K) P2_POS(P2_SLOT(K, 5), 5, CH, K) P2_POS(P2_SLOT(K, 6), 6, CH, K) P2_POS_LAST(P2_SLOT(K, 7), 7, CH) \
-        C32_SYNC()                                                          /* barrier #(CH + 1) */                      \
+        __syncthreads();                                                    /* barrier #(CH + 1) */                      \
     }
 #define P2H_CHUNK(K, CH)                                                                                                  \
     {                                                                                                                    \
@@ -1432,11 +1257,11 @@ __global__ __launch_bounds__(NTH2) void ipa_core32_kernel(const float* __restric
         const int CHPAR = (CH) & 1;                                                                                      \
         u32x4 pkn_; float scn_;                                                                                                  \
         P2H_SM(0, K)                                                                                                      \
-        if (!(C32_ABL & 1024) && !((C32_LAZY & 1) && (__builtin_amdgcn_ballot_w64(scn_ != 1.f) & 0x0fff0fff0fff0fffull) == 0ull)) { _Pragma("unroll") for (int mt_ = 0; mt_ < 4; ++mt_) accP[0][mt_] *= scn_; } \
+        _Pragma("unroll") for (int mt_ = 0; mt_ < 4; ++mt_) accP[0][mt_] *= scn_;                                         \
         __builtin_amdgcn_sched_barrier(0);                                                                               \
         P2H_POS(P2_SLOT(K, 0), 0, CH, K) P2H_POS(P2_SLOT(K, 1), 1, CH, K) P2H_POS(P2_SLOT(K, 2), 2, CH, K) P2H_POS(P2_SLOT(K, 3), 3, CH, K) \
         P2H_POS(P2_SLOT(K, 4), 4, CH, K) P2H_POS(P2_SLOT(K, 5), 5, CH, K) P2H_POS(P2_SLOT(K, 6), 6, CH, K) P2H_POS_LAST(P2_SLOT(K, 7), 7, CH) \
-        C32_SYNC()                                                          /* barrier #(CH + 1) */                      \
+        __syncthreads();                                                    /* barrier #(CH + 1) */                      \
     }
         int ch = 0;
         if constexpr (ZT) {
@@ -1489,7 +1314,6 @@ __global__ __launch_bounds__(NTH2) void ipa_core32_kernel(const float* __restric
                 }
             }
         }
-        C32_REPORT(0)
         __syncthreads();                                                    // F1: lsum visible, C waves done with the last chunk
         __syncthreads();                                                    // F2: aggregated points in LDS
         } else {
@@ -1500,8 +1324,6 @@ __global__ __launch_bounds__(NTH2) void ipa_core32_kernel(const float* __restric
 #pragma unroll
         for (int ii = 0; ii < RPW2; ++ii)
             if (kq == 0) lsum[(il0 + ii) * SCLD + fm] = mlw[ii * 32 + 1];
-        C32_REPORT(0)
-        C32F_STAMP(0)
         __syncthreads();                                                    // F1: lsum visible, every wave is done with the S/P tile (mlr and the key mask are not aliased)
         float rinv[RPW2];
 #pragma unroll
@@ -1520,9 +1342,7 @@ __global__ __launch_bounds__(NTH2) void ipa_core32_kernel(const float* __restric
 #pragma unroll
             for (int q = 0; q < 3; ++q) tt_[q] = t[grow * 3 + q];
         }
-        C32F_STAMP(1)
         __syncthreads();                                                    // E0
-        C32F_STAMP(2)
         // local coordinates / distance / direction of aggregated point number pt of row prow (point_local: the arithmetic of the unfused epilogues)
         auto local_of = [&](int pt, float& lx, float& ly, float& lz, float& d, float& inv) {
             const float* a = ptsf + prow * C32F_PTSLD + pt * 3;
@@ -1547,7 +1367,7 @@ __global__ __launch_bounds__(NTH2) void ipa_core32_kernel(const float* __restric
         for (int p = 0; p < OT_NCH; ++p) {
             // interval p: the consumers read buffer p & 1 (position p); this role fills buffer (p + 1) & 1 with position p + 1
             // (positions 0 and 1 -- the node features -- were written by the C waves before E0)
-            if (p >= 1 && p + 1 < OT_NCH && !(C32F_ABL & 4)) {
+            if (p >= 1 && p + 1 < OT_NCH) {
                 char* buf = stage + ((p + 1) & 1) * OT_STAGE;
                 const int c = ot_chunk_at(p + 1);
                 if (c < 4) {                                                // pair features, channels 16 kq + 4 c + 0..3 of every head (ot_feat_col)
@@ -1578,10 +1398,8 @@ __global__ __launch_bounds__(NTH2) void ipa_core32_kernel(const float* __restric
                     put_points(buf, psub * 12, 64 + psub * 4, 4, true);
                 }
             }
-            C32F_STAMP(3 + p)
             __syncthreads();                                                // E(p + 1)
         }
-        C32F_STAMP(13)
         }
     } else if (wave < NPW2 + 2) {
         // =========================================================================================== A waves: S(t + 1), 6 heads x 2 row tiles
@@ -1603,14 +1421,12 @@ __global__ __launch_bounds__(NTH2) void ipa_core32_kernel(const float* __restric
 #pragma unroll
             for (int hh = 0; hh < HPW; ++hh) {
                 const int h = h0 + hh;
-                if (!(C32_ABL & 2)) { if (hh + 1 < HPW) { if (hh & 1) A2_ISSUE(0, hh + 1, c) else A2_ISSUE(1, hh + 1, c) } else A2_ISSUE(0, 0, c + 1) }
+                if (hh + 1 < HPW) { if (hh & 1) A2_ISSUE(0, hh + 1, c) else A2_ISSUE(1, hh + 1, c) } else A2_ISSUE(0, 0, c + 1)
 #pragma unroll
                 for (int rt = 0; rt < 2; ++rt) {
                     const f32x4 q0 = qr[hh][rt][0], q1 = qr[hh][rt][1], q2 = qr[hh][rt][2], q3 = qr[hh][rt][3];
                     f32x4 acc0 = (f32x4){0.f, 0.f, 0.f, 0.f}, acc1 = acc0;
-                    if (C32_ABL & 8) { acc0 = kf[hh & 1][0] * q0 + kf[hh & 1][1] * q1; acc1 = kf[hh & 1][2] * q2 + kf[hh & 1][3] * q3; }
-                    else if (C32_ABL & 256) { acc0 = kf[hh & 1][0]; acc1 = q0; }
-                    else if constexpr (ZT) {
+                    if constexpr (ZT) {
                         // the 32 channels of q / sqrt(D) and k arrive as two fp16 terms each (node_frags, qk_terms: slot 0 = high, slot 1 = low terms): three 16-cycle
                         // products, smallest first, instead of eight 32-cycle fp32 steps; the point part + norm step (squared distances of global coordinates
                         // cancel there: 24 bits needed) stays on the fp32 chain
@@ -1643,17 +1459,15 @@ __global__ __launch_bounds__(NTH2) void ipa_core32_kernel(const float* __restric
         for (int c = 1; c < nchunk; ++c) {
             produce(c, buf);
             buf = (buf == 2) ? 0 : buf + 1;
-            C32_SYNC()                                                      // barrier #c
+            __syncthreads();                                                // barrier #c
         }
-        C32_SYNC()                                                          // barrier #nchunk
-        C32_REPORT(1)
+        __syncthreads();                                                    // barrier #nchunk
         if constexpr (!FUSE) {
         __syncthreads();                                                    // F1
         __syncthreads();                                                    // F2
         } else {
         WT raw[RD];
         consumer_prefetch(wave - NPW2, raw);                                // the first W_out fragments travel while the other roles finish
-        C32F_STAMP(0)
         __syncthreads();                                                    // F1
         tail_p2_stage_bias(reinterpret_cast<float (*)[F]>(smem_raw + C32F_BIAS_OFF), ta.b0, ta.b1, ta.b2, tid - NPW2 * 64);   // these two waves idle until E0
         consumer(wave - NPW2, raw);                                         // E0 .. E10 inside
@@ -1673,39 +1487,18 @@ __global__ __launch_bounds__(NTH2) void ipa_core32_kernel(const float* __restric
                 for (int k = 0; k < 2; ++k) { accV[hh][rt][k] = (f32x4){0.f, 0.f, 0.f, 0.f}; accT[hh][rt][k] = (f32x4){0.f, 0.f, 0.f, 0.f}; }
 #define C2_ISSUE(B, HH, CH) { const f32x4* fr_ = kvn + ((int64_t)min((CH), nchunk - 1) * H + h0 + (HH)) * 512 + 4 * 64 + lane; \
         _Pragma("unroll") for (int s_ = 0; s_ < 4; ++s_) vf[B][s_] = fr_[s_ * 64]; }
-        // C32_CPIPE (developer switch, round 5): the P rows and rescale factors of head hh + 1 are requested from LDS before the products of head hh
-        // (the chunk's tile is complete behind the barrier), so a head no longer opens with an exposed LDS round trip
         auto consume = [&](int c, int buf) {
             const int par = c & 1;
-            unsigned long long anych_ = 0ull;
-            float scn_[2]; f32x4 pan_[2];
-#define C2_LDS(HH) { _Pragma("unroll") for (int rt_ = 0; rt_ < (C32_CPIPE == 2 ? 1 : 2); ++rt_) {                       \
-                scn_[rt_] = scl[(par * BI2 + rt_ * 16 + fm) * SCLD + h0 + (HH)];                                         \
-                pan_[rt_] = *reinterpret_cast<const f32x4*>(sp + (buf * BI2 + rt_ * 16 + fm) * SROW + sp_off(h0 + (HH), kq)); } }
-            if (C32_CPIPE) C2_LDS(0)
 #pragma unroll
             for (int hh = 0; hh < HPW; ++hh) {
                 const int h = h0 + hh;
-                if (!(C32_ABL & 2)) { if (hh + 1 < HPW) { if (hh & 1) C2_ISSUE(0, hh + 1, c) else C2_ISSUE(1, hh + 1, c) } else C2_ISSUE(0, 0, c + 1) }
-                float scc_[2]; f32x4 pac_[2];
-                if (C32_CPIPE) {
-                    scc_[0] = scn_[0]; pac_[0] = pan_[0];
-                    if (C32_CPIPE == 2) { scc_[1] = scl[(par * BI2 + 16 + fm) * SCLD + h]; pac_[1] = *reinterpret_cast<const f32x4*>(sp + (buf * BI2 + 16 + fm) * SROW + sp_off(h, kq)); }
-                    else { scc_[1] = scn_[1]; pac_[1] = pan_[1]; }
-                    if (hh + 1 < HPW) C2_LDS(hh + 1)
-                    __builtin_amdgcn_sched_barrier(0);
-                }
+                if (hh + 1 < HPW) { if (hh & 1) C2_ISSUE(0, hh + 1, c) else C2_ISSUE(1, hh + 1, c) } else C2_ISSUE(0, 0, c + 1)
 #pragma unroll
                 for (int rt = 0; rt < 2; ++rt) {
-                    const float sc = C32_CPIPE ? scc_[rt] : scl[(par * BI2 + rt * 16 + fm) * SCLD + h];
-                    const f32x4 pa = C32_CPIPE ? pac_[rt] : *reinterpret_cast<const f32x4*>(sp + (buf * BI2 + rt * 16 + fm) * SROW + sp_off(h, kq));
-                    C32_CNT(2, 1) C32_CNT(3, __builtin_amdgcn_ballot_w64(sc != 1.f) == 0ull)
-                    anych_ |= __builtin_amdgcn_ballot_w64(sc != 1.f);
-                    // (all 16 rows of the tile kept their running maximum of this head: factors exactly 1, nothing to rescale)
-                    if (!(C32_ABL & 1024) && !((C32_LAZY & 2) && FUSE && __builtin_amdgcn_ballot_w64(sc != 1.f) == 0ull)) { accV[hh][rt][0] *= sc; accV[hh][rt][1] *= sc; accT[hh][rt][0] *= sc; accT[hh][rt][1] *= sc; }
-                    if (C32_ABL & 512) { accV[hh][rt][0] += pa; }
-                    else if (C32_ABL & 16) { accV[hh][rt][0] += vf[hh & 1][0] * pa; accV[hh][rt][1] += vf[hh & 1][1] * pa; accT[hh][rt][0] += vf[hh & 1][2] * pa; accT[hh][rt][1] += vf[hh & 1][3] * pa; }
-                    else
+                    const float sc = scl[(par * BI2 + rt * 16 + fm) * SCLD + h];
+                    const f32x4 pa = *reinterpret_cast<const f32x4*>(sp + (buf * BI2 + rt * 16 + fm) * SROW + sp_off(h, kq));
+                    // lazy rescale (FUSE only, see above): all 16 rows of the tile kept their running maximum of this head -- factors exactly 1, nothing to rescale
+                    if (!(FUSE && __builtin_amdgcn_ballot_w64(sc != 1.f) == 0ull)) { accV[hh][rt][0] *= sc; accV[hh][rt][1] *= sc; accT[hh][rt][0] *= sc; accT[hh][rt][1] *= sc; }
 #pragma unroll
                     for (int s = 0; s < 4; ++s) {
                         accV[hh][rt][0] = mfma4(vf[hh & 1][s][0], pa[s], accV[hh][rt][0]);
@@ -1716,25 +1509,20 @@ __global__ __launch_bounds__(NTH2) void ipa_core32_kernel(const float* __restric
                 }
                 __builtin_amdgcn_sched_barrier(0);
             }
-#undef C2_LDS
-            C32_CNT(4, 1) C32_CNT(5, anych_ == 0ull)
-            (void)anych_;
         };
         C2_ISSUE(0, 0, 0)
         fill_mask();
         __syncthreads();
         __syncthreads();                                                    // barrier #0
-        C32_SYNC()                                                          // barrier #1: P(0) ready
+        __syncthreads();                                                    // barrier #1: P(0) ready
         int buf = 0;
         for (int c = 1; c < nchunk; ++c) {
             consume(c - 1, buf);
             buf = (buf == 2) ? 0 : buf + 1;
-            C32_SYNC()                                                      // barrier #(c + 1)
+            __syncthreads();                                                // barrier #(c + 1)
         }
         consume(nchunk - 1, buf);
-        C32_REPORT(2)
         WT raw[RD];
-        C32F_STAMP(0)
         __syncthreads();                                                    // F1
         float* pts = FUSE ? ptsf : sp;                                      // [BI2][H][24] aggregated global-frame points; the S/P tile is free now
         char* nbuf = stage + (wave - NPW2 - 2) * OT_STAGE;                  // FUSE: heads 0..5 are chunk 4 = position 0, heads 6..11 chunk 5 = position 1
@@ -1748,20 +1536,16 @@ __global__ __launch_bounds__(NTH2) void ipa_core32_kernel(const float* __restric
                 const float inv = mi ? 1.f / lsum[il * SCLD + h] : 0.f;
                 if constexpr (FUSE) {
                     const f32x4 a0 = accV[hh][rt][0], a1 = accV[hh][rt][1];
-                    if (!(C32F_ABL & 8)) {
                     stage_put4(nbuf, il, hh * D + kq * 4, mul_rn(a0[0], inv), mul_rn(a0[1], inv), mul_rn(a0[2], inv), mul_rn(a0[3], inv));
                     stage_put4(nbuf, il, hh * D + 16 + kq * 4, mul_rn(a1[0], inv), mul_rn(a1[1], inv), mul_rn(a1[2], inv), mul_rn(a1[3], inv));
-                    }
                 } else if (i < L) {
                     float* fo = feat + (rowbase + i) * FEAT + H * C + h * D + kq * 4;
                     *reinterpret_cast<f32x4*>(fo) = accV[hh][rt][0] * inv;
                     *reinterpret_cast<f32x4*>(fo + 16) = accV[hh][rt][1] * inv;
                 }
                 float* po = pts + il * (FUSE ? C32F_PTSLD : H * P * 3) + h * (P * 3) + kq * 3;
-                if (!(FUSE && (C32F_ABL & 16))) {
 #pragma unroll
                 for (int r = 0; r < 3; ++r) { po[r] = accT[hh][rt][0][r] * inv; po[12 + r] = accT[hh][rt][1][r] * inv; }
-                }
             }
         }
         if constexpr (FUSE) {
@@ -1779,13 +1563,11 @@ __global__ __launch_bounds__(NTH2) void ipa_core32_kernel(const float* __restric
         const int64_t row0 = row0f, row_end = row_endf;
         pre = tail_p2_prefetch<NTH2 / 64>(ta.x, ta.ubias, mask, ta.g1, ta.be1, ta.wmf, row0, row_end, wave, lane);
         float (*bias)[F] = reinterpret_cast<float (*)[F]>(smem_raw + C32F_BIAS_OFF);
-        C32F_STAMP(14)
         __syncthreads();                                                    // U: u and the biases are in LDS
         const float (*us)[XLD] = reinterpret_cast<const float (*)[XLD]>(smem_raw + C32F_U_OFF);
         auto get_u = [&](int rl) { return *reinterpret_cast<const float2*>(&us[rl][2 * lane]); };
         tail_p2_run<NTH2 / 64, false>(pre, get_u, reinterpret_cast<float (*)[XLD]>(smem_raw + C32F_YS_OFF), bias, smem_raw + C32F_APA_OFF,
                                       smem_raw + C32F_PTS_OFF, ta.wmf, ta.g2, ta.be2, ta.out, nullptr, 0, row0, row_end, wave, lane, ta.xt);
-        C32F_STAMP(15)
     }
     if (blockIdx.x == 0 && tid == 0) { g_clock_probe[0] = clock64() - probe_c0; g_clock_probe[1] = wall_clock64() - probe_w0; }
     if (prof_slot >= 0 && tid == 0) atomicMax(&g_prof_span[prof_slot][1], (unsigned long long)wall_clock64());
@@ -1794,7 +1576,7 @@ __global__ __launch_bounds__(NTH2) void ipa_core32_kernel(const float* __restric
 // Pair-bias cache: lp[l][n,i,j,h] = z[n,i,j,:] . Wb_l[h,:] for every layer l in ONE pass over z (ga.py:88-90).  z and the weights do
 // not change during the 100 steps of FullDPM.sample, so the sampler builds this once per call and the per-step kernel reads 48
 // bytes per (i,j) instead of spending 64 more MFMAs per (row, chunk) and an LDS transpose on it.
-// Layout per layer: [N*L (query row)][nchunk][12 (head)][16 (key in chunk)] -- the float4 (head, 4 keys) an A wave adds to its
+// Layout per layer: [nchunk][N*L (query row)][12 (head)][16 (key in chunk)] (chunk-major, see the top of this file) -- the float4 (head, 4 keys) an A wave adds to its
 // S tile.  Same MFMA chain order as the in-kernel path => bit-identical logits.
 struct WbList { const float* w[8]; };
 
@@ -1830,7 +1612,7 @@ __global__ __launch_bounds__(256) void pair_bias_cache_kernel(const float* __res
         f32x4 za[4];
 #pragma unroll
         for (int q = 0; q < 4; ++q) za[q] = *reinterpret_cast<const f32x4*>(&zst[wave][fm][kq * 16 + q * 4]);
-        const int64_t u = PBC_CHUNK_MAJOR ? (int64_t)ch * rows + row : row * nchunk + ch;
+        const int64_t u = (int64_t)ch * rows + row;
         auto layer = [&](int l, const f32x4 (&w4)[4]) {
             f32x4 acc4[4];
 #pragma unroll
@@ -1874,7 +1656,7 @@ int launch_pair_bias_cache(const float* z, const float* const* wb, int num_layer
 // its (row, channel) column keeps a NORMAL low term, i.e. 22 significant bits, whatever the magnitudes of other channels or rows; pass B writes, per chunk of
 // 16 keys and channel tile mt, lane (fm, kq)'s 16 bytes
 //     {h(k0), h(k1) | h(k2), h(k3) | l(k0), l(k1) | l(k2), l(k3)},  k_e = key 16 ch + 4 kq + e, of channel c = 4 fm + mt;  h = fp16(S z), l = fp16(S z - h)
-// at float offset ((ch ROWS + row) 4 + mt) 256 + 4 lane with ROWS = N L rows of the whole batch (chunk-major: ZT_CHUNK_MAJOR; keys past L: zeros), and the 64 factors 2^-14 / S_ic of every row (the consumer multiplies its probabilities by 2^14) behind the terms.  Same bytes as z (+ 1.6 %).
+// at float offset ((ch ROWS + row) 4 + mt) 256 + 4 lane with ROWS = N L rows of the whole batch (chunk-major; keys past L: zeros), and the 64 factors 2^-14 / S_ic of every row (the consumer multiplies its probabilities by 2^14) behind the terms.  Same bytes as z (+ 1.6 %).
 size_t pair_terms_floats(int Nz, int L) { return (size_t)Nz * L * ((L + JC - 1) / JC) * (JC * C); }
 size_t pair_terms_blob_floats(int Nz, int L) { return pair_terms_floats(Nz, L) + (size_t)Nz * L * C; }
 
@@ -1912,8 +1694,7 @@ __global__ __launch_bounds__(256) void pair_terms_kernel(const float* __restrict
         S[e] = __uint_as_float((unsigned)(267 - ex) << 23);
         if (wave == 0 && kq == 0) zsc[row * C + fm * 4 + e] = __uint_as_float((unsigned)(ex - 27) << 23);     // 2^-14 / S: the consumer's probabilities carry 2^14
     }
-    const int64_t smp = row / L, ri = row % L;                               // (ZT_CHUNK_MAJOR: [sample][chunk][row of the sample], 256 vectors per (row, chunk))
-    u32x4* out = reinterpret_cast<u32x4*>(terms) + (ZT_CHUNK_MAJOR == 2 ? row * 256 : (ZT_CHUNK_MAJOR ? smp * (int64_t)L * nchunk * 256 + ri * 256 : row * (int64_t)nchunk * 256)) + lane;
+    u32x4* out = reinterpret_cast<u32x4*>(terms) + row * 256 + lane;
     for (int ch = wave; ch < nchunk; ch += 4) {
         f32x4 zn[4];
         load(ch, zn);
@@ -1922,7 +1703,7 @@ __global__ __launch_bounds__(256) void pair_terms_kernel(const float* __restrict
             unsigned h01, l01, h23, l23;
             split_pair2(zn[0][mt] * S[mt], zn[1][mt] * S[mt], h01, l01);
             split_pair2(zn[2][mt] * S[mt], zn[3][mt] * S[mt], h23, l23);
-            out[(ZT_CHUNK_MAJOR == 2 ? (int64_t)ch * gridDim.x * 256 : (ZT_CHUNK_MAJOR ? (int64_t)ch * L * 256 : (int64_t)ch * 256)) + mt * 64] = (u32x4){h01, h23, l01, l23};
+            out[(int64_t)ch * gridDim.x * 256 + mt * 64] = (u32x4){h01, h23, l01, l23};
         }
     }
 }
@@ -1997,18 +1778,6 @@ static int launch_core_variant(const float* qfrag, const float* kvfrag, const fl
                        N, L, nib, (N % 8 == 0) ? 1 : 0, z_shared);
     prof::end(st);
     ABOPT_LAUNCH_CHECK();
-#ifdef CORE_TIMING
-    {
-        long long h[3][8];
-        (void)hipDeviceSynchronize();
-        (void)hipMemcpyFromSymbol(h, HIP_SYMBOL(g_core_timing), sizeof(h));
-        static int calls = 0;
-        if (++calls == 8)
-            for (int r = 0; r < 3; ++r)
-                fprintf(stderr, "[core timing, cycles of WG 17] %s: prologue %lld | work %lld | barrier wait %lld | own epilogue %lld | F1/F2 wait %lld | common epilogue %lld\n",
-                        r == 0 ? "pair" : (r == 1 ? "A   " : "C   "), h[r][0], h[r][1], h[r][2], h[r][3], h[r][4], h[r][5]);
-    }
-#endif
     return ABOPT_OK;
 }
 
@@ -2047,7 +1816,7 @@ static bool use_core32(int N, int L, int cus, int z_shared) {
 bool ipa_core32_applies(int N, int L, int z_shared) {
     int cus = 0;
     if (device_cu_count(&cus)) return false;
-    return !CORE_ABL && use_core32(N, L, cus, z_shared);
+    return use_core32(N, L, cus, z_shared);
 }
 
 // The whole block behind the projections in ONE launch (ipa_core32_kernel<true, ZT>: core + tail) where the 32-row kernel is the core of
@@ -2059,7 +1828,7 @@ int launch_ipa_block_fused(const float* qfrag, const float* kvfrag, const float*
                            const float* be2, float* out, int* fused, const float* pair_terms, float* xt_out) {
     *fused = 0;
     const char* e = getenv("ABOPT_FUSE_TAIL");
-    if (!pair_bias_cache || !wot || !wmf || (e && e[0] == '0') || CORE_ABL || C32_ABL) return ABOPT_OK;
+    if (!pair_bias_cache || !wot || !wmf || (e && e[0] == '0')) return ABOPT_OK;
     int cus = 0;
     if (int rc = device_cu_count(&cus)) return rc;
     if (!use_core32(N, L, cus, z_shared)) return ABOPT_OK;
@@ -2080,20 +1849,6 @@ int launch_ipa_block_fused(const float* qfrag, const float* kvfrag, const float*
     }
     prof::end(st);
     ABOPT_LAUNCH_CHECK();
-#ifdef C32F_TIMING
-    {
-        long long h[8][16];
-        (void)hipDeviceSynchronize();
-        (void)hipMemcpyFromSymbol(h, HIP_SYMBOL(g_c32f_timing), sizeof(h));
-        static int calls = 0;
-        if (++calls == 8)
-            for (int w = 0; w < 8; ++w) {
-                fprintf(stderr, "[c32f timing WG 17 wave %d] cycles since kernel start: at F1 %lld | at E0 %lld, past %lld | arrival at E1..E10:", w, h[w][0], h[w][1], h[w][2]);
-                for (int k = 3; k < 13; ++k) fprintf(stderr, " %lld", h[w][k]);
-                fprintf(stderr, " | past E10 %lld | at U %lld | end %lld\n", h[w][13], h[w][14], h[w][15]);
-            }
-    }
-#endif
     *fused = 1;
     return ABOPT_OK;
 }
@@ -2127,8 +1882,8 @@ int launch_ipa_core_kernel(const float* qfrag, const float* kvfrag, const float*
     ABOPT_CHECK_ARG(!dump == !dump_stats, "ipa_core: the logits dump and its row statistics come together");
     ABOPT_CHECK_ARG(!dump || (int64_t)H * L * L * 4 < (1ll << 31), "ipa_core: L=%d too long for the logits dump", L);
     int cus32 = 0;
-    if (pair_bias_cache && !dump && !CORE_ABL) { if (int rc = device_cu_count(&cus32)) return rc; }
-    if (pair_bias_cache && !dump && !CORE_ABL && use_core32(N, L, cus32, z_shared)) {
+    if (pair_bias_cache && !dump) { if (int rc = device_cu_count(&cus32)) return rc; }
+    if (pair_bias_cache && !dump && use_core32(N, L, cus32, z_shared)) {
         const int nib2 = (L + BI2 - 1) / BI2, nchunk = (L + JC - 1) / JC;
         const size_t lds = sizeof(float) * (3 * BI2 * SROW + 2 * BI2 * SCLD + BI2 * SCLD + BI2 * 32) + (size_t)nchunk * JC;
         ABOPT_CHECK_ARG(lds <= 160 * 1024, "ipa_core: L=%d needs %zu bytes of LDS for the key mask (max 163840)", L, lds);
@@ -2146,31 +1901,6 @@ int launch_ipa_core_kernel(const float* qfrag, const float* kvfrag, const float*
         }
         prof::end(st);
         ABOPT_LAUNCH_CHECK();
-#ifdef C32_COUNT
-        {
-            static int calls = 0;
-            if (++calls % 60 == 0) {
-                unsigned long long h[8];
-                (void)hipDeviceSynchronize();
-                (void)hipMemcpyFromSymbol(h, HIP_SYMBOL(g_c32_count), sizeof(h));
-                fprintf(stderr, "[c32 count after %d launches] pair row-chunks %llu, unchanged %llu (%.1f %%) | C (head, tile, chunk) %llu, unchanged %llu (%.1f %%) | C chunks %llu, unchanged %llu (%.1f %%)\n",
-                        calls, h[0], h[1], 100.0 * h[1] / (h[0] + 1), h[2], h[3], 100.0 * h[3] / (h[2] + 1), h[4], h[5], 100.0 * h[5] / (h[4] + 1));
-            }
-        }
-#endif
-#ifdef C32_TIMING
-        {
-            long long h[3][8];
-            (void)hipDeviceSynchronize();
-            (void)hipMemcpyFromSymbol(h, HIP_SYMBOL(g_core_timing), sizeof(h));
-            static int calls = 0;
-            if (++calls == 8)
-                for (int r = 0; r < 3; ++r)
-                    fprintf(stderr, "[core32 timing, WG 17] %s: %lld cycles to the end of its chunk loop, %lld of them at barriers; %lld wall ticks of 10 ns -> %.2f GHz\n",
-                            r == 0 ? "pair" : (r == 1 ? "A   " : "C   "), h[r][0], h[r][1], h[r][2], h[r][0] / (10.0 * h[r][2]));
-            if (calls == 8) fprintf(stderr, "[core32 timing] SIMD of waves 0..7 (summed over launches, byte per wave): %llx %llx\n", (unsigned long long)h[0][4], (unsigned long long)h[0][5]);
-        }
-#endif
         return ABOPT_OK;
     }
     if (pair_bias_cache && !dump) {
@@ -2179,8 +1909,7 @@ int launch_ipa_core_kernel(const float* qfrag, const float* kvfrag, const float*
         if (int rc = device_cu_count(&cus)) return rc;
         cus &= ~7;                                                          // a multiple of 8 keeps blockIdx & 7 = XCD for every block of a workgroup
         const int total = N * nib;
-#ifndef CORE_NO_PERSIST      // developer A/B switch
-        if (nchunk >= 2 && cus >= 8 && total > cus && !CORE_ABL) {
+        if (nchunk >= 2 && cus >= 8 && total > cus) {
             const size_t lds = sizeof(float) * (3 * BI * SROW + H * 4 * 64 * 4 + 2 * BI * SCLD + BI * SCLD + BI * H * P * 3) + 2 * (size_t)nchunk * JC;
             ABOPT_CHECK_ARG(lds <= 160 * 1024, "ipa_core: L=%d needs %zu bytes of LDS for the key masks (max 163840)", L, lds);
             static LdsConfig lds_cfg;
@@ -2190,22 +1919,10 @@ int launch_ipa_core_kernel(const float* qfrag, const float* kvfrag, const float*
                                (N % 8 == 0) ? 1 : 0, z_shared);
             prof::end(st);
             ABOPT_LAUNCH_CHECK();
-#ifdef PERSIST_TIMING
-            {
-                long long h[3][8];
-                (void)hipDeviceSynchronize();
-                (void)hipMemcpyFromSymbol(h, HIP_SYMBOL(g_core_timing), sizeof(h));
-                static int calls = 0;
-                if (++calls == 8)
-                    for (int r = 0; r < 3; ++r)
-                        fprintf(stderr, "[persist timing, cycles of WG 17] %s: total %lld | barrier wait %lld | waiting for its fragment loads %lld | (C) LDS reads %lld, scale + MFMA issue %lld | barrier wait by interval class (first / middle / last chunk of a block) %lld / %lld / %lld\n", r == 0 ? "pair" : (r == 1 ? "A   " : "C   "), h[r][0], h[r][1], h[r][2], h[r][3], h[r][4], h[r][5], h[r][6], h[r][7]);
-            }
-#endif
             return ABOPT_OK;
         }
-#endif
     }
-    if (pair_bias_cache && !dump && split_ws && !CORE_ABL && !getenv("ABOPT_CORE_NO_SPLIT")) {
+    if (pair_bias_cache && !dump && split_ws && !getenv("ABOPT_CORE_NO_SPLIT")) {
         // small batches: split the keys of every query block over 2 or 4 workgroups (see the SPLIT note at ipa_core_kernel)
         const int nib = (L + BI - 1) / BI, nchunk = (L + JC - 1) / JC, total = N * nib;
         int cus = 0;

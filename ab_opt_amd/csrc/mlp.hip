@@ -206,19 +206,10 @@ int launch_fused_ln_mlp(const float* x, const float* u, int nslab, int64_t slab_
 //  matrix-pipe bound (22k cycles); with it, it is bound by L2 -> CU bandwidth: every CU has to pull all of W_out (1.4 MB as bf16
 //  terms) for its 32 rows and sustains ~35 B/clk while all 256 CUs do the same.  Streaming fp32 weights and splitting them in
 //  registers moves 1/3 fewer bytes but pays it back in VALU work: 40k cycles, same wall time.]
-#ifndef OT_ABL     // developer ablation mask (results are wrong when non-zero): 1 no W stream, 2 no feat staging, 8 no LDS operand reads
-#define OT_ABL 0
-#endif
-#ifdef OT_TIMING   // developer build: section clocks of one workgroup, printed by the launcher
-}  // namespace abopt
-#include <cstdio>
-__device__ long long g_ot_timing[16][8];
-namespace abopt {
-#endif
 
 // DUMP (training): also writes what the backward needs, five [rows,128] slabs: pre-LayerNorm1 sum | y | h0 | h1 | pre-LayerNorm2 sum
 //
-// Schedule (round 3; -DOT_TIMING clocks: prologue 3.5k + phase 1 42k + phase 2 21k cycles before, at EVERY batch size -- the kernel was
+// Schedule (round 3; section clocks of one workgroup: prologue 3.5k + phase 1 42k + phase 2 21k cycles before, at EVERY batch size -- the kernel was
 // bound by its own issue order, not by the W_out stream):
 //  phase 1  a wave's k-steps form one software pipeline across the chunk barriers: while the six MFMAs of k-step i issue, the VALU splits
 //           the fp32 W_out fragment of k-step i + 1 into its bf16 terms (it used to do that right after every barrier, all 16 waves at
@@ -241,9 +232,6 @@ __global__ __launch_bounds__(OT_TH) void out_ln_mlp_kernel(const float* __restri
     const int64_t slab = rows * F;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int64_t row0 = (int64_t)blockIdx.x * MR;
-#ifdef OT_TIMING
-    const long long tc0 = clock64();
-#endif
     // ---------------------------------------------------------------- phase 1: u = feat . W_out^T
     // The ten 192-column chunks are taken in the order ot_chunk_at(0..9) = 4 5 0 1 2 3 6 7 8 9 (tail_common.h: the order in which the
     // fused core + tail kernel can produce them); position p lives in staging buffer p & 1.
@@ -277,9 +265,6 @@ __global__ __launch_bounds__(OT_TH) void out_ln_mlp_kernel(const float* __restri
     }
     if (chunk_ok(1)) fload(ot_chunk_at(1), fv0, fv1);
     __syncthreads();
-#ifdef OT_TIMING
-    const long long tc1 = clock64();
-#endif
     f32x16 acc0;                                                                                          // ONE chain per (column block, K group): see ot_kstep3
     acc_zero(acc0);
     const char* xrd = &sm.stage[0][0] + (lane & 31) * OT_SROW + (kg * OT_SPW) * 32 + (lane >> 5) * 16;
@@ -304,9 +289,6 @@ __global__ __launch_bounds__(OT_TH) void out_ln_mlp_kernel(const float* __restri
     };
     static_assert(OT_NCH % 2 == 0, "two positions per trip");
     for (int c = 0; c < OT_NCH; c += 2) { chunk_steps(c, 0); chunk_steps(c + 1, 1); }
-#ifdef OT_TIMING
-    const long long tc2 = clock64();
-#endif
     // ---------------------------------------------------------------- phase 2: LayerNorm1 (each wave 2 rows), MLP, LayerNorm2 (tail_common.h)
     TailP2Pre<OT_NW> pre = tail_p2_prefetch<OT_NW>(x, ubias, mask, g1, be1, wmf, row0, rows, wave, lane);
     store_partial1(sm.part[kg], acc0, cb, lane);                                                         // the staging planes are dead: the loop ended on a barrier
@@ -321,9 +303,6 @@ __global__ __launch_bounds__(OT_TH) void out_ln_mlp_kernel(const float* __restri
         return make_float2((u0.x + u1.x) + (u2.x + u3.x), (u0.y + u1.y) + (u2.y + u3.y));
     };
     tail_p2_run<OT_NW, DUMP>(pre, get_u, sm.ys, sm.bias, apA, apB, wmf, g2, be2, out, dump, slab, row0, rows, wave, lane, xt_out);
-#ifdef OT_TIMING
-    if (blockIdx.x == 17 && lane == 0) { long long* o = g_ot_timing[wave]; o[0] = tc1 - tc0; o[1] = tc2 - tc1; o[2] = clock64() - tc2; o[3] = 0; o[4] = 0; o[5] = 0; }
-#endif
 }
 
 
@@ -362,16 +341,6 @@ int launch_out_ln_mlp(const float* feat, const float* wof, const float* wmf, con
     if (rows == 0) return ABOPT_OK;
     const int rc = dump ? launch_out_ln_mlp_t<true>(feat, wof, wmf, x, ubias, mask, g1, be1, b0, b1, b2, g2, be2, out, dump, rows, st, xt_out)
                         : launch_out_ln_mlp_t<false>(feat, wof, wmf, x, ubias, mask, g1, be1, b0, b1, b2, g2, be2, out, dump, rows, st, xt_out);
-#ifdef OT_TIMING
-    {
-        long long hh[16][8];
-        (void)hipDeviceSynchronize();
-        (void)hipMemcpyFromSymbol(hh, HIP_SYMBOL(g_ot_timing), sizeof(hh));
-        static int calls = 0;
-        if (++calls == 8)
-            for (int w = 0; w < 16; w += 5) fprintf(stderr, "[ot timing WG 17 wave %d] prologue %lld | phase 1 loop %lld | phase 2 %lld (partials + LayerNorm1 %lld, layer 0 %lld, layers 1 + 2 %lld)\n", w, hh[w][0], hh[w][1], hh[w][2], hh[w][3], hh[w][4], hh[w][5]);
-    }
-#endif
     return rc;
 }
 

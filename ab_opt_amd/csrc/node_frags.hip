@@ -26,27 +26,16 @@
 #include "ipa_common.h"
 #include "kernels.h"
 
-#ifdef NF_TIMING   // developer build: clocks of one workgroup
-#include <cstdio>
-__device__ long long g_nf_timing[16][8];
-#endif
 
 namespace abopt {
 
 constexpr int NF_F = 128;                                       // node feature width (ga.py:54-66 with node_feat_dim = 128)
-#ifndef NF_SPLIT
-#define NF_SPLIT 1       // 1 (round 5): a workgroup owns HALF a head (six tiles, 48 KB of LDS), three 4-wave workgroups per CU | 0: a whole head (96 KB), one 12-wave workgroup per CU
-#endif
-#ifndef NF_WAVES_
-#define NF_WAVES_ (NF_SPLIT ? 4 : 12)
-#endif
-#ifndef NF_WGPC
-#define NF_WGPC 3        // NF_SPLIT: workgroups per CU the grid is sized for
-#endif
-constexpr int NF_TILES = 12, NF_HT = NF_TILES / 2, NF_WAVES = NF_WAVES_;       // 12 waves = 3 per SIMD (152 VGPRs): the task epilogues of one wave hide behind the MFMAs of two others (8 -> 12 waves: 35.8 -> 34.9 us at M = 8192, 205 -> 188 us at M = 48000, same box)
+// A workgroup owns HALF a head (six tiles, 48 KB of LDS), three 4-wave workgroups per CU (round 5; a whole head in 96 KB, one 12-wave workgroup
+// per CU before -- see the header).
+constexpr int NF_TILES = 12, NF_HT = NF_TILES / 2, NF_WAVES = 4;       // 12 waves per CU = 3 per SIMD (152 VGPRs): the task epilogues of one wave hide behind the MFMAs of two others (8 -> 12 waves: 35.8 -> 34.9 us at M = 8192, 205 -> 188 us at M = 48000, same box)
 constexpr int NF_KS = NF_F / 32, NF_SPL = 2;                // k-steps of 32, fp16 terms per fp32 value
 constexpr int NF_HEAD_VEC = NF_TILES * NF_KS * NF_SPL * 64;    // 16-byte vectors (8 fp16) per head: [tile][k-step][term][lane]
-constexpr int NF_LDS_VEC = NF_SPLIT ? NF_HEAD_VEC / 2 : NF_HEAD_VEC;      // what a workgroup keeps in LDS
+constexpr int NF_LDS_VEC = NF_HEAD_VEC / 2;                    // what a workgroup keeps in LDS: half a head
 
 
 __device__ __forceinline__ float quad_bcast0(float v) { return __uint_as_float(__builtin_amdgcn_update_dpp(0u, __float_as_uint(v), 0x00, 0xf, 0xf, false)); }
@@ -87,7 +76,7 @@ __device__ __forceinline__ void nf_task(const float* __restrict__ x, const unsig
     for (int rt = 0; rt < 2; ++rt)
 #pragma unroll
         for (int T = 0; T < NF_HT; ++T) acc[rt][T] = (f32x4){0.f, 0.f, 0.f, 0.f};
-    const u32x4* wh = wl + (NF_SPLIT ? 0 : (HALF * NF_HT) * (NF_KS * NF_SPL * 64)) + lane;
+    const u32x4* wh = wl + lane;
     // weight fragments of step g + 1 are read from LDS before the 12 MFMAs of step g are issued (hipcc left to itself hoists every read)
     u32x4 wa[2][NF_SPL];
 #pragma unroll
@@ -115,20 +104,12 @@ __device__ __forceinline__ void nf_task(const float* __restrict__ x, const unsig
                 }
             }
         }
-#if defined(NF_ABL) && (NF_ABL & 8)
-        if (g == 0) {
-#else
         if (g + 1 < NF_KS * NF_HT) {
-#endif
             const int sn = (g + 1) / NF_HT, Tn = (g + 1) % NF_HT;
 #pragma unroll
             for (int sp = 0; sp < NF_SPL; ++sp) wa[(g + 1) & 1][sp] = wh[((Tn * NF_KS + sn) * NF_SPL + sp) * 64];
         }
-#if defined(NF_ABL) && (NF_ABL & 8)
-        const u32x4 wH = wa[g ? 1 : 0][0], wL = wa[g ? 1 : 0][1];
-#else
         const u32x4 wH = wa[g & 1][0], wL = wa[g & 1][1];
-#endif
         const bool swap = (HALF == 1) && (T >= 2);                               // value tiles: x is the A operand -> accumulator [residue 4 kq + r][channel fm]
         // smallest terms first; the two row tiles alternate so consecutive MFMAs never depend on each other
 #define NF_PROD(XT, WT)                                                                                                         \
@@ -139,13 +120,6 @@ __device__ __forceinline__ void nf_task(const float* __restrict__ x, const unsig
         __builtin_amdgcn_sched_barrier(0);
     }
     auto sq = [](const f32x4& g) { return fmaf(g[2], g[2], fmaf(g[1], g[1], g[0] * g[0])); };
-#if defined(NF_ABL) && (NF_ABL & 4)
-    {
-        float sum = 0.f;
-        for (int rt = 0; rt < 2; ++rt) for (int T = 0; T < NF_HT; ++T) for (int r = 0; r < 4; ++r) sum += acc[rt][T][r];
-        if (sum != 1.2345e-30f) return;
-    }
-#endif
 #pragma unroll
     for (int rt = 0; rt < 2; ++rt) {
         if (tile0 + rt >= total_tiles) break;
@@ -217,14 +191,11 @@ __global__ __launch_bounds__(NF_WAVES * 64) void node_frags_kernel(const float* 
                                                                    int total_tiles, int qk_terms) {
     extern __shared__ __attribute__((aligned(16))) char nf_smem[];
     u32x4* wl = reinterpret_cast<u32x4*>(nf_smem);                             // [12 tiles][4 k-steps][2 terms][64]
-    const int h = NF_SPLIT ? blockIdx.y >> 1 : blockIdx.y, tid = threadIdx.x, lane = tid & 63, fm = lane & 15, kq = lane >> 4;
-    const int half = blockIdx.y & 1;                                           // NF_SPLIT: which six tiles this workgroup owns
+    const int h = blockIdx.y >> 1, tid = threadIdx.x, lane = tid & 63, fm = lane & 15, kq = lane >> 4;
+    const int half = blockIdx.y & 1;                                           // which six tiles this workgroup owns
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-#ifdef NF_TIMING
-    const long long c0 = clock64(), w0 = wall_clock64();
-#endif
     {
-        const u32x4* wg = reinterpret_cast<const u32x4*>(wfrag) + (int64_t)h * NF_HEAD_VEC + (NF_SPLIT ? half * NF_LDS_VEC : 0);
+        const u32x4* wg = reinterpret_cast<const u32x4*>(wfrag) + (int64_t)h * NF_HEAD_VEC + half * NF_LDS_VEC;
         static_assert(NF_LDS_VEC % (NF_WAVES * 64) == 0, "weight load loop");
 #pragma unroll
         for (int e = 0; e < NF_LDS_VEC / (NF_WAVES * 64); ++e) wl[e * (NF_WAVES * 64) + tid] = wg[e * (NF_WAVES * 64) + tid];
@@ -235,32 +206,16 @@ __global__ __launch_bounds__(NF_WAVES * 64) void node_frags_kernel(const float* 
     const float ch_ = (-1.f * gamma * 0.16666666666666666f) / 2.f;               // -gamma sqrt(2/(9*8)) / 2, ga.py:109-110
     const float m2c = -2.f * ch_;
     __syncthreads();
-#ifdef NF_TIMING
-    const long long c1 = clock64();
-#endif
     // every workgroup owns a contiguous, equal (+-1) share of the head's tasks (pair of row tiles, half of the tiles); its waves take
     // them round-robin, so both halves of a row-tile pair run on neighbouring waves and share the x rows in L1
-    // (NF_SPLIT: a task index is a pair of row tiles, all of this workgroup's tasks are of its own half)
-    const int ntask = NF_SPLIT ? (total_tiles + 1) / 2 : 2 * ((total_tiles + 1) / 2);
+    // (a task index is a pair of row tiles, all of this workgroup's tasks are of its own half)
+    const int ntask = (total_tiles + 1) / 2;
     const int t_lo = (int)((int64_t)ntask * blockIdx.x / gridDim.x), t_hi = (int)((int64_t)ntask * (blockIdx.x + 1) / gridDim.x);
-#ifdef NF_TIMING
-    long long te[3] = {0, 0, 0};
-    int ti = 0;
-#endif
     for (int task = t_lo + wave; task < t_hi; task += NF_WAVES) {
-        const int tile0 = NF_SPLIT ? task * 2 : (task >> 1) * 2;
-        if (NF_SPLIT ? half : (task & 1)) nf_task<1, XT>(x, xt, wl, R, t, qfrag, kvfrag, L, nchunk, total_tiles, tile0, h, ch_, m2c, winv, lane, fm, kq, qk_terms);
+        const int tile0 = task * 2;
+        if (half) nf_task<1, XT>(x, xt, wl, R, t, qfrag, kvfrag, L, nchunk, total_tiles, tile0, h, ch_, m2c, winv, lane, fm, kq, qk_terms);
         else          nf_task<0, XT>(x, xt, wl, R, t, qfrag, kvfrag, L, nchunk, total_tiles, tile0, h, ch_, m2c, winv, lane, fm, kq, qk_terms);
-#ifdef NF_TIMING
-        if (ti < 3) te[ti++] = clock64() - c0;
-#endif
     }
-#ifdef NF_TIMING
-    if (blockIdx.x == NF_TIMING && blockIdx.y == 3 && lane == 0) {        // -DNF_TIMING=<row group>: 5 owns 25 tasks at the bench shape, 0 owns 24
-        long long* o = g_nf_timing[wave];
-        o[0] = c1 - c0; o[1] = clock64() - c0; o[2] = wall_clock64() - w0; o[3] = te[0]; o[4] = te[1]; o[5] = (t_hi - t_lo); o[6] = te[2];
-    }
-#endif
 }
 
 size_t node_wfrag_floats() { return (size_t)H * NF_HEAD_VEC * 4 + 4; }      // + {S, 1 / S, 0, 0}
@@ -276,17 +231,11 @@ int launch_node_frags(const float* x, const float* wfrag, const float* R, const 
     if ((rc = ensure_dynamic_lds(xt ? reinterpret_cast<const void*>(node_frags_kernel<true>) : reinterpret_cast<const void*>(node_frags_kernel<false>), NF_LDS_VEC * 16,
                                  lds_cfg[xt])))
         return rc;
-#if NF_SPLIT
-    // 24 (head, half) columns of workgroups x `groups` shares of the row-tile pairs; 48 KB of LDS each: NF_WGPC = 3 per CU.  At the bench shape
+    // 24 (head, half) columns of workgroups x `groups` shares of the row-tile pairs; 48 KB of LDS each: 3 per CU.  At the bench shape
     // (256 pairs, 256 CUs): 32 groups of 8 pairs, two tasks for each of the four waves -- every wave of the chip does the same amount of work.
     const int ntask = (total + 1) / 2;
-    const int groups = max(1, min(cus * NF_WGPC / (2 * H), (ntask + NF_WAVES - 1) / NF_WAVES));
+    const int groups = max(1, min(cus * 3 / (2 * H), (ntask + NF_WAVES - 1) / NF_WAVES));
     const dim3 grid(groups, 2 * H);
-#else
-    const int ntask = 2 * ((total + 1) / 2);
-    const int groups = max(1, min(cus / H, (ntask + NF_WAVES - 1) / NF_WAVES));          // one workgroup per CU: 96 KB of LDS each
-    const dim3 grid(groups, H);
-#endif
     if (xt)
         hipLaunchKernelGGL(node_frags_kernel<true>, grid, dim3(NF_WAVES * 64), NF_LDS_VEC * 16, st, x, reinterpret_cast<const unsigned*>(x_terms), wfrag, R, t,
                            spatial_coef, qfrag, kvfrag, L, nchunk, total, qk_terms);
@@ -294,18 +243,6 @@ int launch_node_frags(const float* x, const float* wfrag, const float* R, const 
         hipLaunchKernelGGL(node_frags_kernel<false>, grid, dim3(NF_WAVES * 64), NF_LDS_VEC * 16, st, x, nullptr, wfrag, R, t, spatial_coef, qfrag, kvfrag, L, nchunk,
                            total, qk_terms);
     ABOPT_LAUNCH_CHECK();
-#ifdef NF_TIMING
-    {
-        long long hh[16][8];
-        (void)hipDeviceSynchronize();
-        (void)hipMemcpyFromSymbol(hh, HIP_SYMBOL(g_nf_timing), sizeof(hh));
-        static int calls = 0;
-        if (++calls == 8)
-            for (int w = 0; w < NF_WAVES; ++w)
-                fprintf(stderr, "[nf timing WG(%d,3) wave %d] W load %lld | total %lld shader clk = %lld x 10 ns wall | task ends %lld %lld %lld | tasks of WG %lld\n",
-                        (int)NF_TIMING, w, hh[w][0], hh[w][1], hh[w][2], hh[w][3], hh[w][4], hh[w][6], hh[w][5]);
-    }
-#endif
     return ABOPT_OK;
 }
 

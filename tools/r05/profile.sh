@@ -1,8 +1,7 @@
 #!/bin/bash
 # Round-5 evidence set on ONE box:  gpurun --timeout 2400 -- 'bash tools/r05/profile.sh gpurun_out/r05_a'
 # 1. the driver's bench command (full line)   2. rocprofv3 --kernel-trace --stats of the SAME command   3. PMC passes (one group per run,
-# --kernel-trace only) on a short eager run, digested for the block's kernels   4. HBM read traffic of the dominant kernel by source (FETCH_SIZE
-# passes of developer builds with one stream removed: W_out terms / key-value fragments / z + bias cache)   5. steady-state training step   6. other shapes
+# --kernel-trace only) on a short eager run, digested for the block's kernels   4. steady-state training step   5. other shapes
 cd "$(dirname "$0")/../.." && ROOT=$(pwd) && OUT=$ROOT/${1:-gpurun_out/r05_a} && mkdir -p $OUT && TAG=$(basename $OUT)
 export TMPDIR=/tmp
 python bench.py --steps 20 --warmup 5 --full > $OUT/bench_full.log 2> $OUT/bench_full.err
@@ -34,31 +33,10 @@ for k in ipa_core node_frags_kernel; do
     python tools/pmc_summary.py $OUT/pmc --kernel $k; } > $OUT/pmc_$k.txt
 done
 rm -rf $OUT/pmc
-# ---- 4. read traffic by source (needs the developer builds abl1 / abl2 / fabl1 under ab_opt_amd/variants; PROFILE_PARTS=123 stops here)
-if [ "${PROFILE_PARTS:-123456}" = 123 ]; then tail -1 $OUT/bench_full.log | cut -c1-1200; head -14 $OUT/kernel_stats.txt | cut -c1-60,92-140; head -8 $OUT/kernel_stats_replay_only.txt | cut -c1-60,92-140; exit 0; fi
-cd /tmp
-{ echo "# HBM read traffic of the dominant kernel by source: rocprofv3 --pmc FETCH_SIZE (KiB; x2 = the gfx950 correction of MI355X_MICROARCH.md) of developer builds with ONE stream removed";
-  echo "# (timing-only builds: their results are wrong by construction).  Command: $CMD  with ABOPT_LIB_PATH=<variant> [ABOPT_FUSE_TAIL=0]"; } > $OUT/traffic_by_source.txt
-for spec in "base:" "fabl1:" "base:ABOPT_FUSE_TAIL=0" "abl2:ABOPT_FUSE_TAIL=0" "abl1:ABOPT_FUSE_TAIL=0"; do
-  v=${spec%%:*}; e=${spec##*:}
-  lib=$ROOT/ab_opt_amd/variants/libabopt_$v.so; [ $v = base ] && lib=$ROOT/ab_opt_amd/libabopt_hip.so
-  [ -f $lib ] || { echo "$spec: variant missing" >> $OUT/traffic_by_source.txt; continue; }
-  env ABOPT_LIB_PATH=$lib ABOPT_CORE32=1 $e rocprofv3 --kernel-trace --pmc FETCH_SIZE -d $OUT/tr_$v --output-format csv -- $CMD > $OUT/tr_$v.log 2>&1
-  python - "$OUT/tr_$v" "$spec" >> $OUT/traffic_by_source.txt <<'PY'
-import csv, glob, sys, os
-tot, n, us = 0.0, 0, 0.0
-for f in glob.glob(os.path.join(sys.argv[1], '**', '*_counter_collection.csv'), recursive=True):
-    for r in csv.DictReader(open(f)):
-        if 'ipa_core32' in r['Kernel_Name'] and r['Counter_Name'] == 'FETCH_SIZE':
-            tot += float(r['Counter_Value']); n += 1; us += (int(r['End_Timestamp']) - int(r['Start_Timestamp'])) / 1e3
-print('%-28s %4d launches  FETCH_SIZE %10.1f KiB -> read %7.1f MB per launch   (%.1f us per launch under the counter pass)' % (sys.argv[2], n, tot / max(n, 1), tot / max(n, 1) * 1024 * 2 / 1e6, us / max(n, 1)))
-PY
-  rm -rf $OUT/tr_$v
-done
-cd $ROOT
-# ---- 5. training, 6. shapes
+# PROFILE_PARTS=123 stops here
+if [ "${PROFILE_PARTS:-12345}" = 123 ]; then tail -1 $OUT/bench_full.log | cut -c1-1200; head -14 $OUT/kernel_stats.txt | cut -c1-60,92-140; head -8 $OUT/kernel_stats_replay_only.txt | cut -c1-60,92-140; exit 0; fi
+# ---- 4. training, 5. shapes
 bash tools/r05/train_prof.sh $TAG/train > /dev/null 2>&1
 bash tools/r03_shapes.sh $TAG/shapes > /dev/null 2>&1
 tail -1 $OUT/bench_full.log | cut -c1-1800
 head -14 $OUT/kernel_stats.txt | cut -c1-60,92-140
-cat $OUT/traffic_by_source.txt
