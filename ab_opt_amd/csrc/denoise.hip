@@ -226,6 +226,24 @@ __global__ __launch_bounds__(256) void commonness_kernel(const float* __restrict
     if (tid == 0) score[b] = (part[0] + part[1] + part[2] + part[3]) / (float)(B - 1);
 }
 
+// G groups of S in one launch: workgroup c scores structure c within its group; commonness_kernel's arithmetic on the group's base pointer
+// (bit-identical to a launch of commonness_kernel per group)
+__global__ __launch_bounds__(256) void commonness_grouped_kernel(const float* __restrict__ x_all, float* __restrict__ score_all, int S, int n) {
+    const int g = blockIdx.x / S, b = blockIdx.x % S, tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+    const float* x = x_all + (int64_t)g * S * n * 3;
+    __shared__ float part[4];
+    float tot = 0.f;
+    for (int o = wave; o < S; o += 4) {
+        float s = 0.f;
+        for (int k = lane; k < n * 3; k += 64) { const float d = x[((int64_t)b * n) * 3 + k] - x[((int64_t)o * n) * 3 + k]; s = fmaf(d, d, s); }
+        s = wave_sum(s);
+        tot += sqrtf(s / (float)n);
+    }
+    if (lane == 0) part[wave] = tot;
+    __syncthreads();
+    if (tid == 0) score_all[blockIdx.x] = (part[0] + part[1] + part[2] + part[3]) / (float)(S - 1);
+}
+
 }  // namespace abopt
 
 using namespace abopt;
@@ -298,6 +316,15 @@ extern "C" int abopt_add_noise(const int64_t* t, const float* alpha_bars, const 
 extern "C" int abopt_commonness_score(const float* structs, float* score, int B, int n, abopt_stream stream) {
     ABOPT_CHECK_ARG(structs && score && B >= 2 && n >= 1, "commonness_score: bad arguments (B=%d n=%d)", B, n);
     hipLaunchKernelGGL(commonness_kernel, dim3(B), dim3(256), 0, (hipStream_t)stream, structs, score, B, n);
+    ABOPT_LAUNCH_CHECK();
+    return ABOPT_OK;
+}
+
+extern "C" int abopt_commonness_score_grouped(const float* structs, float* score, int G, int S, int n, abopt_stream stream) {
+    ABOPT_CHECK_ARG(structs && score && G >= 0 && S >= 2 && n >= 1 && (int64_t)G * S <= 0x7fffffff,
+                    "commonness_score_grouped: bad arguments (G=%d S=%d n=%d)", G, S, n);
+    if (G == 0) return ABOPT_OK;
+    hipLaunchKernelGGL(commonness_grouped_kernel, dim3((unsigned)(G * S)), dim3(256), 0, (hipStream_t)stream, structs, score, S, n);
     ABOPT_LAUNCH_CHECK();
     return ABOPT_OK;
 }

@@ -164,11 +164,104 @@ __global__ __launch_bounds__(256) void dockq_model_kernel(const float* __restric
     }
 }
 
+// ---- G natives per launch (the re-dock screen: every design is the native of its own D re-docks).  The two kernels below are
+// dockq_native_kernel / dockq_model_kernel statement for statement, with the native's tables and inputs offset by blockIdx.y (native pass)
+// or candidate / S (model pass): every candidate's result is bit-identical to abopt_dockq_lite on its group alone.
+__global__ __launch_bounds__(256) void dockq_native_grouped_kernel(const float* __restrict__ pos, const uint8_t* __restrict__ mask,
+                                                                   const int32_t* __restrict__ group, uint8_t* __restrict__ nat5,
+                                                                   uint8_t* __restrict__ interface, int* __restrict__ nat_total, int L, int A) {
+    const int idx = blockIdx.x * blockDim.x + threadIdx.x, g = blockIdx.y;
+    if (idx >= L * L) return;
+    pos += (int64_t)g * L * A * 3; mask += (int64_t)g * L * A; group += (int64_t)g * L;
+    nat5 += (int64_t)g * L * L; interface += (int64_t)g * L;
+    const int a = idx / L, b = idx % L;
+    uint8_t c5 = 0;
+    if (group[a] == 1 && group[b] == 2) {
+        const float d2 = res_min_d2(pos, mask, a, b, A);
+        c5 = d2 <= 25.f;
+        if (d2 <= 100.f) { interface[a] = 1; interface[b] = 1; }          // benign race: every writer stores 1
+        if (c5) atomicAdd(nat_total + g, 1);
+    }
+    nat5[idx] = c5;
+}
+
+__global__ __launch_bounds__(256) void dockq_model_grouped_kernel(const float* __restrict__ model_pos, const uint8_t* __restrict__ model_mask, int mask_shared,
+                                                                  const float* __restrict__ native_pos_all, const uint8_t* __restrict__ native_mask_all,
+                                                                  const int32_t* __restrict__ group_all, const uint8_t* __restrict__ nat5_all,
+                                                                  const uint8_t* __restrict__ interface_all, const int* __restrict__ nat_total_all,
+                                                                  float* __restrict__ out, int S, int L, int A) {
+    __shared__ double red[4], shR[9];
+    __shared__ int cnt_sh[2];
+    const int s = blockIdx.x, tid = threadIdx.x, g = s / S;
+    const float* mp = model_pos + (int64_t)s * L * A * 3;
+    const uint8_t* mm = model_mask + (int64_t)(mask_shared ? g : s) * L * A;
+    const float* native_pos = native_pos_all + (int64_t)g * L * A * 3;
+    const uint8_t* native_mask = native_mask_all + (int64_t)g * L * A;
+    const int32_t* group = group_all + (int64_t)g * L;
+    const uint8_t* nat5 = nat5_all + (int64_t)g * L * L;
+    const uint8_t* interface = interface_all + (int64_t)g * L;
+    // ---- Fnat: native 5 A contacts that are also contacts in the model
+    double correct = 0;
+    for (int idx = tid; idx < L * L; idx += 256)
+        if (nat5[idx] && res_min_d2(mp, mm, idx / L, idx % L, A) <= 25.f) correct += 1;
+    correct = block_sum(correct, red);
+    const int ntot = nat_total_all[g];
+    const double fnat = ntot ? correct / (double)ntot : 0.0;
+    // ---- common CA atoms (atoms_def_in_both, DockQ.py:150-188)
+    auto both = [&](int r) { return group[r] > 0 && mm[r * A + DQ_CA] && native_mask[r * A + DQ_CA]; };
+    double n1 = 0, n2 = 0;
+    for (int r = tid; r < L; r += 256) if (both(r)) { n1 += group[r] == 1; n2 += group[r] == 2; }
+    n1 = block_sum(n1, red); n2 = block_sum(n2, red);
+    if (tid == 0) { cnt_sh[0] = (int)n1; cnt_sh[1] = (int)n2; }
+    __syncthreads();
+    const int rec = cnt_sh[0] > cnt_sh[1] ? 1 : 2, lig = 3 - rec;               // receptor = the chain with more common atoms (DockQ.py:314-318)
+    auto isel = [&](int r) { return both(r) && interface[r]; };
+    const double irms = fit_and_rmsd(mp, native_pos, L, A, isel, isel, red, shR);
+    auto rsel = [&](int r) { return both(r) && group[r] == rec; };
+    auto lsel = [&](int r) { return both(r) && group[r] == lig; };
+    const double lrms = fit_and_rmsd(mp, native_pos, L, A, rsel, lsel, red, shR);
+    if (tid == 0) {
+        out[(int64_t)s * 4 + 0] = (float)fnat;
+        out[(int64_t)s * 4 + 1] = (float)irms;
+        out[(int64_t)s * 4 + 2] = (float)lrms;
+        out[(int64_t)s * 4 + 3] = (irms < 0 || lrms < 0) ? -1.f
+                                                         : (float)((fnat + 1.0 / (1.0 + (irms / 1.5) * (irms / 1.5)) + 1.0 / (1.0 + (lrms / 8.5) * (lrms / 8.5))) / 3.0);
+    }
+}
+
 }  // namespace abopt
 
 using namespace abopt;
 
 extern "C" size_t abopt_dockq_workspace_bytes(int L) { return (size_t)L * L + (size_t)L + 256; }
+
+// nat5 [G,L,L] | interface [G,L] | (64-byte aligned) nat_total [G] int
+extern "C" size_t abopt_dockq_grouped_workspace_bytes(int G, int L) {
+    return (size_t)G * L * L + (size_t)G * L + 64 + (size_t)G * sizeof(int) + 64;
+}
+
+extern "C" int abopt_dockq_lite_grouped(const float* model_pos, const uint8_t* model_mask, int model_mask_shared, const float* native_pos,
+                                        const uint8_t* native_mask, const int32_t* group, int G, int S, int L, int A, float* out,
+                                        void* ws, size_t ws_bytes, abopt_stream stream) {
+    ABOPT_CHECK_ARG(G >= 0 && S >= 0 && L >= 1 && A >= 2 && (int64_t)G * S <= 0x7fffffff && (int64_t)L * L <= 0x7fffffff,
+                    "dockq_lite_grouped: bad dims G=%d S=%d L=%d A=%d", G, S, L, A);
+    if (G == 0 || S == 0) return ABOPT_OK;
+    ABOPT_CHECK_ARG(G <= 65535, "dockq_lite_grouped: G=%d natives exceed one launch (max 65535)", G);
+    ABOPT_CHECK_ARG(model_pos && model_mask && native_pos && native_mask && group && out && ws, "dockq_lite_grouped: NULL argument");
+    if (ws_bytes < abopt_dockq_grouped_workspace_bytes(G, L)) { set_error("dockq_lite_grouped: workspace too small (%zu bytes given)", ws_bytes); return ABOPT_EWORKSPACE; }
+    hipStream_t st = (hipStream_t)stream;
+    uint8_t* nat5 = (uint8_t*)ws;
+    uint8_t* interface = nat5 + (size_t)G * L * L;
+    int* nat_total = (int*)(((uintptr_t)(interface + (size_t)G * L) + 63) & ~(uintptr_t)63);
+    ABOPT_HIP(hipMemsetAsync(interface, 0, (size_t)((uint8_t*)(nat_total + G) - interface), st));
+    hipLaunchKernelGGL(dockq_native_grouped_kernel, dim3((unsigned)((L * L + 255) / 256), (unsigned)G), dim3(256), 0, st, native_pos, native_mask, group,
+                       nat5, interface, nat_total, L, A);
+    ABOPT_LAUNCH_CHECK();
+    hipLaunchKernelGGL(dockq_model_grouped_kernel, dim3((unsigned)(G * S)), dim3(256), 0, st, model_pos, model_mask, model_mask_shared ? 1 : 0,
+                       native_pos, native_mask, group, nat5, interface, nat_total, out, S, L, A);
+    ABOPT_LAUNCH_CHECK();
+    return ABOPT_OK;
+}
 
 extern "C" int abopt_dockq_lite(const float* model_pos, const uint8_t* model_mask, int model_mask_shared, const float* native_pos,
                                 const uint8_t* native_mask, const int32_t* group, int S, int L, int A, float* out,

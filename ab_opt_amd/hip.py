@@ -12,7 +12,7 @@ import torch
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # ABOPT_LIB_PATH: developer override to load a variant build of the same ABI (csrc/Makefile VARIANT=...: A/B of two source trees)
 LIB_PATH = os.environ.get('ABOPT_LIB_PATH') or os.path.join(_HERE, 'libabopt_hip.so')
-ABI_VERSION = 41
+ABI_VERSION = 42
 
 c_f = C.c_void_p        # device float*
 c_i64 = C.c_void_p      # device int64*
@@ -81,7 +81,7 @@ EXPORTS = ['abopt_abi_version', 'abopt_last_error', 'abopt_device_info', 'abopt_
            'abopt_add_noise', 'abopt_gemm', 'abopt_gemm_tn_grouped', 'abopt_colsum', 'abopt_adam_step', 'abopt_adam_ws_floats', 'abopt_bucket_colsum', 'abopt_segment_bucket_colsum', 'abopt_heads_epilogue_forward', 'abopt_heads_epilogue_backward', 'abopt_dpm_losses', 'abopt_abdock_losses', 'abopt_layer_norm_forward', 'abopt_layer_norm_backward', 'abopt_residue_features', 'abopt_residue_features_workspace_bytes', 'abopt_commonness_score', 'abopt_prof_enable', 'abopt_prof_collect', 'abopt_prof_peek', 'abopt_prof_clock', 'abopt_prof_spans_reset', 'abopt_prof_spans',
            'abopt_reconstruct_backbone_partially', 'abopt_ipa_train_workspace_bytes', 'abopt_ipa_core_train_forward', 'abopt_ipa_points_backward', 'abopt_ipa_backward_operands', 'abopt_ipa_backward_assemble', 'abopt_ipa_pair_backward', 'abopt_ipa_dz_assemble',
            'abopt_residue_embed_workspace_bytes', 'abopt_residue_embed_forward', 'abopt_pair_embed_workspace_bytes', 'abopt_pair_embed_forward',
-           'abopt_pair_embed_backward_workspace_bytes', 'abopt_pair_embed_backward', 'abopt_dockq_workspace_bytes', 'abopt_dockq_lite', 'abopt_node_frag_source_row', 'abopt_node_frag_floats',
+           'abopt_pair_embed_backward_workspace_bytes', 'abopt_pair_embed_backward', 'abopt_dockq_workspace_bytes', 'abopt_dockq_lite', 'abopt_dockq_grouped_workspace_bytes', 'abopt_dockq_lite_grouped', 'abopt_commonness_score_grouped', 'abopt_node_frag_source_row', 'abopt_node_frag_floats',
            'abopt_out_frag_floats', 'abopt_out_terms_floats', 'abopt_out_frag_terms', 'abopt_heads_frag_floats', 'abopt_mixer_frag_floats', 'abopt_mlp_frag_floats', 'abopt_pack_tail_weights', 'abopt_block_tail_forward', 'abopt_block_tail_backward']
 
 _lib = None
@@ -173,6 +173,10 @@ def lib():
         L.abopt_dockq_workspace_bytes.restype = C.c_size_t
         L.abopt_dockq_workspace_bytes.argtypes = [C.c_int]
         L.abopt_dockq_lite.argtypes = [c_f, c_u8, C.c_int, c_f, c_u8, C.c_void_p, C.c_int, C.c_int, C.c_int, c_f, C.c_void_p, C.c_size_t, C.c_void_p]
+        L.abopt_dockq_grouped_workspace_bytes.restype = C.c_size_t
+        L.abopt_dockq_grouped_workspace_bytes.argtypes = [C.c_int] * 2
+        L.abopt_dockq_lite_grouped.argtypes = [c_f, c_u8, C.c_int, c_f, c_u8, C.c_void_p] + [C.c_int] * 4 + [c_f, C.c_void_p, C.c_size_t, C.c_void_p]
+        L.abopt_commonness_score_grouped.argtypes = [c_f, c_f] + [C.c_int] * 3 + [C.c_void_p]
         L.abopt_out_frag_floats.restype = C.c_size_t
         L.abopt_out_terms_floats.restype = C.c_size_t
         L.abopt_out_frag_terms.argtypes = [c_f, c_f, C.c_void_p]
@@ -570,6 +574,19 @@ def commonness_score(structs):
     return score
 
 
+def commonness_score_grouped(structs, group_size):
+    """structs (G*S, n, 3), S = group_size -> (G*S,) commonness of every structure within its own group of S (abopt_commonness_score_grouped;
+    row-for-row the bits of commonness_score called on each group)."""
+    structs = structs.contiguous().float()
+    B, n, _ = structs.shape
+    S = int(group_size)
+    if S < 2 or B % S:
+        raise ValueError(f'commonness_score_grouped: {B} structures are not whole groups of {S} >= 2')
+    score = torch.empty(B, device=structs.device)
+    _check(lib().abopt_commonness_score_grouped(ptr(structs), ptr(score), B // S, S, n, stream()))
+    return score
+
+
 def pair_bias_cache_layers(w_pair_bias_list, pair_feat):
     """The cache from bare proj_pair_bias weights (training: built once per step for all blocks) -> list of per-layer views."""
     n = len(w_pair_bias_list)
@@ -777,6 +794,32 @@ def dockq_lite(model_pos, model_mask, native_pos, native_mask, group, check=True
     if check and S > 0 and bool((out[:, 1:3] < 0).any()):
         bad = (out[:, 1:3] < 0).any(1).nonzero().flatten().tolist()
         raise ValueError(f'dockq_lite: candidates {bad} have an empty interface / receptor / ligand CA selection (no atoms in both model and native)')
+    return out
+
+
+def dockq_lite_grouped(model_pos, model_mask, native_pos, native_mask, group, check=True):
+    """DockQ of G*S candidates against G natives in one launch (include/abopt.h: abopt_dockq_lite_grouped) -> (G*S, 4) = fnat, irms, Lrms, DockQ;
+    candidate c is scored against native c // S, and every row equals dockq_lite on its group alone, bit for bit.
+    model_pos (G*S,L,A,3); model_mask (G*S,L,A), or (G,L,A) shared by the S candidates of a native; native_pos (G,L,A,3); native_mask (G,L,A);
+    group (G,L) int {0,1,2}.  check: as dockq_lite."""
+    G, L, A, _ = native_pos.shape
+    N = model_pos.shape[0]
+    if G == 0 or N % G or tuple(model_pos.shape[1:]) != (L, A, 3):
+        raise ValueError(f'dockq_lite_grouped: {tuple(model_pos.shape)} candidates do not split into groups of the {G} natives {tuple(native_pos.shape)}')
+    S = N // G
+    shared = model_mask.shape[0] != N or S == 1
+    if tuple(model_mask.shape) != ((G if shared else N), L, A):
+        raise ValueError(f'dockq_lite_grouped: model_mask {tuple(model_mask.shape)} is neither per candidate nor per native')
+    model_pos, model_mask, native_pos, native_mask = _contig(model_pos.float(), model_mask, native_pos.float(), native_mask)
+    group = group.to(torch.int32).contiguous()
+    out = torch.empty(N, 4, dtype=torch.float32, device=model_pos.device)
+    nb = lib().abopt_dockq_grouped_workspace_bytes(G, L)
+    buf = Workspace.get(nb, model_pos.device)
+    _check(lib().abopt_dockq_lite_grouped(ptr(model_pos, torch.float32), ptr(model_mask, torch.bool), int(shared), ptr(native_pos, torch.float32),
+                                          ptr(native_mask, torch.bool), ptr(group, torch.int32), G, S, L, A, ptr(out), ptr(buf), buf.numel(), stream()))
+    if check and N > 0 and bool((out[:, 1:3] < 0).any()):
+        bad = (out[:, 1:3] < 0).any(1).nonzero().flatten().tolist()
+        raise ValueError(f'dockq_lite_grouped: candidates {bad} have an empty interface / receptor / ligand CA selection (no atoms in both model and native)')
     return out
 
 

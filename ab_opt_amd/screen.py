@@ -1,0 +1,225 @@
+"""The antibody optimisation screen of AbDock/optimize_ab.py on the device: dock, redesign, re-dock.
+
+The reference runs three programs per antibody, fanned out as Ray subprocesses that each reload a checkpoint and exchange PDB files
+(AbDock/optimize_ab.py:12-98, driven by ab_opt.ipynb / ab_opt_analysis_4mutations.ipynb):
+  1. dock       dock_pdb.py -c configs/test/dock_cdr.yml -n P: P poses of the docked residues (structure only, sequence fixed)
+  2. redesign   seq_design_batch: the sequence-design model (configs/test/seq_design.yml, backbone+CB) samples S designs on every fixed
+                pose backbone, optionally limited by a contig; AAR and PPL per design (design_for_pdb.py:241-290)
+  3. re-dock    dock_seqs: the first design of every pose (.../H_CDR3/0000.pdb) docked again D times; CA-only DockQ against that design's
+                complex and the prmsd of every sample (design_for_pdb.py:311-321); the notebook keeps the designs at or below the medians
+                of DockQ_std, prmsd_std and prmsd_avg (`screen_filter`).
+Here the complex stays a batch dict on the device from start to end: the poses and designs are rebuilt with
+`geometry.reconstruct_backbone_partially`, every stage walks its poses in chunks of `poses_per_launch` (each pose encoded once, its samples
+share its pair features: `sampler.sample_replicated` / `sampler.sample_grouped`), and a chunk's re-docks are scored by ONE grouped DockQ
+launch and ONE grouped commonness launch (hip.dockq_lite_grouped, hip.commonness_score_grouped).  No relax stage (the reference's
+--no_rosetta path), no PDB write / re-parse; the residues to dock, redesign and re-dock are given as masks instead of by renumbering files.
+
+Randomness: stage k draws from Philox seed `stage_seed(seed, k)`, and sample i of a stage (i = its GLOBAL index: pose, pose x S + design,
+(pose x k + screened design) x D + re-dock) reads the counters from i L on, as `sampler.launch_rng_offset` lays them out.  Results
+therefore do not depend on `poses_per_launch` or on the number of ranks (bit for bit where the launches of different sizes take the same
+kernel forms: DESIGN.md section 3.1b).  Multi-GPU: rank r owns the poses `sampler.shard_range(P, world, r)` through all three stages;
+one tensor all_gather per result field at the end.
+"""
+import time
+
+import torch
+import torch.distributed as dist
+
+from . import geometry, hip, sampler
+from .model import generate_mask_from_str
+
+STAGES = ('dock', 'design', 'redock')
+
+
+def stage_seed(seed, stage):
+    """Philox seed of a stage ('dock', 'design', 'redock'): distinct per stage and per screen seed."""
+    return int(seed) * len(STAGES) + STAGES.index(stage)
+
+
+def samples_per_pose(stage, designs_per_pose, screened_per_pose, redocks_per_design):
+    return {'dock': 1, 'design': int(designs_per_pose), 'redock': int(screened_per_pose) * int(redocks_per_design)}[stage]
+
+
+def stage_rng_offset(stage, first_pose, L, designs_per_pose, screened_per_pose, redocks_per_design):
+    """Philox counter base of the launch of `stage` whose first pose is `first_pose` (complex length L): its samples are poses x
+    samples_per_pose in global order, so the launches of all chunks and ranks tile [0, P x samples_per_pose x L)."""
+    return sampler.launch_rng_offset(first_pose, samples_per_pose(stage, designs_per_pose, screened_per_pose, redocks_per_design), L)
+
+
+def launch_plan(num_poses, poses_per_launch, world=1, rank=0):
+    """[(lo, hi), ...]: the global pose ranges of rank `rank`'s launches (its shard, in chunks of poses_per_launch)."""
+    a, b = sampler.shard_range(int(num_poses), int(world), int(rank))
+    step = max(1, int(poses_per_launch))
+    return [(lo, min(lo + step, b)) for lo in range(a, b, step)]
+
+
+def design_mask(design_flag, contig=''):
+    """The residues the design stage redesigns: design_flag, limited to the contig 'start-end' (1-based along L, inclusive) the way
+    model.sample applies it for AbDock (diffab.py:114-140)."""
+    if not contig:
+        return design_flag.bool()
+    return torch.logical_and(design_flag.bool(), generate_mask_from_str(contig, design_flag))
+
+
+def chain_groups(fragment_type):
+    """DockQ's two chains from fragment_type: antibody chains (1, 2) -> 1, antigen (3) -> 2, anything else 0 (sampler.dockq_scores)."""
+    return torch.where(fragment_type == 3, 2, torch.where(fragment_type > 0, 1, 0))
+
+
+def _with(one, **kw):
+    out = dict(one)
+    out.update(kw)
+    return out
+
+
+def _rebuild(pos, mask, traj0, lo, hi, aa, flag, one):
+    """Samples lo .. hi - 1 of a finished trajectory -> (pos, mask) with the residues of `flag` rebuilt from their final frames and types,
+    everything else copied from `pos` / `mask` (per-sample contexts, (hi - lo, L, A, 3) / (hi - lo, L, A)); aa (hi - lo, L) input types."""
+    v, p, s = traj0[0][lo:hi], traj0[1][lo:hi], traj0[2][lo:hi]
+    n = hi - lo
+    rep = lambda a: a[:1].expand(n, *a.shape[1:]).contiguous()
+    gen = flag[None].expand(n, -1).contiguous()
+    return geometry.reconstruct_backbone_partially(pos, hip.so3_exp(v), p, torch.where(gen, s, aa), rep(one['chain_nb']), rep(one['res_nb']),
+                                                   mask, gen)
+
+
+@torch.no_grad()
+def optimize_antibody(dock_model, design_model, complex_, num_poses, designs_per_pose, redocks_per_design, design_flag=None, redock_flag=None,
+                      contig='', screened_per_pose=1, seed=0, poses_per_launch=8, group=None, screen_by='first', timings=None):
+    """Dock -> redesign -> re-dock screen of one antibody-antigen complex (module docstring).
+
+    complex_: batch dict with batch dim 1 (cropped, as sample_replicated takes it); its generate_flag marks the residues to dock.
+    design_flag / redock_flag (L,) or (1, L) bool: residues to redesign / re-dock (default: generate_flag; the reference's
+    --label_heavy_as_cdr re-dock corresponds to every heavy-chain residue).  contig limits design_flag ('start-end', 1-based).
+    screened_per_pose k designs of every pose go on to the re-dock: the first k (screen_by='first', as the reference takes 0000.pdb) or the
+    k of lowest PPL (screen_by='ppl', stable order).  num_poses >= 2 and redocks_per_design >= 2 (commonness needs two structures).
+    timings (optional dict): receives the seconds each stage took on this rank (device-synchronised) and of the final gather.
+
+    -> dict of device tensors in global pose order (P poses, S designs, k screened, D re-docks; n_* = residues in the mask):
+      pose_ca (P, n_dock, 3), pose_score (P,)           CA of the docked residues of every pose, its commonness among the P poses
+      seqs (P, S, n_design) int64, aar (P, S), ppl (P, S)  designed residues, recovery of the input sequence on them, perplexity
+      chosen (P, k) int64                                 the designs that were re-docked
+      dockq (P, k, D, 4)                                  fnat, irms, Lrms, DockQ of every re-dock against its design (-1: empty selection)
+      prmsd (P, k, D), redock_score (P, k, D)             prmsd of every re-dock (traj[0][3]: the head's per-sample value, which the
+                                                          reference's prmsd[i].mean() returns, design_for_pdb.py:241); commonness of its
+                                                          re-docked residues' CA among the D
+      dockq_mean / dockq_std / prmsd_mean / prmsd_std (P, k)   over the D re-docks (np.mean / np.std, as the notebook)"""
+    world, rank = (dist.get_world_size(group), dist.get_rank(group)) if dist.is_initialized() else (1, 0)
+    one = {k: (v[:1] if torch.is_tensor(v) else v) for k, v in complex_.items()}
+    P, S, D, k = int(num_poses), int(designs_per_pose), int(redocks_per_design), int(screened_per_pose)
+    if P < 2 or D < 2 or S < 1 or not 1 <= k <= S:
+        raise ValueError(f'optimize_antibody: need num_poses >= 2, redocks_per_design >= 2 and 1 <= screened_per_pose <= designs_per_pose '
+                         f'(got P={P}, S={S}, k={k}, D={D})')
+    if screen_by not in ('first', 'ppl'):
+        raise ValueError(f"screen_by must be 'first' or 'ppl', not {screen_by!r}")
+    L = int(one['aa'].shape[1])
+    dev = one['aa'].device
+    gen = one['generate_flag'][0].bool()
+    dflag = design_mask((gen if design_flag is None else design_flag.reshape(-1).to(dev)), contig)
+    rflag = gen if redock_flag is None else redock_flag.reshape(-1).to(dev).bool()
+    n_dock, n_design, n_redock = int(gen.sum()), int(dflag.sum()), int(rflag.sum())
+    if min(n_dock, n_design, n_redock) == 0:
+        raise ValueError('optimize_antibody: the dock, design and re-dock masks must each select at least one residue')
+    plan = launch_plan(P, poses_per_launch, world, rank)
+    a, b = sampler.shard_range(P, world, rank)
+    mine = b - a
+    rngs = lambda stage, lo: dict(seed=stage_seed(seed, stage), rng_offset=stage_rng_offset(stage, lo, L, S, k, D))
+    aa = one['aa'][0]
+    f32 = dict(dtype=torch.float32, device=dev)
+    clock = {}
+
+    def tick(name, t0):
+        if timings is not None:
+            torch.cuda.synchronize(dev)
+            clock[name] = time.perf_counter() - t0
+        return time.perf_counter()
+
+    # ---- stage 1: P poses of the docked residues (structure only), one complex encoded once per launch
+    t0 = tick('start', time.perf_counter())
+    pose_pos = torch.empty(mine, L, *one['pos_heavyatom'].shape[2:], **f32)
+    pose_mask = torch.empty(mine, L, one['mask_heavyatom'].shape[2], dtype=torch.bool, device=dev)
+    pose_ca = torch.empty(mine, n_dock, 3, **f32)
+    for lo, hi in plan:
+        n = hi - lo
+        traj = sampler.sample_replicated(dock_model, one, n, dict(sample_structure=True, sample_sequence=False, **rngs('dock', lo)))
+        rep = lambda t: t.expand(n, *t.shape[1:]).contiguous()
+        pos, mask = _rebuild(rep(one['pos_heavyatom']), rep(one['mask_heavyatom']), traj[0], 0, n, rep(one['aa']), gen, one)
+        pose_pos[lo - a:hi - a], pose_mask[lo - a:hi - a] = pos, mask
+        pose_ca[lo - a:hi - a] = traj[0][1][:, gen]
+    t0 = tick('dock', t0)
+
+    # ---- stage 2: S designs per pose on the fixed pose backbone, each pose encoded once, its designs share its pair features
+    seqs = torch.empty(mine, S, n_design, dtype=torch.int64, device=dev)
+    aar, ppl = torch.empty(mine, S, **f32), torch.empty(mine, S, **f32)
+    chosen = torch.empty(mine, k, dtype=torch.int64, device=dev)
+    des_pos = torch.empty(mine, k, *pose_pos.shape[1:], **f32)
+    des_mask = torch.empty(mine, k, *pose_mask.shape[1:], dtype=torch.bool, device=dev)
+    des_aa = torch.empty(mine, k, L, dtype=torch.int64, device=dev)
+    native = aa[dflag]
+    for lo, hi in plan:
+        G = hi - lo
+        cx = [_with(one, pos_heavyatom=pose_pos[i - a:i - a + 1], mask_heavyatom=pose_mask[i - a:i - a + 1], generate_flag=dflag[None])
+              for i in range(lo, hi)]
+        traj = sampler.sample_grouped(design_model, cx, S, dict(sample_structure=False, sample_sequence=True, **rngs('design', lo)), pad_to=L)
+        s_fin = traj[0][2]
+        sq = s_fin[:, dflag]                                                             # (G*S, n_design)
+        seqs[lo - a:hi - a] = sq.view(G, S, n_design)
+        aar[lo - a:hi - a] = ((sq == native).sum(-1).float() / n_design).view(G, S)
+        pp = traj[0][4].to(dev).view(G, S)
+        ppl[lo - a:hi - a] = pp
+        if screen_by == 'first':
+            ch = torch.arange(k, device=dev).expand(G, k)
+        else:
+            ch = torch.sort(pp, dim=1, stable=True)[1][:, :k]
+        chosen[lo - a:hi - a] = ch
+        rows = (torch.arange(G, device=dev)[:, None] * S + ch).reshape(-1)               # (G*k,) rows of the launch, pose-major
+        src = (torch.arange(G, device=dev) + (lo - a)).repeat_interleave(k)
+        sub = [t[rows] for t in traj[0][:3]]
+        pos, mask = _rebuild(pose_pos[src], pose_mask[src], sub, 0, G * k, aa.expand(G * k, L), dflag, one)
+        des_pos[lo - a:hi - a] = pos.view(G, k, *pos.shape[1:])
+        des_mask[lo - a:hi - a] = mask.view(G, k, *mask.shape[1:])
+        des_aa[lo - a:hi - a] = torch.where(dflag, sub[2], aa).view(G, k, L)
+    t0 = tick('design', t0)
+
+    # ---- stage 3: D re-docks of every screened design, one grouped DockQ + one grouped commonness launch per chunk
+    dockq = torch.empty(mine, k, D, 4, **f32)
+    prmsd, redock_score = torch.empty(mine, k, D, **f32), torch.empty(mine, k, D, **f32)
+    grp = chain_groups(one['fragment_type'][0])
+    for lo, hi in plan:
+        Gk = (hi - lo) * k
+        npos, nmask, naa = (t[lo - a:hi - a].reshape(Gk, *t.shape[2:]) for t in (des_pos, des_mask, des_aa))
+        cx = [_with(one, pos_heavyatom=npos[i:i + 1], mask_heavyatom=nmask[i:i + 1], aa=naa[i:i + 1], generate_flag=rflag[None]) for i in range(Gk)]
+        traj = sampler.sample_grouped(dock_model, cx, D, dict(sample_structure=True, sample_sequence=False, **rngs('redock', lo)), pad_to=L)
+        rep = lambda t: t.repeat_interleave(D, dim=0)
+        pos, mask = _rebuild(rep(npos), rep(nmask), traj[0], 0, Gk * D, rep(naa), rflag, one)
+        out = hip.dockq_lite_grouped(pos, mask, npos, nmask, grp[None].expand(Gk, L), check=False)
+        dockq[lo - a:hi - a] = out.view(hi - lo, k, D, 4)
+        prmsd[lo - a:hi - a] = traj[0][3].to(dev).view(hi - lo, k, D)
+        ca = traj[0][1][:, rflag].contiguous()                                          # (Gk*D, n_redock, 3)
+        redock_score[lo - a:hi - a] = hip.commonness_score_grouped(ca, D).view(hi - lo, k, D)
+    t0 = tick('redock', t0)
+
+    res = dict(pose_ca=pose_ca, seqs=seqs, aar=aar, ppl=ppl, chosen=chosen, dockq=dockq, prmsd=prmsd, redock_score=redock_score)
+    if world > 1:
+        counts = [e - s_ for s_, e in (sampler.shard_range(P, world, r) for r in range(world))]
+        res = {name: sampler.all_gather_candidates(t, counts, group) for name, t in res.items()}
+    res['pose_score'] = hip.commonness_score(res['pose_ca'])
+    q, pr = res['dockq'][..., 3], res['prmsd']
+    res.update(dockq_mean=q.mean(-1), dockq_std=q.std(-1, unbiased=False), prmsd_mean=pr.mean(-1), prmsd_std=pr.std(-1, unbiased=False))
+    tick('gather', t0)
+    if timings is not None:
+        clock.pop('start', None)
+        timings.update(clock)
+    return res
+
+
+def screen_filter(res):
+    """The notebook's median rule (ab_opt_analysis_4mutations.ipynb, cell 7): keep the designs whose DockQ_std, prmsd_std and prmsd_avg
+    are each at or below the median over all screened designs (pandas' quantile(0.5): the mean of the two middle values for an even count).
+    -> bool (P, k)."""
+    med = lambda t: torch.quantile(t.reshape(-1).double(), 0.5)
+    keep = torch.ones_like(res['dockq_std'], dtype=torch.bool)
+    for name in ('dockq_std', 'prmsd_std', 'prmsd_mean'):
+        t = res[name]
+        keep &= t.double() <= med(t)
+    return keep

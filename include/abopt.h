@@ -23,7 +23,7 @@
 extern "C" {
 #endif
 
-#define ABOPT_ABI_VERSION 41
+#define ABOPT_ABI_VERSION 42
 
 enum { ABOPT_OK = 0, ABOPT_EINVAL = 1, ABOPT_EHIP = 2, ABOPT_EUNSUPPORTED = 3, ABOPT_EWORKSPACE = 4 };
 
@@ -311,6 +311,16 @@ int abopt_dockq_lite(const float* model_pos, const uint8_t* model_mask, int mode
                      const uint8_t* native_mask, const int32_t* group, int S, int L, int A, float* out,
                      void* ws, size_t ws_bytes, abopt_stream stream);
 
+/* The same scoring for G natives at once (ABI 42): the re-dock screen of AbDock/optimize_ab.py:73-98 (dock_seqs) scores the D re-docks of
+ * EVERY design against that design's own complex (design_for_pdb.py:311-321), one calc_DockQ per candidate.  native_pos [G,L,A,3],
+ * native_mask [G,L,A], group [G,L]; model_pos [G*S,L,A,3], candidate c scored against native c / S; model_mask [G*S,L,A], or [G,L,A]
+ * (one mask per native) with model_mask_shared = 1.  out [G*S,4] as abopt_dockq_lite, -1 markers included; every row is bit-identical
+ * to abopt_dockq_lite called on its group alone.  ws: abopt_dockq_grouped_workspace_bytes(G, L). */
+size_t abopt_dockq_grouped_workspace_bytes(int G, int L);
+int abopt_dockq_lite_grouped(const float* model_pos, const uint8_t* model_mask, int model_mask_shared, const float* native_pos,
+                             const uint8_t* native_mask, const int32_t* group, int G, int S, int L, int A, float* out,
+                             void* ws, size_t ws_bytes, abopt_stream stream);
+
 /* ---- Batched-sampling reduction: D/tools/runner/design_for_testset.py:556-589 (calc_per_rmsd +
  * rank_commoness score).  structs [B,n,3] -> score [B] = mean_{b'} RMSD(b,b') * B/(B-1). */
 /* ---- Training side of the IPA core (FullDPM.forward, D/modules/diffusion/dpm_full.py:156-234; the autograd of
@@ -531,6 +541,10 @@ int abopt_adam_step(int count, float* const* params, const float* const* grads, 
                     int64_t* step, float* ws, size_t ws_floats, float* grad_norm_out, const double* hyper_dev, abopt_stream stream);
 
 int abopt_commonness_score(const float* structs, float* score, int B, int n, abopt_stream stream);
+/* G groups of S structures in one launch (ABI 42; the re-docks of every design of AbDock/optimize_ab.py:73-98, ranked like
+ * design_for_pdb.py:326-345 ranks one run's candidates): structs [G*S,n,3] -> score [G*S], each score the commonness within its own group
+ * of S, bit-identical to abopt_commonness_score called on that group.  S >= 2. */
+int abopt_commonness_score_grouped(const float* structs, float* score, int G, int S, int n, abopt_stream stream);
 
 /* ---- Measurement hook (bench.py's roofline leg).  When enabled, every launch of the IPA-core kernel is bracketed
  * by hipEvents on the stream it is launched on; abopt_prof_collect synchronises those events and returns the number
