@@ -322,6 +322,10 @@ extern "C" int abopt_ipa_core_train_forward(const float* proj_local, const float
     if ((rc = check_dims(N, L, F, Cd))) return rc;
     if ((int64_t)N * L == 0) return ABOPT_OK;
     ABOPT_CHECK_ARG(proj_local && R && t && pair_feat && mask && w_pair_bias && spatial_coef && feat && alpha && ws, "ipa_core_train_forward: NULL argument");
+    if (pair_bias_cache && !bias_slab_fits_u32(N, L)) {                     // before anything is launched
+        set_error("ipa_core_train_forward: the training core reads a pair-bias cache through 32-bit offsets and this one (%d x %d rows) is 4 GB or more per layer; pass none", N, L);
+        return ABOPT_EUNSUPPORTED;
+    }
     if (ws_bytes < ipa_train_ws_floats(N, L) * sizeof(float)) { set_error("ipa_core_train_forward: workspace too small (%zu bytes given)", ws_bytes); return ABOPT_EWORKSPACE; }
     return launch_ipa_train_forward(proj_local, R, t, pair_feat, mask, w_pair_bias, spatial_coef, pair_bias_cache, feat, alpha, N, L, (float*)ws,
                                     (hipStream_t)stream);
@@ -453,6 +457,8 @@ extern "C" int abopt_nonfinite_flag(int reset, abopt_stream stream) {
     const int rc = nonfinite_flag_read(reset, (hipStream_t)stream, &flag);
     return rc ? -1 : flag;
 }
+
+extern "C" int abopt_nonfinite_flag_reset(abopt_stream stream) { return nonfinite_flag_reset((hipStream_t)stream); }
 
 extern "C" size_t abopt_pair_terms_bytes(int N, int L) { return pair_terms_blob_floats(N, L) * sizeof(float); }
 

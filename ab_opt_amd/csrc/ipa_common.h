@@ -131,6 +131,7 @@ int launch_ipa_core_kernel(const float* qfrag, const float* kvfrag, const float*
                            const float* w_pair_bias, float* feat, float* dump, float* dump_stats, const float* pair_bias_cache, int N, int L,
                            hipStream_t st, int z_shared, float* split_ws = nullptr, size_t split_ws_floats = 0, const float* pair_terms = nullptr);
 bool ipa_core32_applies(int N, int L, int z_shared = 0);           // the launch geometry takes the 32-row kernels (with a bias cache)
+bool bias_slab_fits_u32(int N, int L, int z_shared = 0);          // one layer of the bias cache of this batch is below 4 GB (ipa_core.hip)
 size_t pair_terms_floats(int Nz, int L);
 size_t pair_terms_blob_floats(int Nz, int L);
 int launch_pair_terms(const float* z, float* blob, int Nz, int L, hipStream_t st);

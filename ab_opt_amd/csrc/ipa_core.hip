@@ -23,6 +23,7 @@
 // Operands arrive pre-arranged in MFMA fragment order (ipa.hip: ipa_frags_kernel): every global load of the A / C waves and
 // every LDS access of the S/P tile is a conflict-free, fully coalesced 16 bytes per lane.
 #include <cstdlib>
+#include <type_traits>
 #include "tail_common.h"
 #include "kernels.h"
 
@@ -151,7 +152,12 @@ __global__ __launch_bounds__(NTH) void ipa_core_kernel(const float* __restrict__
 #pragma unroll
         for (int ii = 0; ii < RPW; ++ii)
             pbrow[ii] = CACHED ? reinterpret_cast<const char*>(pbc + (zbase + min(i0 + il0 + ii, L - 1)) * (H * JC)) : nullptr;
-        const unsigned pb_chunk = (unsigned)((N / (z_shared ? z_shared : 1)) * L) * (unsigned)(H * JC * 4);      // bytes from a row's chunk to its next one
+        // bytes from a row's chunk to its next one: the rows of the whole batch.  In the sampler's form (neither DUMP nor SPLIT) this and the chunk offset below, a
+        // wave-uniform product, are 64 bits wide: from 1366 distinct samples at L = 256 a layer's slab passes 4 GB, and the dispatcher sends exactly those batches to the
+        // 16-row kernels (use_core32).  DUMP and SPLIT keep 32-bit offsets (wider ones cost them 16 / 36 more bytes of scratch per lane) and are never launched on such
+        // a slab (bias_slab_fits_u32: launch_ipa_core_kernel)
+        using pbo_t = std::conditional_t<DUMP || SPLIT, unsigned, size_t>;
+        const pbo_t pb_chunk = (pbo_t)(N / (z_shared ? z_shared : 1)) * (pbo_t)L * (pbo_t)(H * JC * 4);
         const unsigned pb_lane = (unsigned)(min(fm, H - 1) * JC + kq * 4) * 4u;
         // the dump goes out through a buffer descriptor: base = this sample's [12,L,L] slab (SGPRs), one lane-constant byte offset
         // (head, key group) and a wave-uniform row/chunk offset -- no 64-bit per-lane addresses in the hot loop
@@ -165,7 +171,7 @@ __global__ __launch_bounds__(NTH) void ipa_core_kernel(const float* __restrict__
         const int ch_ = chunk_of(min((CH), ncl - 1));                          /* past the end: harmless re-read */      \
         _Pragma("unroll") for (int r_ = 0; r_ < 4; ++r_)                                                                \
             ring[SLOT][r_] = ZLOAD(reinterpret_cast<const f32x4*>(zrow[II] + ((unsigned)min(ch_ * JC + kq * 4 + r_, L - 1) * (unsigned)(C * 4) + lane_b))); \
-        if (CACHED) ringb[SLOT] = ZLOAD(reinterpret_cast<const f32x4*>(pbrow[II] + ((unsigned)ch_ * pb_chunk + pb_lane))); \
+        if (CACHED) ringb[SLOT] = ZLOAD(reinterpret_cast<const f32x4*>(pbrow[II] + ((pbo_t)ch_ * pb_chunk + pb_lane))); \
     }
 // z and its bias cache are read once per launch: non-temporal loads (measured 182 -> 174 us per launch at N=32, L=256)
 #define ZLOAD(p) __builtin_nontemporal_load(p)
@@ -518,7 +524,7 @@ __global__ __launch_bounds__(NTH) void ipa_core_persist_kernel(const float* __re
         const unsigned lane_b = (unsigned)fm * 16u;
         const unsigned pb_lane = (unsigned)(min(fm, H - 1) * JC + kq * 4) * 4u;
         const char *zrow[RPW], *pbrow[RPW], *zrow_n[RPW], *pbrow_n[RPW];     // wave-uniform row bases of the current and the next block
-        const unsigned pb_chunk = (unsigned)(((total_blocks / nib) / (z_shared ? z_shared : 1)) * L) * (unsigned)(H * JC * 4);
+        const size_t pb_chunk = (size_t)((total_blocks / nib) / (z_shared ? z_shared : 1)) * (size_t)L * (size_t)(H * JC * 4);     // 64 bits, as in ipa_core_kernel
         auto rows_of = [&](const PBlk& b, const char** zr, const char** pr) {
 #pragma unroll
             for (int ii = 0; ii < RPW; ++ii) {
@@ -538,7 +544,7 @@ __global__ __launch_bounds__(NTH) void ipa_core_persist_kernel(const float* __re
         const char* pr_ = (nx_ && has_next) ? pbrow_n[II] : pbrow[II];                                                   \
         _Pragma("unroll") for (int r_ = 0; r_ < 4; ++r_)                                                                \
             ring[SLOT][r_] = ZLOAD(reinterpret_cast<const f32x4*>(zr_ + ((unsigned)min(ch_ * JC + kq * 4 + r_, L - 1) * (unsigned)(C * 4) + lane_b))); \
-        ringb[SLOT] = ZLOAD(reinterpret_cast<const f32x4*>(pr_ + ((unsigned)ch_ * pb_chunk + pb_lane)));   \
+        ringb[SLOT] = ZLOAD(reinterpret_cast<const f32x4*>(pr_ + ((size_t)ch_ * pb_chunk + pb_lane)));     \
     }
         PBlk bk = blk(0);
         rows_of(bk, zrow, pbrow);
@@ -1796,11 +1802,15 @@ static int core32_remap(int N, int z_shared) {
     if (z_shared > 1 && z_shared < N && N % z_shared == 0 && (N / z_shared) % 8 == 0) return 2;
     return (N % 8 == 0) ? 1 : 0;
 }
+// Whether 32-bit byte offsets reach every element of one layer's chunk-major slab of the bias cache (distinct samples x L rows x chunks x 768 bytes < 4 GB: up to 1365
+// distinct samples at L = 256).  Beyond it only ipa_core_persist_kernel and ipa_core_kernel<false, true, false> run, whose offsets are 64 bits wide.
+bool bias_slab_fits_u32(int N, int L, int z_shared) {
+    return (int64_t)(z_shared > 1 ? N / z_shared : N) * L * ((L + JC - 1) / JC) * (H * JC * 4) < (1ll << 32);
+}
 static bool use_core32(int N, int L, int cus, int z_shared) {
     const char* e = getenv("ABOPT_CORE32");
     if (L > 2048) return false;                                 // its buffer descriptors address a sample's z slab (L^2 * 256 bytes) with 32-bit offsets
-    // ... and ONE descriptor addresses a block's whole chunk-major slab of the bias cache (distinct samples x L rows x chunks x 768 bytes): 1365 distinct samples at L = 256
-    if ((int64_t)(z_shared > 1 ? N / z_shared : N) * L * ((L + JC - 1) / JC) * (H * JC * 4) >= (1ll << 32)) return false;
+    if (!bias_slab_fits_u32(N, L, z_shared)) return false;      // ... and ONE descriptor addresses a block's whole slab of the bias cache
     if (e && e[0] == '0') return false;
     if (e && e[0] == '1') return L > BI;
     if (cus < 8) return false;
@@ -1881,6 +1891,10 @@ int launch_ipa_core_kernel(const float* qfrag, const float* kvfrag, const float*
                            int z_shared, float* split_ws, size_t split_ws_floats, const float* pair_terms) {
     ABOPT_CHECK_ARG(!dump == !dump_stats, "ipa_core: the logits dump and its row statistics come together");
     ABOPT_CHECK_ARG(!dump || (int64_t)H * L * L * 4 < (1ll << 31), "ipa_core: L=%d too long for the logits dump", L);
+    if (dump && pair_bias_cache && !bias_slab_fits_u32(N, L, z_shared)) {
+        set_error("ipa_core: the logits dump reads a pair-bias cache through 32-bit offsets and this one (%d x %d rows) is 4 GB or more per layer; pass none", N, L);
+        return ABOPT_EUNSUPPORTED;
+    }
     int cus32 = 0;
     if (pair_bias_cache && !dump) { if (int rc = device_cu_count(&cus32)) return rc; }
     if (pair_bias_cache && !dump && use_core32(N, L, cus32, z_shared)) {
@@ -1922,7 +1936,7 @@ int launch_ipa_core_kernel(const float* qfrag, const float* kvfrag, const float*
             return ABOPT_OK;
         }
     }
-    if (pair_bias_cache && !dump && split_ws && !getenv("ABOPT_CORE_NO_SPLIT")) {
+    if (pair_bias_cache && !dump && split_ws && !getenv("ABOPT_CORE_NO_SPLIT") && bias_slab_fits_u32(N, L, z_shared)) {
         // small batches: split the keys of every query block over 2 or 4 workgroups (see the SPLIT note at ipa_core_kernel)
         const int nib = (L + BI - 1) / BI, nchunk = (L + JC - 1) / JC, total = N * nib;
         int cus = 0;

@@ -67,6 +67,7 @@ struct HeadsEpilogue { const float *R = nullptr, *v_t = nullptr; const uint8_t* 
 // rows.hip: the device word the heads' epilogue raises on a non-finite output (abopt_nonfinite_flag)
 unsigned* nonfinite_flag_ptr();
 int nonfinite_flag_read(int reset, hipStream_t st, int* flag);
+int nonfinite_flag_reset(hipStream_t st);
 int launch_heads_mlp(const float* xe, const float* beta, const float* wfrag, const float* w1, int ld1, const float* b1, const float* b2c,
                      const float* b2r, const float* b2s, const float* b3c, const float* b3r, const float* b3s, float* out3, int64_t rows, int L,
                      hipStream_t st,

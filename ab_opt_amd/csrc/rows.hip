@@ -120,6 +120,7 @@ __global__ __launch_bounds__(256) void heads_epilogue_kernel(const float* __rest
 }
 
 __device__ unsigned g_nonfinite_flag;
+// TODO (ADVICE.md, round 6, rows.hip): one cached symbol address for the whole process -- a second device in the same process needs its own (per ordinal, as LdsConfig)
 unsigned* nonfinite_flag_ptr() {
     static unsigned* p = nullptr;
     if (!p && hipGetSymbolAddress(reinterpret_cast<void**>(&p), HIP_SYMBOL(g_nonfinite_flag)) != hipSuccess) p = nullptr;
@@ -133,6 +134,14 @@ int nonfinite_flag_read(int reset, hipStream_t st, int* flag) {
     ABOPT_HIP(hipStreamSynchronize(st));
     if (reset && h) ABOPT_HIP(hipMemsetAsync(p, 0, sizeof(h), st));
     *flag = h ? 1 : 0;
+    return ABOPT_OK;
+}
+
+// Clears the flag in stream order: no copy to the host, no synchronisation (legal inside a stream capture, where it becomes a memset node).
+int nonfinite_flag_reset(hipStream_t st) {
+    unsigned* p = nonfinite_flag_ptr();
+    ABOPT_CHECK_ARG(p != nullptr, "nonfinite_flag: no device symbol");
+    ABOPT_HIP(hipMemsetAsync(p, 0, sizeof(unsigned), st));
     return ABOPT_OK;
 }
 

@@ -245,14 +245,14 @@ class FullDPM(nn.Module):
         """Range guard of the two-term fp16 layers (include/abopt.h: abopt_nonfinite_flag): the reference's fp32 layers take activations beyond 65504, the
         fp16 terms do not (inf -> NaN in the heads' outputs, which raises a device flag).  One flag read per call; if it is up, the whole loop is repeated
         with the dense layers as fp32 GEMMs -- the caller gets what the reference's arithmetic gives (NaN only where fp32 itself overflows)."""
-        hip.nonfinite_flag(reset=True)
+        hip.nonfinite_flag_reset()                   # in stream order, no synchronisation: the flag read below is this call's
         out = run()
-        if hip.nonfinite_flag(reset=True):
+        if hip.nonfinite_flag(reset=False):
             import warnings
             warnings.warn('ab_opt_amd: a denoiser activation left the fp16 range (|x| >= 65504) or an input was not finite; this call is repeated with '
                           'the dense layers as fp32 GEMMs (slower, fp32 range)', RuntimeWarning, stacklevel=3)
             out = rerun()
-            hip.nonfinite_flag(reset=True)
+            hip.nonfinite_flag_reset()
         return out
 
     def _to_traj(self, T0, tv, tp, ts, tpr, tpp, first_extra):

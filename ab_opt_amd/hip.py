@@ -12,7 +12,7 @@ import torch
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # ABOPT_LIB_PATH: developer override to load a variant build of the same ABI (csrc/Makefile VARIANT=...: A/B of two source trees)
 LIB_PATH = os.environ.get('ABOPT_LIB_PATH') or os.path.join(_HERE, 'libabopt_hip.so')
-ABI_VERSION = 42
+ABI_VERSION = 43
 
 c_f = C.c_void_p        # device float*
 c_i64 = C.c_void_p      # device int64*
@@ -77,7 +77,7 @@ class StepNoise(C.Structure):
 
 EXPORTS = ['abopt_abi_version', 'abopt_last_error', 'abopt_device_info', 'abopt_so3_exp', 'abopt_so3_log',
            'abopt_ga_workspace_bytes', 'abopt_ga_block_forward', 'abopt_ga_block_forward_cached', 'abopt_ga_encoder_forward',
-           'abopt_eps_workspace_bytes', 'abopt_eps_net_forward', 'abopt_pair_bias_cache_bytes', 'abopt_pair_bias_cache', 'abopt_pair_terms_bytes', 'abopt_pair_terms', 'abopt_pair_terms_used', 'abopt_nonfinite_flag', 'abopt_denoise_step', 'abopt_sample_init',
+           'abopt_eps_workspace_bytes', 'abopt_eps_net_forward', 'abopt_pair_bias_cache_bytes', 'abopt_pair_bias_cache', 'abopt_pair_terms_bytes', 'abopt_pair_terms', 'abopt_pair_terms_used', 'abopt_nonfinite_flag', 'abopt_nonfinite_flag_reset', 'abopt_denoise_step', 'abopt_sample_init',
            'abopt_add_noise', 'abopt_gemm', 'abopt_gemm_tn_grouped', 'abopt_colsum', 'abopt_adam_step', 'abopt_adam_ws_floats', 'abopt_bucket_colsum', 'abopt_segment_bucket_colsum', 'abopt_heads_epilogue_forward', 'abopt_heads_epilogue_backward', 'abopt_dpm_losses', 'abopt_abdock_losses', 'abopt_layer_norm_forward', 'abopt_layer_norm_backward', 'abopt_residue_features', 'abopt_residue_features_workspace_bytes', 'abopt_commonness_score', 'abopt_prof_enable', 'abopt_prof_collect', 'abopt_prof_peek', 'abopt_prof_clock', 'abopt_prof_spans_reset', 'abopt_prof_spans',
            'abopt_reconstruct_backbone_partially', 'abopt_ipa_train_workspace_bytes', 'abopt_ipa_core_train_forward', 'abopt_ipa_points_backward', 'abopt_ipa_backward_operands', 'abopt_ipa_backward_assemble', 'abopt_ipa_pair_backward', 'abopt_ipa_dz_assemble',
            'abopt_residue_embed_workspace_bytes', 'abopt_residue_embed_forward', 'abopt_pair_embed_workspace_bytes', 'abopt_pair_embed_forward',
@@ -123,6 +123,7 @@ def lib():
         L.abopt_pair_terms.argtypes = [c_f, c_f, C.c_int, C.c_int, C.c_int, C.c_void_p]
         L.abopt_pair_terms_used.argtypes = [C.c_int] * 3
         L.abopt_nonfinite_flag.argtypes = [C.c_int, C.c_void_p]
+        L.abopt_nonfinite_flag_reset.argtypes = [C.c_void_p]
         L.abopt_pair_bias_cache_bytes.restype = C.c_size_t
         L.abopt_pair_bias_cache_bytes.argtypes = [C.c_int] * 3
         L.abopt_pair_bias_cache.argtypes = [C.POINTER(GaWeights), C.c_int, c_f, c_f, C.c_int, C.c_int, C.c_int, C.c_void_p]
@@ -472,6 +473,11 @@ def nonfinite_flag(reset=True):
     if r < 0:
         raise RuntimeError('abopt_nonfinite_flag: ' + last_error())
     return bool(r)
+
+
+def nonfinite_flag_reset():
+    """Clears the flag in stream order on the current stream: no synchronisation (include/abopt.h: abopt_nonfinite_flag_reset)."""
+    _check(lib().abopt_nonfinite_flag_reset(stream()))
 
 
 def pair_terms_bytes(N, L):

@@ -197,6 +197,7 @@ class EpsilonNet(nn.Module):
         if no_bins is not None:
             self.prmsd_predictor = PerResidueRMSDCaPredictor(no_bins, F + 3, F)
         self._pack = None
+        self._pack32 = None                      # packed_fp32(): built by the first range-guard fallback
         # packed (kernel-layout) weight copies are keyed on (data_ptr, _version, device) of their sources; writes that bypass the
         # version counter (`p.data.copy_(ema)`) are invisible to that key, so the usual entry points drop the packs outright
         self.register_load_state_dict_post_hook(_drop_packs)
@@ -204,7 +205,7 @@ class EpsilonNet(nn.Module):
     def invalidate_packed(self):
         """Forget the kernel-layout weight copies (rebuilt at the next call).  Call after writing parameters through `.data`
         (EMA swaps); `load_state_dict`, `train()` and `eval()` call it for you."""
-        self._pack = None
+        self._pack = self._pack32 = None
         for b in self.encoder.blocks:
             b.invalidate_packed()
 
@@ -215,7 +216,7 @@ class EpsilonNet(nn.Module):
 
     def __getstate__(self):
         d = dict(self.__dict__)
-        d['_pack'] = None                        # ctypes structs + device copies: rebuilt on first use
+        d['_pack'] = d['_pack32'] = None         # ctypes structs + device copies: rebuilt on first use
         return d
 
     def _sources(self):
@@ -272,7 +273,7 @@ class EpsilonNet(nn.Module):
         """The same weights WITHOUT the packed two-term fp16 operands: every dense layer then runs as an fp32 GEMM (fp32's range; the fallback of the
         range guard, include/abopt.h: abopt_nonfinite_flag).  Cached next to packed()."""
         ew = self.packed()
-        if getattr(self, '_pack32', None) is not None and self._pack32[0] is ew:
+        if self._pack32 is not None and self._pack32[0] is ew:
             return self._pack32[2]
         n = len(self.encoder.blocks)
         arr = (hip.GaWeights * max(n, 1))()
@@ -289,17 +290,24 @@ class EpsilonNet(nn.Module):
 
     @torch.no_grad()
     def forward(self, v_t, p_t, s_t, res_feat, pair_feat, beta, mask_generate, mask_res, grad_mode=False):
-        """dpm_full.py:70-112 -> (v_next, R_next, eps_pos, c_denoised[, prmsd_logits])."""
-        hip.nonfinite_flag(reset=True)
+        """dpm_full.py:70-112 -> (v_next, R_next, eps_pos, c_denoised[, prmsd_logits]).
+
+        Range guard (include/abopt.h: abopt_nonfinite_flag): the flag is cleared in stream order before the call and read ONCE after it (the only synchronisation),
+        so it reports this call alone -- a flag left up by earlier work on the stream (a raw hip.eps_net_forward) is not inherited -- and it is down again when
+        forward returns.  While the current stream is capturing (a caller's own torch.cuda.graph around this call) the host can neither read nor clear the flag:
+        the call is recorded as it is, without a fallback, and the caller reads hip.nonfinite_flag() after a replay."""
+        guard = res_feat.is_cuda and not torch.cuda.is_current_stream_capturing()
+        if guard:
+            hip.nonfinite_flag_reset()
         o = hip.eps_net_forward(self.packed(), v_t, p_t, s_t, res_feat, pair_feat, beta, mask_generate, mask_res,
                                 self.no_bins is not None, self.no_bins or 0, grad_mode)
-        if hip.nonfinite_flag(reset=True):          # range guard of the two-term fp16 layers (include/abopt.h: abopt_nonfinite_flag): repeat on fp32 GEMMs
+        if guard and hip.nonfinite_flag(reset=False):          # range guard of the two-term fp16 layers: repeat on fp32 GEMMs
             import warnings
             warnings.warn('ab_opt_amd: a denoiser activation left the fp16 range (|x| >= 65504) or an input was not finite; EpsilonNet.forward is repeated '
                           'with the dense layers as fp32 GEMMs', RuntimeWarning, stacklevel=2)
             o = hip.eps_net_forward(self.packed_fp32(), v_t, p_t, s_t, res_feat, pair_feat, beta, mask_generate, mask_res,
                                     self.no_bins is not None, self.no_bins or 0, grad_mode)
-            hip.nonfinite_flag(reset=True)
+            hip.nonfinite_flag_reset()                         # (fp32 itself may overflow: the answer is then the reference's, and the flag is this call's to clear)
         if self.no_bins is not None:
             return o['v_next'], o['R_next'], o['eps_pos'], o['c'], o['prmsd_logits']
         return o['v_next'], o['R_next'], o['eps_pos'], o['c']

@@ -373,7 +373,11 @@ def eps_net(net, v_t, p_t, s_t, res_feat, pair_feat, beta, mask_generate, mask_r
     R = hip.so3_exp(v_t.detach().float())
     x = _mlp(net.res_feat_mixer, torch.cat([res_feat, embed_rows(net.current_sequence_embedding, s_t)], dim=-1))
     # proj_pair_bias(pair_feat) of all blocks in one pass over pair_feat (the sampler's per-call cache, rebuilt every training step)
-    caches = hip.pair_bias_cache_layers([blk.proj_pair_bias.weight for blk in net.encoder.blocks], pair_feat.detach())
+    # (the training core addresses a layer's slab with 32-bit offsets and refuses one of 4 GB or more: such a batch computes the bias in place, the same bits)
+    if hip.pair_bias_cache_bytes(pair_feat.shape[0], L, 1) < (1 << 32):
+        caches = hip.pair_bias_cache_layers([blk.proj_pair_bias.weight for blk in net.encoder.blocks], pair_feat.detach())
+    else:
+        caches = [None] * len(net.encoder.blocks)
     zsink = dict(buf=None, users=0) if pair_feat.requires_grad else None
     for blk, pbc in zip(net.encoder.blocks, caches):
         x = ga_block(blk, R, p_t, x, pair_feat, mask_res, pbc=pbc, zsink=zsink)

@@ -23,7 +23,7 @@
 extern "C" {
 #endif
 
-#define ABOPT_ABI_VERSION 42
+#define ABOPT_ABI_VERSION 43
 
 enum { ABOPT_OK = 0, ABOPT_EINVAL = 1, ABOPT_EHIP = 2, ABOPT_EUNSUPPORTED = 3, ABOPT_EWORKSPACE = 4 };
 
@@ -184,6 +184,13 @@ int abopt_pair_bias_cache(const abopt_ga_weights* blocks, int num_layers, const 
  * sees 1 repeats the work with the packed-weight pointers set to NULL: the same layers then run as fp32 GEMMs with fp32's range (ab_opt_amd/dpm.py does,
  * once per sample() / optimize() call; tests/test_hip_parity.py::test_fp16_range_guard_falls_back_to_fp32_layers). */
 int abopt_nonfinite_flag(int reset, abopt_stream stream);
+/* The same flag cleared in stream order (ABI 43): a memset enqueued on `stream`, no copy to the host and no synchronisation.  A guarded call is
+ *   abopt_nonfinite_flag_reset -> abopt_eps_net_forward ... -> abopt_nonfinite_flag(reset = 1)        (one synchronisation, after the work)
+ * so a flag left up by earlier work on the stream is not taken for this call's.  abopt_nonfinite_flag itself synchronises and therefore must not be called while
+ * `stream` is capturing: a caller that captures abopt_eps_net_forward in a graph of its own gets no fallback inside the graph (ab_opt_amd.modules.EpsilonNet.forward
+ * then touches the flag neither before nor after) and reads abopt_nonfinite_flag after a replay -- a replay that produced a non-finite head output leaves it up
+ * (tests/test_large_and_guard.py::test_eps_net_captured_in_a_user_graph_leaves_the_flag_to_the_caller). */
+int abopt_nonfinite_flag_reset(abopt_stream stream);
 
 /* Per-call pair terms (ABI 41): pair_feat re-laid as the fp16 operands of the pair aggregation sum_j alpha[i,j,h] z[i,j,:] (ga.py:114-118), built once per
  * FullDPM.sample / optimize call next to the bias cache (same constancy argument).  Every value becomes two fp16 terms h = fp16(S_i z), l = fp16(S_i z - h)

@@ -34,6 +34,34 @@ def test_library_exports_every_declared_symbol():
     assert hip.lib() is not None
 
 
+def test_size_queries_are_exact_past_32_bits():
+    """abopt_pair_bias_cache_bytes / abopt_pair_terms_bytes against the closed forms of include/abopt.h, on either side of the documented 32-bit limits: a layer of the
+    bias cache is rows x chunks x 768 bytes (rows = N L, chunks = ceil(L / 16)) and passes 4 GB between 1365 and 1366 samples of L = 256; the terms are
+    rows x chunks x 4096 bytes + 256 bytes of scales per row.  A count computed in 32 bits anywhere on the way would come back modulo 2^32."""
+    for N, L in [(1365, 256), (1366, 256), (3000, 256), (1, 2048), (1, 2049), (7, 2049), (1, 1), (0, 256)]:
+        rows, chunks = N * L, (L + 15) // 16
+        for layers in (1, 6, 8):
+            assert hip.pair_bias_cache_bytes(N, L, layers) == layers * rows * chunks * 768, (N, L, layers)
+        assert hip.pair_terms_bytes(N, L) == rows * chunks * 4096 + rows * 256, (N, L)
+    assert hip.pair_bias_cache_bytes(1365, 256, 1) < (1 << 32) <= hip.pair_bias_cache_bytes(1366, 256, 1)
+    assert hip.pair_bias_cache_bytes(3000, 256, 6) == 56623104000
+
+
+def test_training_core_refuses_a_bias_cache_slab_of_4GB_before_any_launch():
+    """The training core (the logits-dumping kernel) keeps 32-bit offsets into the bias cache, so abopt_ipa_core_train_forward refuses a cache whose layer is 4 GB or
+    more with ABOPT_EUNSUPPORTED and a message -- ahead of the workspace check and of every launch: the 16-byte dummies below are never touched (no device is needed).
+    One sample fewer passes the size check and stops at the (equally early) workspace check; without a cache the size does not matter."""
+    L_ = hip.lib()
+    dummy = (ctypes.c_char * 16)()
+    a = ctypes.c_void_p(ctypes.addressof(dummy))
+    call = lambda N, pbc: L_.abopt_ipa_core_train_forward(a, a, a, a, a, a, a, pbc, a, a, N, 256, 64, a, 16, None)
+    assert call(1366, a) == 3                                               # ABOPT_EUNSUPPORTED
+    msg = L_.abopt_last_error().decode()
+    assert '4 GB' in msg and '1366 x 256' in msg, msg
+    assert call(1365, a) == 4 and 'workspace too small' in L_.abopt_last_error().decode()       # ABOPT_EWORKSPACE
+    assert call(1366, None) == 4
+
+
 def test_struct_layouts_match_header_field_order():
     """ctypes mirrors must list the header's fields in order (layout is positional)."""
     src = open(HEADER).read()
