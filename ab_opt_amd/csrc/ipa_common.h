@@ -1,10 +1,10 @@
 // Shared constants / helpers of the IPA-core kernels (gfx950).
 #pragma once
 #include "abopt_common.h"
+#include "ipa_plan.h"     // H, D, P, C, BI, JC, BI2, SPLIT_ROW and the dispatch of the core (host only)
 
 namespace abopt {
 
-constexpr int H = ABOPT_HEADS, D = ABOPT_QK_DIM, P = ABOPT_POINTS, C = 64;
 // Row layout of the per-residue projection buffer: the 2016 outputs of the fused node projection GEMM
 // (q|k|v|q_pts|k_pts|v_pts) followed by the squared norms of the 8 global-frame query / key points of every head
 // (written by points_to_global), padded to 2048 floats = one 8 KB row.
@@ -15,8 +15,6 @@ constexpr int FEAT = ABOPT_IPA_FEAT;         // 1824
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
-constexpr int BI = 16;            // query rows per workgroup
-constexpr int JC = 16;            // key rows per chunk
 constexpr int PLD = JC + 4;       // row stride of the S/P tile (floats)
 constexpr int ZSLD = C + 4;       // row stride of the z staging tile (floats)
 constexpr int NPT = H * P * 3;    // 288 point coordinates per residue
@@ -131,11 +129,9 @@ int launch_ipa_core_kernel(const float* qfrag, const float* kvfrag, const float*
                            const float* w_pair_bias, float* feat, float* dump, float* dump_stats, const float* pair_bias_cache, int N, int L,
                            hipStream_t st, int z_shared, float* split_ws = nullptr, size_t split_ws_floats = 0, const float* pair_terms = nullptr);
 bool ipa_core32_applies(int N, int L, int z_shared = 0);           // the launch geometry takes the 32-row kernels (with a bias cache)
-bool bias_slab_fits_u32(int N, int L, int z_shared = 0);          // one layer of the bias cache of this batch is below 4 GB (ipa_core.hip)
 size_t pair_terms_floats(int Nz, int L);
 size_t pair_terms_blob_floats(int Nz, int L);
 int launch_pair_terms(const float* z, float* blob, int Nz, int L, hipStream_t st);
-size_t ipa_split_ws_floats(int N, int L);
 int read_clock_probe(long long* cycles, long long* wall_ticks);
 int launch_pair_bias_cache(const float* z, const float* const* wb, int num_layers, float* cache, int N, int L, hipStream_t st);
 

@@ -39,7 +39,6 @@ constexpr float kLog2e = 1.4426950408889634f;
 constexpr float kSqrt13 = 0.5773502691896258f;   // sqrt(1/3), ga.py:165
 constexpr float kScale2 = kSqrt13 * kLog2e;            // logits are kept in base-2 units: p = exp2(l2 - m2)
 constexpr float kMask2 = 1e5f * kLog2e;           // the reference's additive -1e5 on masked pairs (ga.py:20-23), same units
-constexpr int SPLIT_ROW = H * C + H * D + H * P * 3;   // 1440 unnormalised accumulators per row and key slice
 
 // position of key group kq (keys 4 kq .. 4 kq + 3) inside head h's 16-key row of the S/P tile.  The rotation by h >> 1 makes the
 // pair waves' 16-byte reads AND writes (lane = (head, key group)) bank-conflict free; see DESIGN.md section 3.1.
@@ -154,8 +153,8 @@ __global__ __launch_bounds__(NTH) void ipa_core_kernel(const float* __restrict__
             pbrow[ii] = CACHED ? reinterpret_cast<const char*>(pbc + (zbase + min(i0 + il0 + ii, L - 1)) * (H * JC)) : nullptr;
         // bytes from a row's chunk to its next one: the rows of the whole batch.  In the sampler's form (neither DUMP nor SPLIT) this and the chunk offset below, a
         // wave-uniform product, are 64 bits wide: from 1366 distinct samples at L = 256 a layer's slab passes 4 GB, and the dispatcher sends exactly those batches to the
-        // 16-row kernels (use_core32).  DUMP and SPLIT keep 32-bit offsets (wider ones cost them 16 / 36 more bytes of scratch per lane) and are never launched on such
-        // a slab (bias_slab_fits_u32: launch_ipa_core_kernel)
+        // 16-row kernels.  DUMP and SPLIT keep 32-bit offsets (wider ones cost them 16 / 36 more bytes of scratch per lane) and are never launched on such
+        // a slab (ipa_plan.h: plan_ipa_core, slab_u32)
         using pbo_t = std::conditional_t<DUMP || SPLIT, unsigned, size_t>;
         const pbo_t pb_chunk = (pbo_t)(N / (z_shared ? z_shared : 1)) * (pbo_t)L * (pbo_t)(H * JC * 4);
         const unsigned pb_lane = (unsigned)(min(fm, H - 1) * JC + kq * 4) * 4u;
@@ -485,6 +484,10 @@ __device__ __attribute__((noinline)) void persist_point_epilogue(const float* __
     }
 }
 
+// dynamic LDS of ipa_core_persist_kernel, in the order of its carve-up: sp | qf | scl | lsum | ptsb | two key masks
+__host__ __device__ constexpr size_t persist_lds_bytes(int nchunk) {
+    return sizeof(float) * (3 * BI * SROW + H * 4 * 64 * 4 + 2 * BI * SCLD + BI * SCLD + BI * H * P * 3) + 2 * (size_t)nchunk * JC;
+}
 // Short crops (L <= 64, the reference's CDR + 20 antigen residues: a block is over after 2..4 positions and the per-block pieces set the
 // pace -- at L = 48, by barrier waits per interval class: the A waves' point epilogue ~10k cycles, their q' swap ~6k,
 // the C waves' block epilogue ~7k on top of 3 x 9k of positions, the pair waves waiting at 60 % of the barriers) were tried in a
@@ -821,7 +824,7 @@ __global__ __launch_bounds__(NTH) void ipa_core_persist_kernel(const float* __re
 // core: +4.5 %.
 // Pair terms (ZT) are chunk-major, [chunk][row of the batch][4 KB]: every workgroup of a launch reads the SAME chunk of its rows at the same time,
 // so the live set of a chunk interval is ONE dense plane (33 MB at the bench shape) instead of 4 KB out of every 64 KB row.
-constexpr int BI2 = 32, NPW2 = 4, RPW2 = BI2 / NPW2, NTH2 = 512, HPW = 6;
+constexpr int NPW2 = 4, RPW2 = BI2 / NPW2, NTH2 = 512, HPW = 6;
 
 #define C32_L2(x, r) __builtin_fmaf((x), kScale2, mterm_[r])
 // FUSE (round 4): the block's tail -- out_transform, mask, residual, LayerNorm, mlp_transition, LayerNorm (ga.py:174-177) -- runs as the
@@ -858,6 +861,7 @@ struct TailArgs {
     unsigned* xt;           // optional: the output rows as two fp16 terms as well (tail_common.h: tail_p2_run)
 };
 constexpr int C32_LOOP_LDS_FLOATS = 3 * 32 * SROW + 2 * 32 * SCLD + 32 * SCLD + 32 * 32;      // sp | scl | lsum | mlr (then the key mask)
+__host__ __device__ constexpr size_t core32_lds_bytes(int nchunk) { return sizeof(float) * C32_LOOP_LDS_FLOATS + (size_t)nchunk * JC; }     // ipa_core32_kernel<false, ZT>
 constexpr int C32F_PTS_OFF = ((C32_LOOP_LDS_FLOATS * 4 + 2048 + 255) / 256) * 256;               // aggregated points [32][12][24] fp32, behind the key mask of L <= 2048
 constexpr int C32F_PTSLD = H * P * 3 + 4;                                                          // row stride of the aggregated points (292 floats: rows 36 banks apart)
 constexpr int C32F_LDS_BYTES = C32F_PTS_OFF + 32 * C32F_PTSLD * 4;
@@ -1766,13 +1770,22 @@ __global__ __launch_bounds__(256) void ipa_split_merge_kernel(const float* __res
     }
 }
 
-size_t ipa_split_ws_floats(int N, int L) {
-    const int nib = (L + BI - 1) / BI;
-    return ((int64_t)N * nib * 2 <= 256) ? (size_t)4 * N * L * (SPLIT_ROW + 2 * H) : 0;
+// The launch geometry as plan_ipa_core (ipa_plan.h) wants it: the CU count of the current device (needed only by the cached, non-dumping forms) and the
+// ABOPT_CORE32 / ABOPT_CORE_NO_SPLIT switches, read at every call
+static int core_query(int N, int L, int z_shared, bool cache, bool dump, bool split_ws, size_t split_ws_floats, CoreQuery* q) {
+    const char* e = getenv("ABOPT_CORE32");
+    *q = CoreQuery{N, L, z_shared, 0, cache, dump, split_ws, split_ws_floats, (e && e[0] == '0') ? 0 : ((e && e[0] == '1') ? 1 : -1), getenv("ABOPT_CORE_NO_SPLIT") != nullptr};
+    return (cache && !dump) ? device_cu_count(&q->cus) : ABOPT_OK;
+}
+
+bool ipa_core32_applies(int N, int L, int z_shared) {
+    CoreQuery q;
+    if (core_query(N, L, z_shared, true, false, false, 0, &q)) return false;
+    return plan_is_core32(q);
 }
 
 template <bool DUMP, bool CACHED>
-static int launch_core_variant(const float* qfrag, const float* kvfrag, const float* z, const uint8_t* mask, const float* R, const float* t,
+static int launch_core_variant(const CorePlan& plan, const float* qfrag, const float* kvfrag, const float* z, const uint8_t* mask, const float* R, const float* t,
                                const float* Wb, float* feat, float* dump, float* dump_stats, const float* pbc, int N, int L, hipStream_t st, int z_shared) {
     const int nib = (L + BI - 1) / BI, nchunk = (L + JC - 1) / JC;
     const size_t lds = core_lds_fixed_bytes<CACHED>() + (size_t)nchunk * JC;
@@ -1780,53 +1793,29 @@ static int launch_core_variant(const float* qfrag, const float* kvfrag, const fl
     static LdsConfig lds_cfg;                                               // per instantiation
     if (int rc = ensure_dynamic_lds(reinterpret_cast<const void*>(ipa_core_kernel<DUMP, CACHED>), lds, lds_cfg)) return rc;
     prof::begin(st);
-    hipLaunchKernelGGL((ipa_core_kernel<DUMP, CACHED>), dim3((unsigned)(N * nib)), dim3(NTH), lds, st, qfrag, kvfrag, z, mask, R, t, Wb, feat, dump, dump_stats, pbc,
-                       N, L, nib, (N % 8 == 0) ? 1 : 0, z_shared);
+    hipLaunchKernelGGL((ipa_core_kernel<DUMP, CACHED>), dim3(plan.grid), dim3(NTH), lds, st, qfrag, kvfrag, z, mask, R, t, Wb, feat, dump, dump_stats, pbc,
+                       N, L, nib, plan.remap, z_shared);
     prof::end(st);
     ABOPT_LAUNCH_CHECK();
     return ABOPT_OK;
 }
 
-// The 32-row kernel runs one block per workgroup, so it pays where its N * ceil(L / 32) workgroups fill the CUs in whole rounds
-// (tools/r03_c32_sweep.sh, r03_c32_sweep2.sh; microseconds per launch against the 16-row kernels on the same box):
-//   one round, more than half full, where the 16-row blocks no longer fit one round themselves (N L / 16 > CUs: the persistent kernel
-//   then walks two blocks per CU):  N = 23 / 24 / 28 / 32 at L = 256: 145 / 145 / 154 / 167 against 156 / 155 / 168 / 175; N = 32,
-//   L = 200: 123 against 132.  Up to N L / 16 = CUs the one-block 16-row kernel is the faster one (N = 16: 90 against 124).
-//   several rounds at least 95 % full:  N = 62 / 64: 334 / 335 against 344 / 345.  A half-empty last round loses (N = 48: 288 against
-//   259; N = 20, L = 400: 385 against 258).
-//   short lengths gain nothing (L = 128: equal; L = 64: 134 against 128).
-// ABOPT_CORE32=0 / 1 overrides (1: whenever 16 < L <= 2048).
-// block -> (sample, query block) mapping of the 32-row kernels: 2 = by complex (groups of z_shared samples, a multiple of 8 complexes),
-// 1 = all query blocks of a sample on one XCD (N % 8 == 0), 0 = plain
-static int core32_remap(int N, int z_shared) {
-    if (z_shared > 1 && z_shared < N && N % z_shared == 0 && (N / z_shared) % 8 == 0) return 2;
-    return (N % 8 == 0) ? 1 : 0;
-}
-// Whether 32-bit byte offsets reach every element of one layer's chunk-major slab of the bias cache (distinct samples x L rows x chunks x 768 bytes < 4 GB: up to 1365
-// distinct samples at L = 256).  Beyond it only ipa_core_persist_kernel and ipa_core_kernel<false, true, false> run, whose offsets are 64 bits wide.
-bool bias_slab_fits_u32(int N, int L, int z_shared) {
-    return (int64_t)(z_shared > 1 ? N / z_shared : N) * L * ((L + JC - 1) / JC) * (H * JC * 4) < (1ll << 32);
-}
-static bool use_core32(int N, int L, int cus, int z_shared) {
-    const char* e = getenv("ABOPT_CORE32");
-    if (L > 2048) return false;                                 // its buffer descriptors address a sample's z slab (L^2 * 256 bytes) with 32-bit offsets
-    if (!bias_slab_fits_u32(N, L, z_shared)) return false;      // ... and ONE descriptor addresses a block's whole slab of the bias cache
-    if (e && e[0] == '0') return false;
-    if (e && e[0] == '1') return L > BI;
-    if (cus < 8) return false;
-    const int64_t total = (int64_t)N * ((L + BI2 - 1) / BI2), rounds = (total + cus - 1) / cus;
-    // short crops (pose sampling: N = 1000 x L = 48): since the epilogue runs on two fp16 terms (round 5) the fused 32-row kernel wins wherever it fills
-    // the chip once -- 4.10 -> 3.80 ms per step at N = 1000 x L = 48, 3.60 -> 2.88 at 600 x 64, 0.95 -> 0.81 at 64 x 128; it loses below one workgroup
-    // per CU (32 x 128: 0.64 -> 0.72).  Rounds 3-4 had excluded L < 192 (three key chunks did not amortise a 40 us epilogue).
-    if (L < 192) return L > BI && total >= cus;
-    if (rounds == 1) return total * 100 >= (int64_t)cus * 53 && (int64_t)N * ((L + BI - 1) / BI) > cus;
-    return total * 100 >= rounds * cus * 95;
-}
-
-bool ipa_core32_applies(int N, int L, int z_shared) {
-    int cus = 0;
-    if (device_cu_count(&cus)) return false;
-    return use_core32(N, L, cus, z_shared);
+// ipa_core32_kernel<FUSE, ZT> from a Core32 plan: the core alone into `feat`, or (FUSE) core + tail with `ta`.  ZT: `pair_terms` is given.
+template <bool FUSE, bool ZT>
+static int launch_core32(const CorePlan& plan, const float* qfrag, const float* kvfrag, const float* z, const uint8_t* mask, const float* R, const float* t, float* feat,
+                         const float* pbc, int N, int L, hipStream_t st, int z_shared, const TailArgs& ta, const float* pair_terms) {
+    const int nib2 = (L + BI2 - 1) / BI2, nchunk = (L + JC - 1) / JC;
+    const size_t lds = FUSE ? (size_t)C32F_LDS_BYTES : core32_lds_bytes(nchunk);
+    ABOPT_CHECK_ARG(lds <= 160 * 1024, "ipa_core: L=%d needs %zu bytes of LDS for the key mask (max 163840)", L, lds);
+    static LdsConfig lds_cfg;                                               // per instantiation
+    if (int rc = ensure_dynamic_lds(reinterpret_cast<const void*>(ipa_core32_kernel<FUSE, ZT>), lds, lds_cfg)) return rc;
+    const float* zsc = ZT ? pair_terms + pair_terms_floats(z_shared ? N / z_shared : N, L) : nullptr;
+    prof::begin(st);
+    hipLaunchKernelGGL((ipa_core32_kernel<FUSE, ZT>), dim3(plan.grid), dim3(NTH2), lds, st, qfrag, kvfrag, z, mask, R, t, feat, pbc, L, nib2, plan.remap, z_shared, ta,
+                       prof::next_span_slot(), ZT ? pair_terms : nullptr, zsc);
+    prof::end(st);
+    ABOPT_LAUNCH_CHECK();
+    return ABOPT_OK;
 }
 
 // The whole block behind the projections in ONE launch (ipa_core32_kernel<true, ZT>: core + tail) where the 32-row kernel is the core of
@@ -1839,26 +1828,13 @@ int launch_ipa_block_fused(const float* qfrag, const float* kvfrag, const float*
     *fused = 0;
     const char* e = getenv("ABOPT_FUSE_TAIL");
     if (!pair_bias_cache || !wot || !wmf || (e && e[0] == '0')) return ABOPT_OK;
-    int cus = 0;
-    if (int rc = device_cu_count(&cus)) return rc;
-    if (!use_core32(N, L, cus, z_shared)) return ABOPT_OK;
-    const int nib2 = (L + BI2 - 1) / BI2;
-    static LdsConfig lds_cfg, lds_cfg_t;
-    TailArgs ta{wot, wmf, x, ubias, g1, be1, b0, b1, b2, g2, be2, out, reinterpret_cast<unsigned*>(xt_out)};
-    const float* zsc = pair_terms ? pair_terms + pair_terms_floats(z_shared ? N / z_shared : N, L) : nullptr;
-    if (pair_terms) {
-        if (int rc = ensure_dynamic_lds(reinterpret_cast<const void*>(ipa_core32_kernel<true, true>), C32F_LDS_BYTES, lds_cfg_t)) return rc;
-        prof::begin(st);
-        hipLaunchKernelGGL((ipa_core32_kernel<true, true>), dim3((unsigned)(N * nib2)), dim3(NTH2), C32F_LDS_BYTES, st, qfrag, kvfrag, z, mask, R, t, (float*)nullptr,
-                           pair_bias_cache, L, nib2, core32_remap(N, z_shared), z_shared, ta, prof::next_span_slot(), pair_terms, zsc);
-    } else {
-        if (int rc = ensure_dynamic_lds(reinterpret_cast<const void*>(ipa_core32_kernel<true, false>), C32F_LDS_BYTES, lds_cfg)) return rc;
-        prof::begin(st);
-        hipLaunchKernelGGL((ipa_core32_kernel<true, false>), dim3((unsigned)(N * nib2)), dim3(NTH2), C32F_LDS_BYTES, st, qfrag, kvfrag, z, mask, R, t, (float*)nullptr,
-                           pair_bias_cache, L, nib2, core32_remap(N, z_shared), z_shared, ta, prof::next_span_slot(), (const float*)nullptr, (const float*)nullptr);
-    }
-    prof::end(st);
-    ABOPT_LAUNCH_CHECK();
+    CoreQuery q;
+    if (int rc = core_query(N, L, z_shared, true, false, false, 0, &q)) return rc;
+    const CorePlan plan = plan_ipa_core(q);
+    if (plan.form != CoreForm::Core32) return ABOPT_OK;
+    const TailArgs ta{wot, wmf, x, ubias, g1, be1, b0, b1, b2, g2, be2, out, reinterpret_cast<unsigned*>(xt_out)};
+    if (int rc = pair_terms ? launch_core32<true, true>(plan, qfrag, kvfrag, z, mask, R, t, nullptr, pair_bias_cache, N, L, st, z_shared, ta, pair_terms)
+                            : launch_core32<true, false>(plan, qfrag, kvfrag, z, mask, R, t, nullptr, pair_bias_cache, N, L, st, z_shared, ta, nullptr)) return rc;
     *fused = 1;
     return ABOPT_OK;
 }
@@ -1891,81 +1867,55 @@ int launch_ipa_core_kernel(const float* qfrag, const float* kvfrag, const float*
                            int z_shared, float* split_ws, size_t split_ws_floats, const float* pair_terms) {
     ABOPT_CHECK_ARG(!dump == !dump_stats, "ipa_core: the logits dump and its row statistics come together");
     ABOPT_CHECK_ARG(!dump || (int64_t)H * L * L * 4 < (1ll << 31), "ipa_core: L=%d too long for the logits dump", L);
-    if (dump && pair_bias_cache && !bias_slab_fits_u32(N, L, z_shared)) {
+    CoreQuery q;
+    if (int rc = core_query(N, L, z_shared, pair_bias_cache != nullptr, dump != nullptr, split_ws != nullptr, split_ws_floats, &q)) return rc;
+    const CorePlan plan = plan_ipa_core(q);
+    const int nib = (L + BI - 1) / BI, nchunk = (L + JC - 1) / JC;
+    switch (plan.form) {
+    case CoreForm::Unsupported:
         set_error("ipa_core: the logits dump reads a pair-bias cache through 32-bit offsets and this one (%d x %d rows) is 4 GB or more per layer; pass none", N, L);
         return ABOPT_EUNSUPPORTED;
-    }
-    int cus32 = 0;
-    if (pair_bias_cache && !dump) { if (int rc = device_cu_count(&cus32)) return rc; }
-    if (pair_bias_cache && !dump && use_core32(N, L, cus32, z_shared)) {
-        const int nib2 = (L + BI2 - 1) / BI2, nchunk = (L + JC - 1) / JC;
-        const size_t lds = sizeof(float) * (3 * BI2 * SROW + 2 * BI2 * SCLD + BI2 * SCLD + BI2 * 32) + (size_t)nchunk * JC;
-        ABOPT_CHECK_ARG(lds <= 160 * 1024, "ipa_core: L=%d needs %zu bytes of LDS for the key mask (max 163840)", L, lds);
-        static LdsConfig lds_cfg, lds_cfg_t;
-        if (pair_terms) {
-            if (int rc = ensure_dynamic_lds(reinterpret_cast<const void*>(ipa_core32_kernel<false, true>), lds, lds_cfg_t)) return rc;
-            prof::begin(st);
-            hipLaunchKernelGGL((ipa_core32_kernel<false, true>), dim3((unsigned)(N * nib2)), dim3(NTH2), lds, st, qfrag, kvfrag, z, mask, R, t, feat, pair_bias_cache, L, nib2,
-                               core32_remap(N, z_shared), z_shared, TailArgs{}, prof::next_span_slot(), pair_terms, pair_terms + pair_terms_floats(z_shared ? N / z_shared : N, L));
-        } else {
-            if (int rc = ensure_dynamic_lds(reinterpret_cast<const void*>(ipa_core32_kernel<false, false>), lds, lds_cfg)) return rc;
-            prof::begin(st);
-            hipLaunchKernelGGL((ipa_core32_kernel<false, false>), dim3((unsigned)(N * nib2)), dim3(NTH2), lds, st, qfrag, kvfrag, z, mask, R, t, feat, pair_bias_cache, L, nib2,
-                               core32_remap(N, z_shared), z_shared, TailArgs{}, prof::next_span_slot(), (const float*)nullptr, (const float*)nullptr);
-        }
+    case CoreForm::Core32:
+        return pair_terms ? launch_core32<false, true>(plan, qfrag, kvfrag, z, mask, R, t, feat, pair_bias_cache, N, L, st, z_shared, TailArgs{}, pair_terms)
+                          : launch_core32<false, false>(plan, qfrag, kvfrag, z, mask, R, t, feat, pair_bias_cache, N, L, st, z_shared, TailArgs{}, nullptr);
+    case CoreForm::Persist: {
+        const size_t lds = persist_lds_bytes(nchunk);
+        ABOPT_CHECK_ARG(lds <= 160 * 1024, "ipa_core: L=%d needs %zu bytes of LDS for the key masks (max 163840)", L, lds);
+        static LdsConfig lds_cfg;
+        if (int rc = ensure_dynamic_lds(reinterpret_cast<const void*>(ipa_core_persist_kernel), lds, lds_cfg)) return rc;
+        prof::begin(st);
+        hipLaunchKernelGGL(ipa_core_persist_kernel, dim3(plan.grid), dim3(NTH), lds, st, qfrag, kvfrag, z, mask, R, t, feat, pair_bias_cache, L, nib, N * nib, plan.remap,
+                           z_shared);
         prof::end(st);
         ABOPT_LAUNCH_CHECK();
         return ABOPT_OK;
     }
-    if (pair_bias_cache && !dump) {
-        const int nib = (L + BI - 1) / BI, nchunk = (L + JC - 1) / JC;
-        int cus = 0;
-        if (int rc = device_cu_count(&cus)) return rc;
-        cus &= ~7;                                                          // a multiple of 8 keeps blockIdx & 7 = XCD for every block of a workgroup
-        const int total = N * nib;
-        if (nchunk >= 2 && cus >= 8 && total > cus) {
-            const size_t lds = sizeof(float) * (3 * BI * SROW + H * 4 * 64 * 4 + 2 * BI * SCLD + BI * SCLD + BI * H * P * 3) + 2 * (size_t)nchunk * JC;
-            ABOPT_CHECK_ARG(lds <= 160 * 1024, "ipa_core: L=%d needs %zu bytes of LDS for the key masks (max 163840)", L, lds);
-            static LdsConfig lds_cfg;
-            if (int rc = ensure_dynamic_lds(reinterpret_cast<const void*>(ipa_core_persist_kernel), lds, lds_cfg)) return rc;
-            prof::begin(st);
-            hipLaunchKernelGGL(ipa_core_persist_kernel, dim3((unsigned)cus), dim3(NTH), lds, st, qfrag, kvfrag, z, mask, R, t, feat, pair_bias_cache, L, nib, total,
-                               (N % 8 == 0) ? 1 : 0, z_shared);
-            prof::end(st);
-            ABOPT_LAUNCH_CHECK();
-            return ABOPT_OK;
-        }
-    }
-    if (pair_bias_cache && !dump && split_ws && !getenv("ABOPT_CORE_NO_SPLIT") && bias_slab_fits_u32(N, L, z_shared)) {
-        // small batches: split the keys of every query block over 2 or 4 workgroups (see the SPLIT note at ipa_core_kernel)
-        const int nib = (L + BI - 1) / BI, nchunk = (L + JC - 1) / JC, total = N * nib;
-        int cus = 0;
-        if (int rc = device_cu_count(&cus)) return rc;
-        int nsplit = (total * 4 <= cus && nchunk >= 8) ? 4 : ((total * 2 <= cus && nchunk >= 4) ? 2 : 1);
+    case CoreForm::Split: {
         const int64_t rows = (int64_t)N * L;
-        if (nsplit > 1 && (size_t)nsplit * rows * (SPLIT_ROW + 2 * H) <= split_ws_floats) {
-            float* part = split_ws;
-            float* pstats = split_ws + (size_t)nsplit * rows * SPLIT_ROW;
-            const size_t lds = core_lds_fixed_bytes<true>() + (size_t)nchunk * JC;
-            ABOPT_CHECK_ARG(lds <= 160 * 1024, "ipa_core: L=%d needs %zu bytes of LDS for the key mask (max 163840)", L, lds);
-            static LdsConfig lds_cfg;
-            if (int rc = ensure_dynamic_lds(reinterpret_cast<const void*>(ipa_core_kernel<false, true, true>), lds, lds_cfg)) return rc;
-            prof::begin(st);
-            hipLaunchKernelGGL((ipa_core_kernel<false, true, true>), dim3((unsigned)(total * nsplit)), dim3(NTH), lds, st, qfrag, kvfrag, z, mask, R, t, w_pair_bias, feat,
-                               nullptr, nullptr, pair_bias_cache, N, L, nib, (N % 8 == 0) ? 1 : 0, z_shared, part, pstats, nsplit);
-            ABOPT_LAUNCH_CHECK();
-            hipLaunchKernelGGL(ipa_split_merge_kernel, dim3((unsigned)rows), dim3(256), 0, st, part, pstats, mask, R, t, feat, rows, nsplit);
-            prof::end(st);
-            ABOPT_LAUNCH_CHECK();
-            return ABOPT_OK;
-        }
+        float* part = split_ws;
+        float* pstats = split_ws + (size_t)plan.nsplit * rows * SPLIT_ROW;
+        const size_t lds = core_lds_fixed_bytes<true>() + (size_t)nchunk * JC;
+        ABOPT_CHECK_ARG(lds <= 160 * 1024, "ipa_core: L=%d needs %zu bytes of LDS for the key mask (max 163840)", L, lds);
+        static LdsConfig lds_cfg;
+        if (int rc = ensure_dynamic_lds(reinterpret_cast<const void*>(ipa_core_kernel<false, true, true>), lds, lds_cfg)) return rc;
+        prof::begin(st);
+        hipLaunchKernelGGL((ipa_core_kernel<false, true, true>), dim3(plan.grid), dim3(NTH), lds, st, qfrag, kvfrag, z, mask, R, t, w_pair_bias, feat, nullptr, nullptr,
+                           pair_bias_cache, N, L, nib, plan.remap, z_shared, part, pstats, plan.nsplit);
+        ABOPT_LAUNCH_CHECK();
+        hipLaunchKernelGGL(ipa_split_merge_kernel, dim3((unsigned)rows), dim3(256), 0, st, part, pstats, mask, R, t, feat, rows, plan.nsplit);
+        prof::end(st);
+        ABOPT_LAUNCH_CHECK();
+        return ABOPT_OK;
+    }
+    case CoreForm::OneBlock:
+        break;
     }
     if (pair_bias_cache) {
-        if (dump) return launch_core_variant<true, true>(qfrag, kvfrag, z, mask, R, t, w_pair_bias, feat, dump, dump_stats, pair_bias_cache, N, L, st, z_shared);
-        return launch_core_variant<false, true>(qfrag, kvfrag, z, mask, R, t, w_pair_bias, feat, nullptr, nullptr, pair_bias_cache, N, L, st, z_shared);
+        if (dump) return launch_core_variant<true, true>(plan, qfrag, kvfrag, z, mask, R, t, w_pair_bias, feat, dump, dump_stats, pair_bias_cache, N, L, st, z_shared);
+        return launch_core_variant<false, true>(plan, qfrag, kvfrag, z, mask, R, t, w_pair_bias, feat, nullptr, nullptr, pair_bias_cache, N, L, st, z_shared);
     }
-    if (dump) return launch_core_variant<true, false>(qfrag, kvfrag, z, mask, R, t, w_pair_bias, feat, dump, dump_stats, nullptr, N, L, st, z_shared);
-    return launch_core_variant<false, false>(qfrag, kvfrag, z, mask, R, t, w_pair_bias, feat, nullptr, nullptr, nullptr, N, L, st, z_shared);
+    if (dump) return launch_core_variant<true, false>(plan, qfrag, kvfrag, z, mask, R, t, w_pair_bias, feat, dump, dump_stats, nullptr, N, L, st, z_shared);
+    return launch_core_variant<false, false>(plan, qfrag, kvfrag, z, mask, R, t, w_pair_bias, feat, nullptr, nullptr, nullptr, N, L, st, z_shared);
 }
 
 }  // namespace abopt

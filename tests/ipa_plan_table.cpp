@@ -1,0 +1,29 @@
+// Tabulates plan_ipa_core (ab_opt_amd/csrc/ipa_plan.h) over a grid of launch geometries, one line per query, for tests/test_ipa_plan.py.
+// Host C++17 only: no HIP, no device.  Columns:
+//   N L cus z_shared cache dump ws ws_floats override no_split | form nsplit remap grid applies
+// ws: 0 = no key-split scratch, 1 = ipa_split_ws_floats(N, L) as the GABlock workspace carves it (absent where that is 0), 2 = room for two key slices only.
+// applies: plan_is_core32 of the same geometry asked without scratch and without ABOPT_CORE_NO_SPLIT, as ipa_core32_applies asks.
+#include <cstdio>
+#include "../ab_opt_amd/csrc/ipa_plan.h"
+
+using namespace abopt;
+
+int main() {
+    const int Ns[] = {1, 2, 8, 16, 23, 32, 48, 62, 64, 1000, 1365, 1366, 2732, 3000};
+    const int Ls[] = {1, 16, 17, 48, 64, 128, 192, 200, 256, 400, 2048, 2049};
+    const int cuss[] = {4, 8, 250, 256, 304};
+    const int zs[] = {0, 2, 16};
+    const char* names[] = {"OneBlock", "Persist", "Split", "Core32", "Unsupported"};
+    for (int N : Ns) for (int L : Ls) for (int cus : cuss) for (int z : zs)
+        for (int cache = 0; cache < 2; ++cache) for (int dump = 0; dump < 2; ++dump) for (int ws = 0; ws < 3; ++ws)
+            for (int ovr = -1; ovr <= 1; ++ovr) for (int no_split = 0; no_split < 2; ++no_split) {
+                const size_t wsf = ws == 0 ? 0 : (ws == 1 ? ipa_split_ws_floats(N, L) : (size_t)2 * N * L * (SPLIT_ROW + 2 * H));
+                const CoreQuery q{N, L, z, cus, cache != 0, dump != 0, wsf != 0, wsf, ovr, no_split != 0};
+                const CorePlan p = plan_ipa_core(q);
+                CoreQuery a = q;
+                a.split_ws = false; a.split_ws_floats = 0; a.no_split = false;
+                std::printf("%d %d %d %d %d %d %d %zu %d %d | %s %d %d %u %d\n", N, L, cus, z, cache, dump, ws, wsf, ovr, no_split, names[(int)p.form], p.nsplit, p.remap,
+                            p.grid, plan_is_core32(a) ? 1 : 0);
+            }
+    return 0;
+}

@@ -1,0 +1,102 @@
+"""The dispatch of the IPA core (ab_opt_amd/csrc/ipa_plan.h: plan_ipa_core) without a device: tests/ipa_plan_table.cpp, a host-only program, tabulates the
+plan over a grid of launch geometries; the invariants the kernels rely on are checked on every line and ten rows are pinned."""
+import os
+import shutil
+import subprocess
+from collections import namedtuple
+
+import pytest
+
+from conftest import ROOT
+
+NS = (1, 2, 8, 16, 23, 32, 48, 62, 64, 1000, 1365, 1366, 2732, 3000)
+LS = (1, 16, 17, 48, 64, 128, 192, 200, 256, 400, 2048, 2049)
+CUS = (4, 8, 250, 256, 304)
+ZS = (0, 2, 16)
+BI, JC, HEADS = 16, 16, 12
+SPLIT_FLOATS_PER_ROW = 12 * 64 + 12 * 32 + 12 * 8 * 3 + 2 * HEADS     # SPLIT_ROW + 2 H: 1440 accumulators and the maximum / sum of 12 heads, per row and key slice
+
+Row = namedtuple('Row', 'N L cus z cache dump ws wsf ovr no_split form nsplit remap grid applies')
+
+
+@pytest.fixture(scope='module')
+def table(tmp_path_factory):
+    cxx = next((c for c in ('/opt/rocm/lib/llvm/bin/clang++', shutil.which('g++'), shutil.which('clang++')) if c and os.path.exists(c)), None)
+    assert cxx, 'no host C++ compiler (clang++ of the ROCm LLVM directory, g++)'
+    exe = str(tmp_path_factory.mktemp('ipa_plan') / 'ipa_plan_table')
+    subprocess.run([cxx, '-std=c++17', '-O1', '-Wall', '-Werror', os.path.join(ROOT, 'tests', 'ipa_plan_table.cpp'), '-o', exe], check=True)
+    rows = []
+    for line in subprocess.run([exe], check=True, capture_output=True, text=True).stdout.splitlines():
+        q, p = line.split(' | ')
+        form, *rest = p.split()
+        rows.append(Row(*map(int, q.split()), form, *map(int, rest)))
+    return rows
+
+
+def slab_fits_u32(r):
+    """one layer's slab of the bias cache -- distinct samples x L rows x key chunks x 768 bytes -- is below 4 GB"""
+    return (r.N // r.z if r.z > 1 else r.N) * r.L * ((r.L + JC - 1) // JC) * 768 < (1 << 32)
+
+
+def test_grid_is_complete(table):
+    assert len(table) == len(NS) * len(LS) * len(CUS) * len(ZS) * 2 * 2 * 3 * 3 * 2
+    assert {(r.N, r.L, r.cus, r.z) for r in table} == {(n, l, c, z) for n in NS for l in LS for c in CUS for z in ZS}
+    assert {r.form for r in table} == {'OneBlock', 'Persist', 'Split', 'Core32', 'Unsupported'}
+    for ws in (1, 2):               # both kinds of scratch occur, and the small one does refuse a four-way split somewhere
+        assert any(r.form == 'Split' and r.ws == ws for r in table)
+    assert any(r.form == 'Split' and r.nsplit == 4 for r in table) and any(r.form == 'Split' and r.nsplit == 2 for r in table)
+
+
+def test_invariants_over_the_grid(table):
+    for r in table:
+        fits = slab_fits_u32(r)
+        if not fits:
+            assert r.form not in ('Core32', 'Split'), r
+            if r.dump and r.cache:
+                assert r.form == 'Unsupported', r
+        assert (r.form == 'Unsupported') == bool(r.dump and r.cache and not fits), r
+        if r.L > 2048:
+            assert r.form != 'Core32', r
+        if r.form in ('Core32', 'Persist', 'Split'):
+            assert r.cache and not r.dump, r
+        if r.form == 'Split':
+            assert r.nsplit in (2, 4) and r.ws and not r.no_split and r.nsplit * r.N * r.L * SPLIT_FLOATS_PER_ROW <= r.wsf, r
+        else:
+            assert r.nsplit == 1, r
+        if r.form == 'Persist':
+            assert r.cus >= 8 and r.grid == r.cus & ~7 and r.grid % 8 == 0, r
+        if r.ovr == 0:
+            assert r.form != 'Core32', r
+        if r.ovr == 1 and r.cache and not r.dump:
+            assert (r.form == 'Core32') == (BI < r.L <= 2048 and fits), r
+        if r.form == 'Core32':
+            by_complex = r.z > 1 and r.z < r.N and r.N % r.z == 0 and (r.N // r.z) % 8 == 0
+            assert r.remap == (2 if by_complex else int(r.N % 8 == 0)) and r.grid == r.N * ((r.L + 31) // 32), r
+        elif r.form != 'Unsupported':
+            assert r.remap == int(r.N % 8 == 0), r
+            if r.form != 'Persist':
+                assert r.grid == r.N * ((r.L + BI - 1) // BI) * r.nsplit, r
+        if r.cache and not r.dump:
+            assert r.applies == (r.form == 'Core32'), r         # ipa_core32_applies, asked without the scratch, agrees with the launch
+
+
+def test_scratch_and_no_split_only_move_the_split_form(table):
+    """What the caller holds as key-split scratch, and ABOPT_CORE_NO_SPLIT, decide between Split and OneBlock and nothing else."""
+    by_geometry = {}
+    for r in table:
+        by_geometry.setdefault((r.N, r.L, r.cus, r.z, r.cache, r.dump, r.ovr), set()).add(r.form)
+    for k, forms in by_geometry.items():
+        assert len(forms) == 1 or forms == {'Split', 'OneBlock'}, (k, forms)
+
+
+@pytest.mark.parametrize('N,L,form,nsplit', [(2, 256, 'Split', 4), (8, 256, 'Split', 2), (16, 256, 'OneBlock', 1), (32, 256, 'Core32', 1), (48, 256, 'Persist', 1),
+                                             (64, 256, 'Core32', 1), (32, 128, 'OneBlock', 1), (1000, 48, 'Core32', 1), (1366, 256, 'Persist', 1)])
+def test_pinned_rows_at_256_cus(table, N, L, form, nsplit):
+    """Derived by hand from the rules as they stood before plan_ipa_core existed (256 CUs, a cache, no dump, the workspace's own scratch, no switches)."""
+    (r,) = [r for r in table if (r.N, r.L, r.cus, r.z, r.cache, r.dump, r.ws, r.ovr, r.no_split) == (N, L, 256, 0, 1, 0, 1, -1, 0)]
+    assert (r.form, r.nsplit) == (form, nsplit), r
+
+
+def test_pinned_row_past_the_z_descriptor_reach(table):
+    (r,) = [r for r in table if (r.N, r.L, r.cus, r.z, r.cache, r.dump, r.ws, r.ovr, r.no_split) == (1, 2049, 256, 0, 1, 0, 1, -1, 0)]
+    assert r.form != 'Core32', r

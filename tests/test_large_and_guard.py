@@ -21,7 +21,7 @@ def test_pair_bias_cache_slab_above_4GB(monkeypatch):
 
     The cached 16-row kernels read a row's bias of key chunk ch at byte  ch * (N * L * 768) + row * 768 + lane offset  of the layer's
     chunk-major slab (csrc/ipa_core.hip: pb_chunk).  nchunk = 16 at L = 256, so
-        the slab passes 2^32 bytes from           N >= 2^32 / (16 * 256 * 768) = 1365.3   (the 32-row kernel stands aside from there: use_core32)
+        the slab passes 2^32 bytes from           N >= 2^32 / (16 * 256 * 768) = 1365.3   (the 32-row kernel stands aside from there: plan_ipa_core)
         chunk 15 starts beyond 2^32 for ALL rows  N >= 2^32 / (15 * 256 * 768) = 1456.4
     N = 1504: chunk 15 of every sample starts at byte 4,435,476,480 (140 MB of margin) and chunk 14 lies beyond 2^32 from sample 790 on.
     A 32-bit product wraps INSIDE the allocation and reads another row's bias (every sample has its own z).  N % 8 == 0 selects the XCD-aware block
