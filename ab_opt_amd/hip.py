@@ -5,6 +5,7 @@ PyTorch is used only as the owner of device memory and streams: every call passe
 if the library is missing or a tensor is not on a HIP device, these functions raise.
 """
 import ctypes as C
+from ctypes import POINTER, c_char_p, c_double, c_float, c_int, c_int64, c_longlong, c_size_t, c_uint64, c_void_p
 import os
 import threading
 import torch
@@ -75,14 +76,92 @@ class StepNoise(C.Structure):
     _fields_ = [('axis', c_f), ('bin', c_i64), ('ubin', c_f), ('gauss', c_f), ('z', c_f), ('s_next', c_i64)]
 
 
-EXPORTS = ['abopt_abi_version', 'abopt_last_error', 'abopt_device_info', 'abopt_so3_exp', 'abopt_so3_log',
-           'abopt_ga_workspace_bytes', 'abopt_ga_block_forward', 'abopt_ga_block_forward_cached', 'abopt_ga_encoder_forward',
-           'abopt_eps_workspace_bytes', 'abopt_eps_net_forward', 'abopt_pair_bias_cache_bytes', 'abopt_pair_bias_cache', 'abopt_pair_terms_bytes', 'abopt_pair_terms', 'abopt_pair_terms_used', 'abopt_nonfinite_flag', 'abopt_nonfinite_flag_reset', 'abopt_denoise_step', 'abopt_sample_init',
-           'abopt_add_noise', 'abopt_gemm', 'abopt_gemm_tn_grouped', 'abopt_colsum', 'abopt_adam_step', 'abopt_adam_ws_floats', 'abopt_bucket_colsum', 'abopt_segment_bucket_colsum', 'abopt_heads_epilogue_forward', 'abopt_heads_epilogue_backward', 'abopt_dpm_losses', 'abopt_abdock_losses', 'abopt_layer_norm_forward', 'abopt_layer_norm_backward', 'abopt_residue_features', 'abopt_residue_features_workspace_bytes', 'abopt_commonness_score', 'abopt_prof_enable', 'abopt_prof_collect', 'abopt_prof_peek', 'abopt_prof_clock', 'abopt_prof_spans_reset', 'abopt_prof_spans',
-           'abopt_reconstruct_backbone_partially', 'abopt_ipa_train_workspace_bytes', 'abopt_ipa_core_train_forward', 'abopt_ipa_points_backward', 'abopt_ipa_backward_operands', 'abopt_ipa_backward_assemble', 'abopt_ipa_pair_backward', 'abopt_ipa_dz_assemble',
-           'abopt_residue_embed_workspace_bytes', 'abopt_residue_embed_forward', 'abopt_pair_embed_workspace_bytes', 'abopt_pair_embed_forward',
-           'abopt_pair_embed_backward_workspace_bytes', 'abopt_pair_embed_backward', 'abopt_dockq_workspace_bytes', 'abopt_dockq_lite', 'abopt_dockq_grouped_workspace_bytes', 'abopt_dockq_lite_grouped', 'abopt_commonness_score_grouped', 'abopt_node_frag_source_row', 'abopt_node_frag_floats',
-           'abopt_out_frag_floats', 'abopt_out_terms_floats', 'abopt_out_frag_terms', 'abopt_heads_frag_floats', 'abopt_mixer_frag_floats', 'abopt_mlp_frag_floats', 'abopt_pack_tail_weights', 'abopt_block_tail_forward', 'abopt_block_tail_backward']
+c_i32 = C.c_void_p      # device int32*
+c_stream = C.c_void_p   # abopt_stream (a hipStream_t)
+
+# The one Python statement of the C ABI: name -> (restype, argtypes) of every function of include/abopt.h, in the header's order, each entry reading
+# like its prototype (tests/test_abi.py::test_binding_signatures_match_header holds it to the header).  Device and host data pointers are c_void_p (the
+# aliases above name what a device pointer points to); pointer-to-pointer parameters and host arrays (adam's numel, position_mean) are c_void_p too and
+# take the ctypes arrays the wrappers build; `const abopt_X*` is POINTER of the mirror; int* / double* / long long* are host out-parameters.
+_SIGNATURES = {
+    'abopt_abi_version': (c_int, []),
+    'abopt_last_error': (c_char_p, []),
+    'abopt_device_info': (c_int, [POINTER(c_int), POINTER(c_int), c_char_p, c_int]),
+    'abopt_so3_exp': (c_int, [c_f, c_f, c_int64, c_stream]),
+    'abopt_so3_log': (c_int, [c_f, c_f, c_int64, c_int, c_stream]),
+    'abopt_node_frag_source_row': (c_int, [c_int, c_int, c_int]),
+    'abopt_node_frag_floats': (c_size_t, []),
+    'abopt_out_frag_floats': (c_size_t, []),
+    'abopt_heads_frag_floats': (c_size_t, []),
+    'abopt_mixer_frag_floats': (c_size_t, []),
+    'abopt_mlp_frag_floats': (c_size_t, []),
+    'abopt_out_terms_floats': (c_size_t, []),
+    'abopt_out_frag_terms': (c_int, [c_f, c_f, c_stream]),
+    'abopt_pack_tail_weights': (c_int, [c_f] * 7 + [c_stream]),
+    'abopt_block_tail_forward': (c_int, [c_f] * 5 + [c_u8] + [c_f] * 9 + [c_int64, c_stream]),
+    'abopt_block_tail_backward': (c_int, [c_f, c_f, c_f, c_u8] + [c_f] * 6 + [c_int64, c_stream]),
+    'abopt_ga_workspace_bytes': (c_size_t, [c_int] * 4),
+    'abopt_ga_block_forward': (c_int, [POINTER(GaWeights)] + [c_f] * 4 + [c_u8, c_f] + [c_int] * 4 + [POINTER(GaDebug), c_void_p, c_size_t, c_stream]),
+    'abopt_ga_block_forward_cached': (c_int, [POINTER(GaWeights)] + [c_f] * 4 + [c_u8, c_f] + [c_int] * 4 + [c_f, c_f, c_int, c_f, c_void_p, c_size_t, c_stream]),
+    'abopt_ga_encoder_forward': (c_int, [POINTER(GaWeights), c_int] + [c_f] * 4 + [c_u8, c_f] + [c_int] * 4 + [c_void_p, c_size_t, c_stream]),
+    'abopt_eps_workspace_bytes': (c_size_t, [c_int] * 4),
+    'abopt_pair_bias_cache_bytes': (c_size_t, [c_int, c_int, c_int]),
+    'abopt_pair_bias_cache': (c_int, [POINTER(GaWeights), c_int, c_f, c_f, c_int, c_int, c_int, c_stream]),
+    'abopt_nonfinite_flag': (c_int, [c_int, c_stream]),
+    'abopt_nonfinite_flag_reset': (c_int, [c_stream]),
+    'abopt_pair_terms_bytes': (c_size_t, [c_int, c_int]),
+    'abopt_pair_terms': (c_int, [c_f, c_f, c_int, c_int, c_int, c_stream]),
+    'abopt_pair_terms_used': (c_int, [c_int, c_int, c_int]),
+    'abopt_eps_net_forward': (c_int, [POINTER(EpsWeights), c_f, c_f, c_i64, c_f, c_f, c_f, c_u8, c_u8] + [c_f] * 5 + [c_int] * 5 +
+                              [c_f, c_int, c_f, c_void_p, c_size_t, c_stream]),
+    'abopt_denoise_step': (c_int, [POINTER(StepParams), POINTER(StepNoise), c_uint64, c_uint64, c_f, c_f, c_i64] + [c_f] * 4 + [c_u8, c_f, c_f, c_int, c_int] +
+                           [c_f, c_f, c_i64] + [c_f] * 4 + [c_void_p, c_int, c_int, c_stream]),
+    'abopt_sample_init': (c_int, [c_f, c_f, c_i64, c_u8, c_f, c_f, c_i64, c_uint64, c_uint64, c_float, c_void_p, c_int, c_int, c_f, c_f, c_i64, c_int, c_int, c_stream]),
+    'abopt_add_noise': (c_int, [c_i64, c_f, c_f, c_u8, c_f, c_f, c_int, c_int, POINTER(AddNoiseNoise), c_uint64, c_uint64, c_f, c_f, c_i64, c_u8, c_float, c_void_p, c_int, c_int, c_int,
+                        c_f, c_f, c_i64, c_f, c_f, c_void_p, c_int, c_int, c_stream]),
+    'abopt_dockq_workspace_bytes': (c_size_t, [c_int]),
+    'abopt_dockq_lite': (c_int, [c_f, c_u8, c_int, c_f, c_u8, c_i32, c_int, c_int, c_int, c_f, c_void_p, c_size_t, c_stream]),
+    'abopt_dockq_grouped_workspace_bytes': (c_size_t, [c_int, c_int]),
+    'abopt_dockq_lite_grouped': (c_int, [c_f, c_u8, c_int, c_f, c_u8, c_i32] + [c_int] * 4 + [c_f, c_void_p, c_size_t, c_stream]),
+    'abopt_ipa_train_workspace_bytes': (c_size_t, [c_int, c_int]),
+    'abopt_ipa_core_train_forward': (c_int, [c_f] * 4 + [c_u8] + [c_f] * 5 + [c_int, c_int, c_int, c_void_p, c_size_t, c_stream]),
+    'abopt_ipa_points_backward': (c_int, [c_f, c_int] + [c_f] * 5 + [c_int, c_int, c_stream]),
+    'abopt_ipa_backward_operands': (c_int, [c_f] * 6 + [c_int, c_int, c_stream]),
+    'abopt_ipa_backward_assemble': (c_int, [c_f] * 9 + [c_int, c_int, c_stream]),
+    'abopt_ipa_pair_backward': (c_int, [c_f] * 5 + [c_int] + [c_f] * 4 + [c_int] * 4 + [c_stream]),
+    'abopt_ipa_dz_assemble': (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_f, c_int, c_int, c_int, c_stream]),
+    'abopt_residue_embed_workspace_bytes': (c_size_t, [c_int] * 4),
+    'abopt_residue_embed_forward': (c_int, [POINTER(EncodeInputs), POINTER(ResidueEmbedWeights), c_f, c_f, c_f, c_void_p, c_size_t, c_stream]),
+    'abopt_residue_features_workspace_bytes': (c_size_t, [c_int, c_int]),
+    'abopt_residue_features': (c_int, [POINTER(EncodeInputs), POINTER(ResidueEmbedWeights), c_f, c_f, c_f, c_void_p, c_size_t, c_stream]),
+    'abopt_pair_embed_workspace_bytes': (c_size_t, [c_int, c_int, c_int]),
+    'abopt_pair_embed_forward': (c_int, [POINTER(EncodeInputs), POINTER(PairEmbedWeights)] + [c_f] * 4 + [c_void_p, c_size_t, c_stream]),
+    'abopt_pair_embed_backward_workspace_bytes': (c_size_t, [c_int, c_int, c_int]),
+    'abopt_pair_embed_backward': (c_int, [POINTER(EncodeInputs), POINTER(PairEmbedWeights)] + [c_f] * 6 + [c_void_p, c_size_t, c_stream]),
+    'abopt_dpm_losses': (c_int, [c_f] * 5 + [c_i64, c_i64, c_f, c_u8, c_int, c_int] + [c_f] * 4 + [c_stream]),
+    'abopt_abdock_losses': (c_int, [c_f] * 5 + [c_u8, c_u8, c_f, c_int, c_int, c_int, c_float, c_int, c_f, c_f, c_f, c_stream]),
+    'abopt_layer_norm_forward': (c_int, [c_f, c_f, c_f, c_int, c_float, c_int64, c_f, c_f, c_f, c_stream]),
+    'abopt_layer_norm_backward': (c_int, [c_f] * 4 + [c_int, c_int64, c_f, c_f, c_stream]),
+    'abopt_heads_epilogue_forward': (c_int, [c_f] * 4 + [c_u8, c_f, c_f, c_f, c_int64, c_int, c_stream]),
+    'abopt_heads_epilogue_backward': (c_int, [c_f, c_f, c_u8] + [c_f] * 4 + [c_int64, c_stream]),
+    'abopt_reconstruct_backbone_partially': (c_int, [c_f, c_f, c_f, c_i64, c_i64, c_i64, c_u8, c_u8, c_f, c_f, c_f, c_u8, c_int, c_int, c_int, c_stream]),
+    'abopt_gemm': (c_int, [c_f, c_int, c_int64, c_int, c_f, c_int, c_int64, c_int, c_f, c_int, c_int64] + [c_int] * 4 + [c_float, c_f, c_int, c_void_p, c_size_t, c_stream]),
+    'abopt_gemm_tn_grouped': (c_int, [POINTER(GemmTnProblem), c_int, c_void_p, c_size_t, c_stream]),
+    'abopt_colsum': (c_int, [c_f, c_int, c_int64, c_int, c_f, c_void_p, c_size_t, c_stream]),
+    'abopt_bucket_colsum': (c_int, [c_f, c_int, c_int64, c_int, c_i32, c_int, c_f, c_void_p, c_size_t, c_stream]),
+    'abopt_segment_bucket_colsum': (c_int, [c_f] + [c_int] * 4 + [c_i32, c_int, c_int, c_f, c_stream]),
+    'abopt_adam_ws_floats': (c_size_t, [c_int, c_void_p]),
+    'abopt_adam_step': (c_int, [c_int] + [c_void_p] * 5 + [c_double] * 6 + [c_i64, c_f, c_size_t, c_f, c_void_p, c_stream]),
+    'abopt_commonness_score': (c_int, [c_f, c_f, c_int, c_int, c_stream]),
+    'abopt_commonness_score_grouped': (c_int, [c_f, c_f, c_int, c_int, c_int, c_stream]),
+    'abopt_prof_enable': (c_int, [c_int]),
+    'abopt_prof_spans_reset': (c_int, [c_stream]),
+    'abopt_prof_spans': (c_int, [POINTER(c_int), POINTER(c_double)]),
+    'abopt_prof_collect': (c_int, [POINTER(c_int), POINTER(c_double)]),
+    'abopt_prof_clock': (c_int, [POINTER(c_longlong), POINTER(c_longlong)]),
+    'abopt_prof_peek': (c_int, [POINTER(c_int), POINTER(c_double)]),
+}
+EXPORTS = list(_SIGNATURES)
 
 _lib = None
 _lock = threading.Lock()
@@ -100,95 +179,9 @@ def lib():
             raise RuntimeError(f'{LIB_PATH} not found: build it with `python -c "import __graft_entry__ as g; g.build()"` '
                                '(or `make -C ab_opt_amd/csrc`).  ab_opt_amd has no non-HIP execution path.')
         L = C.CDLL(LIB_PATH)
-        L.abopt_abi_version.restype = C.c_int
-        L.abopt_last_error.restype = C.c_char_p
-        L.abopt_ga_workspace_bytes.restype = C.c_size_t
-        L.abopt_ga_workspace_bytes.argtypes = [C.c_int] * 4
-        L.abopt_eps_workspace_bytes.restype = C.c_size_t
-        L.abopt_eps_workspace_bytes.argtypes = [C.c_int] * 4
-        L.abopt_device_info.argtypes = [C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_char_p, C.c_int]
-        L.abopt_so3_exp.argtypes = [c_f, c_f, C.c_int64, C.c_void_p]
-        L.abopt_so3_log.argtypes = [c_f, c_f, C.c_int64, C.c_int, C.c_void_p]
-        L.abopt_ga_block_forward.argtypes = [C.POINTER(GaWeights), c_f, c_f, c_f, c_f, c_u8, c_f, C.c_int, C.c_int, C.c_int, C.c_int,
-                                             C.POINTER(GaDebug), C.c_void_p, C.c_size_t, C.c_void_p]
-        L.abopt_ga_encoder_forward.argtypes = [C.POINTER(GaWeights), C.c_int, c_f, c_f, c_f, c_f, c_u8, c_f, C.c_int, C.c_int, C.c_int, C.c_int,
-                                               C.c_void_p, C.c_size_t, C.c_void_p]
-        L.abopt_eps_net_forward.argtypes = [C.POINTER(EpsWeights), c_f, c_f, c_i64, c_f, c_f, c_f, c_u8, c_u8,
-                                            c_f, c_f, c_f, c_f, c_f, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, c_f, C.c_int, c_f,
-                                            C.c_void_p, C.c_size_t, C.c_void_p]
-        L.abopt_ga_block_forward_cached.argtypes = [C.POINTER(GaWeights), c_f, c_f, c_f, c_f, c_u8, c_f, C.c_int, C.c_int, C.c_int, C.c_int, c_f, c_f, C.c_int, c_f,
-                                                    C.c_void_p, C.c_size_t, C.c_void_p]
-        L.abopt_pair_terms_bytes.restype = C.c_size_t
-        L.abopt_pair_terms_bytes.argtypes = [C.c_int] * 2
-        L.abopt_pair_terms.argtypes = [c_f, c_f, C.c_int, C.c_int, C.c_int, C.c_void_p]
-        L.abopt_pair_terms_used.argtypes = [C.c_int] * 3
-        L.abopt_nonfinite_flag.argtypes = [C.c_int, C.c_void_p]
-        L.abopt_nonfinite_flag_reset.argtypes = [C.c_void_p]
-        L.abopt_pair_bias_cache_bytes.restype = C.c_size_t
-        L.abopt_pair_bias_cache_bytes.argtypes = [C.c_int] * 3
-        L.abopt_pair_bias_cache.argtypes = [C.POINTER(GaWeights), C.c_int, c_f, c_f, C.c_int, C.c_int, C.c_int, C.c_void_p]
-        L.abopt_denoise_step.argtypes = [C.POINTER(StepParams), C.POINTER(StepNoise), C.c_uint64, C.c_uint64,
-                                         c_f, c_f, c_i64, c_f, c_f, c_f, c_f, c_u8, c_f, c_f, C.c_int, C.c_int,
-                                         c_f, c_f, c_i64, c_f, c_f, c_f, c_f, C.c_void_p, C.c_int, C.c_int, C.c_void_p]
-        L.abopt_sample_init.argtypes = [c_f, c_f, c_i64, c_u8, c_f, c_f, c_i64, C.c_uint64, C.c_uint64,
-                                        C.c_float, C.POINTER(C.c_float), C.c_int, C.c_int, c_f, c_f, c_i64, C.c_int, C.c_int, C.c_void_p]
-        L.abopt_commonness_score.argtypes = [c_f, c_f, C.c_int, C.c_int, C.c_void_p]
-        L.abopt_add_noise.argtypes = [c_i64, c_f, c_f, c_u8, c_f, c_f, C.c_int, C.c_int, C.POINTER(AddNoiseNoise), C.c_uint64, C.c_uint64,
-                                      c_f, c_f, c_i64, c_u8, C.c_float, C.POINTER(C.c_float), C.c_int, C.c_int, C.c_int,
-                                      c_f, c_f, c_i64, c_f, c_f, C.c_void_p, C.c_int, C.c_int, C.c_void_p]
-        L.abopt_gemm.argtypes = [c_f, C.c_int, C.c_int64, C.c_int, c_f, C.c_int, C.c_int64, C.c_int, c_f, C.c_int, C.c_int64,
-                                 C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, c_f, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p]
-        L.abopt_colsum.argtypes = [c_f, C.c_int, C.c_int64, C.c_int, c_f, C.c_void_p, C.c_size_t, C.c_void_p]
-        L.abopt_gemm_tn_grouped.argtypes = [C.POINTER(GemmTnProblem), C.c_int, C.c_void_p, C.c_size_t, C.c_void_p]
-        L.abopt_prof_enable.argtypes = [C.c_int]
-        L.abopt_prof_collect.argtypes = [C.POINTER(C.c_int), C.POINTER(C.c_double)]
-        L.abopt_prof_peek.argtypes = [C.POINTER(C.c_int), C.POINTER(C.c_double)]
-        L.abopt_reconstruct_backbone_partially.argtypes = [c_f, c_f, c_f, c_i64, c_i64, c_i64, c_u8, c_u8, c_f, c_f, c_f, c_u8] + [C.c_int] * 3 + [C.c_void_p]
-        L.abopt_ipa_train_workspace_bytes.restype = C.c_size_t
-        L.abopt_ipa_train_workspace_bytes.argtypes = [C.c_int] * 2
-        L.abopt_ipa_core_train_forward.argtypes = [c_f, c_f, c_f, c_f, c_u8, c_f, c_f, c_f, c_f, c_f, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p]
-        L.abopt_ipa_points_backward.argtypes = [c_f, C.c_int, c_f, c_f, c_f, c_f, c_f, C.c_int, C.c_int, C.c_void_p]
-        L.abopt_ipa_backward_operands.argtypes = [c_f] * 6 + [C.c_int, C.c_int, C.c_void_p]
-        L.abopt_ipa_backward_assemble.argtypes = [c_f] * 9 + [C.c_int, C.c_int, C.c_void_p]
-        L.abopt_ipa_pair_backward.argtypes = [c_f, c_f, c_f, c_f, c_f, C.c_int, c_f, c_f, c_f, c_f, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]
-        L.abopt_residue_embed_workspace_bytes.restype = C.c_size_t
-        L.abopt_residue_features_workspace_bytes.restype = C.c_size_t
-        L.abopt_residue_features_workspace_bytes.argtypes = [C.c_int] * 2
-        L.abopt_residue_features.argtypes = [C.POINTER(EncodeInputs), C.POINTER(ResidueEmbedWeights), c_f, c_f, c_f, C.c_void_p, C.c_size_t, C.c_void_p]
-        L.abopt_residue_embed_workspace_bytes.argtypes = [C.c_int] * 4
-        L.abopt_pair_embed_workspace_bytes.restype = C.c_size_t
-        L.abopt_pair_embed_workspace_bytes.argtypes = [C.c_int] * 3
-        L.abopt_residue_embed_forward.argtypes = [C.POINTER(EncodeInputs), C.POINTER(ResidueEmbedWeights), c_f, c_f, c_f, C.c_void_p, C.c_size_t, C.c_void_p]
-        L.abopt_pair_embed_forward.argtypes = [C.POINTER(EncodeInputs), C.POINTER(PairEmbedWeights), c_f, c_f, c_f, c_f, C.c_void_p, C.c_size_t, C.c_void_p]
-        L.abopt_pair_embed_backward_workspace_bytes.restype = C.c_size_t
-        L.abopt_pair_embed_backward_workspace_bytes.argtypes = [C.c_int] * 3
-        L.abopt_pair_embed_backward.argtypes = [C.POINTER(EncodeInputs), C.POINTER(PairEmbedWeights), c_f, c_f, c_f, c_f, c_f, c_f, C.c_void_p, C.c_size_t, C.c_void_p]
-        L.abopt_node_frag_source_row.argtypes = [C.c_int] * 3
-        L.abopt_node_frag_floats.restype = C.c_size_t
-        L.abopt_abdock_losses.argtypes = [c_f, c_f, c_f, c_f, c_f, c_u8, c_u8, c_f, C.c_int, C.c_int, C.c_int, C.c_float, C.c_int, c_f, c_f, c_f, C.c_void_p]
-        L.abopt_layer_norm_forward.argtypes = [c_f, c_f, c_f, C.c_int, C.c_float, C.c_int64, c_f, c_f, c_f, C.c_void_p]
-        L.abopt_layer_norm_backward.argtypes = [c_f, c_f, c_f, c_f, C.c_int, C.c_int64, c_f, c_f, C.c_void_p]
-        L.abopt_adam_ws_floats.restype = C.c_size_t
-        L.abopt_adam_ws_floats.argtypes = [C.c_int, C.c_void_p]
-        L.abopt_adam_step.argtypes = [C.c_int] + [C.c_void_p] * 5 + [C.c_double] * 6 + [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p]
-        L.abopt_dockq_workspace_bytes.restype = C.c_size_t
-        L.abopt_dockq_workspace_bytes.argtypes = [C.c_int]
-        L.abopt_dockq_lite.argtypes = [c_f, c_u8, C.c_int, c_f, c_u8, C.c_void_p, C.c_int, C.c_int, C.c_int, c_f, C.c_void_p, C.c_size_t, C.c_void_p]
-        L.abopt_dockq_grouped_workspace_bytes.restype = C.c_size_t
-        L.abopt_dockq_grouped_workspace_bytes.argtypes = [C.c_int] * 2
-        L.abopt_dockq_lite_grouped.argtypes = [c_f, c_u8, C.c_int, c_f, c_u8, C.c_void_p] + [C.c_int] * 4 + [c_f, C.c_void_p, C.c_size_t, C.c_void_p]
-        L.abopt_commonness_score_grouped.argtypes = [c_f, c_f] + [C.c_int] * 3 + [C.c_void_p]
-        L.abopt_out_frag_floats.restype = C.c_size_t
-        L.abopt_out_terms_floats.restype = C.c_size_t
-        L.abopt_out_frag_terms.argtypes = [c_f, c_f, C.c_void_p]
-        L.abopt_heads_frag_floats.restype = C.c_size_t
-        L.abopt_mixer_frag_floats.restype = C.c_size_t
-        L.abopt_mlp_frag_floats.restype = C.c_size_t
-        L.abopt_pack_tail_weights.argtypes = [c_f] * 7 + [C.c_void_p]
-        L.abopt_block_tail_forward.argtypes = [c_f] * 5 + [c_u8] + [c_f] * 9 + [C.c_int64, C.c_void_p]
-        L.abopt_block_tail_backward.argtypes = [c_f] * 3 + [c_u8] + [c_f] * 6 + [C.c_int64, C.c_void_p]
-        for name in EXPORTS:
-            getattr(L, name)          # AttributeError here = a symbol of include/abopt.h is missing
+        for name, (restype, argtypes) in _SIGNATURES.items():
+            fn = getattr(L, name)     # AttributeError here = a symbol of include/abopt.h is missing
+            fn.restype, fn.argtypes = restype, argtypes
         if L.abopt_abi_version() != ABI_VERSION:
             raise RuntimeError(f'libabopt_hip.so ABI {L.abopt_abi_version()} != expected {ABI_VERSION}; rebuild it')
         _lib = L
@@ -994,7 +987,7 @@ def abdock_losses(prmsd_logits, p_pred, p0n, coef_a, coef_b, mask_generate, mask
     gl, gp = torch.empty_like(prmsd_logits), torch.empty_like(p_pred)
     _check(lib().abopt_abdock_losses(ptr(prmsd_logits, torch.float32), ptr(p_pred, torch.float32), ptr(p0n, torch.float32), ptr(ca, torch.float32, optional=True),
                                      ptr(cb, torch.float32, optional=True), ptr(mask_generate, torch.bool), ptr(mask_res, torch.bool), ptr(offsets, torch.float32), nb, N, L,
-                                     C.c_float(float(scale)), int(bool(pred_x0)), ptr(part), ptr(gl), ptr(gp), stream()))
+                                     float(scale), int(bool(pred_x0)), ptr(part), ptr(gl), ptr(gp), stream()))
     return part, gl, gp
 
 
@@ -1006,7 +999,7 @@ def layer_norm_forward(x, gamma, beta, eps, save=True):
     y = torch.empty_like(x2)
     xhat = torch.empty_like(x2) if save else None
     rstd = torch.empty(rows, dtype=torch.float32, device=x2.device) if save else None
-    _check(lib().abopt_layer_norm_forward(ptr(x2, torch.float32), ptr(gamma, torch.float32), ptr(beta, torch.float32), cols, C.c_float(float(eps)), C.c_int64(rows), ptr(y),
+    _check(lib().abopt_layer_norm_forward(ptr(x2, torch.float32), ptr(gamma, torch.float32), ptr(beta, torch.float32), cols, float(eps), rows, ptr(y),
                                           ptr(xhat, torch.float32, optional=True), ptr(rstd, torch.float32, optional=True), stream()))
     return y.view(x.shape), xhat, rstd
 
@@ -1017,7 +1010,7 @@ def layer_norm_backward(dy, xhat, rstd, gamma):
     dy2, gamma = _contig(dy.float().reshape(-1, cols), gamma.detach().float())
     rows = dy2.shape[0]
     dx, dyx = torch.empty_like(dy2), torch.empty_like(dy2)
-    _check(lib().abopt_layer_norm_backward(ptr(dy2, torch.float32), ptr(xhat, torch.float32), ptr(rstd, torch.float32), ptr(gamma, torch.float32), cols, C.c_int64(rows),
+    _check(lib().abopt_layer_norm_backward(ptr(dy2, torch.float32), ptr(xhat, torch.float32), ptr(rstd, torch.float32), ptr(gamma, torch.float32), cols, rows,
                                            ptr(dx), ptr(dyx), stream()))
     return dx.view(dy.shape), colsum(dyx), colsum(dy2)
 
@@ -1028,7 +1021,7 @@ def heads_epilogue_forward(R, eps_crd, eps_rot, mask_generate):
     rows = mask_generate.numel()
     R_next, eps_pos = torch.empty_like(R), torch.empty_like(eps_crd)
     _check(lib().abopt_heads_epilogue_forward(ptr(R, torch.float32), None, ptr(eps_crd, torch.float32), ptr(eps_rot, torch.float32), ptr(mask_generate, torch.bool),
-                                              None, ptr(R_next), ptr(eps_pos), C.c_int64(rows), 0, stream()))
+                                              None, ptr(R_next), ptr(eps_pos), rows, 0, stream()))
     return R_next, eps_pos
 
 
@@ -1040,7 +1033,7 @@ def heads_epilogue_backward(R, eps_rot, mask_generate, dR_next, deps_pos):
     rows = mask_generate.numel()
     d_crd, d_rot = torch.empty_like(eps_rot), torch.empty_like(eps_rot)
     _check(lib().abopt_heads_epilogue_backward(ptr(R, torch.float32), ptr(eps_rot, torch.float32), ptr(mask_generate, torch.bool), ptr(dR_next, torch.float32, optional=True),
-                                               ptr(deps_pos, torch.float32, optional=True), ptr(d_crd), ptr(d_rot), C.c_int64(rows), stream()))
+                                               ptr(deps_pos, torch.float32, optional=True), ptr(d_crd), ptr(d_rot), rows, stream()))
     return d_crd, d_rot
 
 

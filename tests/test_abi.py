@@ -13,10 +13,72 @@ from ab_opt_amd import hip
 HEADER = os.path.join(ROOT, 'include', 'abopt.h')
 
 
-def declared_symbols():
-    src = open(HEADER).read()
-    src = re.sub(r'/\*.*?\*/', '', src, flags=re.S)
-    return sorted(set(re.findall(r'\b(abopt_[a-z0-9_]+)\s*\(', src)))
+# abopt_X -> its ctypes mirror in hip.py: the ten structs of the header
+STRUCTS = {'abopt_ga_weights': hip.GaWeights, 'abopt_ga_debug': hip.GaDebug, 'abopt_eps_weights': hip.EpsWeights, 'abopt_step_params': hip.StepParams,
+           'abopt_step_noise': hip.StepNoise, 'abopt_addnoise_noise': hip.AddNoiseNoise, 'abopt_encode_inputs': hip.EncodeInputs,
+           'abopt_residue_embed_weights': hip.ResidueEmbedWeights, 'abopt_pair_embed_weights': hip.PairEmbedWeights,
+           'abopt_gemm_tn_problem': hip.GemmTnProblem}
+# C spelling -> ctypes class.  Data pointers (device or host) and pointer-to-pointer are c_void_p; non-const int* / double* / long long* are host out-parameters.
+CTYPES = {'int': ctypes.c_int, 'int64_t': ctypes.c_int64, 'uint64_t': ctypes.c_uint64, 'size_t': ctypes.c_size_t, 'float': ctypes.c_float, 'double': ctypes.c_double,
+          'float[3]': ctypes.c_float * 3, 'char*': ctypes.c_char_p, 'const char*': ctypes.c_char_p,
+          'int*': ctypes.POINTER(ctypes.c_int), 'double*': ctypes.POINTER(ctypes.c_double), 'long long*': ctypes.POINTER(ctypes.c_longlong),
+          **{p: ctypes.c_void_p for p in ('abopt_stream', 'void*', 'const float*', 'float*', 'const int64_t*', 'int64_t*', 'const uint8_t*', 'uint8_t*', 'const int32_t*',
+                                          'const uint64_t*', 'const double*', 'const float* const*', 'float* const*')},
+          **{f'const {name}*': ctypes.POINTER(mirror) for name, mirror in STRUCTS.items()}}
+
+
+def ctype_of(spelling):
+    assert spelling in CTYPES, f'include/abopt.h spells a type this test cannot map: {spelling!r}'
+    return CTYPES[spelling]
+
+
+def parse_header():
+    """-> ({function: (return spelling, [argument spellings])}, {struct: [(field, spelling)]}, comment-stripped source) of include/abopt.h."""
+    src = re.sub(r'/\*.*?\*/', ' ', open(HEADER).read(), flags=re.S)
+    norm = lambda t: re.sub(r'\s*\*', '*', ' '.join(t.split()))                                      # 'const float*   x' and 'const float *x' spell one type
+    split = lambda decl: re.match(r'(.*?)(\w+)\s*((?:\[\d+\])?)$', decl.strip(), re.S).groups()      # 'type name[n]' -> (type, name, '[n]' or '')
+    protos = {}
+    for ret, name, args in re.findall(r'^\s*((?:const\s+)?\w+[\s*]+)(abopt_\w+)\s*\(([^()]*)\)\s*;', src, re.M):
+        protos[name] = (norm(ret), [] if args.strip() == 'void' else [norm(split(a)[0]) for a in args.split(',')])
+    structs = {}
+    for body, name in re.findall(r'typedef\s+struct\s*\{(.*?)\}\s*(abopt_\w+)\s*;', src, re.S):
+        structs[name] = []
+        for decl in filter(str.strip, body.split(';')):
+            first, *more = decl.split(',')                                                          # 'int N, L' declares two fields of one type
+            typ, field, arr = split(first)
+            structs[name] += [(f, norm(typ) + a) for f, a in [(field, arr)] + [split(m)[1:] for m in more]]
+    return protos, structs, src
+
+
+def signature_mismatches(table, protos):
+    """{function: what is wrong} for every entry of a name -> (restype, argtypes) table that is missing, surplus or not the header's prototype."""
+    bad = {name: 'not declared in the header' for name in table if name not in protos}
+    for name, (ret, args) in protos.items():
+        if name not in table:
+            bad[name] = 'missing from the table'
+            continue
+        restype, argtypes = table[name]
+        want = [ctype_of(a) for a in args]
+        if restype is not ctype_of(ret) or restype not in (ctypes.c_int, ctypes.c_size_t, ctypes.c_char_p):
+            bad[name] = f'restype {restype.__name__}, header returns {ret}'
+        elif len(argtypes) != len(want):
+            bad[name] = f'{len(argtypes)} arguments, header has {len(want)}'
+        elif any(g is not w for g, w in zip(argtypes, want)):
+            bad[name] = '; '.join(f'argument {i}: {g.__name__}, header has {a}' for i, (g, w, a) in enumerate(zip(argtypes, want, args)) if g is not w)
+    return bad
+
+
+def test_binding_signatures_match_header():
+    """hip._SIGNATURES against every prototype of include/abopt.h: same names, restype, argument count and the ctypes class of every argument."""
+    protos, _, src = parse_header()
+    assert len(protos) == len(set(re.findall(r'\b(abopt_\w+)\s*\(', src))), 'a prototype of the header escaped the parser'
+    assert signature_mismatches(hip._SIGNATURES, protos) == {}
+    # ... and the comparison can fail: a narrowed int64_t and a dropped argument are reported, and nothing else
+    broken = dict(hip._SIGNATURES)
+    ret, args = broken['abopt_so3_exp']
+    broken['abopt_so3_exp'] = (ret, [ctypes.c_int if a is ctypes.c_int64 else a for a in args])
+    broken['abopt_colsum'] = (broken['abopt_colsum'][0], broken['abopt_colsum'][1][:-1])
+    assert ctypes.c_int64 in args and set(signature_mismatches(broken, protos)) == {'abopt_so3_exp', 'abopt_colsum'}
 
 
 def test_library_exports_every_declared_symbol():
@@ -24,7 +86,7 @@ def test_library_exports_every_declared_symbol():
         import __graft_entry__
         __graft_entry__.build()
     L = ctypes.CDLL(hip.LIB_PATH)
-    syms = declared_symbols()
+    syms = sorted(parse_header()[0])
     assert len(syms) >= 13
     for s in syms:
         assert hasattr(L, s), f'{s} declared in include/abopt.h but not exported'
@@ -32,6 +94,9 @@ def test_library_exports_every_declared_symbol():
     L.abopt_abi_version.restype = ctypes.c_int
     assert L.abopt_abi_version() == hip.ABI_VERSION
     assert hip.lib() is not None
+    for name, (restype, argtypes) in hip._SIGNATURES.items():       # the loaded library carries the table: no function is left to ctypes' int defaults
+        fn = getattr(hip.lib(), name)
+        assert fn.argtypes is not None and list(fn.argtypes) == list(argtypes) and fn.restype is restype, name
 
 
 def test_size_queries_are_exact_past_32_bits():
@@ -63,16 +128,17 @@ def test_training_core_refuses_a_bias_cache_slab_of_4GB_before_any_launch():
 
 
 def test_struct_layouts_match_header_field_order():
-    """ctypes mirrors must list the header's fields in order (layout is positional)."""
-    src = open(HEADER).read()
-    body = src[src.index('typedef struct {', src.index('One GABlock')):src.index('} abopt_ga_weights;')]
-    names = re.findall(r'const float\*\s*(\w+);', body)
-    assert names == [n for n, _ in hip.GaWeights._fields_]
-    body = src[src.index('typedef struct {', src.index('Schedule scalars')):src.index('} abopt_step_params;')]
-    body = re.sub(r'/\*.*?\*/', '', body, flags=re.S)
-    names = re.findall(r'(?:int|float)\s+([\w, ]+?)(?:\[3\])?;', body)
-    flat = [x.strip() for n in names for x in n.split(',')]
-    assert flat == [n for n, _ in hip.StepParams._fields_]
+    """ctypes mirrors must list the header's fields in order (layout is positional), each with the ctypes type of its C spelling: all ten structs."""
+    structs = parse_header()[1]
+    assert set(structs) == set(STRUCTS) and len(STRUCTS) == 10
+    for name, fields in structs.items():
+        mirror = STRUCTS[name]._fields_
+        assert [f for f, _ in fields] == [f for f, _ in mirror], name
+        for (field, spelling), (_, ctype) in zip(fields, mirror):
+            assert ctype is ctype_of(spelling), f'{name}.{field}: {ctype.__name__}, header has {spelling}'
+    # the parser saw the spellings that are not plain data pointers: comma-separated declarators, an array, a struct pointer
+    assert structs['abopt_encode_inputs'][:4] == [(f, 'int') for f in ('N', 'L', 'atoms_in', 'atoms')]
+    assert ('position_mean', 'float[3]') in structs['abopt_step_params'] and ('blocks', 'const abopt_ga_weights*') in structs['abopt_eps_weights']
 
 
 def test_no_cpu_fallback():
