@@ -13,16 +13,56 @@ deliberate and MI355X-first:
     16-byte device buffer at execution time, inputs are copied into the graph's static buffers before a replay.
 """
 import collections
+import dataclasses
 import weakref
 import os
 import torch
 import torch.nn as nn
 
 from . import hip
-from .modules import (EpsilonNet, RotationTransition, PositionTransition, AminoacidCategoricalTransition, pRMSDCa)
+from .modules import (EpsilonNet, RotationTransition, PositionTransition, AminoacidCategoricalTransition, pRMSDCa, _Derived, _range_guarded)
 
 
-class FullDPM(nn.Module):
+@dataclasses.dataclass(frozen=True)
+class _LoopSpec:
+    """One denoising loop, from step t_start down to 0 (or for stop_after steps).  Everything below FullDPM._run takes the loop as this one value, and a
+    captured loop's cache key holds it whole: an option added here tells graphs apart with no further edit."""
+    t_start: int
+    stop_after: int | None = None
+    sample_structure: bool = True
+    sample_sequence: bool = True
+    ppl_masked: bool = True                     # perplexity over the generated residues (sample) or over all of them (optimize)
+    optimize_mode: bool = False                 # the net's third output is the position update's noise whatever `obj` is
+    use_bias_cache: bool | None = None          # None: FullDPM._denoise decides by free memory, once
+
+
+def _graph_key(spec, inputs, token):
+    """A captured loop serves calls with this device, these shapes, this spec and these packed weights (`token`: whoever stores the key keeps it alive)."""
+    res_feat, pair_feat, _, mask_res = inputs
+    return (res_feat.device.index, *mask_res.shape, tuple(res_feat.shape), tuple(pair_feat.shape), spec, id(token))
+
+
+def _free_bytes(dev):
+    """The driver's figure + what torch's caching allocator holds unused: a choice by free memory does not depend on what ran before in this process."""
+    return torch.cuda.mem_get_info(dev)[0] + torch.cuda.memory_reserved(dev) - torch.cuda.memory_allocated(dev)
+
+
+def _loop_inputs(inputs):
+    """(res_feat, pair_feat, mask_generate, mask_res) checked and as the kernels read them (contiguous, features fp32): the caller's own tensors where they already are.
+    Replicated-complex batches (one crop, N samples: design_for_pdb.py:141-147) may pass the context ONCE: res_feat (1,L,F) / pair_feat (1,L,L,C) are then shared by all
+    N samples -- the kernels index pair_feat and its bias cache with batch stride 0, so the 100 x 6 passes over it are served from L2/MALL instead of HBM.  And a test set
+    of complexes x S samples may pass G complexes once each: pair_feat (G,L,L,C), samples S c .. S c + S - 1 share entry c (design_for_testset.py:556-589; BASELINE config 4)."""
+    res_feat, pair_feat, mask_generate, mask_res = inputs
+    N, Nc = mask_res.shape[0], pair_feat.shape[0]
+    if Nc < 1 or N % Nc:
+        raise ValueError(f'pair_feat holds {Nc} complexes for a batch of {N} samples: the batch must be a whole number of samples per complex')
+    if res_feat.shape[0] not in (N, Nc):
+        raise ValueError('res_feat must hold one entry per sample or one per complex')
+    return res_feat.contiguous().float(), pair_feat.contiguous().float(), mask_generate.contiguous(), mask_res.contiguous()
+
+
+class FullDPM(_Derived, nn.Module):
+    _DERIVED = {'_graphs': collections.OrderedDict, '_graph_seen': set, '_host_sched': type(None)}       # captured loops and host-side caches: per-process objects
 
     def __init__(self, res_feat_dim, pair_feat_dim, num_steps, eps_net_opt={}, trans_rot_opt={}, trans_pos_opt={},
                  trans_seq_opt={}, position_mean=[0.0, 0.0, 0.0], position_scale=[10.0], obj='pred_noise',
@@ -42,17 +82,10 @@ class FullDPM(nn.Module):
         self.num_bins, self.dist_min, self.dist_max = num_bins, dist_min, dist_max
         if self.abdock:
             self.prmsd = pRMSDCa(num_bins, dist_min=dist_min, dist_max=dist_max)
-        self._host_sched = None
-        self._graphs, self._graph_seen = collections.OrderedDict(), set()
+        self._drop_derived()
         self.graph_mode = 'auto'          # 'auto': eager first, captured from the second call with the same signature; True / False
         self.max_graphs = 4               # captured loops kept (least recently used first out): each pins its own copy of pair_feat, the
                                           # pair-bias cache, the trajectory and a scratch slab -- about 1.2 GB at N=32, L=256
-
-    def __getstate__(self):
-        """Captured graphs and host-side caches are per-process objects: a pickled / deep-copied model starts without them."""
-        d = dict(self.__dict__)
-        d['_graphs'], d['_graph_seen'], d['_host_sched'] = collections.OrderedDict(), set(), None
-        return d
 
     def clear_graphs(self):
         """Drop every captured loop (and the memory its private pool pins).  Runners that walk many structures of different padded
@@ -102,6 +135,11 @@ class FullDPM(nn.Module):
     def _new_seed():
         return int(torch.randint(0, 2 ** 62, (1,)).item())
 
+    def _begin(self, seed):
+        """What sample() and optimize() start with: the library loaded, a seed from torch's CPU generator unless one is given, the schedule scalars."""
+        hip.lib()
+        return (self._new_seed() if seed is None else int(seed)), self._sched_host()
+
     # ------------------------------------------------------------------ training loss
     def forward(self, v_0, p_0, s_0, res_feat, pair_feat, mask_generate, mask_res, denoise_structure, denoise_sequence, t=None, noise=None):
         """dpm_full.py:156-234.  Noising, the denoiser (forward and backward: custom autograd functions over libabopt_hip.so) and the
@@ -112,50 +150,55 @@ class FullDPM(nn.Module):
     # ------------------------------------------------------------------ sampling
     def _run(self, state, t_start, res_feat, pair_feat, mask_generate, mask_res, sample_structure, sample_sequence,
              ppl_masked, noise, seed, rng_offset, pbar, stop_after=None, optimize_mode=False, use_bias_cache=None, graph=None):
-        """Denoise from step t_start down to 0.  state = (v, p_angstrom, s) on device.  graph: None = self.graph_mode."""
+        """Denoise from step t_start down to 0.  state = (v, p_angstrom, s) on device.  graph: None = self.graph_mode.
+        The positional form of benchmarks and tools: the one place that turns such arguments into a _LoopSpec."""
+        spec = _LoopSpec(t_start, stop_after, bool(sample_structure), bool(sample_sequence), bool(ppl_masked), bool(optimize_mode), use_bias_cache)
+        return self._denoise(spec, state, (res_feat, pair_feat, mask_generate, mask_res), noise, seed, rng_offset, pbar, graph)
+
+    def _denoise(self, spec, state, inputs, noise, seed, rng_offset, pbar, graph=None, range_safe=False):
+        """The loop `spec` on inputs = (res_feat, pair_feat, mask_generate, mask_res), eagerly or from its captured graph.  Settles spec.use_bias_cache,
+        here and nowhere else.  range_safe: eagerly, the dense layers as fp32 GEMMs (the answer to a raised range guard)."""
         graph = self.graph_mode if graph is None else graph
-        if noise is not None or pbar or not graph or not res_feat.is_cuda:     # (a CPU tensor reaches hip.ptr()'s "no CPU path" error)
-            return self._run_eager(state, t_start, res_feat, pair_feat, mask_generate, mask_res, sample_structure, sample_sequence,
-                                   ppl_masked, noise, seed, rng_offset, pbar, stop_after, optimize_mode, use_bias_cache)
-        N, L = mask_res.shape
-        shared = pair_feat.shape[0] != N
-        self.eps_net.packed()
-        mk = lambda cache: (res_feat.device.index, N, L, t_start, stop_after, bool(sample_structure), bool(sample_sequence), bool(ppl_masked),
-                            bool(optimize_mode), tuple(res_feat.shape), tuple(pair_feat.shape), bool(cache), id(self.eps_net._pack))
-        if use_bias_cache is None:
-            # a captured loop with the cache owns its memory already: no need to ask the allocator again (torch.cuda.memory_stats is 0.1 ms of host time per call)
-            use_bias_cache = shared or mk(True) in self._graphs or self._bias_cache_fits(pair_feat.shape[0], L, res_feat.device, graph=True)
-        key = mk(use_bias_cache)
-        g = self._graphs.get(key)
-        if g is None:
-            if graph == 'auto' and key not in self._graph_seen:         # a one-off call should not pay for a capture
-                if len(self._graph_seen) >= 64:
-                    self._graph_seen.clear()
-                self._graph_seen.add(key)
-                return self._run_eager(state, t_start, res_feat, pair_feat, mask_generate, mask_res, sample_structure, sample_sequence,
-                                       ppl_masked, noise, seed, rng_offset, pbar, stop_after, optimize_mode, use_bias_cache)
-            for k in [k for k, v in self._graphs.items() if v.pack is not self.eps_net._pack]:
+        res_feat, pair_feat, _, mask_res = inputs
+        capturable = bool(graph) and noise is None and not pbar and not range_safe and res_feat.is_cuda     # (a CPU tensor reaches hip.ptr()'s "no CPU path" error)
+        (N, L), Nc = mask_res.shape, pair_feat.shape[0]
+        token = self.eps_net.packed() if capturable else None
+        cache = spec.use_bias_cache
+        if cache is None:
+            # shared pair features need the cache; a captured loop with the cache owns its memory already: no need to ask the allocator again (torch.cuda.memory_stats
+            # is 0.1 ms of host time per call); a loop that is or will be captured is judged with the graph's own copy of pair_feat on top
+            cache = (Nc != N or (capturable and _graph_key(dataclasses.replace(spec, use_bias_cache=True), inputs, token) in self._graphs)
+                     or self._bias_cache_fits(Nc, L, res_feat.device, graph=capturable))
+        spec = dataclasses.replace(spec, use_bias_cache=bool(cache))
+        key = _graph_key(spec, inputs, token)
+        if capturable and key not in self._graphs and graph == 'auto' and key not in self._graph_seen:       # a one-off call should not pay for a capture
+            if len(self._graph_seen) >= 64:
+                self._graph_seen.clear()
+            self._graph_seen.add(key)
+            capturable = False
+        if not capturable:
+            return self._run_eager(spec, state, inputs, noise, seed, rng_offset, pbar, range_safe=range_safe)
+        if key not in self._graphs:
+            for k in [k for k, g in self._graphs.items() if g.token is not token]:
                 del self._graphs[k]                                     # weights were repacked: those graphs point at dead copies
             while len(self._graphs) >= max(1, int(self.max_graphs)):
                 self._graphs.popitem(last=False)                        # least recently used: its pool goes back to the allocator
-            g = self._graphs[key] = _LoopGraph(self, state, t_start, res_feat, pair_feat, mask_generate, mask_res, sample_structure,
-                                               sample_sequence, ppl_masked, stop_after, optimize_mode, use_bias_cache)
+            self._graphs[key] = _LoopGraph(self, spec, state, inputs, token)
         self._graphs.move_to_end(key)
+        g = self._graphs[key]
         self.last_run_info = g.info
-        return g.replay(state, res_feat, pair_feat, mask_generate, mask_res, seed, rng_offset)
+        return g.replay(state, inputs, seed, rng_offset)
 
     def _bias_cache_fits(self, n_pair, L, dev, graph=False):
         """The cache costs num_layers * N * L^2 * 48 B next to pair_feat's N * L^2 * 256 B: take it when it fits comfortably
         (a captured graph also keeps its own copy of pair_feat), otherwise the kernels compute the pair bias in place
-        (bit-identical, test_pair_bias_cache_is_bit_identical).  Free = what the driver reports + what torch's caching allocator
-        holds but is not using, so the choice does not depend on what ran before in this process."""
+        (bit-identical, test_pair_bias_cache_is_bit_identical)."""
         if dev.type != 'cuda':
             return False
         need = hip.pair_bias_cache_bytes(n_pair, L, len(self.eps_net.encoder.blocks)) + (hip.pair_terms_bytes(n_pair, L) if L <= 2048 else 0)
         if graph:
             need += n_pair * L * L * 64 * 4
-        free = torch.cuda.mem_get_info(dev)[0] + torch.cuda.memory_reserved(dev) - torch.cuda.memory_allocated(dev)
-        return need <= free // 2
+        return need <= _free_bytes(dev) // 2
 
     def _pair_terms_wanted(self, N, L, n_pair, dev):
         """The fp16 pair terms pay where the library's launch geometry takes the 32-row block kernels (abopt_pair_terms_used) and their
@@ -167,16 +210,21 @@ class FullDPM(nn.Module):
         # pair features and 7-9 % with distinct ones (the pair aggregation alone bought nothing there: the block kernel then sat on its streams)
         if e != '1' and not hip.pair_terms_used(N, L, N // n_pair if n_pair != N else 0):
             return False
-        free = torch.cuda.mem_get_info(dev)[0] + torch.cuda.memory_reserved(dev) - torch.cuda.memory_allocated(dev)
-        return hip.pair_terms_bytes(n_pair, L) <= free // 2
+        return hip.pair_terms_bytes(n_pair, L) <= _free_bytes(dev) // 2
 
-    def _run_eager(self, state, t_start, res_feat, pair_feat, mask_generate, mask_res, sample_structure, sample_sequence,
-                   ppl_masked, noise, seed, rng_offset, pbar, stop_after=None, optimize_mode=False, use_bias_cache=None, seed_dev=None, range_safe=False):
-        """The loop itself, one C call per network evaluation and one per transition.  seed_dev: device {seed, offset} (graph capture).
-        range_safe: the dense layers as fp32 GEMMs (the answer to a raised range guard, _guarded)."""
+    def _run_eager(self, spec, state, inputs, noise, seed, rng_offset, pbar, seed_dev=None, range_safe=False):
+        """The loop itself, one C call per network evaluation and one per transition; spec.use_bias_cache is settled (_denoise).
+        seed_dev: device {seed, offset} (graph capture)."""
+        res_feat, pair_feat, mask_generate, mask_res = _loop_inputs(inputs)
         dev = res_feat.device
         N, L = mask_res.shape
-        T0 = t_start
+        T0, Nc, use_bias_cache = spec.t_start, pair_feat.shape[0], spec.use_bias_cache
+        group = N // Nc
+        shared = group > 1
+        if shared and not use_bias_cache:
+            raise ValueError('a shared pair_feat requires the pair-bias cache')
+        if res_feat.shape[0] != N:
+            res_feat = res_feat.repeat_interleave(group, dim=0)
         f32 = dict(dtype=torch.float32, device=dev)
         tv = torch.empty(T0 + 1, N, L, 3, **f32)
         tp = torch.empty(T0 + 1, N, L, 3, **f32)
@@ -184,78 +232,39 @@ class FullDPM(nn.Module):
         tv[T0], tp[T0], ts[T0] = state
         tpr = torch.zeros(T0 + 1, N, **f32) if self.abdock else None
         tpp = torch.zeros(T0 + 1, N, **f32) if self.abdock else None
-
-        # Replicated-complex batches (one crop, N samples: design_for_pdb.py:141-147) may pass the context ONCE: res_feat
-        # (1,L,F) / pair_feat (1,L,L,C) are then shared by all N samples -- the kernels index pair_feat and its bias cache
-        # with batch stride 0, so the 100 x 6 passes over it are served from L2/MALL instead of HBM.
-        # ... and a test set of complexes x S samples may pass G complexes once each: pair_feat (G,L,L,C), samples S c .. S c + S - 1 share
-        # entry c (design_for_testset.py:556-589 runs them one structure at a time; BASELINE config 4).
-        Nc = pair_feat.shape[0]
-        if Nc < 1 or N % Nc:
-            raise ValueError(f'pair_feat holds {Nc} complexes for a batch of {N} samples: the batch must be a whole number of samples per complex')
-        group = N // Nc
-        shared = group > 1
-        if use_bias_cache is None:
-            use_bias_cache = shared or self._bias_cache_fits(Nc, L, dev)
-        if shared and not use_bias_cache:
-            raise ValueError('a shared pair_feat requires the pair-bias cache')
-        if res_feat.shape[0] != N:
-            if res_feat.shape[0] != Nc:
-                raise ValueError('res_feat must hold one entry per sample or one per complex')
-            res_feat = res_feat.repeat_interleave(group, dim=0)
-        res_feat, pair_feat = res_feat.contiguous().float(), pair_feat.contiguous().float()
-        mask_generate, mask_res = mask_generate.contiguous(), mask_res.contiguous()
         ew = self.eps_net.packed_fp32() if range_safe else self.eps_net.packed()
         # pair_feat and the weights are constant over the loop: project the pair bias of all blocks once (dpm_full.py:274-283 feeds
         # the same pair_feat to every step); ~0.4 ms at N=32, L=256, outside nothing -- it is part of this call
         pbc = hip.pair_bias_cache(self.eps_net.encoder.packed_array(), len(self.eps_net.encoder.blocks), pair_feat) if use_bias_cache else None
         # ... and, where the 32-row block kernels will run, re-lay pair_feat once as the fp16 operands of their pair aggregation (hip.pair_terms; ~0.25 ms)
         pterms = hip.pair_terms(pair_feat) if (use_bias_cache and self._pair_terms_wanted(N, L, Nc, dev)) else None
-        h = self._sched_host()
         inv = self.trans_rot.angular_distrib_inv
         X, cdf = inv.X, (inv.cdf() if noise is None else None)
         beta_rows = self.trans_pos.var_sched.betas[:T0 + 1, None].expand(T0 + 1, N).contiguous()    # beta_t per sample, one row per step
         net = dict(v_next=torch.empty(N, L, 3, **f32), R_next=torch.empty(N, L, 3, 3, **f32), eps_pos=torch.empty(N, L, 3, **f32),
                    c=torch.empty(N, L, 20, **f32), prmsd_logits=torch.empty(N, self.num_bins, **f32) if self.abdock else None)
         p_norm = torch.empty(N, L, 3, **f32)
-        scale, mean = self.position_scale, self.position_mean
         it = range(T0, 0, -1)
         if pbar:
             from tqdm.auto import tqdm
             it = tqdm(it, total=T0, desc='Sampling')
         # dpm_full.py:276: p_t = normalize(traj[t].p) -- here for the first step, afterwards written by the step kernel itself
-        torch.sub(tp[T0], mean, out=p_norm).div_(scale)
+        torch.sub(tp[T0], self.position_mean, out=p_norm).div_(self.position_scale)
         for t in it:
-            if stop_after is not None and T0 - t >= stop_after:
+            if spec.stop_after is not None and T0 - t >= spec.stop_after:
                 break
-            beta = beta_rows[t]
-            hip.eps_net_forward(ew, tv[t], p_norm, ts[t], res_feat, pair_feat, beta, mask_generate, mask_res,
+            hip.eps_net_forward(ew, tv[t], p_norm, ts[t], res_feat, pair_feat, beta_rows[t], mask_generate, mask_res,
                                 self.abdock, self.num_bins, False, out=net, pair_bias_cache=pbc, pair_feat_shared=(group if shared else 0), pair_terms=pterms)
-            sp = self._step_params(t, sample_structure, sample_sequence, ppl_masked, optimize_mode)
             out = dict(v=tv[t - 1], p=tp[t - 1], s=ts[t - 1], p_norm=p_norm)
             if self.abdock:
                 out.update(prmsd=tpr[t - 1], ppl=tpp[t - 1])
-            hip.denoise_step(sp, noise[t] if noise is not None else None, seed, rng_offset,
-                             tv[t], tp[t], ts[t], net['v_next'], net['eps_pos'], net['c'], net['prmsd_logits'], mask_generate,
-                             X[t], cdf[t] if cdf is not None else None, self.num_bins, out, seed_dev=seed_dev)
-        self.last_run_info = dict(bias_cache=bool(use_bias_cache), pair_terms=pterms is not None, shared_context=bool(shared), graph=seed_dev is not None)
+            hip.denoise_step(self._step_params(t, spec.sample_structure, spec.sample_sequence, spec.ppl_masked, spec.optimize_mode),
+                             noise[t] if noise is not None else None, seed, rng_offset, tv[t], tp[t], ts[t], net['v_next'], net['eps_pos'], net['c'],
+                             net['prmsd_logits'], mask_generate, X[t], cdf[t] if cdf is not None else None, self.num_bins, out, seed_dev=seed_dev)
+        self.last_run_info = dict(bias_cache=use_bias_cache, pair_terms=pterms is not None, shared_context=shared, graph=seed_dev is not None)
         return tv, tp, ts, tpr, tpp
 
-    def _guarded(self, run, rerun):
-        """Range guard of the two-term fp16 layers (include/abopt.h: abopt_nonfinite_flag): the reference's fp32 layers take activations beyond 65504, the
-        fp16 terms do not (inf -> NaN in the heads' outputs, which raises a device flag).  One flag read per call; if it is up, the whole loop is repeated
-        with the dense layers as fp32 GEMMs -- the caller gets what the reference's arithmetic gives (NaN only where fp32 itself overflows)."""
-        hip.nonfinite_flag_reset()                   # in stream order, no synchronisation: the flag read below is this call's
-        out = run()
-        if hip.nonfinite_flag(reset=False):
-            import warnings
-            warnings.warn('ab_opt_amd: a denoiser activation left the fp16 range (|x| >= 65504) or an input was not finite; this call is repeated with '
-                          'the dense layers as fp32 GEMMs (slower, fp32 range)', RuntimeWarning, stacklevel=3)
-            out = rerun()
-            hip.nonfinite_flag_reset()
-        return out
-
-    def _to_traj(self, T0, tv, tp, ts, tpr, tpp, first_extra):
+    def _to_traj(self, T0, tv, tp, ts, tpr, tpp):
         """Reference layout: dict t -> [v, p, s(, prmsd, ppl)], t>0 on the host, t=0 on the device."""
         hv, hp, hs = tv[1:].cpu(), tp[1:].cpu(), ts[1:].cpu()       # one bulk D2H each
         traj = {}
@@ -263,8 +272,8 @@ class FullDPM(nn.Module):
             hpr, hpp = tpr.cpu(), tpp.cpu()
         for t in range(T0, 0, -1):
             e = [hv[t - 1], hp[t - 1], hs[t - 1]]
-            if self.abdock:
-                e += list(first_extra(hs[t - 1])) if t == T0 else [hpr[t], hpp[t]]
+            if self.abdock:         # dpm_full.py:269: the first entry carries zeros_like(s) / ones_like(s) in the two extra slots
+                e += [torch.zeros_like(e[2]), torch.ones_like(e[2])] if t == T0 else [hpr[t], hpp[t]]
             traj[t] = e if self.abdock else tuple(e)
         e0 = [tv[0].clone(), tp[0].clone(), ts[0].clone()]       # own storage: the buffers may be a captured graph's static ones
         if self.abdock:
@@ -277,26 +286,18 @@ class FullDPM(nn.Module):
                pbar=False, noise=None, seed=None, rng_offset=0, use_bias_cache=None, graph=None, **kwargs):
         """dpm_full.py:236-302.  `noise` (optional) = {'init': {q4,p,s}, t: {axis,bin,ubin,gauss,z,s_next}} replays
         recorded draws; otherwise a Philox stream seeded from torch's CPU generator is used."""
-        hip.lib()
-        seed = self._new_seed() if seed is None else int(seed)
-        h = self._sched_host()
+        seed, h = self._begin(seed)
         state = hip.sample_init(v.float(), p.float(), s, mask_generate, noise['init'] if noise is not None else None, seed, rng_offset,
                                 h['scale'], h['mean'], sample_structure, sample_sequence)
-        T = self.num_steps
-        out = self._guarded(lambda: self._run(state, T, res_feat, pair_feat, mask_generate, mask_res, sample_structure, sample_sequence, True,
-                                              noise, seed, rng_offset, pbar, use_bias_cache=use_bias_cache, graph=graph),
-                            lambda: self._run_eager(state, T, res_feat, pair_feat, mask_generate, mask_res, sample_structure, sample_sequence, True,
-                                                    noise, seed, rng_offset, pbar, use_bias_cache=use_bias_cache, range_safe=True))
-        # dpm_full.py:269: the first entry carries zeros_like(s) / ones_like(s) in the two extra slots
-        return self._to_traj(T, *out, first_extra=lambda s_: (torch.zeros_like(s_), torch.ones_like(s_)))
+        spec = _LoopSpec(self.num_steps, None, bool(sample_structure), bool(sample_sequence), ppl_masked=True, use_bias_cache=use_bias_cache)
+        inputs = (res_feat, pair_feat, mask_generate, mask_res)
+        return self._to_traj(spec.t_start, *_range_guarded(lambda safe: self._denoise(spec, state, inputs, noise, seed, rng_offset, pbar, graph, safe)))
 
     @torch.no_grad()
     def optimize(self, v, p, s, opt_step, res_feat, pair_feat, mask_generate, mask_res, sample_structure=True,
                  sample_sequence=True, pbar=False, noise=None, seed=None, rng_offset=0, use_bias_cache=None, graph=None):
         """dpm_full.py:304-367: noise the input to step `opt_step`, then denoise."""
-        hip.lib()
-        seed = self._new_seed() if seed is None else int(seed)
-        h = self._sched_host()
+        seed, h = self._begin(seed)
         N = v.shape[0]
         t = torch.full([N], opt_step, dtype=torch.long, device=res_feat.device)
         init_noise = noise.get('init') if noise is not None else None
@@ -307,11 +308,10 @@ class FullDPM(nn.Module):
         state = (state[0], state[1], torch.where(mask_generate, state[2], s))       # dpm_full.py:335
         # dpm_full.py:351-358: the loop feeds the net's third output to the position update as noise whatever `obj` is,
         # and averages the perplexity over all residues (calc_perplexity(logits) without a mask)
-        out = self._guarded(lambda: self._run(state, opt_step, res_feat, pair_feat, mask_generate, mask_res, sample_structure, sample_sequence, False,
-                                              noise, seed, rng_offset, pbar, optimize_mode=True, use_bias_cache=use_bias_cache, graph=graph),
-                            lambda: self._run_eager(state, opt_step, res_feat, pair_feat, mask_generate, mask_res, sample_structure, sample_sequence, False,
-                                                    noise, seed, rng_offset, pbar, optimize_mode=True, use_bias_cache=use_bias_cache, range_safe=True))     # same counters as add_noise, other sub-sequence tags (csrc/denoise.hip): a sample's stream position does not depend on the batch it sits in
-        traj = self._to_traj(opt_step, *out, first_extra=lambda s_: (torch.zeros_like(s_), torch.ones_like(s_)))
+        spec = _LoopSpec(opt_step, None, bool(sample_structure), bool(sample_sequence), ppl_masked=False, optimize_mode=True, use_bias_cache=use_bias_cache)
+        inputs = (res_feat, pair_feat, mask_generate, mask_res)
+        # same counters as add_noise, other sub-sequence tags (csrc/denoise.hip): a sample's stream position does not depend on the batch it sits in
+        traj = self._to_traj(opt_step, *_range_guarded(lambda safe: self._denoise(spec, state, inputs, noise, seed, rng_offset, pbar, graph, safe)))
         return {k: tuple(e) for k, e in traj.items()}
 
 
@@ -322,20 +322,15 @@ class _LoopGraph:
     is the capturing stream, and every tensor the loop allocates (trajectory, network outputs, pair-bias cache, workspace) comes from
     the graph's private pool and keeps its address across replays.  Nothing in the loop reads device memory on the host."""
 
-    def __init__(self, dpm, state, t_start, res_feat, pair_feat, mask_generate, mask_res, sample_structure, sample_sequence, ppl_masked,
-                 stop_after, optimize_mode, use_bias_cache):
-        dev = res_feat.device
-        self.pack = dpm.eps_net._pack                                   # keeps the packed weights this graph points at alive
+    def __init__(self, dpm, spec, state, inputs, token):
+        self.token = token                                              # EpsilonNet.packed() at capture: keeps the packed weights this graph points at alive
         self.state = tuple(a.clone() for a in state)
-        self.res_feat, self.pair_feat = res_feat.contiguous().float().clone(), pair_feat.contiguous().float().clone()
-        self.mask_generate, self.mask_res = mask_generate.contiguous().clone(), mask_res.contiguous().clone()
-        self.seed_dev = torch.zeros(2, dtype=torch.int64, device=dev)
-        args = (self.state, t_start, self.res_feat, self.pair_feat, self.mask_generate, self.mask_res, sample_structure, sample_sequence,
-                ppl_masked, None, 0, 0, False)
-        kw = dict(optimize_mode=optimize_mode, use_bias_cache=use_bias_cache, seed_dev=self.seed_dev)
+        self.res_feat, self.pair_feat, self.mask_generate, self.mask_res = static = tuple(a.clone() for a in _loop_inputs(inputs))
+        self.seed_dev = torch.zeros(2, dtype=torch.int64, device=self.res_feat.device)
+        run = lambda stop_after: dpm._run_eager(dataclasses.replace(spec, stop_after=stop_after), self.state, static, None, 0, 0, False, seed_dev=self.seed_dev)
         hip.prof_enable(False)
-        dpm._run_eager(*args, stop_after=1, **kw)                       # warm: kernel attributes, host-side caches, cdf tables
-        torch.cuda.synchronize(dev)
+        run(1)                                                          # warm: kernel attributes, host-side caches, cdf tables
+        torch.cuda.synchronize(self.res_feat.device)
         self.graph = torch.cuda.CUDAGraph()
         before = set(hip.Workspace._bufs)
         hip.prof_enable(hip.GRAPH_CAPTURE_EVENTS)                       # normally off: the measurement hook's event pairs stay out of the graph
@@ -343,7 +338,7 @@ class _LoopGraph:
             hip.lib().abopt_prof_enable(3)               # span slots for the dominant kernel's launches, baked into the captured nodes
         try:
             with torch.cuda.graph(self.graph):
-                self.out = dpm._run_eager(*args, stop_after=stop_after, **kw)
+                self.out = run(spec.stop_after)
         finally:
             if hip.GRAPH_CAPTURE_EVENTS:
                 hip.lib().abopt_prof_enable(2)           # stop bracketing launches, keep the pairs the graph re-records
@@ -354,7 +349,8 @@ class _LoopGraph:
         self.info = dict(dpm.last_run_info)
         self._pf_src = None                                             # (weakref to the caller's pair_feat, its _version) of the last copy
 
-    def replay(self, state, res_feat, pair_feat, mask_generate, mask_res, seed, rng_offset):
+    def replay(self, state, inputs, seed, rng_offset):
+        res_feat, pair_feat, mask_generate, mask_res = inputs
         for dst, src in zip(self.state, state):
             dst.copy_(src)
         self.res_feat.copy_(res_feat if res_feat.shape == self.res_feat.shape else res_feat.expand_as(self.res_feat))

@@ -38,13 +38,42 @@ def _drop_packs(module, incompatible_keys):
     module.invalidate_packed()
 
 
+class _Derived:
+    """What a module derives from its parameters or its process (kernel-layout weight copies, ctypes structs, captured graphs), named ONCE per class: _DERIVED maps
+    attribute -> factory of its empty value.  Construction, invalidation and pickling / deep-copying read that one list: a cache added to it is missed by none."""
+    _DERIVED = {}
+
+    def _drop_derived(self):
+        self.__dict__.update({k: empty() for k, empty in self._DERIVED.items()})
+
+    def __getstate__(self):
+        return {**self.__dict__, **{k: empty() for k, empty in self._DERIVED.items()}}
+
+
+def _range_guarded(run, repeated='this call is repeated with the dense layers as fp32 GEMMs (slower, fp32 range)'):
+    """Range guard of the two-term fp16 layers (include/abopt.h: abopt_nonfinite_flag): the reference's fp32 layers take activations beyond 65504, the fp16 terms do
+    not (inf -> NaN in the heads' outputs, which raises a device flag).  The flag is cleared in stream order before run(False) and read ONCE after it (the only
+    synchronisation), so it reports that call alone: a flag left up by earlier work on the stream is not inherited.  If it is up, run(True) repeats the work with the
+    dense layers as fp32 GEMMs (NaN only where fp32 itself overflows, as in the reference) and the flag, this call's to clear, is down again on return.
+    `repeated` ends the warning's sentence; the warning names the line that called this function's caller."""
+    hip.nonfinite_flag_reset()
+    out = run(False)
+    if hip.nonfinite_flag(reset=False):
+        import warnings
+        warnings.warn('ab_opt_amd: a denoiser activation left the fp16 range (|x| >= 65504) or an input was not finite; ' + repeated, RuntimeWarning, stacklevel=3)
+        out = run(True)
+        hip.nonfinite_flag_reset()
+    return out
+
+
 def _snapshot(params):
     """Cheap fingerprint of a parameter list: rebuilt packs when a tensor is replaced, moved or updated in place."""
     return tuple((p.data_ptr(), p._version, p.device) for p in params)
 
 
-class GABlock(nn.Module):
+class GABlock(_Derived, nn.Module):
     """Invariant point attention block (ga.py:40-178)."""
+    _DERIVED = {'_pack': type(None)}
 
     def __init__(self, node_feat_dim, pair_feat_dim, value_dim=32, query_key_dim=32, num_query_points=8,
                  num_value_points=8, num_heads=12, bias=False):
@@ -70,7 +99,7 @@ class GABlock(nn.Module):
                                             nn.Linear(node_feat_dim, node_feat_dim), nn.ReLU(),
                                             nn.Linear(node_feat_dim, node_feat_dim))
         self.layer_norm_2 = LayerNorm(node_feat_dim)
-        self._pack = None
+        self._drop_derived()
 
     def _sources(self):
         return [self.proj_query.weight, self.proj_key.weight, self.proj_value.weight, self.proj_query_point.weight,
@@ -104,13 +133,7 @@ class GABlock(nn.Module):
         self._pack = (snap, t, s)
         return t, s
 
-    def invalidate_packed(self):
-        self._pack = None
-
-    def __getstate__(self):
-        d = dict(self.__dict__)
-        d['_pack'] = None
-        return d
+    invalidate_packed = _Derived._drop_derived
 
     @torch.no_grad()
     def forward(self, R, t, x, z, mask, return_parts=False):
@@ -181,8 +204,9 @@ def _pad_k(w, k_to):
     return out
 
 
-class EpsilonNet(nn.Module):
+class EpsilonNet(_Derived, nn.Module):
     """dpm_full.py:35-112.  `no_bins=None` builds the AbDesign variant (no prmsd head, A/...:33-102)."""
+    _DERIVED = {'_pack': type(None), '_pack32': type(None)}      # _pack32 = packed_fp32(): built by the first range-guard fallback
 
     def __init__(self, res_feat_dim, pair_feat_dim, num_layers, no_bins=None, encoder_opt={}):
         super().__init__()
@@ -196,8 +220,7 @@ class EpsilonNet(nn.Module):
         self.no_bins = no_bins
         if no_bins is not None:
             self.prmsd_predictor = PerResidueRMSDCaPredictor(no_bins, F + 3, F)
-        self._pack = None
-        self._pack32 = None                      # packed_fp32(): built by the first range-guard fallback
+        self._drop_derived()
         # packed (kernel-layout) weight copies are keyed on (data_ptr, _version, device) of their sources; writes that bypass the
         # version counter (`p.data.copy_(ema)`) are invisible to that key, so the usual entry points drop the packs outright
         self.register_load_state_dict_post_hook(_drop_packs)
@@ -205,7 +228,7 @@ class EpsilonNet(nn.Module):
     def invalidate_packed(self):
         """Forget the kernel-layout weight copies (rebuilt at the next call).  Call after writing parameters through `.data`
         (EMA swaps); `load_state_dict`, `train()` and `eval()` call it for you."""
-        self._pack = self._pack32 = None
+        self._drop_derived()
         for b in self.encoder.blocks:
             b.invalidate_packed()
 
@@ -213,11 +236,6 @@ class EpsilonNet(nn.Module):
         if bool(mode) != self.training:          # an actual train <-> eval switch (EMA swaps happen around these), not every .eval() call
             self.invalidate_packed()
         return super().train(mode)
-
-    def __getstate__(self):
-        d = dict(self.__dict__)
-        d['_pack'] = d['_pack32'] = None         # ctypes structs + device copies: rebuilt on first use
-        return d
 
     def _sources(self):
         # every parameter outside the encoder (whose blocks fingerprint their own), in named_parameters() order, without walking the encoder's modules
@@ -229,10 +247,12 @@ class EpsilonNet(nn.Module):
 
     @torch.no_grad()
     def packed(self):
+        """The ctypes struct the kernels read (cached).  It owns the device copies it points at (`.tensors`), so whoever holds it -- a captured loop, whose
+        identity token it also is -- keeps them alive; a repack returns another object."""
         arr = self.encoder.packed_array()
         snap = _snapshot(self._sources()) + tuple(b._pack[0] for b in self.encoder.blocks)        # (packed_array() has just verified / rebuilt every block's own fingerprint)
         if self._pack is not None and self._pack[0] == snap:
-            return self._pack[2]
+            return self._pack[1]
         f = lambda p: p.detach().float().contiguous()
         F = self.current_sequence_embedding.weight.shape[1]
         crd, rot, seq = self.eps_crd_net, self.eps_rot_net, self.eps_seq_net
@@ -265,7 +285,8 @@ class EpsilonNet(nn.Module):
                 ew.num_bins = self.no_bins or 0
             else:
                 setattr(ew, name, hip.ptr(t[name], torch.float32) if name in t else None)
-        self._pack = (snap, (t, arr), ew)
+        ew.tensors = (t, arr)
+        self._pack = (snap, ew)
         return ew
 
     @torch.no_grad()
@@ -292,22 +313,15 @@ class EpsilonNet(nn.Module):
     def forward(self, v_t, p_t, s_t, res_feat, pair_feat, beta, mask_generate, mask_res, grad_mode=False):
         """dpm_full.py:70-112 -> (v_next, R_next, eps_pos, c_denoised[, prmsd_logits]).
 
-        Range guard (include/abopt.h: abopt_nonfinite_flag): the flag is cleared in stream order before the call and read ONCE after it (the only synchronisation),
-        so it reports this call alone -- a flag left up by earlier work on the stream (a raw hip.eps_net_forward) is not inherited -- and it is down again when
-        forward returns.  While the current stream is capturing (a caller's own torch.cuda.graph around this call) the host can neither read nor clear the flag:
-        the call is recorded as it is, without a fallback, and the caller reads hip.nonfinite_flag() after a replay."""
-        guard = res_feat.is_cuda and not torch.cuda.is_current_stream_capturing()
-        if guard:
-            hip.nonfinite_flag_reset()
-        o = hip.eps_net_forward(self.packed(), v_t, p_t, s_t, res_feat, pair_feat, beta, mask_generate, mask_res,
-                                self.no_bins is not None, self.no_bins or 0, grad_mode)
-        if guard and hip.nonfinite_flag(reset=False):          # range guard of the two-term fp16 layers: repeat on fp32 GEMMs
-            import warnings
-            warnings.warn('ab_opt_amd: a denoiser activation left the fp16 range (|x| >= 65504) or an input was not finite; EpsilonNet.forward is repeated '
-                          'with the dense layers as fp32 GEMMs', RuntimeWarning, stacklevel=2)
-            o = hip.eps_net_forward(self.packed_fp32(), v_t, p_t, s_t, res_feat, pair_feat, beta, mask_generate, mask_res,
-                                    self.no_bins is not None, self.no_bins or 0, grad_mode)
-            hip.nonfinite_flag_reset()                         # (fp32 itself may overflow: the answer is then the reference's, and the flag is this call's to clear)
+        Runs under the range guard (_range_guarded): the flag it acts on is this call's own, and it is down again when forward returns.  While the current
+        stream is capturing (a caller's own torch.cuda.graph around this call) the host can neither read nor clear the flag: the call is recorded as it is,
+        without a fallback, and the caller reads hip.nonfinite_flag() after a replay."""
+        run = lambda range_safe: hip.eps_net_forward(self.packed_fp32() if range_safe else self.packed(), v_t, p_t, s_t, res_feat, pair_feat, beta,
+                                                     mask_generate, mask_res, self.no_bins is not None, self.no_bins or 0, grad_mode)
+        if res_feat.is_cuda and not torch.cuda.is_current_stream_capturing():
+            o = _range_guarded(run, 'EpsilonNet.forward is repeated with the dense layers as fp32 GEMMs')
+        else:
+            o = run(False)
         if self.no_bins is not None:
             return o['v_next'], o['R_next'], o['eps_pos'], o['c'], o['prmsd_logits']
         return o['v_next'], o['R_next'], o['eps_pos'], o['c']

@@ -16,6 +16,7 @@ import torch.nn.functional as F
 import cases
 from conftest import load_golden, build_model, max_abs
 from ab_opt_amd.utils import synth
+from ab_opt_amd.dpm import _LoopSpec
 from test_oracle_golden import standalone_block_sd, standalone_abdesign_dpm, noise_dict
 
 pytestmark = pytest.mark.gpu
@@ -1432,7 +1433,7 @@ def test_fp16_range_guard_falls_back_to_fp32_layers():
     assert all(torch.isfinite(traj[t][1]).all() for t in traj)
     hh = d._sched_host()
     state = hip.sample_init(v.float(), (p * 10).float(), s, gen, None, 5, 0, hh['scale'], hh['mean'], True, True)
-    tv, tp, ts, _, _ = d._run_eager(state, T, big, pf, gen, mres, True, True, True, None, 5, 0, False, range_safe=True)
+    tv, tp, ts, _, _ = d._denoise(_LoopSpec(T), state, (big, pf, gen, mres), None, 5, 0, False, range_safe=True)
     assert torch.equal(traj[0][1], tp[0]) and torch.equal(traj[0][2], ts[0])
     with warnings.catch_warnings():
         warnings.simplefilter('error')
