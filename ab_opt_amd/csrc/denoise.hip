@@ -30,7 +30,7 @@ __global__ __launch_bounds__(256) void denoise_step_kernel(abopt_step_params sp,
                                                            const float* __restrict__ igX, const float* __restrict__ igCdf, int bins, int num_bins,
                                                            float* __restrict__ v_next, float* __restrict__ p_next, int64_t* __restrict__ s_next,
                                                            float* __restrict__ prmsd, float* __restrict__ ppl, float* __restrict__ post_out,
-                                                           float* __restrict__ p_next_norm, int L, int ppl_masked) {
+                                                           float* __restrict__ p_next_norm, const int32_t* __restrict__ aa_allowed, int L, int ppl_masked) {
     const int n = blockIdx.x, tid = threadIdx.x;
     const bool injected = nz.axis != nullptr;
     if (seed_dev) { seed = seed_dev[0]; offset = seed_dev[1]; }     // graph replays: the stream position comes from device memory
@@ -47,7 +47,7 @@ __global__ __launch_bounds__(256) void denoise_step_kernel(abopt_step_params sp,
         __syncthreads();
     }
 
-    const DenoiseRowIO io{v_t, p_t, s_t, v_net, p_net, c_net, mask_generate, igX, igCdf, bins, v_next, p_next, s_next, post_out, p_next_norm};
+    const DenoiseRowIO io{v_t, p_t, s_t, v_net, p_net, c_net, mask_generate, aa_allowed, igX, igCdf, bins, v_next, p_next, s_next, post_out, p_next_norm};
     for (int l = tid; l < L; l += 256) {
         const int64_t i = (int64_t)n * L + l;
         float nx_, ny_, nz_;
@@ -79,10 +79,12 @@ __global__ __launch_bounds__(256) void sample_init_kernel(const float* __restric
                                                           const uint8_t* __restrict__ mask_generate, const float* __restrict__ q4,
                                                           const float* __restrict__ pn, const int64_t* __restrict__ sr, uint64_t seed, uint64_t offset,
                                                           float scale, float m0, float m1, float m2, int sample_structure, int sample_sequence,
-                                                          float* __restrict__ v_init, float* __restrict__ p_init, int64_t* __restrict__ s_init, int64_t rows) {
+                                                          float* __restrict__ v_init, float* __restrict__ p_init, int64_t* __restrict__ s_init,
+                                                          const int32_t* __restrict__ aa_allowed, int64_t rows) {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= rows) return;
     const bool gen = mask_generate[i] != 0;
+    const uint32_t allow = aa_allowed_set(aa_allowed, i, gen);
     const float mean[3] = {m0, m1, m2};
     float q[4], g[3];
     int64_t srand_;
@@ -99,7 +101,13 @@ __global__ __launch_bounds__(256) void sample_init_kernel(const float* __restric
         box_muller(r1.x, r1.y, g[0], g[1]);
         box_muller(r1.z, r1.w, g[2], d0);
         const Philox rng2(seed ^ 0x5bd1e995ull);
-        srand_ = (int64_t)(rng2(offset + (uint64_t)i, 0xFFFF02ull).x % 19u);     // randint_like(low=0, high=19): TYR never drawn
+        // randint_like(low=0, high=19): TYR never drawn.  Under a constraint: uniform over the allowed types among 0..18, the (r % count)-th set bit (r % 19 itself
+        // when all are allowed); TYR only where nothing else is allowed
+        const uint32_t r = rng2(offset + (uint64_t)i, 0xFFFF02ull).x;
+        uint32_t low = allow & (AA_ALL >> 1);
+        const uint32_t nth = low ? r % (uint32_t)__popc(low) : 0u;
+        for (uint32_t c = 0; c < nth; ++c) low &= low - 1u;                       // drop the nth lowest allowed types: the next one is the draw
+        srand_ = low ? (int64_t)(__ffs((int)low) - 1) : (int64_t)(KAA - 1);
         if (sr) srand_ = sr[i];      // sample_structure = False draws the sequence alone (dpm_full.py:262-267): it can be injected alone
     }
     // random_uniform_so3: F.normalize then quaternion_to_rotation_matrix (which normalises again), so3.py:66-68
@@ -113,7 +121,7 @@ __global__ __launch_bounds__(256) void sample_init_kernel(const float* __restric
         v_init[i * 3 + k] = rnd ? wr[k] : v[i * 3 + k];
         p_init[i * 3 + k] = (rnd ? g[k] : pnorm) * scale + mean[k];
     }
-    s_init[i] = (gen && sample_sequence) ? srand_ : s[i];
+    s_init[i] = (gen && sample_sequence && allow != 0u) ? srand_ : s[i];        // an empty set: the type is frozen
 }
 
 // Forward noising of all three modalities (transition.py:62-78,120-144,179-200); one thread per residue.
@@ -125,11 +133,13 @@ __global__ __launch_bounds__(256) void add_noise_kernel(const int64_t* __restric
                                                         const uint8_t* __restrict__ mask_generate, float scale, float m0, float m1, float m2,
                                                         int noise_structure, int noise_sequence, int grad_mode,
                                                         float* __restrict__ v_noisy, float* __restrict__ p_noisy, int64_t* __restrict__ s_noisy,
-                                                        float* __restrict__ eps_p, float* __restrict__ c_noisy, int L, int64_t rows) {
+                                                        float* __restrict__ eps_p, float* __restrict__ c_noisy, const int32_t* __restrict__ aa_allowed,
+                                                        int L, int64_t rows) {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= rows) return;
     const int64_t tt = t[i / L];
     const bool gen = mask_generate[i] != 0;
+    const uint32_t allow = aa_allowed_set(aa_allowed, i, gen);
     const float abar = alpha_bars[tt];
     const float c0 = sqrtf(abar), c1 = sqrtf(1.f - abar);
     const float mean[3] = {m0, m1, m2};
@@ -193,16 +203,17 @@ __global__ __launch_bounds__(256) void add_noise_kernel(const int64_t* __restric
             const float oh = (ok && s0 == k) ? 1.f : 0.f;
             const float ck = gen ? (abar * oh) + ((1.f - abar) / (float)KAA) : oh;       // c_t, transition.py:196-198
             if (c_noisy) c_noisy[i * KAA + k] = ck;
-            c[k] = ck + 1e-8f;                                                             // _sample adds 1e-8 (transition.py:179)
-            tot += c[k];
+            c[k] = ((allow >> k) & 1u) ? ck + 1e-8f : 0.f;                                 // _sample adds 1e-8 (transition.py:179); a disallowed class is skipped
+            tot += c[k];                                                                   // (c_noisy above stays the reference's unconstrained c_t)
         }
         if (injected) sn = nz.s_noisy[i];
         else {
             const float target = useq * tot;
             float cum = 0.f;
-            sn = KAA - 1;
-            for (int k = 0; k < KAA; ++k) { cum += c[k]; if (cum > target) { sn = k; break; } }
+            sn = aa_last_allowed(allow);
+            for (int k = 0; k < KAA; ++k) { cum += c[k]; if (((allow >> k) & 1u) && cum > target) { sn = k; break; } }
         }
+        if (allow == 0u) sn = s0;                                                          // an empty set: the type is frozen
     } else if (c_noisy) {
 #pragma unroll
         for (int k = 0; k < KAA; ++k) c_noisy[i * KAA + k] = (s0 == k) ? 1.f : 0.f;      // c_0 = clampped_one_hot(s_0), transition.py:189
@@ -253,7 +264,8 @@ extern "C" int abopt_denoise_step(const abopt_step_params* sp, const abopt_step_
                                   const float* v_net, const float* p_net, const float* c_net, const float* prmsd_logits,
                                   const uint8_t* mask_generate, const float* igso3_X, const float* igso3_cdf, int igso3_bins, int num_bins,
                                   float* v_next, float* p_next, int64_t* s_next, float* prmsd, float* perplexity,
-                                  float* post_out, float* p_next_norm, const uint64_t* seed_offset_dev, int N, int L, abopt_stream stream) {
+                                  float* post_out, float* p_next_norm, const uint64_t* seed_offset_dev, const int32_t* aa_allowed,
+                                  int N, int L, abopt_stream stream) {
     ABOPT_CHECK_ARG(sp && v_t && p_t && s_t && v_net && p_net && c_net && mask_generate && v_next && p_next && s_next, "denoise_step: NULL argument");
     ABOPT_CHECK_ARG(igso3_X && igso3_bins >= 2, "denoise_step: IGSO(3) histogram row missing");
     abopt_step_noise nz = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
@@ -266,7 +278,7 @@ extern "C" int abopt_denoise_step(const abopt_step_params* sp, const abopt_step_
     if (N == 0 || L == 0) return ABOPT_OK;
     hipLaunchKernelGGL(denoise_step_kernel, dim3(N), dim3(256), 0, (hipStream_t)stream, *sp, nz, seed, offset, seed_offset_dev, v_t, p_t, s_t, v_net, p_net, c_net,
                        prmsd_logits, mask_generate, igso3_X, igso3_cdf, igso3_bins, num_bins, v_next, p_next, s_next, prmsd, perplexity, post_out,
-                       p_next_norm, L, sp->ppl_masked);
+                       p_next_norm, aa_allowed, L, sp->ppl_masked);
     ABOPT_LAUNCH_CHECK();
     return ABOPT_OK;
 }
@@ -274,14 +286,14 @@ extern "C" int abopt_denoise_step(const abopt_step_params* sp, const abopt_step_
 extern "C" int abopt_sample_init(const float* v, const float* p, const int64_t* s, const uint8_t* mask_generate,
                                  const float* q4, const float* pn, const int64_t* sr, uint64_t seed, uint64_t offset,
                                  float position_scale, const float* position_mean, int sample_structure, int sample_sequence,
-                                 float* v_init, float* p_init, int64_t* s_init, int N, int L, abopt_stream stream) {
+                                 float* v_init, float* p_init, int64_t* s_init, const int32_t* aa_allowed, int N, int L, abopt_stream stream) {
     ABOPT_CHECK_ARG(v && p && s && mask_generate && v_init && p_init && s_init && position_mean, "sample_init: NULL argument");
     ABOPT_CHECK_ARG((q4 == nullptr) == (pn == nullptr), "sample_init: q4 and pn must be given together");
     const int64_t rows = (int64_t)N * L;
     if (rows == 0) return ABOPT_OK;
     hipLaunchKernelGGL(sample_init_kernel, dim3((unsigned)((rows + 255) / 256)), dim3(256), 0, (hipStream_t)stream, v, p, s, mask_generate, q4, pn, sr,
                        seed, offset, position_scale, position_mean[0], position_mean[1], position_mean[2], sample_structure, sample_sequence,
-                       v_init, p_init, s_init, rows);
+                       v_init, p_init, s_init, aa_allowed, rows);
     ABOPT_LAUNCH_CHECK();
     return ABOPT_OK;
 }
@@ -292,7 +304,7 @@ extern "C" int abopt_add_noise(const int64_t* t, const float* alpha_bars, const 
                                const float* v_0, const float* p_0, const int64_t* s_0, const uint8_t* mask_generate,
                                float position_scale, const float* position_mean, int noise_structure, int noise_sequence, int grad_mode,
                                float* v_noisy, float* p_noisy, int64_t* s_noisy, float* eps_p, float* c_noisy, const uint64_t* seed_offset_dev,
-                               int N, int L, abopt_stream stream) {
+                               const int32_t* aa_allowed, int N, int L, abopt_stream stream) {
     ABOPT_CHECK_ARG(t && alpha_bars && fwd_stddevs && fwd_approx && fwd_X && v_0 && p_0 && s_0 && mask_generate && position_mean &&
                     v_noisy && p_noisy && s_noisy && bins >= 2 && num_sched >= 1, "add_noise: bad arguments");
     abopt_addnoise_noise nz = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
@@ -308,7 +320,7 @@ extern "C" int abopt_add_noise(const int64_t* t, const float* alpha_bars, const 
     if (rows == 0) return ABOPT_OK;
     hipLaunchKernelGGL(add_noise_kernel, dim3((unsigned)((rows + 255) / 256)), dim3(256), 0, (hipStream_t)stream, t, alpha_bars, fwd_stddevs, fwd_approx,
                        fwd_X, fwd_cdf, bins, nz, seed, offset, seed_offset_dev, v_0, p_0, s_0, mask_generate, position_scale, position_mean[0], position_mean[1],
-                       position_mean[2], noise_structure, noise_sequence, grad_mode, v_noisy, p_noisy, s_noisy, eps_p, c_noisy, L, rows);
+                       position_mean[2], noise_structure, noise_sequence, grad_mode, v_noisy, p_noisy, s_noisy, eps_p, c_noisy, aa_allowed, L, rows);
     ABOPT_LAUNCH_CHECK();
     return ABOPT_OK;
 }

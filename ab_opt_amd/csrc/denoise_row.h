@@ -3,6 +3,10 @@
 //   AminoacidCategoricalTransition.denoise (transition.py:202-245), and the residue's perplexity term (dpm_full.py:392-396)
 // as ONE device function shared by denoise_step_kernel (denoise.hip: one workgroup per sample) and by the mixer kernel of the NEXT network evaluation
 // (heads.hip, round 5: the step's transitions run on an otherwise idle wave of that launch) -- the same arithmetic in the same order, bit for bit.
+//
+// Allowed residue types (include/abopt.h: aa_allowed): one int32 word per residue, bit k = type k may be drawn, read on generated residues only.  A disallowed
+// class leaves the categorical BEFORE it is normalised (its unnormalised product becomes 0), so post_out, the draw and the perplexity term all see the distribution
+// that is sampled; with every bit set each operation below is the unconstrained one on the same values in the same order.
 #pragma once
 #include "abopt_common.h"
 #include "kernels.h"
@@ -11,9 +15,18 @@ namespace abopt {
 
 constexpr int KAA = ABOPT_AA;
 constexpr float PI_F = 3.14159265358979323846f;
+constexpr uint32_t AA_ALL = (1u << KAA) - 1u;
+
+// The set a residue's type is drawn from: every type where there is no constraint or the residue is not generated; bits KAA.. of the word are ignored.
+// 0 (an empty word on a generated residue) freezes the residue's type.
+__device__ __forceinline__ uint32_t aa_allowed_set(const int32_t* aa_allowed, int64_t i, bool gen) {
+    return (aa_allowed && gen) ? ((uint32_t)aa_allowed[i] & AA_ALL) : AA_ALL;
+}
+// highest allowed class: where an inverse-CDF walk ends when rounding leaves it short of its target (KAA - 1 without a constraint)
+__device__ __forceinline__ int aa_last_allowed(uint32_t allow) { return 31 - __clz((int)allow); }
 
 struct DenoiseRowIO {
-    const float* v_t; const float* p_t; const int64_t* s_t; const float* v_net; const float* p_net; const float* c_net; const uint8_t* mask_generate;
+    const float* v_t; const float* p_t; const int64_t* s_t; const float* v_net; const float* p_net; const float* c_net; const uint8_t* mask_generate; const int32_t* aa_allowed;
     const float* igX; const float* igCdf; int bins;
     float* v_next; float* p_next; int64_t* s_next; float* post_out; float* p_next_norm;
 };
@@ -100,19 +113,23 @@ __device__ __forceinline__ void denoise_row(int64_t i, const abopt_step_params& 
     // ---- sequence (transition.py:202-245): NOTE alpha_bar_t multiplies both factors (reference quirk)
     const int64_t st = s_t[i];
     const bool st_ok = st >= 0 && st < KAA;
+    const uint32_t allow = aa_allowed_set(io.aa_allowed, i, gen);
+    const bool draws = gen && allow != 0u;          // an empty set: the type is frozen, its posterior is onehot(s_t) like a context residue's (the structure above still moved)
     float post[KAA], tot = 0.f;
     const float ab = sp.alpha_bar, unif = (1.f - ab) / (float)KAA;
 #pragma unroll
     for (int k = 0; k < KAA; ++k) {
         const float ct = (st_ok && st == k) ? 1.f : 0.f;
-        post[k] = ((ab * ct) + unif) * ((ab * c_net[i * KAA + k]) + unif);
-        tot += post[k];
+        const float raw = ((ab * ct) + unif) * ((ab * c_net[i * KAA + k]) + unif);
+        const bool ok = ((allow >> k) & 1u) != 0u;
+        tot = ok ? tot + raw : tot;                 // `tot + raw` as the unconstrained code spells it: the compiler contracts it to the same fma
+        post[k] = ok ? raw : 0.f;
     }
     float pmax = -INFINITY;
 #pragma unroll
     for (int k = 0; k < KAA; ++k) {
         const float ct = (st_ok && st == k) ? 1.f : 0.f;
-        post[k] = gen ? post[k] / (tot + 1e-8f) : ct;
+        post[k] = draws ? post[k] / (tot + 1e-8f) : ct;
         pmax = fmaxf(pmax, post[k]);
         if (post_out) post_out[i * KAA + k] = post[k];
     }
@@ -121,12 +138,16 @@ __device__ __forceinline__ void denoise_row(int64_t i, const abopt_step_params& 
     else {
         float cum = 0.f, total = 0.f;
 #pragma unroll
-        for (int k = 0; k < KAA; ++k) total += post[k] + 1e-8f;
+        for (int k = 0; k < KAA; ++k) total += ((allow >> k) & 1u) ? post[k] + 1e-8f : 0.f;
         const float target = useq * total;
-        sn = KAA - 1;
-        for (int k = 0; k < KAA; ++k) { cum += post[k] + 1e-8f; if (cum > target) { sn = k; break; } }
+        sn = aa_last_allowed(allow);
+        for (int k = 0; k < KAA; ++k) {
+            const bool ok = ((allow >> k) & 1u) != 0u;
+            cum += ok ? post[k] + 1e-8f : 0.f;
+            if (ok && cum > target) { sn = k; break; }
+        }
     }
-    s_next[i] = sp.sample_sequence ? sn : st;
+    s_next[i] = (sp.sample_sequence && allow != 0u) ? sn : st;
     // perplexity term: max softmax(post) (dpm_full.py:392-396)
     float se = 0.f;
 #pragma unroll

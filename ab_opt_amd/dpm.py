@@ -34,11 +34,12 @@ class _LoopSpec:
     ppl_masked: bool = True                     # perplexity over the generated residues (sample) or over all of them (optimize)
     optimize_mode: bool = False                 # the net's third output is the position update's noise whatever `obj` is
     use_bias_cache: bool | None = None          # None: FullDPM._denoise decides by free memory, once
+    constrained: bool = False                   # the loop's inputs end with aa_allowed, the allowed residue types per residue (the contents are data, not key)
 
 
 def _graph_key(spec, inputs, token):
     """A captured loop serves calls with this device, these shapes, this spec and these packed weights (`token`: whoever stores the key keeps it alive)."""
-    res_feat, pair_feat, _, mask_res = inputs
+    res_feat, pair_feat, _, mask_res = inputs[:4]
     return (res_feat.device.index, *mask_res.shape, tuple(res_feat.shape), tuple(pair_feat.shape), spec, id(token))
 
 
@@ -48,17 +49,44 @@ def _free_bytes(dev):
 
 
 def _loop_inputs(inputs):
-    """(res_feat, pair_feat, mask_generate, mask_res) checked and as the kernels read them (contiguous, features fp32): the caller's own tensors where they already are.
+    """(res_feat, pair_feat, mask_generate, mask_res[, aa_allowed]) checked and as the kernels read them (contiguous, features fp32): the caller's own tensors where
+    they already are.  aa_allowed, the fifth input of a constrained loop (_LoopSpec.constrained), is the int32 (N, L) tensor of _checked_allowed.
     Replicated-complex batches (one crop, N samples: design_for_pdb.py:141-147) may pass the context ONCE: res_feat (1,L,F) / pair_feat (1,L,L,C) are then shared by all
     N samples -- the kernels index pair_feat and its bias cache with batch stride 0, so the 100 x 6 passes over it are served from L2/MALL instead of HBM.  And a test set
     of complexes x S samples may pass G complexes once each: pair_feat (G,L,L,C), samples S c .. S c + S - 1 share entry c (design_for_testset.py:556-589; BASELINE config 4)."""
-    res_feat, pair_feat, mask_generate, mask_res = inputs
+    res_feat, pair_feat, mask_generate, mask_res, *allowed = inputs
     N, Nc = mask_res.shape[0], pair_feat.shape[0]
     if Nc < 1 or N % Nc:
         raise ValueError(f'pair_feat holds {Nc} complexes for a batch of {N} samples: the batch must be a whole number of samples per complex')
     if res_feat.shape[0] not in (N, Nc):
         raise ValueError('res_feat must hold one entry per sample or one per complex')
-    return res_feat.contiguous().float(), pair_feat.contiguous().float(), mask_generate.contiguous(), mask_res.contiguous()
+    return (res_feat.contiguous().float(), pair_feat.contiguous().float(), mask_generate.contiguous(), mask_res.contiguous(), *(a.contiguous() for a in allowed))
+
+
+AA_ALL = (1 << 20) - 1          # every residue type: bits 0..19 of an aa_allowed word (include/abopt.h)
+
+
+def _checked_allowed(aa_allowed, mask_generate):
+    """aa_allowed of sample() / optimize() -> None, or the int32 (N, L) tensor the kernels read (bits 20.. cleared).  Accepts (N, L), (1, L) or (L,) int32 / int64, bit k
+    of a word = residue type k may be drawn there.  An empty set on a generated residue is refused here, before any launch: one host read per call, outside any captured
+    graph (the C ABI defines it -- the type is frozen -- but from Python it is a mistake in building the mask)."""
+    if aa_allowed is None:
+        return None
+    N, L = mask_generate.shape
+    a = torch.as_tensor(aa_allowed, device=mask_generate.device)
+    if a.dtype not in (torch.int32, torch.int64):
+        raise TypeError(f'aa_allowed must be int32 or int64, got {a.dtype}')
+    if a.dim() == 1:
+        a = a[None]
+    if a.dim() != 2 or a.shape[1] != L or a.shape[0] not in (1, N):
+        raise ValueError(f'aa_allowed must be ({N}, {L}), (1, {L}) or ({L},), got {tuple(torch.as_tensor(aa_allowed).shape)}')
+    a = (a & AA_ALL).to(torch.int32).expand(N, L).contiguous()
+    empty = torch.logical_and(mask_generate, a == 0).flatten()
+    first = int(torch.where(empty, torch.arange(N * L, device=a.device), N * L).min()) if N * L else 0
+    if first < N * L:
+        raise ValueError(f'aa_allowed: generated residue {first % L + 1} of sample {first // L} has an empty set of allowed types '
+                         '(at least one of bits 0..19 must be set wherever generate_flag is)')
+    return a
 
 
 class FullDPM(_Derived, nn.Module):
@@ -149,17 +177,23 @@ class FullDPM(_Derived, nn.Module):
 
     # ------------------------------------------------------------------ sampling
     def _run(self, state, t_start, res_feat, pair_feat, mask_generate, mask_res, sample_structure, sample_sequence,
-             ppl_masked, noise, seed, rng_offset, pbar, stop_after=None, optimize_mode=False, use_bias_cache=None, graph=None):
+             ppl_masked, noise, seed, rng_offset, pbar, stop_after=None, optimize_mode=False, use_bias_cache=None, graph=None, aa_allowed=None):
         """Denoise from step t_start down to 0.  state = (v, p_angstrom, s) on device.  graph: None = self.graph_mode.
         The positional form of benchmarks and tools: the one place that turns such arguments into a _LoopSpec."""
-        spec = _LoopSpec(t_start, stop_after, bool(sample_structure), bool(sample_sequence), bool(ppl_masked), bool(optimize_mode), use_bias_cache)
-        return self._denoise(spec, state, (res_feat, pair_feat, mask_generate, mask_res), noise, seed, rng_offset, pbar, graph)
+        allowed = _checked_allowed(aa_allowed, mask_generate)
+        spec = _LoopSpec(t_start, stop_after, bool(sample_structure), bool(sample_sequence), bool(ppl_masked), bool(optimize_mode), use_bias_cache, allowed is not None)
+        return self._denoise(spec, state, self._inputs(res_feat, pair_feat, mask_generate, mask_res, allowed), noise, seed, rng_offset, pbar, graph)
+
+    @staticmethod
+    def _inputs(res_feat, pair_feat, mask_generate, mask_res, allowed):
+        """The loop inputs: the four tensors every loop takes and, for a constrained one, the checked aa_allowed behind them."""
+        return (res_feat, pair_feat, mask_generate, mask_res) + (() if allowed is None else (allowed,))
 
     def _denoise(self, spec, state, inputs, noise, seed, rng_offset, pbar, graph=None, range_safe=False):
-        """The loop `spec` on inputs = (res_feat, pair_feat, mask_generate, mask_res), eagerly or from its captured graph.  Settles spec.use_bias_cache,
+        """The loop `spec` on inputs = (res_feat, pair_feat, mask_generate, mask_res[, aa_allowed]), eagerly or from its captured graph.  Settles spec.use_bias_cache,
         here and nowhere else.  range_safe: eagerly, the dense layers as fp32 GEMMs (the answer to a raised range guard)."""
         graph = self.graph_mode if graph is None else graph
-        res_feat, pair_feat, _, mask_res = inputs
+        res_feat, pair_feat, _, mask_res = inputs[:4]
         capturable = bool(graph) and noise is None and not pbar and not range_safe and res_feat.is_cuda     # (a CPU tensor reaches hip.ptr()'s "no CPU path" error)
         (N, L), Nc = mask_res.shape, pair_feat.shape[0]
         token = self.eps_net.packed() if capturable else None
@@ -215,7 +249,10 @@ class FullDPM(_Derived, nn.Module):
     def _run_eager(self, spec, state, inputs, noise, seed, rng_offset, pbar, seed_dev=None, range_safe=False):
         """The loop itself, one C call per network evaluation and one per transition; spec.use_bias_cache is settled (_denoise).
         seed_dev: device {seed, offset} (graph capture)."""
-        res_feat, pair_feat, mask_generate, mask_res = _loop_inputs(inputs)
+        res_feat, pair_feat, mask_generate, mask_res, *allowed = _loop_inputs(inputs)
+        if spec.constrained != bool(allowed):
+            raise ValueError('a constrained loop takes aa_allowed as its fifth input, an unconstrained one takes four')
+        aa_allowed = allowed[0] if allowed else None
         dev = res_feat.device
         N, L = mask_res.shape
         T0, Nc, use_bias_cache = spec.t_start, pair_feat.shape[0], spec.use_bias_cache
@@ -260,7 +297,8 @@ class FullDPM(_Derived, nn.Module):
                 out.update(prmsd=tpr[t - 1], ppl=tpp[t - 1])
             hip.denoise_step(self._step_params(t, spec.sample_structure, spec.sample_sequence, spec.ppl_masked, spec.optimize_mode),
                              noise[t] if noise is not None else None, seed, rng_offset, tv[t], tp[t], ts[t], net['v_next'], net['eps_pos'], net['c'],
-                             net['prmsd_logits'], mask_generate, X[t], cdf[t] if cdf is not None else None, self.num_bins, out, seed_dev=seed_dev)
+                             net['prmsd_logits'], mask_generate, X[t], cdf[t] if cdf is not None else None, self.num_bins, out, seed_dev=seed_dev,
+                             aa_allowed=aa_allowed)
         self.last_run_info = dict(bias_cache=use_bias_cache, pair_terms=pterms is not None, shared_context=shared, graph=seed_dev is not None)
         return tv, tp, ts, tpr, tpp
 
@@ -283,20 +321,25 @@ class FullDPM(_Derived, nn.Module):
 
     @torch.no_grad()
     def sample(self, v, p, s, res_feat, pair_feat, mask_generate, mask_res, sample_structure=True, sample_sequence=True,
-               pbar=False, noise=None, seed=None, rng_offset=0, use_bias_cache=None, graph=None, **kwargs):
+               pbar=False, noise=None, seed=None, rng_offset=0, use_bias_cache=None, graph=None, aa_allowed=None, **kwargs):
         """dpm_full.py:236-302.  `noise` (optional) = {'init': {q4,p,s}, t: {axis,bin,ubin,gauss,z,s_next}} replays
-        recorded draws; otherwise a Philox stream seeded from torch's CPU generator is used."""
+        recorded draws; otherwise a Philox stream seeded from torch's CPU generator is used.
+        aa_allowed (optional; no reference counterpart): the residue types that may appear at each generated residue, (N, L) / (1, L) / (L,) int32 or int64 words with
+        bit k = type k (model.aa_allowed_mask builds them).  The initial state and every step draw from the allowed types only, so a forbidden type never enters s_t."""
+        allowed = _checked_allowed(aa_allowed, mask_generate)
         seed, h = self._begin(seed)
         state = hip.sample_init(v.float(), p.float(), s, mask_generate, noise['init'] if noise is not None else None, seed, rng_offset,
-                                h['scale'], h['mean'], sample_structure, sample_sequence)
-        spec = _LoopSpec(self.num_steps, None, bool(sample_structure), bool(sample_sequence), ppl_masked=True, use_bias_cache=use_bias_cache)
-        inputs = (res_feat, pair_feat, mask_generate, mask_res)
+                                h['scale'], h['mean'], sample_structure, sample_sequence, aa_allowed=allowed)
+        spec = _LoopSpec(self.num_steps, None, bool(sample_structure), bool(sample_sequence), ppl_masked=True, use_bias_cache=use_bias_cache,
+                         constrained=allowed is not None)
+        inputs = self._inputs(res_feat, pair_feat, mask_generate, mask_res, allowed)
         return self._to_traj(spec.t_start, *_range_guarded(lambda safe: self._denoise(spec, state, inputs, noise, seed, rng_offset, pbar, graph, safe)))
 
     @torch.no_grad()
     def optimize(self, v, p, s, opt_step, res_feat, pair_feat, mask_generate, mask_res, sample_structure=True,
-                 sample_sequence=True, pbar=False, noise=None, seed=None, rng_offset=0, use_bias_cache=None, graph=None):
-        """dpm_full.py:304-367: noise the input to step `opt_step`, then denoise."""
+                 sample_sequence=True, pbar=False, noise=None, seed=None, rng_offset=0, use_bias_cache=None, graph=None, aa_allowed=None):
+        """dpm_full.py:304-367: noise the input to step `opt_step`, then denoise.  aa_allowed: as in sample(); the forward noising draws from the allowed types too."""
+        allowed = _checked_allowed(aa_allowed, mask_generate)
         seed, h = self._begin(seed)
         N = v.shape[0]
         t = torch.full([N], opt_step, dtype=torch.long, device=res_feat.device)
@@ -304,12 +347,13 @@ class FullDPM(_Derived, nn.Module):
         # dpm_full.py:320-339: noise structure and/or sequence to step opt_step (position in Angstrom in and out)
         state = hip.add_noise(t, self.trans_pos.var_sched.alpha_bars, self.trans_rot.angular_distrib_fwd, init_noise, seed, rng_offset,
                               v.float(), p.float(), s, mask_generate, h['scale'], h['mean'],
-                              noise_structure=sample_structure, noise_sequence=sample_sequence, grad_mode=False)
+                              noise_structure=sample_structure, noise_sequence=sample_sequence, grad_mode=False, aa_allowed=allowed)
         state = (state[0], state[1], torch.where(mask_generate, state[2], s))       # dpm_full.py:335
         # dpm_full.py:351-358: the loop feeds the net's third output to the position update as noise whatever `obj` is,
         # and averages the perplexity over all residues (calc_perplexity(logits) without a mask)
-        spec = _LoopSpec(opt_step, None, bool(sample_structure), bool(sample_sequence), ppl_masked=False, optimize_mode=True, use_bias_cache=use_bias_cache)
-        inputs = (res_feat, pair_feat, mask_generate, mask_res)
+        spec = _LoopSpec(opt_step, None, bool(sample_structure), bool(sample_sequence), ppl_masked=False, optimize_mode=True, use_bias_cache=use_bias_cache,
+                         constrained=allowed is not None)
+        inputs = self._inputs(res_feat, pair_feat, mask_generate, mask_res, allowed)
         # same counters as add_noise, other sub-sequence tags (csrc/denoise.hip): a sample's stream position does not depend on the batch it sits in
         traj = self._to_traj(opt_step, *_range_guarded(lambda safe: self._denoise(spec, state, inputs, noise, seed, rng_offset, pbar, graph, safe)))
         return {k: tuple(e) for k, e in traj.items()}
@@ -325,7 +369,9 @@ class _LoopGraph:
     def __init__(self, dpm, spec, state, inputs, token):
         self.token = token                                              # EpsilonNet.packed() at capture: keeps the packed weights this graph points at alive
         self.state = tuple(a.clone() for a in state)
-        self.res_feat, self.pair_feat, self.mask_generate, self.mask_res = static = tuple(a.clone() for a in _loop_inputs(inputs))
+        static = tuple(a.clone() for a in _loop_inputs(inputs))
+        self.res_feat, self.pair_feat, self.mask_generate, self.mask_res = static[:4]
+        self.aa_allowed = static[4] if spec.constrained else None      # a constrained loop's mask is an input like mask_generate: refreshed before each replay
         self.seed_dev = torch.zeros(2, dtype=torch.int64, device=self.res_feat.device)
         run = lambda stop_after: dpm._run_eager(dataclasses.replace(spec, stop_after=stop_after), self.state, static, None, 0, 0, False, seed_dev=self.seed_dev)
         hip.prof_enable(False)
@@ -350,7 +396,7 @@ class _LoopGraph:
         self._pf_src = None                                             # (weakref to the caller's pair_feat, its _version) of the last copy
 
     def replay(self, state, inputs, seed, rng_offset):
-        res_feat, pair_feat, mask_generate, mask_res = inputs
+        res_feat, pair_feat, mask_generate, mask_res, *allowed = inputs
         for dst, src in zip(self.state, state):
             dst.copy_(src)
         self.res_feat.copy_(res_feat if res_feat.shape == self.res_feat.shape else res_feat.expand_as(self.res_feat))
@@ -371,6 +417,8 @@ class _LoopGraph:
             self._pf_src = (weakref.ref(pair_feat), ver) if ver is not None else None
         self.mask_generate.copy_(mask_generate)
         self.mask_res.copy_(mask_res)
+        if self.aa_allowed is not None:
+            self.aa_allowed.copy_(allowed[0])
         self.seed_dev.copy_(torch.tensor([int(seed), int(rng_offset)], dtype=torch.int64))
         self.graph.replay()
         return self.out

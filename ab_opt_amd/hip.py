@@ -13,7 +13,7 @@ import torch
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # ABOPT_LIB_PATH: developer override to load a variant build of the same ABI (csrc/Makefile VARIANT=...: A/B of two source trees)
 LIB_PATH = os.environ.get('ABOPT_LIB_PATH') or os.path.join(_HERE, 'libabopt_hip.so')
-ABI_VERSION = 43
+ABI_VERSION = 44
 
 c_f = C.c_void_p        # device float*
 c_i64 = C.c_void_p      # device int64*
@@ -115,10 +115,10 @@ _SIGNATURES = {
     'abopt_eps_net_forward': (c_int, [POINTER(EpsWeights), c_f, c_f, c_i64, c_f, c_f, c_f, c_u8, c_u8] + [c_f] * 5 + [c_int] * 5 +
                               [c_f, c_int, c_f, c_void_p, c_size_t, c_stream]),
     'abopt_denoise_step': (c_int, [POINTER(StepParams), POINTER(StepNoise), c_uint64, c_uint64, c_f, c_f, c_i64] + [c_f] * 4 + [c_u8, c_f, c_f, c_int, c_int] +
-                           [c_f, c_f, c_i64] + [c_f] * 4 + [c_void_p, c_int, c_int, c_stream]),
-    'abopt_sample_init': (c_int, [c_f, c_f, c_i64, c_u8, c_f, c_f, c_i64, c_uint64, c_uint64, c_float, c_void_p, c_int, c_int, c_f, c_f, c_i64, c_int, c_int, c_stream]),
+                           [c_f, c_f, c_i64] + [c_f] * 4 + [c_void_p, c_i32, c_int, c_int, c_stream]),
+    'abopt_sample_init': (c_int, [c_f, c_f, c_i64, c_u8, c_f, c_f, c_i64, c_uint64, c_uint64, c_float, c_void_p, c_int, c_int, c_f, c_f, c_i64, c_i32, c_int, c_int, c_stream]),
     'abopt_add_noise': (c_int, [c_i64, c_f, c_f, c_u8, c_f, c_f, c_int, c_int, POINTER(AddNoiseNoise), c_uint64, c_uint64, c_f, c_f, c_i64, c_u8, c_float, c_void_p, c_int, c_int, c_int,
-                        c_f, c_f, c_i64, c_f, c_f, c_void_p, c_int, c_int, c_stream]),
+                        c_f, c_f, c_i64, c_f, c_f, c_void_p, c_i32, c_int, c_int, c_stream]),
     'abopt_dockq_workspace_bytes': (c_size_t, [c_int]),
     'abopt_dockq_lite': (c_int, [c_f, c_u8, c_int, c_f, c_u8, c_i32, c_int, c_int, c_int, c_f, c_void_p, c_size_t, c_stream]),
     'abopt_dockq_grouped_workspace_bytes': (c_size_t, [c_int, c_int]),
@@ -503,9 +503,17 @@ def pair_bias_cache(blocks_array, num_layers, pair_feat):
     return cache
 
 
+def _allowed_ptr(aa_allowed, mask_generate):
+    """aa_allowed (optional): contiguous int32 (N, L) device tensor, bit k of a word = residue type k may be drawn there (include/abopt.h)."""
+    if aa_allowed is not None and aa_allowed.shape != mask_generate.shape:
+        raise ValueError(f'aa_allowed must have the shape of mask_generate {tuple(mask_generate.shape)}, got {tuple(aa_allowed.shape)}')
+    return ptr(aa_allowed, torch.int32, optional=True)
+
+
 def denoise_step(sp, noise, seed, offset, v_t, p_t, s_t, v_net, p_net, c_net, prmsd_logits, mask_generate,
-                 ig_X_row, ig_cdf_row, num_bins, out, want_post=False, seed_dev=None):
-    """seed_dev (optional): int64 device tensor {seed, offset} read by the kernel in place of the two host values (graph replays)."""
+                 ig_X_row, ig_cdf_row, num_bins, out, want_post=False, seed_dev=None, aa_allowed=None):
+    """seed_dev (optional): int64 device tensor {seed, offset} read by the kernel in place of the two host values (graph replays).
+    aa_allowed (optional): the allowed residue types per residue (_allowed_ptr)."""
     N, L = mask_generate.shape
     nz = None
     if noise is not None:
@@ -519,11 +527,11 @@ def denoise_step(sp, noise, seed, offset, v_t, p_t, s_t, v_net, p_net, c_net, pr
                                     ptr(ig_X_row, torch.float32), ptr(ig_cdf_row, optional=True), ig_X_row.numel(), num_bins,
                                     ptr(out['v']), ptr(out['p']), ptr(out['s']), ptr(out.get('prmsd'), optional=True),
                                     ptr(out.get('ppl'), optional=True), ptr(post, optional=True), ptr(out.get('p_norm'), optional=True),
-                                    ptr(seed_dev, torch.int64, optional=True), N, L, stream()))
+                                    ptr(seed_dev, torch.int64, optional=True), _allowed_ptr(aa_allowed, mask_generate), N, L, stream()))
     return post
 
 
-def sample_init(v, p, s, mask_generate, init_noise, seed, offset, scale, mean, sample_structure, sample_sequence):
+def sample_init(v, p, s, mask_generate, init_noise, seed, offset, scale, mean, sample_structure, sample_sequence, aa_allowed=None):
     N, L = mask_generate.shape
     v_i, p_i, s_i = torch.empty_like(v), torch.empty_like(p), torch.empty_like(s)
     q4 = pn = sr = None
@@ -534,13 +542,13 @@ def sample_init(v, p, s, mask_generate, init_noise, seed, offset, scale, mean, s
     _check(lib().abopt_sample_init(ptr(v, torch.float32), ptr(p, torch.float32), ptr(s, torch.int64),
                                    ptr(mask_generate, torch.bool), ptr(q4, optional=True), ptr(pn, optional=True),
                                    ptr(sr, optional=True), seed, offset, float(scale), mean_arr, int(sample_structure), int(sample_sequence),
-                                   ptr(v_i), ptr(p_i), ptr(s_i), N, L, stream()))
+                                   ptr(v_i), ptr(p_i), ptr(s_i), _allowed_ptr(aa_allowed, mask_generate), N, L, stream()))
     return v_i, p_i, s_i
 
 
 def add_noise(t, alpha_bars, fwd, noise, seed, offset, v_0, p_0, s_0, mask_generate, scale, mean,
-              noise_structure=True, noise_sequence=True, grad_mode=False, want_eps=False, want_probs=False, seed_dev=None):
-    """fwd: ApproxAngularDistribution of the forward process (buffers stddevs, approx_flag, X + cdf())."""
+              noise_structure=True, noise_sequence=True, grad_mode=False, want_eps=False, want_probs=False, seed_dev=None, aa_allowed=None):
+    """fwd: ApproxAngularDistribution of the forward process (buffers stddevs, approx_flag, X + cdf()).  aa_allowed (optional): _allowed_ptr."""
     N, L = mask_generate.shape
     v_n, p_n, s_n = torch.empty_like(v_0), torch.empty_like(p_0), torch.empty_like(s_0)
     eps = torch.empty_like(p_0) if want_eps else None
@@ -560,7 +568,7 @@ def add_noise(t, alpha_bars, fwd, noise, seed, offset, v_0, p_0, s_0, mask_gener
                                  ptr(v_0, torch.float32), ptr(p_0, torch.float32), ptr(s_0, torch.int64),
                                  ptr(mask_generate, torch.bool), float(scale), mean_arr, int(noise_structure), int(noise_sequence),
                                  int(grad_mode), ptr(v_n), ptr(p_n), ptr(s_n), ptr(eps, optional=True), ptr(probs, optional=True),
-                                 ptr(seed_dev, torch.int64, optional=True), N, L, stream()))
+                                 ptr(seed_dev, torch.int64, optional=True), _allowed_ptr(aa_allowed, mask_generate), N, L, stream()))
     out = (v_n, p_n, s_n) + ((eps,) if want_eps else ()) + ((probs,) if want_probs else ())
     return out
 

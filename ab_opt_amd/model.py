@@ -46,6 +46,30 @@ def generate_mask_from_str(str_input, tensor):
     return mask
 
 
+AA_LETTERS = 'ACDEFGHIKLMNPQRSTVWY'      # residue type k of the kernels = AA_LETTERS[k]: the reference's AA enum (utils/protein/constants.py)
+
+
+def _aa_bits(letters):
+    bits = 0
+    for c in letters:
+        k = AA_LETTERS.find(c.upper()) if len(c) == 1 else -1
+        if k < 0:
+            raise ValueError(f'unknown residue type {c!r}: the twenty types are {AA_LETTERS}')
+        bits |= 1 << k
+    return bits
+
+
+def aa_allowed_mask(length, exclude='', at=None, device=None):
+    """The per-residue sets of allowed types that batch['aa_allowed'] takes, for one complex: int32 (length,), bit k of a word = type AA_LETTERS[k] may be designed there.
+    Every position allows all twenty types minus the letters of `exclude`; at = {position: 'letters'} replaces the set at that position (1-based, like `contig`)."""
+    mask = torch.full((int(length),), (1 << len(AA_LETTERS)) - 1 & ~_aa_bits(exclude), dtype=torch.int32)
+    for pos, letters in (at or {}).items():
+        if not 1 <= int(pos) <= length:
+            raise ValueError(f'position {pos} is outside 1..{length}')
+        mask[int(pos) - 1] = _aa_bits(letters)
+    return mask.to(device) if device is not None else mask
+
+
 def generate_random_mask_from(tensor, mask_ratio_min, mask_ratio_max):
     """diffab.py:166-180."""
     ratio = float(torch.empty(1).uniform_(mask_ratio_min, mask_ratio_max))
@@ -116,7 +140,8 @@ class _DiffabBase(nn.Module):
                                                     remove_sequence=sample_opt.get('sample_sequence', True))
         v_0 = hip.so3_log(R_0, grad_mode=False)
         opt = {k: v for k, v in sample_opt.items() if k != 'contig'}
-        return self.diffusion.sample(v_0, p_0, batch['aa'], res_feat, pair_feat, mask_generate, mask_res, **opt)
+        # batch['aa_allowed'] (optional, (N, L); no reference counterpart): the types each generated residue may take -- with a contig, at those that remain generated
+        return self.diffusion.sample(v_0, p_0, batch['aa'], res_feat, pair_feat, mask_generate, mask_res, aa_allowed=batch.get('aa_allowed'), **opt)
 
     @torch.no_grad()
     def optimize(self, batch, opt_step, optimize_opt={'sample_structure': True, 'sample_sequence': True}):
@@ -125,7 +150,8 @@ class _DiffabBase(nn.Module):
         res_feat, pair_feat, R_0, p_0 = self.encode(batch, remove_structure=optimize_opt.get('sample_structure', True),
                                                     remove_sequence=optimize_opt.get('sample_sequence', True))
         v_0 = hip.so3_log(R_0, grad_mode=False)
-        return self.diffusion.optimize(v_0, p_0, batch['aa'], opt_step, res_feat, pair_feat, mask_generate, mask_res, **optimize_opt)
+        return self.diffusion.optimize(v_0, p_0, batch['aa'], opt_step, res_feat, pair_feat, mask_generate, mask_res, aa_allowed=batch.get('aa_allowed'),
+                                       **optimize_opt)
 
 
 @register_model('diffab_abdock')

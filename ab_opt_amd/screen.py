@@ -85,7 +85,7 @@ def _rebuild(pos, mask, traj0, lo, hi, aa, flag, one):
 
 @torch.no_grad()
 def optimize_antibody(dock_model, design_model, complex_, num_poses, designs_per_pose, redocks_per_design, design_flag=None, redock_flag=None,
-                      contig='', screened_per_pose=1, seed=0, poses_per_launch=8, group=None, screen_by='first', timings=None):
+                      contig='', screened_per_pose=1, seed=0, poses_per_launch=8, group=None, screen_by='first', timings=None, allowed_aa=None):
     """Dock -> redesign -> re-dock screen of one antibody-antigen complex (module docstring).
 
     complex_: batch dict with batch dim 1 (cropped, as sample_replicated takes it); its generate_flag marks the residues to dock.
@@ -93,6 +93,9 @@ def optimize_antibody(dock_model, design_model, complex_, num_poses, designs_per
     --label_heavy_as_cdr re-dock corresponds to every heavy-chain residue).  contig limits design_flag ('start-end', 1-based).
     screened_per_pose k designs of every pose go on to the re-dock: the first k (screen_by='first', as the reference takes 0000.pdb) or the
     k of lowest PPL (screen_by='ppl', stable order).  num_poses >= 2 and redocks_per_design >= 2 (commonness needs two structures).
+    allowed_aa (optional, (L,) or (1, L) int32 / int64; default: complex_['aa_allowed'] if it has one): the residue types each redesigned residue may take, bit k of a
+    word = type k (model.aa_allowed_mask).  It constrains the redesign stage alone -- the docking stages draw no types -- inside the sampler, so no design is thrown away:
+    seqs, the re-docked designs and everything downstream hold allowed types only; aar still counts recovery of the input sequence.
     timings (optional dict): receives the seconds each stage took on this rank (device-synchronised) and of the final gather.
 
     -> dict of device tensors in global pose order (P poses, S designs, k screened, D re-docks; n_* = residues in the mask):
@@ -114,6 +117,9 @@ def optimize_antibody(dock_model, design_model, complex_, num_poses, designs_per
         raise ValueError(f"screen_by must be 'first' or 'ppl', not {screen_by!r}")
     L = int(one['aa'].shape[1])
     dev = one['aa'].device
+    given = one.pop('aa_allowed', None)
+    allowed_aa = given if allowed_aa is None else allowed_aa
+    design_extra = {} if allowed_aa is None else dict(aa_allowed=allowed_aa.reshape(1, L).to(dev))
     gen = one['generate_flag'][0].bool()
     dflag = design_mask((gen if design_flag is None else design_flag.reshape(-1).to(dev)), contig)
     rflag = gen if redock_flag is None else redock_flag.reshape(-1).to(dev).bool()
@@ -158,7 +164,7 @@ def optimize_antibody(dock_model, design_model, complex_, num_poses, designs_per
     native = aa[dflag]
     for lo, hi in plan:
         G = hi - lo
-        cx = [_with(one, pos_heavyatom=pose_pos[i - a:i - a + 1], mask_heavyatom=pose_mask[i - a:i - a + 1], generate_flag=dflag[None])
+        cx = [_with(one, pos_heavyatom=pose_pos[i - a:i - a + 1], mask_heavyatom=pose_mask[i - a:i - a + 1], generate_flag=dflag[None], **design_extra)
               for i in range(lo, hi)]
         traj = sampler.sample_grouped(design_model, cx, S, dict(sample_structure=False, sample_sequence=True, **rngs('design', lo)), pad_to=L)
         s_fin = traj[0][2]

@@ -23,7 +23,7 @@
 extern "C" {
 #endif
 
-#define ABOPT_ABI_VERSION 43
+#define ABOPT_ABI_VERSION 44
 
 enum { ABOPT_OK = 0, ABOPT_EINVAL = 1, ABOPT_EHIP = 2, ABOPT_EUNSUPPORTED = 3, ABOPT_EWORKSPACE = 4 };
 
@@ -256,6 +256,23 @@ typedef struct {
     const int64_t* s_next;  /* [N,L]    the multinomial sample itself                 (transition.py:176-177) */
 } abopt_step_noise;
 
+/* Allowed residue types (ABI 44): the optional last data argument `aa_allowed` [N,L] of the three functions that draw a residue type
+ * (abopt_denoise_step, abopt_sample_init, abopt_add_noise).  One int32 word per residue; bit k (0..19, the order ACDEFGHIKLMNPQRSTVWY of the
+ * reference's AA enum, utils/protein/constants.py) set = type k may be drawn there; bits 20.. are ignored, so -1 means "all".  The word is read on
+ * residues with mask_generate set and nowhere else: context residues behave as without the argument.  NULL = no constraint; a word with all of bits
+ * 0..19 set is the same arithmetic in the same order, so NULL, 0xFFFFF and -1 give bit-identical outputs.
+ *   abopt_denoise_step: a disallowed class leaves the posterior BEFORE it is normalised -- its unnormalised product
+ *     ((ab ct) + unif) ((ab c_net) + unif) (transition.py:166-174) is replaced by 0, then post[k] = raw[k] / (sum + 1e-8) as ever -- so post_out and the
+ *     perplexity term are those of the distribution that is sampled; the inverse-CDF walk over post[k] + 1e-8 skips disallowed classes and ends, when
+ *     rounding leaves it short, on the last allowed one (class 19 without a constraint).
+ *   abopt_sample_init: the initial type is uniform over the allowed types among 0..18 -- the (r % count)-th set bit for the random word r that
+ *     is r % 19 without a constraint (randint_like(high=19) never draws TYR) -- and 19 where bit 19 alone is set.
+ *   abopt_add_noise: the walk over c_t + 1e-8 skips disallowed classes and ends on the last allowed one; c_noisy stays the unconstrained c_t.
+ * An injected draw (noise->s_next, sr, noise->s_noisy) is taken as it is.
+ * A word with NONE of bits 0..19 set on a generated residue is defined: the residue's type is frozen -- s_next = s_t, s_init = s, s_noisy = s_0,
+ * injected draws included -- its posterior is reported as onehot(s_t) like a context residue's (and enters the perplexity so), and its structure
+ * still moves.  (The Python layer refuses such a word before any launch.) */
+
 /* One loop iteration after eps_net: state (v_t, p_t in Angstrom, s_t) -> (v_next, p_next in Angstrom, s_next),
  * plus per-sample prmsd [N] and perplexity [N] (either may be NULL).
  * igso3_X / igso3_cdf: row t of the inverse-process histogram, [bins] bin starts and [bins-1] normalised CDF
@@ -272,6 +289,7 @@ int abopt_denoise_step(const abopt_step_params* sp, const abopt_step_noise* nois
                        const uint64_t* seed_offset_dev /* optional DEVICE pointer to {seed, offset}: read by the kernel instead of the
                                                           two by-value arguments, so a captured hipGraph of the loop can be replayed
                                                           with a fresh stream position (the values are read at execution time) */,
+                       const int32_t* aa_allowed /* optional [N,L]: allowed residue types, see above */,
                        int N, int L, abopt_stream stream);
 
 /* Initial state of FullDPM.sample (dpm_full.py:255-269): q4 [N,L,4], pn [N,L,3], sr [N,L] are the
@@ -279,7 +297,9 @@ int abopt_denoise_step(const abopt_step_params* sp, const abopt_step_noise* nois
 int abopt_sample_init(const float* v, const float* p, const int64_t* s, const uint8_t* mask_generate,
                       const float* q4, const float* pn, const int64_t* sr, uint64_t seed, uint64_t offset,
                       float position_scale, const float* position_mean, int sample_structure, int sample_sequence,
-                      float* v_init, float* p_init, int64_t* s_init, int N, int L, abopt_stream stream);
+                      float* v_init, float* p_init, int64_t* s_init,
+                      const int32_t* aa_allowed /* optional [N,L]: allowed residue types, see above abopt_denoise_step */,
+                      int N, int L, abopt_stream stream);
 
 /* ---- Forward noising: RotationTransition.add_noise (D/modules/diffusion/transition.py:120-144), PositionTransition.add_noise
  * (:62-78), AminoacidCategoricalTransition.add_noise (:179-200); used by FullDPM.optimize (dpm_full.py:320-339) and by the
@@ -303,6 +323,7 @@ int abopt_add_noise(const int64_t* t, const float* alpha_bars, const float* fwd_
                     float position_scale, const float* position_mean, int noise_structure, int noise_sequence, int grad_mode,
                     float* v_noisy, float* p_noisy, int64_t* s_noisy, float* eps_p, float* c_noisy,
                     const uint64_t* seed_offset_dev /* optional device {seed, offset}, as in abopt_denoise_step */,
+                    const int32_t* aa_allowed /* optional [N,L]: allowed residue types, see above abopt_denoise_step; the training loss passes NULL */,
                     int N, int L, abopt_stream stream);
 
 /* ---- DockQ scoring of docked candidates: D/tools/runner/design_for_pdb.py:316-321 calls calc_DockQ(model, native, use_CA_only=True)

@@ -1,7 +1,7 @@
 """The dock -> redesign -> re-dock screen (ab_opt_amd/screen.py) on a synthetic complex with hash-filled weights: prints the time of every
 stage and the designs the notebook's median filter keeps.
 
-    python tools/example_screen.py [--poses 16 --designs 8 --redocks 8 --screened 1 --steps 100 --per-launch 8 --contig 97-103]
+    python tools/example_screen.py [--poses 16 --designs 8 --redocks 8 --screened 1 --steps 100 --per-launch 8 --contig 97-103 --exclude CM]
 
 The weights are not a trained checkpoint, so the numbers say nothing about antibodies; the stage times are what a screen of this size costs.
 """
@@ -15,7 +15,7 @@ sys.path.insert(0, ROOT)
 
 import torch  # noqa: E402
 
-from ab_opt_amd import get_model, screen  # noqa: E402
+from ab_opt_amd import get_model, model, screen  # noqa: E402
 from ab_opt_amd.utils import synth  # noqa: E402
 
 AA = 'ACDEFGHIKLMNPQRSTVWY'
@@ -31,6 +31,7 @@ def main():
     ap.add_argument('--per-launch', type=int, default=8)
     ap.add_argument('--contig', default='97-103')
     ap.add_argument('--seed', type=int, default=0)
+    ap.add_argument('--exclude', default='', metavar='LETTERS', help='residue types no design may contain, e.g. CM (constrains the sampler itself)')
     args = ap.parse_args()
     dev = torch.device('cuda:0')
     dock = synth.build_model(args.steps, 3, device=dev)                     # dock_cdr.yml: AbDock, full heavy atoms
@@ -41,7 +42,8 @@ def main():
     one['generate_flag'] = gen[None]
     heavy = one['fragment_type'][0] == 1                                   # the re-dock labels the whole heavy chain (--label_heavy_as_cdr)
     kw = dict(num_poses=args.poses, designs_per_pose=args.designs, redocks_per_design=args.redocks, screened_per_pose=args.screened,
-              contig=args.contig, seed=args.seed, poses_per_launch=args.per_launch, redock_flag=heavy)
+              contig=args.contig, seed=args.seed, poses_per_launch=args.per_launch, redock_flag=heavy,
+              allowed_aa=model.aa_allowed_mask(one['aa'].shape[1], exclude=args.exclude, device=dev) if args.exclude else None)
     print(f'L={one["aa"].shape[1]} P={args.poses} S={args.designs} k={args.screened} D={args.redocks} T={args.steps} per_launch={args.per_launch} '
           f'contig={args.contig!r} device={torch.cuda.get_device_name(dev)}')
     t0 = time.perf_counter()
