@@ -1,6 +1,7 @@
 // C-ABI entry points that orchestrate kernel launches (declared in include/abopt.h).
 #include <cstdarg>
 #include <cstdio>
+#include <cstdlib>
 #include <cstring>
 #include <mutex>
 #include "ipa_common.h"
@@ -74,40 +75,59 @@ static GaScratch carve_ga(Carver& cv, int64_t M, int N, int L) {
     return s;
 }
 
-static int ga_block(const abopt_ga_weights* w, const float* R, const float* t, const float* x, const float* z, const uint8_t* mask,
-                    float* x_out, int N, int L, const abopt_ga_debug* dbg, const GaScratch& s, hipStream_t st, const float* pbc = nullptr, int z_shared = 0,
-                    const float* pair_terms = nullptr, float* feat_out = nullptr, const float* x_terms = nullptr, float* xt_out = nullptr) {
+// The five environment switches of the forward path, read once per C-ABI call (never cached: callers flip them between the calls of one process)
+static Switches read_switches() {
+    const auto first = [](const char* name) { const char* e = getenv(name); return e ? e[0] : '\0'; };
+    const char c32 = first("ABOPT_CORE32");
+    return {c32 == '0' ? 0 : (c32 == '1' ? 1 : -1), getenv("ABOPT_CORE_NO_SPLIT") != nullptr, first("ABOPT_FUSE_TAIL") != '0', first("ABOPT_X_TERMS") != '0',
+            first("ABOPT_FUSE_HEADS") != '0'};
+}
+
+// What every forward entry knows of its ForwardQuery (forward_plan.h): geometry, the CU count (asked once per entry), operands and scratch held, which blocks are
+// packed, the switches; dbg / dump / feat_out and the network's own operands are the entry's to add
+static int forward_query(int N, int L, int z_shared, const GaScratch& s, const abopt_ga_weights* blocks, int num_blocks, const float* pbc, const float* pair_terms,
+                         ForwardQuery* q) {
+    ABOPT_CHECK_ARG(num_blocks <= kMaxBlocks, "an encoder of %d blocks (at most %d)", num_blocks, kMaxBlocks);
+    *q = ForwardQuery{};
+    q->N = N; q->L = L; q->z_shared = z_shared;
+    q->cache = pbc != nullptr; q->terms = pbc && pair_terms;
+    q->split_ws = s.split != nullptr; q->split_ws_floats = s.split_floats;
+    q->num_blocks = num_blocks;
+    for (int i = 0; i < num_blocks; ++i) q->blocks[i] = {blocks[i].w_node_frag != nullptr, blocks[i].w_out_frag != nullptr, blocks[i].w_mlp_frag != nullptr, blocks[i].w_out_terms != nullptr};
+    q->sw = read_switches();
+    return device_cu_count(&q->cus);
+}
+
+// what one block runs on, besides its plan, its weights and the scratch
+struct BlockArgs { const float *R, *t, *x, *z; const uint8_t* mask; float* x_out; const float *pbc = nullptr, *pair_terms = nullptr; const abopt_ga_debug* dbg = nullptr; float* feat_out = nullptr; };
+
+static int ga_block(const BlockPlan& p, const ForwardQuery& q, const abopt_ga_weights* w, const BlockArgs& a, const GaScratch& s, hipStream_t st) {
+    const int N = q.N, L = q.L;
     const int64_t M = (int64_t)N * L;
+    const float* pair_terms = p.qk_terms ? a.pair_terms : nullptr;          // the term forms go together: q / k term fragments only for the core that reads pair terms
+    float* xt_out = p.xt_write >= 0 ? s.xt[p.xt_write] : nullptr;
     int rc;
     // node projections q|k|v|qp|kp|vp, points to the global frame, MFMA fragment layout: one fused kernel when the packed weights are given
-    // the term forms (round 6) go together: fragments with q / k channel terms are written only for the kernels that read them, the 32-row block kernels
-    // handed pair terms -- every other core reads fp32 channel slots
-    if (!(pbc && pair_terms && !dbg && w->w_node_frag && ipa_core32_applies(N, L, z_shared))) pair_terms = nullptr;
-    if (w->w_node_frag) {
-        if ((rc = launch_node_frags(x, w->w_node_frag, R, t, w->spatial_coef, s.qf, s.kvf, N, L, st, pair_terms ? 1 : 0, x_terms))) return rc;
+    if (p.node == NodeForm::Kernel) {
+        if ((rc = launch_node_frags(a.x, w->w_node_frag, a.R, a.t, w->spatial_coef, s.qf, s.kvf, N, L, st, q.cus, p.qk_terms, p.xt_read >= 0 ? s.xt[p.xt_read] : nullptr))) return rc;
     } else {
-        if ((rc = launch_linear(x, F, w->w_node, F, nullptr, s.proj, NP, (int)M, ABOPT_NODE_PROJ, F, false, st))) return rc;
-        if ((rc = launch_ipa_frags(s.proj, R, t, w->spatial_coef, s.qf, s.kvf, N, L, st))) return rc;
+        if ((rc = launch_linear(a.x, F, w->w_node, F, nullptr, s.proj, NP, (int)M, ABOPT_NODE_PROJ, F, false, st))) return rc;
+        if ((rc = launch_ipa_frags(s.proj, a.R, a.t, w->spatial_coef, s.qf, s.kvf, N, L, st))) return rc;
     }
-    if (!dbg && !feat_out && pbc && w->w_out_terms && w->w_mlp_frag) {
-        // core + tail as one kernel (feat stays on the chip) wherever the 32-row core is the one to run; bit-identical to the two launches below
-        int fused = 0;
-        if ((rc = launch_ipa_block_fused(s.qf, s.kvf, z, mask, R, t, pbc, N, L, st, z_shared, w->w_out_terms, w->w_mlp_frag, x, w->b_out, w->ln1_gamma,
-                                         w->ln1_beta, w->b_mlp0, w->b_mlp1, w->b_mlp2, w->ln2_gamma, w->ln2_beta, x_out, &fused, pair_terms, xt_out))) return rc;
-        if (fused) return ABOPT_OK;
-    }
-    float* feat = (dbg && dbg->feat) ? dbg->feat : (feat_out ? feat_out : s.feat);
-    if ((rc = launch_ipa_core(s.qf, s.kvf, z, mask, R, t, w->w_pair_bias, feat,
-                              dbg ? dbg->logits : nullptr, dbg ? dbg->alpha : nullptr, pbc, N, L, st, z_shared, s.split, s.split_floats, pair_terms))) return rc;
+    // core + tail as one kernel (feat stays on the chip); bit-identical to the two launches below
+    if (p.tail == TailForm::InCore)
+        return launch_ipa_block_fused(p.core, s.qf, s.kvf, a.z, a.mask, a.R, a.t, a.pbc, N, L, st, q.z_shared, w->w_out_terms, w->w_mlp_frag, a.x, w->b_out, w->ln1_gamma,
+                                      w->ln1_beta, w->b_mlp0, w->b_mlp1, w->b_mlp2, w->ln2_gamma, w->ln2_beta, a.x_out, pair_terms, xt_out);
+    float* feat = (a.dbg && a.dbg->feat) ? a.dbg->feat : (a.feat_out ? a.feat_out : s.feat);
+    if ((rc = launch_ipa_core(p.core, s.qf, s.kvf, a.z, a.mask, a.R, a.t, w->w_pair_bias, feat, a.dbg ? a.dbg->logits : nullptr, a.dbg ? a.dbg->alpha : nullptr, a.pbc,
+                              N, L, st, q.z_shared, s.split, pair_terms))) return rc;
     // out_transform -> mask -> +x -> LN1 -> MLP -> +res -> LN2
-    if (w->w_out_frag && w->w_mlp_frag)
-        return launch_out_ln_mlp(feat, w->w_out_frag, w->w_mlp_frag, x, w->b_out, mask, w->ln1_gamma, w->ln1_beta, w->b_mlp0, w->b_mlp1, w->b_mlp2,
-                                 w->ln2_gamma, w->ln2_beta, x_out, nullptr, M, st, xt_out);
-    if ((rc = launch_linear(feat, ABOPT_IPA_FEAT, w->w_out, ABOPT_IPA_FEAT, nullptr, s.u, F, (int)M, F, ABOPT_IPA_FEAT, false, st,
-                            OUT_KSPLIT, M * F))) return rc;
-    if ((rc = launch_fused_ln_mlp(x, s.u, OUT_KSPLIT, M * F, w->b_out, mask, w->ln1_gamma, w->ln1_beta, w->w_mlp0, w->b_mlp0, w->w_mlp1, w->b_mlp1,
-                                  w->w_mlp2, w->b_mlp2, w->ln2_gamma, w->ln2_beta, x_out, M, st))) return rc;
-    return ABOPT_OK;
+    if (p.tail == TailForm::OutLnMlp)
+        return launch_out_ln_mlp(feat, w->w_out_frag, w->w_mlp_frag, a.x, w->b_out, a.mask, w->ln1_gamma, w->ln1_beta, w->b_mlp0, w->b_mlp1, w->b_mlp2,
+                                 w->ln2_gamma, w->ln2_beta, a.x_out, nullptr, M, st, xt_out);
+    if ((rc = launch_linear(feat, ABOPT_IPA_FEAT, w->w_out, ABOPT_IPA_FEAT, nullptr, s.u, F, (int)M, F, ABOPT_IPA_FEAT, false, st, OUT_KSPLIT, M * F))) return rc;
+    return launch_fused_ln_mlp(a.x, s.u, OUT_KSPLIT, M * F, w->b_out, a.mask, w->ln1_gamma, w->ln1_beta, w->w_mlp0, w->b_mlp0, w->w_mlp1, w->b_mlp1,
+                               w->w_mlp2, w->b_mlp2, w->ln2_gamma, w->ln2_beta, a.x_out, M, st);
 }
 
 static int check_ga_weights(const abopt_ga_weights* w) {
@@ -386,7 +406,12 @@ extern "C" int abopt_ga_block_forward(const abopt_ga_weights* w, const float* R,
     Carver cv(ws, ws_bytes);
     GaScratch s = carve_ga(cv, (int64_t)N * L, N, L);
     if (!cv.ok) { set_error("ga_block_forward: workspace too small (%zu bytes given)", ws_bytes); return ABOPT_EWORKSPACE; }
-    return ga_block(w, R, t, x, z, mask, x_out, N, L, dbg, s, (hipStream_t)stream);
+    ForwardQuery q;
+    if ((rc = forward_query(N, L, 0, s, w, 1, nullptr, nullptr, &q))) return rc;
+    q.dbg = dbg != nullptr; q.dump = dbg && (dbg->logits || dbg->alpha);
+    BlockArgs a{R, t, x, z, mask, x_out};
+    a.dbg = dbg;
+    return ga_block(plan_block(q, 0), q, w, a, s, (hipStream_t)stream);
 }
 
 extern "C" int abopt_ga_block_forward_cached(const abopt_ga_weights* w, const float* R, const float* t, const float* x, const float* z,
@@ -402,31 +427,25 @@ extern "C" int abopt_ga_block_forward_cached(const abopt_ga_weights* w, const fl
     GaScratch s = carve_ga(cv, (int64_t)N * L, N, L);
     if (!cv.ok) { set_error("ga_block_forward_cached: workspace too small (%zu bytes given)", ws_bytes); return ABOPT_EWORKSPACE; }
     const int zg = pair_feat_shared == 1 ? N : pair_feat_shared;
-    return ga_block(w, R, t, x, z, mask, x_out, N, L, nullptr, s, (hipStream_t)stream, pair_bias_cache, zg, pair_terms, feat_out);
+    ForwardQuery q;
+    if ((rc = forward_query(N, L, zg, s, w, 1, pair_bias_cache, pair_terms, &q))) return rc;
+    q.feat_out = feat_out != nullptr;
+    BlockArgs a{R, t, x, z, mask, x_out, pair_bias_cache, pair_terms};
+    a.feat_out = feat_out;
+    return ga_block(plan_block(q, 0), q, w, a, s, (hipStream_t)stream);
 }
 
-static int ga_encoder(const abopt_ga_weights* blocks, int num_layers, const float* R, const float* t, const float* x, const float* z,
-                      const uint8_t* mask, float* x_out, int N, int L, const GaScratch& s, float* pong, hipStream_t st,
-                      const float* pair_bias_cache = nullptr, int z_shared = 0, const float* pair_terms = nullptr, const float* x_terms = nullptr) {
-    // ga.py:190-193: the same R, t, z feed every block.  Ping-pong so the last block writes x_out.
-    const float* cur = x;
-    // x as fp16 terms travels with x from block to block (round 6): block i reads the terms its producer wrote (the mixer for block 0, `x_terms`; the tail of block
-    // i - 1 afterwards) and has its own tail write block i + 1's -- where the packed weights put node_frags and the term-writing tails on the path; ABOPT_X_TERMS=0: never
-    const bool xt_off = getenv("ABOPT_X_TERMS") && getenv("ABOPT_X_TERMS")[0] == '0';
-    const float* xt_cur = xt_off ? nullptr : x_terms;
-    for (int i = 0; i < num_layers; ++i) {
-        float* dst = ((num_layers - 1 - i) % 2 == 0) ? x_out : pong;
-        const abopt_ga_weights* w = &blocks[i];
-        const bool writes = !xt_off && i + 1 < num_layers && w->w_out_frag && w->w_mlp_frag && blocks[i + 1].w_node_frag;
-        float* xt_dst = writes ? s.xt[i & 1] : nullptr;
-        int rc = ga_block(w, R, t, cur, z, mask, dst, N, L, nullptr, s, st,
-                          pair_bias_cache ? pair_bias_cache + (size_t)i * pair_bias_layer_floats(z_shared ? N / z_shared : N, L) : nullptr, z_shared, pair_bias_cache ? pair_terms : nullptr,
-                          nullptr, xt_cur, xt_dst);
-        if (rc) return rc;
-        cur = dst;
-        xt_cur = xt_dst;
+static int ga_encoder(const EncoderPlan& e, const ForwardQuery& q, const abopt_ga_weights* blocks, BlockArgs a, const GaScratch& s, float* pong, hipStream_t st) {
+    // ga.py:190-193: the same R, t, z feed every block.  Ping-pong so the last block writes x_out.  (x as fp16 terms travels with x through the slots of the plan.)
+    float* const x_out = a.x_out;
+    const float* const pbc = a.pbc;
+    for (int i = 0; i < e.num_blocks; ++i) {            // a plan that ends in an Unsupported core ends here with that core's error
+        a.x_out = ((q.num_blocks - 1 - i) % 2 == 0) ? x_out : pong;
+        a.pbc = pbc ? pbc + (size_t)i * pair_bias_layer_floats(q.z_shared ? q.N / q.z_shared : q.N, q.L) : nullptr;
+        if (int rc = ga_block(e.blocks[i], q, &blocks[i], a, s, st)) return rc;
+        a.x = a.x_out;
     }
-    if (num_layers == 0) ABOPT_HIP(hipMemcpyAsync(x_out, x, (size_t)N * L * F * sizeof(float), hipMemcpyDeviceToDevice, st));
+    if (q.num_blocks == 0) ABOPT_HIP(hipMemcpyAsync(x_out, a.x, (size_t)q.N * q.L * F * sizeof(float), hipMemcpyDeviceToDevice, st));
     return ABOPT_OK;
 }
 
@@ -445,7 +464,9 @@ extern "C" int abopt_ga_encoder_forward(const abopt_ga_weights* blocks, int num_
     GaScratch s = carve_ga(cv, M, N, L);
     float* pong = cv.f((size_t)M * F);
     if (!cv.ok) { set_error("ga_encoder_forward: workspace too small (%zu bytes given)", ws_bytes); return ABOPT_EWORKSPACE; }
-    return ga_encoder(blocks, num_layers, R, t, x, z, mask, x_out, N, L, s, pong, (hipStream_t)stream);
+    ForwardQuery q;
+    if ((rc = forward_query(N, L, 0, s, blocks, num_layers, nullptr, nullptr, &q))) return rc;
+    return ga_encoder(plan_encoder(q), q, blocks, BlockArgs{R, t, x, z, mask, x_out}, s, pong, (hipStream_t)stream);
 }
 
 extern "C" size_t abopt_pair_bias_cache_bytes(int N, int L, int num_layers) {
@@ -463,8 +484,9 @@ extern "C" int abopt_nonfinite_flag_reset(abopt_stream stream) { return nonfinit
 extern "C" size_t abopt_pair_terms_bytes(int N, int L) { return pair_terms_blob_floats(N, L) * sizeof(float); }
 
 extern "C" int abopt_pair_terms_used(int N, int L, int pair_feat_shared) {
-    if (N <= 0 || L <= 0) return 0;
-    return ipa_core32_applies(N, L, pair_feat_shared) ? 1 : 0;
+    int cus = 0;
+    if (N <= 0 || L <= 0 || device_cu_count(&cus)) return 0;
+    return plan_pair_terms_used(N, L, pair_feat_shared, cus, read_switches()) ? 1 : 0;
 }
 
 extern "C" int abopt_pair_terms(const float* pair_feat, float* terms, int N, int L, int Cd, abopt_stream stream) {
@@ -545,12 +567,14 @@ extern "C" int abopt_eps_net_forward(const abopt_eps_weights* w, const float* v_
     EpsScratch e = carve_eps(cv, M, N, L, 64);
     if (!cv.ok) { set_error("eps_net_forward: workspace too small (%zu bytes given, %zu needed)", ws_bytes, abopt_eps_workspace_bytes(N, L, Fd, Cd)); return ABOPT_EWORKSPACE; }
 
+    ForwardQuery q;
+    if ((rc = forward_query(N, L, zg, e.ga, w->blocks, w->num_layers, pair_bias_cache, pair_terms, &q))) return rc;
+    q.mix_frag = w->w_mix_frag && w->mix_table; q.heads_frag = w->w_heads_frag != nullptr; q.prmsd = has_prmsd;
+    const NetPlan plan = plan_network(q);
+
     // dpm_full.py:86  R = exp(v_t)   and   dpm_full.py:89  res_feat_mixer([res_feat | Embedding(s_t)])
-    float* x0_terms = nullptr;
-    if (w->w_mix_frag && w->mix_table) {
-        const bool xt0 = w->num_layers > 0 && w->blocks[0].w_node_frag && !(getenv("ABOPT_X_TERMS") && getenv("ABOPT_X_TERMS")[0] == '0');
-        x0_terms = xt0 ? e.ga.xt[1] : nullptr;                                 // (block 0 writes xt[0], block 1 xt[1], ...: the mixer's copy is read before it is overwritten)
-        if ((rc = launch_mixer(res_feat, s_t, w->w_mix_frag, w->mix_table, w->b_mix1, e.cat, M, st, v_t, e.R, x0_terms))) return rc;       // one launch for both
+    if (plan.mixer_kernel) {
+        if ((rc = launch_mixer(res_feat, s_t, w->w_mix_frag, w->mix_table, w->b_mix1, e.cat, M, st, v_t, e.R, plan.mixer_xt >= 0 ? e.ga.xt[plan.mixer_xt] : nullptr))) return rc;       // one launch for both
     } else {
         if ((rc = launch_so3_exp(v_t, e.R, M, st))) return rc;
         if ((rc = launch_embed_concat(res_feat, s_t, w->seq_embed, e.cat, M, st))) return rc;
@@ -558,20 +582,15 @@ extern "C" int abopt_eps_net_forward(const abopt_eps_weights* w, const float* v_
         if ((rc = launch_linear(e.x0, F, w->w_mix1, F, w->b_mix1, e.cat, F, (int)M, F, F, false, st))) return rc;   // reuse cat[:, :F] as x (ld = F)
     }
     // dpm_full.py:90  encoder
-    if ((rc = ga_encoder(w->blocks, w->num_layers, e.R, p_t, e.cat, pair_feat, mask_res, e.xe, N, L, e.ga, e.pong, st, pair_bias_cache, zg, pair_terms, x0_terms))) return rc;
-    bool heads_fused = false;
-    if (w->w_heads_frag) {
-        // dpm_full.py:92-101: time features + the three heads in one launch (heads.hip)
-        if (has_prmsd && (rc = launch_build_infeat(e.xe, beta, e.infeat, w->prmsd_ln_gamma, w->prmsd_ln_beta, e.infeat_ln, N, L, st))) return rc;
-        // ... and, unless ABOPT_FUSE_HEADS=0 (A/B, tests), their geometric epilogue as the tail of the same kernel
-        const char* fh = getenv("ABOPT_FUSE_HEADS");
-        heads_fused = !(fh && fh[0] == '0');
+    if ((rc = ga_encoder(plan.enc, q, w->blocks, BlockArgs{e.R, p_t, e.cat, pair_feat, mask_res, e.xe, pair_bias_cache, pair_terms}, e.ga, e.pong, st))) return rc;
+    // dpm_full.py:92-93 time features (the heads kernel takes them as an affine term: then only the prmsd head's LayerNorm'd copy is needed)
+    if (plan.build_infeat && (rc = launch_build_infeat(e.xe, beta, e.infeat, w->prmsd_ln_gamma, w->prmsd_ln_beta, plan.prmsd ? e.infeat_ln : nullptr, N, L, st))) return rc;
+    if (plan.heads_kernel) {
+        // dpm_full.py:92-101: time features + the three heads in one launch (heads.hip) and, unless ABOPT_FUSE_HEADS=0 (A/B, tests), their geometric epilogue as its tail
         const HeadsEpilogue hep{e.R, v_t, mask_generate, v_next, R_next, eps_pos, c_denoised, grad_mode, nonfinite_flag_ptr()};
         if ((rc = launch_heads_mlp(e.xe, beta, w->w_heads_frag, w->w_head1, FI, w->b_head1, w->b_crd2, w->b_rot2, w->b_seq2, w->b_crd3, w->b_rot3,
-                                   w->b_seq3, e.out3, M, L, st, heads_fused ? &hep : nullptr))) return rc;
+                                   w->b_seq3, e.out3, M, L, st, plan.heads_epilogue ? &hep : nullptr))) return rc;
     } else {
-    // dpm_full.py:92-93 time features
-    if ((rc = launch_build_infeat(e.xe, beta, e.infeat, w->prmsd_ln_gamma, w->prmsd_ln_beta, has_prmsd ? e.infeat_ln : nullptr, N, L, st))) return rc;
     // three heads, first layers fused (shared input): [M,132] x [384,132]^T
     if ((rc = launch_linear(e.infeat, FI, w->w_head1, FI, w->b_head1, e.hh1, 3 * F, (int)M, 3 * F, FI, true, st))) return rc;
     if ((rc = launch_linear(e.hh1 + 0 * F, 3 * F, w->w_crd2, F, w->b_crd2, e.hh2 + 0 * F, 3 * F, (int)M, F, F, true, st))) return rc;
@@ -582,9 +601,9 @@ extern "C" int abopt_eps_net_forward(const abopt_eps_weights* w, const float* v_
     if ((rc = launch_linear(e.hh2 + 1 * F, 3 * F, w->w_rot3, F, w->b_rot3, e.out3 + 4, 32, (int)M, 3, F, false, st))) return rc;
     if ((rc = launch_linear(e.hh2 + 2 * F, 3 * F, w->w_seq3, F, w->b_seq3, e.out3 + 8, 32, (int)M, ABOPT_AA, F, false, st))) return rc;
     }
-    if (!heads_fused && (rc = launch_heads_epilogue(e.R, v_t, e.out3 + 0, e.out3 + 4, e.out3 + 8, 32, 32, mask_generate, v_next, R_next, eps_pos, c_denoised,
-                                                    M, grad_mode, st))) return rc;
-    if (has_prmsd) {
+    if (!plan.heads_epilogue && (rc = launch_heads_epilogue(e.R, v_t, e.out3 + 0, e.out3 + 4, e.out3 + 8, 32, 32, mask_generate, v_next, R_next, eps_pos, c_denoised,
+                                                            M, grad_mode, st))) return rc;
+    if (plan.prmsd) {
         // PerResiduePredictor (nn.py:179-188) then mean over L (dpm_full.py:109-110)
         if ((rc = launch_linear(e.infeat_ln, FI, w->w_prmsd1, FI, w->b_prmsd1, e.pr1, F, (int)M, F, FI, true, st))) return rc;
         if ((rc = launch_linear(e.pr1, F, w->w_prmsd2, F, w->b_prmsd2, e.pr2, F, (int)M, F, F, true, st))) return rc;

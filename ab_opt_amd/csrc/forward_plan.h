@@ -1,0 +1,109 @@
+// Which launches a denoiser forward is made of: the ONE place that decides (api.hip reads the switches once per entry, builds a ForwardQuery and walks the plan;
+// the launchers of ipa_core.hip / ipa.hip take the CorePlan they are handed).  plan_ipa_core (ipa_plan.h) is called from here and from nowhere else on the
+// forward path.  Plain host C++17, no HIP: tests/forward_plan_table.cpp tabulates the functions without a device (tests/test_forward_plan.py).
+#pragma once
+#include "ipa_plan.h"
+
+namespace abopt {
+
+constexpr int kMaxBlocks = 8;       // blocks of one encoder (the pair-bias cache holds as many layers)
+
+// The environment switches as values (api.hip: read_switches, once per C-ABI call -- callers flip them between calls of one process)
+struct Switches {
+    int core32_override = -1;       // ABOPT_CORE32: -1 unset, 0, 1
+    bool no_split = false;          // ABOPT_CORE_NO_SPLIT
+    bool fuse_tail = true;          // ABOPT_FUSE_TAIL=0: core and tail as two launches where the 32-row core runs
+    bool x_terms = true;            // ABOPT_X_TERMS=0: no kernel writes x as fp16 terms, every node_frags splits x for itself
+    bool fuse_heads = true;         // ABOPT_FUSE_HEADS=0: the heads' geometric epilogue as a launch of its own
+};
+
+struct BlockWeights { bool node_frag, out_frag, mlp_frag, out_terms; };     // which packed operands of abopt_ga_weights are given
+
+// A forward by what the choice depends on, and nothing else
+struct ForwardQuery {
+    int N, L, z_shared, cus;
+    bool cache, terms;              // a pair-bias cache / the pair terms of the same pair_feat are given
+    bool dbg, dump;                 // abopt_ga_debug is given; it asks for logits or alpha (the dumping core)
+    bool feat_out;                  // the core's features are wanted in the caller's buffer
+    bool split_ws;                  // key-split scratch is held, of
+    size_t split_ws_floats;         // ... this many floats
+    int num_blocks;
+    BlockWeights blocks[kMaxBlocks];
+    bool mix_frag, heads_frag, prmsd;       // network only: w_mix_frag + mix_table, w_heads_frag, the prmsd head
+    Switches sw;
+};
+
+enum class NodeForm { Kernel, Gemm };               // node_frags | projection GEMM + ipa_frags
+enum class TailForm { InCore, OutLnMlp, Gemm };     // epilogue of ipa_core32_kernel<true, *> | out_ln_mlp | split-K GEMM + fused_ln_mlp
+struct BlockPlan {
+    NodeForm node;
+    bool qk_terms;                  // node_frags writes the q / k channel slots as fp16 terms: read by ipa_core32_kernel<*, true> and by no other core
+    CorePlan core;
+    TailForm tail;
+    int xt_read, xt_write;          // slot of the workspace's x-terms pair that node_frags reads / the tail writes; -1: none
+};
+struct EncoderPlan {
+    bool ok;                        // false: the last planned block's core is Unsupported and nothing is planned after it
+    int num_blocks;
+    BlockPlan blocks[kMaxBlocks];
+};
+struct NetPlan {
+    bool mixer_kernel;              // the mixer kernel (with R = exp(v_t) fused) | so3_exp + embed_concat + two GEMMs
+    int mixer_xt;                   // slot the mixer writes x's terms to; -1: none
+    EncoderPlan enc;
+    bool heads_kernel;              // the heads kernel | the GEMM chain
+    bool heads_epilogue;            // the geometric epilogue rides in the heads kernel
+    bool build_infeat, prmsd;       // build_infeat runs (GEMM heads, or the prmsd head's LayerNorm'd copy); the prmsd chain runs
+};
+
+inline CoreQuery core_query(const ForwardQuery& q) {
+    return {q.N, q.L, q.z_shared, q.cus, q.cache, q.dump, q.split_ws, q.split_ws_floats, q.sw.core32_override, q.sw.no_split};
+}
+
+// What abopt_pair_terms_used answers: the cached forward of this geometry takes the 32-row kernels (which alone read the terms), whatever scratch is held
+inline bool plan_pair_terms_used(int N, int L, int z_shared, int cus, const Switches& sw) {
+    return plan_is_core32({N, L, z_shared, cus, true, false, false, 0, sw.core32_override, sw.no_split});
+}
+
+// Block i of the query.  x as fp16 terms travels with x: the block reads the slot its producer wrote (`produced`; -1: none) if its node step is the kernel, and
+// writes `next_slot` for a successor whose node step is the kernel -- from one of the two term-writing tails, never the slot it reads
+inline BlockPlan plan_block(const ForwardQuery& q, int i, int produced = -1, int next_slot = -1) {
+    const BlockWeights& w = q.blocks[i];
+    BlockPlan p;
+    p.node = w.node_frag ? NodeForm::Kernel : NodeForm::Gemm;
+    p.core = plan_ipa_core(core_query(q));
+    const bool core32 = p.core.form == CoreForm::Core32 && !q.dbg;        // (Core32 implies a cache and no dump)
+    p.qk_terms = core32 && q.terms && w.node_frag;
+    p.tail = (core32 && w.out_terms && w.mlp_frag && !q.feat_out && q.sw.fuse_tail) ? TailForm::InCore
+           : (w.out_frag && w.mlp_frag) ? TailForm::OutLnMlp : TailForm::Gemm;
+    p.xt_read = w.node_frag ? produced : -1;
+    const bool writes = q.sw.x_terms && next_slot >= 0 && next_slot != p.xt_read && i + 1 < q.num_blocks && q.blocks[i + 1].node_frag && w.out_frag && w.mlp_frag;
+    p.xt_write = writes ? next_slot : -1;
+    return p;
+}
+
+// The blocks of an encoder: block 0's producer wrote `produced` (the mixer; -1: nobody), block i writes slot i & 1
+inline EncoderPlan plan_encoder(const ForwardQuery& q, int produced = -1) {
+    EncoderPlan e{true, 0, {}};
+    for (int i = 0; i < q.num_blocks && e.ok; ++i) {
+        const BlockPlan& p = e.blocks[e.num_blocks++] = plan_block(q, i, produced, i & 1);
+        produced = p.xt_write;
+        e.ok = p.core.form != CoreForm::Unsupported;
+    }
+    return e;
+}
+
+inline NetPlan plan_network(const ForwardQuery& q) {
+    NetPlan n{};
+    n.mixer_kernel = q.mix_frag;
+    n.mixer_xt = (q.mix_frag && q.sw.x_terms && q.num_blocks > 0 && q.blocks[0].node_frag) ? 1 : -1;     // slot 1: block 0 writes slot 0 after it has read this one
+    n.enc = plan_encoder(q, n.mixer_xt);
+    if (!n.enc.ok) return n;
+    n.heads_kernel = q.heads_frag;
+    n.heads_epilogue = q.heads_frag && q.sw.fuse_heads;
+    n.build_infeat = !q.heads_frag || q.prmsd;
+    n.prmsd = q.prmsd;
+    return n;
+}
+
+}  // namespace abopt

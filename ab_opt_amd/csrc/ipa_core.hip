@@ -1770,20 +1770,6 @@ __global__ __launch_bounds__(256) void ipa_split_merge_kernel(const float* __res
     }
 }
 
-// The launch geometry as plan_ipa_core (ipa_plan.h) wants it: the CU count of the current device (needed only by the cached, non-dumping forms) and the
-// ABOPT_CORE32 / ABOPT_CORE_NO_SPLIT switches, read at every call
-static int core_query(int N, int L, int z_shared, bool cache, bool dump, bool split_ws, size_t split_ws_floats, CoreQuery* q) {
-    const char* e = getenv("ABOPT_CORE32");
-    *q = CoreQuery{N, L, z_shared, 0, cache, dump, split_ws, split_ws_floats, (e && e[0] == '0') ? 0 : ((e && e[0] == '1') ? 1 : -1), getenv("ABOPT_CORE_NO_SPLIT") != nullptr};
-    return (cache && !dump) ? device_cu_count(&q->cus) : ABOPT_OK;
-}
-
-bool ipa_core32_applies(int N, int L, int z_shared) {
-    CoreQuery q;
-    if (core_query(N, L, z_shared, true, false, false, 0, &q)) return false;
-    return plan_is_core32(q);
-}
-
 template <bool DUMP, bool CACHED>
 static int launch_core_variant(const CorePlan& plan, const float* qfrag, const float* kvfrag, const float* z, const uint8_t* mask, const float* R, const float* t,
                                const float* Wb, float* feat, float* dump, float* dump_stats, const float* pbc, int N, int L, hipStream_t st, int z_shared) {
@@ -1818,25 +1804,16 @@ static int launch_core32(const CorePlan& plan, const float* qfrag, const float* 
     return ABOPT_OK;
 }
 
-// The whole block behind the projections in ONE launch (ipa_core32_kernel<true, ZT>: core + tail) where the 32-row kernel is the core of
-// choice; *fused = 0 and nothing launched otherwise (the caller then runs core and tail separately -- same results bit for bit).
-// ABOPT_FUSE_TAIL=0 keeps the two-launch form (A/B, tests).
-int launch_ipa_block_fused(const float* qfrag, const float* kvfrag, const float* z, const uint8_t* mask, const float* R, const float* t,
+// The whole block behind the projections in ONE launch (ipa_core32_kernel<true, ZT>: core + tail) from the Core32 plan of a block whose tail the plan put
+// inside the core (forward_plan.h: TailForm::InCore) -- the same results as core and tail on their own, bit for bit
+int launch_ipa_block_fused(const CorePlan& plan, const float* qfrag, const float* kvfrag, const float* z, const uint8_t* mask, const float* R, const float* t,
                            const float* pair_bias_cache, int N, int L, hipStream_t st, int z_shared, const float* wot, const float* wmf, const float* x,
                            const float* ubias, const float* g1, const float* be1, const float* b0, const float* b1, const float* b2, const float* g2,
-                           const float* be2, float* out, int* fused, const float* pair_terms, float* xt_out) {
-    *fused = 0;
-    const char* e = getenv("ABOPT_FUSE_TAIL");
-    if (!pair_bias_cache || !wot || !wmf || (e && e[0] == '0')) return ABOPT_OK;
-    CoreQuery q;
-    if (int rc = core_query(N, L, z_shared, true, false, false, 0, &q)) return rc;
-    const CorePlan plan = plan_ipa_core(q);
-    if (plan.form != CoreForm::Core32) return ABOPT_OK;
+                           const float* be2, float* out, const float* pair_terms, float* xt_out) {
+    ABOPT_CHECK_ARG(plan.form == CoreForm::Core32 && pair_bias_cache && wot && wmf, "ipa_block_fused: not a 32-row plan with a cache and packed tail weights");
     const TailArgs ta{wot, wmf, x, ubias, g1, be1, b0, b1, b2, g2, be2, out, reinterpret_cast<unsigned*>(xt_out)};
-    if (int rc = pair_terms ? launch_core32<true, true>(plan, qfrag, kvfrag, z, mask, R, t, nullptr, pair_bias_cache, N, L, st, z_shared, ta, pair_terms)
-                            : launch_core32<true, false>(plan, qfrag, kvfrag, z, mask, R, t, nullptr, pair_bias_cache, N, L, st, z_shared, ta, nullptr)) return rc;
-    *fused = 1;
-    return ABOPT_OK;
+    return pair_terms ? launch_core32<true, true>(plan, qfrag, kvfrag, z, mask, R, t, nullptr, pair_bias_cache, N, L, st, z_shared, ta, pair_terms)
+                      : launch_core32<true, false>(plan, qfrag, kvfrag, z, mask, R, t, nullptr, pair_bias_cache, N, L, st, z_shared, ta, nullptr);
 }
 
 int prof_spans_reset(hipStream_t st) {
@@ -1862,14 +1839,14 @@ int read_clock_probe(long long* cycles, long long* wall_ticks) {
     return ABOPT_OK;
 }
 
-int launch_ipa_core_kernel(const float* qfrag, const float* kvfrag, const float* z, const uint8_t* mask, const float* R, const float* t,
+// The core alone, in the form of the plan it is handed (forward_plan.h plans the forward path, ipa_train.hip its own dumping launch)
+int launch_ipa_core_kernel(const CorePlan& plan, const float* qfrag, const float* kvfrag, const float* z, const uint8_t* mask, const float* R, const float* t,
                            const float* w_pair_bias, float* feat, float* dump, float* dump_stats, const float* pair_bias_cache, int N, int L, hipStream_t st,
-                           int z_shared, float* split_ws, size_t split_ws_floats, const float* pair_terms) {
+                           int z_shared, float* split_ws, const float* pair_terms) {
     ABOPT_CHECK_ARG(!dump == !dump_stats, "ipa_core: the logits dump and its row statistics come together");
     ABOPT_CHECK_ARG(!dump || (int64_t)H * L * L * 4 < (1ll << 31), "ipa_core: L=%d too long for the logits dump", L);
-    CoreQuery q;
-    if (int rc = core_query(N, L, z_shared, pair_bias_cache != nullptr, dump != nullptr, split_ws != nullptr, split_ws_floats, &q)) return rc;
-    const CorePlan plan = plan_ipa_core(q);
+    const bool cached_form = plan.form == CoreForm::Core32 || plan.form == CoreForm::Persist || plan.form == CoreForm::Split;
+    ABOPT_CHECK_ARG(!cached_form || (pair_bias_cache && !dump && (plan.form != CoreForm::Split || split_ws)), "ipa_core: the plan does not fit the operands given");
     const int nib = (L + BI - 1) / BI, nchunk = (L + JC - 1) / JC;
     switch (plan.form) {
     case CoreForm::Unsupported:

@@ -460,7 +460,8 @@ int launch_ipa_train_forward(const float* proj_local, const float* R, const floa
     if ((rc = launch_ipa_frags(proj_local, R, t, spatial_coef, qf, kvf, N, L, st, ABOPT_NODE_PROJ))) return rc;
     float* stats = qf + ipa_qfrag_floats(N, L);
     // the core writes its scaled logits head-major into the alpha buffer; one elementwise pass turns them into alpha in place
-    if ((rc = launch_ipa_core_kernel(qf, kvf, z, mask, R, t, Wb, feat, alpha, stats, pbc, N, L, st, 0))) return rc;
+    const CorePlan plan = plan_ipa_core({N, L, 0, 0, pbc != nullptr, true, false, 0, -1, false});           // the dumping core: one block per workgroup
+    if ((rc = launch_ipa_core_kernel(plan, qf, kvf, z, mask, R, t, Wb, feat, alpha, stats, pbc, N, L, st, 0))) return rc;
     if ((L & 3) == 0) {
         const int64_t quads = (int64_t)N * H * L * (L / 4);
         hipLaunchKernelGGL(alpha_finalize_kernel, dim3((unsigned)((quads + 255) / 256)), dim3(256), 0, st, alpha, stats, mask, L, quads);

@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "../../include/abopt.h"
+#include "ipa_plan.h"
 
 namespace abopt {
 
@@ -26,22 +27,23 @@ size_t ipa_qfrag_floats(int N, int L);
 size_t pair_bias_layer_floats(int N, int L);
 // ldp: row stride of proj in floats (NP for the library's own buffer; 2016 reads the projections' output in place: rows stay 16-byte aligned)
 int launch_ipa_frags(const float* proj, const float* R, const float* t, const float* spatial_coef, float* qfrag, float* kvfrag, int N, int L, hipStream_t st, int ldp = 2048);
-int launch_ipa_core(const float* qfrag, const float* kvfrag, const float* z, const uint8_t* mask, const float* R, const float* t,
+// plan: the form of the core as forward_plan.h planned it for these operands (a dump: dbg_logits or dbg_alpha given)
+int launch_ipa_core(const CorePlan& plan, const float* qfrag, const float* kvfrag, const float* z, const uint8_t* mask, const float* R, const float* t,
                     const float* w_pair_bias, float* feat, float* dbg_logits, float* dbg_alpha, const float* pair_bias_cache,
                     int N, int L, hipStream_t st, int z_shared = 0 /* 1: z and the pair-bias cache hold ONE sample that every batch entry shares */,
-                    float* split_ws = nullptr, size_t split_ws_floats = 0 /* scratch of the key-split form (small batches), ipa_split_ws_floats(N, L) */,
+                    float* split_ws = nullptr /* scratch of the key-split form (small batches), ipa_split_ws_floats(N, L) */,
                     const float* pair_terms = nullptr /* abopt_pair_terms blob of the same pair_feat: the 32-row kernels then aggregate on the fp16 matrix instructions */);
 
-// ipa_core.hip: core + tail of a block in one launch where the 32-row core applies (sets *fused; otherwise launches nothing)
-int launch_ipa_block_fused(const float* qfrag, const float* kvfrag, const float* z, const uint8_t* mask, const float* R, const float* t,
+// ipa_core.hip: core + tail of a block in one launch, from a Core32 plan
+int launch_ipa_block_fused(const CorePlan& plan, const float* qfrag, const float* kvfrag, const float* z, const uint8_t* mask, const float* R, const float* t,
                            const float* pair_bias_cache, int N, int L, hipStream_t st, int z_shared, const float* wot /* W_out as bf16 terms */, const float* wmf, const float* x,
                            const float* ubias, const float* g1, const float* be1, const float* b0, const float* b1, const float* b2, const float* g2,
-                           const float* be2, float* out, int* fused, const float* pair_terms = nullptr, float* xt_out = nullptr);
+                           const float* be2, float* out, const float* pair_terms = nullptr, float* xt_out = nullptr);
 
 // node_frags.hip: x [N*L,128] -> qfrag / kvfrag directly (projection GEMM + frame transform + fragment layout in one kernel)
 size_t node_wfrag_floats();
 int launch_node_frags(const float* x, const float* wfrag, const float* R, const float* t, const float* spatial_coef, float* qfrag, float* kvfrag,
-                      int N, int L, hipStream_t st,
+                      int N, int L, hipStream_t st, int cus /* CUs of the current device */,
                       int qk_terms = 0 /* 1: the q / k channel slots as two fp16 terms each (high terms in slot 0, low terms in slot 1): what ipa_core32_kernel<*, true> reads */,
                       const float* x_terms = nullptr /* optional: x as two fp16 terms per value, written by the kernel that produced x (tail / mixer): no split here */);
 

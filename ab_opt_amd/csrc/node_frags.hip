@@ -221,11 +221,10 @@ __global__ __launch_bounds__(NF_WAVES * 64) void node_frags_kernel(const float* 
 size_t node_wfrag_floats() { return (size_t)H * NF_HEAD_VEC * 4 + 4; }      // + {S, 1 / S, 0, 0}
 
 int launch_node_frags(const float* x, const float* wfrag, const float* R, const float* t, const float* spatial_coef, float* qfrag, float* kvfrag,
-                      int N, int L, hipStream_t st, int qk_terms, const float* x_terms) {
+                      int N, int L, hipStream_t st, int cus, int qk_terms, const float* x_terms) {
     if ((int64_t)N * L == 0) return ABOPT_OK;
     const int nchunk = (L + JC - 1) / JC, total = N * nchunk;
-    int cus = 0, rc;
-    if ((rc = device_cu_count(&cus))) return rc;
+    int rc;
     static LdsConfig lds_cfg[2];
     const bool xt = x_terms != nullptr;
     if ((rc = ensure_dynamic_lds(xt ? reinterpret_cast<const void*>(node_frags_kernel<true>) : reinterpret_cast<const void*>(node_frags_kernel<false>), NF_LDS_VEC * 16,

@@ -1466,6 +1466,45 @@ def test_node_feature_terms_travel_with_x_bit_identically(flavour, N, L, monkeyp
             assert torch.isfinite(o[k]).all() and torch.equal(o[k], outs[0][k]), k
 
 
+@pytest.mark.parametrize('k', [0, 1, 2])
+@pytest.mark.parametrize('N,L,core32', [(2, 33, '1'), (3, 70, None)])
+def test_x_terms_chain_around_one_plain_block_is_bit_identical(N, L, core32, k, monkeypatch):
+    """A block list in which one block is plain: a three-block EpsilonNet whose block k carries none of the four packed operands, with a bias cache and pair terms.
+    The chain of x terms breaks at that block (its predecessor writes none for it, it writes none for its successor) and the forms around it differ per block;
+    ABOPT_X_TERMS=0 against the default must not change a bit of any output.  (2, 33) with ABOPT_CORE32=1: the 32-row kernels, fused block and term path, one full
+    and one one-row query block per sample; (3, 70): the 16-row kernels."""
+    import ctypes as C
+    from ab_opt_amd import hip
+    d = build_model(100, 2, device=DEV).diffusion
+    ew = d.eps_net.packed()
+    arr = (hip.GaWeights * 3)()
+    for i, b in enumerate(list(d.eps_net.encoder.blocks)[:3]):
+        src = b.packed()[1]
+        for name, _ in hip.GaWeights._fields_:
+            setattr(arr[i], name, None if i == k and name in ('w_node_frag', 'w_out_frag', 'w_out_terms', 'w_mlp_frag') else getattr(src, name))
+    net = hip.EpsWeights()
+    for name, _ in hip.EpsWeights._fields_:
+        setattr(net, name, getattr(ew, name))
+    net.blocks, net.num_layers = C.cast(arr, C.POINTER(hip.GaWeights)), 3
+    if core32 is not None:
+        monkeypatch.setenv('ABOPT_CORE32', core32)
+    lens = [L - 9 * i for i in range(N)]
+    v, p, s, rf, pf, gen, mres = _rand_eps_inputs(N, L, lens, 9300 + N, [(5, 14), (22, 30)])
+    beta = d.trans_pos.var_sched.betas[37].expand([N]).contiguous()
+    pbc, terms = hip.pair_bias_cache(arr, 3, pf), hip.pair_terms(pf)
+    assert hip.pair_terms_used(N, L) == (core32 == '1')
+    outs = []
+    for xt in (None, '0'):
+        if xt is not None:
+            monkeypatch.setenv('ABOPT_X_TERMS', xt)
+        o = hip.eps_net_forward(net, v, p, s, rf, pf, beta, gen, mres, d.abdock, d.num_bins, False, pair_bias_cache=pbc, pair_terms=terms)
+        outs.append({name: a.clone() for name, a in o.items() if a is not None})
+    assert len(outs[0]) == 5
+    for name in outs[0]:
+        assert torch.isfinite(outs[0][name]).all(), name
+        assert torch.equal(outs[0][name].view(torch.int32), outs[1][name].view(torch.int32)), name
+
+
 def _pair_terms_statement(z, L):
     """torch statement of abopt_pair_terms (include/abopt.h): per (row, channel) power-of-two scale, two fp16 terms, K-packed layout."""
     N = z.shape[0]
