@@ -38,9 +38,9 @@ __global__ __launch_bounds__(256) void denoise_step_kernel(abopt_step_params sp,
     float ppl_num = 0.f, ppl_den = 0.f;
     // The histogram bin is the only long dependent chain of a residue (13 probes of the 8191-entry CDF row): the row is staged in LDS by
     // coalesced loads first (same comparisons on the same values), and not searched at all where its result cannot reach the output
-    // (Gaussian branch of so3.py:129-138, t <= 1: e = 0, injected noise).
+    // (Gaussian branch of so3.py:129-138, the step that lands on 0: e = 0, injected noise).
     __shared__ float cdf_s[8192];
-    const bool need_bin = !injected && !sp.igso3_gaussian && sp.t > 1;
+    const bool need_bin = !injected && !sp.igso3_gaussian && sp.t_prev > 0;
     const bool cdf_lds = need_bin && bins - 1 <= 8192;
     if (cdf_lds) {
         for (int k = tid; k < bins - 1; k += 256) cdf_s[k] = igCdf[k];
@@ -221,6 +221,72 @@ __global__ __launch_bounds__(256) void add_noise_kernel(const int64_t* __restric
     s_noisy[i] = sn;
 }
 
+// ---- IGSO(3) angle histograms for arbitrary standard deviations (include/abopt.h: abopt_igso3_tables): what ApproxAngularDistribution builds on the host at
+// construction (so3.py:82-109; 8192 x 1024-element fp32 tensor ops per row), for the strides of a respaced loop, whose sigmas are chosen per call.
+// One lane per bin, a wave per 64 consecutive bins; the l-dependent factor a_l of a row is staged in LDS once per workgroup.  Every lane walks l upwards on its own, in
+// fp64: no cross-lane reduction, so the order of the sum is fixed, and the factors that do not depend on l (c and the denominator of b) multiply the finished sum.
+constexpr int IG_CHUNK = 1024;
+constexpr double PI_D = 3.14159265358979323846;
+
+// at::linspace(0, pi, bins)[i] in fp32, bit for bit: fl(step i) below the midpoint and pi - step (bins - 1 - i) in one rounding from it on; step = fl(fl(pi) / (bins - 1))
+__device__ __forceinline__ float linspace_0_pi(float step, int bins, int i) {
+    return (i < bins / 2) ? step * (float)i : fmaf(-step, (float)(bins - 1 - i), PI_F);
+}
+
+__global__ __launch_bounds__(256) void igso3_hist_kernel(const float* __restrict__ stddevs, int bins, int iters, float step, float* __restrict__ X, float* __restrict__ Y) {
+    const int r = blockIdx.y, tid = threadIdx.x;
+    const int64_t b = (int64_t)blockIdx.x * 256 + tid;
+    const bool live = b < bins;
+    __shared__ double a_s[IG_CHUNK];
+    const double sd = (double)stddevs[r], var = sd * sd;
+    const float xf = linspace_0_pi(step, bins, live ? (int)b : 0);
+    const double x = (double)xf;
+    double acc = 0.0;
+    for (int l0 = 0; l0 < iters; l0 += IG_CHUNK) {
+        const int n = min(IG_CHUNK, iters - l0);
+        __syncthreads();
+        for (int k = tid; k < n; k += 256) {
+            const double l = (double)(l0 + k);
+            a_s[k] = (2.0 * l + 1.0) * exp(-l * (l + 1.0) * var);
+        }
+        __syncthreads();
+        if (live)
+            for (int k = 0; k < n; ++k) acc += a_s[k] * (sin(((double)(l0 + k) + 0.5) * x) + 1e-6);
+    }
+    if (!live) return;
+    const double c = (1.0 - cos(x)) / PI_D, den = sin(x / 2.0) + 1e-6;
+    float y = (float)(c * acc / den);
+    if (y != y) y = 0.f;                                        // nan_to_num, clamp_min(0)
+    y = fminf(fmaxf(y, 0.f), 3.402823466e+38f);
+    const int64_t o = (int64_t)r * bins + b;
+    Y[o] = y;
+    if (X) X[o] = xf;
+}
+
+// cdf[r, :] = cumsum(Y[r, :bins-1]) / sum(Y[r, :bins-1]) in fp64 (ApproxAngularDistribution.cdf); one workgroup per row, a contiguous run of cells per thread
+__global__ __launch_bounds__(256) void igso3_cdf_kernel(const float* __restrict__ Y, int bins, float* __restrict__ cdf) {
+    const int tid = threadIdx.x;
+    const int64_t n = (int64_t)bins - 1, per = (n + 255) / 256;
+    const int64_t lo = min((int64_t)tid * per, n), hi = min(lo + per, n);
+    const float* y = Y + (int64_t)blockIdx.x * bins;
+    float* c = cdf + (int64_t)blockIdx.x * n;
+    __shared__ double part[256];
+    __shared__ double total;
+    double s = 0.0;
+    for (int64_t k = lo; k < hi; ++k) s += (double)y[k];
+    part[tid] = s;
+    __syncthreads();
+    if (tid == 0) {
+        double run = 0.0;
+        for (int i = 0; i < 256; ++i) { const double v = part[i]; part[i] = run; run += v; }
+        total = run;
+    }
+    __syncthreads();
+    const double tot = total > 0.0 ? total : 1.0;
+    double run = part[tid];
+    for (int64_t k = lo; k < hi; ++k) { run += (double)y[k]; c[k] = (float)(run / tot); }
+}
+
 // score[b] = sum_b' sqrt(mean_n |x_b - x_b'|^2) / (B - 1)   (design_for_testset.py:556-563,586-588)
 __global__ __launch_bounds__(256) void commonness_kernel(const float* __restrict__ x, float* __restrict__ score, int B, int n) {
     const int b = blockIdx.x, tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
@@ -268,6 +334,7 @@ extern "C" int abopt_denoise_step(const abopt_step_params* sp, const abopt_step_
                                   int N, int L, abopt_stream stream) {
     ABOPT_CHECK_ARG(sp && v_t && p_t && s_t && v_net && p_net && c_net && mask_generate && v_next && p_next && s_next, "denoise_step: NULL argument");
     ABOPT_CHECK_ARG(igso3_X && igso3_bins >= 2, "denoise_step: IGSO(3) histogram row missing");
+    ABOPT_CHECK_ARG(sp->t_prev >= 0 && sp->t_prev < sp->t, "denoise_step: the step must land below where it starts (t=%d t_prev=%d)", sp->t, sp->t_prev);
     abopt_step_noise nz = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
     if (noise && noise->axis) {
         ABOPT_CHECK_ARG(noise->bin && noise->ubin && noise->gauss && noise->z && noise->s_next, "denoise_step: injected noise must provide all six draws");
@@ -279,6 +346,18 @@ extern "C" int abopt_denoise_step(const abopt_step_params* sp, const abopt_step_
     hipLaunchKernelGGL(denoise_step_kernel, dim3(N), dim3(256), 0, (hipStream_t)stream, *sp, nz, seed, offset, seed_offset_dev, v_t, p_t, s_t, v_net, p_net, c_net,
                        prmsd_logits, mask_generate, igso3_X, igso3_cdf, igso3_bins, num_bins, v_next, p_next, s_next, prmsd, perplexity, post_out,
                        p_next_norm, aa_allowed, L, sp->ppl_masked);
+    ABOPT_LAUNCH_CHECK();
+    return ABOPT_OK;
+}
+
+extern "C" int abopt_igso3_tables(const float* stddevs, int rows, int bins, int iters, float* X, float* Y, float* cdf, abopt_stream stream) {
+    ABOPT_CHECK_ARG(stddevs && Y && cdf, "igso3_tables: NULL argument");
+    ABOPT_CHECK_ARG(rows >= 0 && rows <= 65535 && bins >= 2 && iters >= 1, "igso3_tables: bad sizes (rows=%d bins=%d iters=%d)", rows, bins, iters);
+    if (rows == 0) return ABOPT_OK;
+    const float step = PI_F / (float)(bins - 1);
+    hipLaunchKernelGGL(igso3_hist_kernel, dim3((unsigned)((bins + 255) / 256), (unsigned)rows), dim3(256), 0, (hipStream_t)stream, stddevs, bins, iters, step, X, Y);
+    ABOPT_LAUNCH_CHECK();
+    hipLaunchKernelGGL(igso3_cdf_kernel, dim3((unsigned)rows), dim3(256), 0, (hipStream_t)stream, Y, bins, cdf);
     ABOPT_LAUNCH_CHECK();
     return ABOPT_OK;
 }

@@ -76,7 +76,7 @@ __device__ __forceinline__ void denoise_row(int64_t i, const abopt_step_params& 
         const float gau = fmodf(fabsf(sp.igso3_std * 2.f + gss * sp.igso3_std), PI_F);
         const float th = sp.igso3_gaussian ? gau : hist;
         float ex = ax / nrm * th, ey = ay / nrm * th, ez = az / nrm * th;
-        if (!(sp.t > 1)) { ex = 0.f; ey = 0.f; ez = 0.f; }
+        if (!(sp.t_prev > 0)) { ex = 0.f; ey = 0.f; ez = 0.f; }       // no noise on the step that lands on 0 (the reference's t > 1: t_prev = t - 1 there)
         const Mat3 E = so3_exp(ex, ey, ez);
         const Mat3 Rn = matmul3(E, so3_exp(v_net[i * 3], v_net[i * 3 + 1], v_net[i * 3 + 2]));
         const Vec3 w = so3_log(Rn, false);
@@ -95,7 +95,7 @@ __device__ __forceinline__ void denoise_row(int64_t i, const abopt_step_params& 
             const float pnet = p_net[i * 3 + k];
             float eps = pnet;
             if (sp.pred_x0) eps = gen ? (sp.sqrt_recip_abar * pt[k] - pnet) / sp.sqrt_recipm1_abar : pt[k];
-            const float zk = (sp.t > 1) ? zn[k] : 0.f;
+            const float zk = (sp.t_prev > 0) ? zn[k] : 0.f;
             const float nx = c0 * (pt[k] - c1 * eps) + sp.sigma * zk;
             pn[k] = gen ? nx : pt[k];
         }

@@ -13,7 +13,9 @@ deliberate and MI355X-first:
     16-byte device buffer at execution time, inputs are copied into the graph's static buffers before a replay.
 """
 import collections
+import ctypes
 import dataclasses
+import math
 import weakref
 import os
 import torch
@@ -35,6 +37,37 @@ class _LoopSpec:
     optimize_mode: bool = False                 # the net's third output is the position update's noise whatever `obj` is
     use_bias_cache: bool | None = None          # None: FullDPM._denoise decides by free memory, once
     constrained: bool = False                   # the loop's inputs end with aa_allowed, the allowed residue types per residue (the contents are data, not key)
+    timesteps: tuple | int = 0                  # the steps the loop visits: 0 every step t_start .. 1; K > 0 the K evenly respaced ones, respaced_steps(t_start, K);
+                                                # a tuple: these (t_start first, strictly decreasing, >= 1)
+
+
+def respaced_steps(t_start, steps=None, timesteps=None):
+    """The steps a loop from t_start down to 0 visits (0, where it lands, is implied), as a strictly decreasing tuple that starts at t_start.
+    steps = K, 1 <= K <= t_start: the K steps tau_K .. tau_1 of the evenly respaced sub-sequence tau_i = (i t_start + K // 2) // K (tau_0 = 0, tau_K = t_start; the
+    strided sampling of improved DDPM).  timesteps: the list itself, checked.  Neither: every step, t_start .. 1.  Both: an error."""
+    T = int(t_start)
+    if steps is not None and timesteps is not None:
+        raise ValueError('give steps= or timesteps=, not both')
+    if timesteps is not None:
+        ts = tuple(int(t) for t in timesteps)
+        if not ts or ts[0] != T or ts[-1] < 1 or any(a <= b for a, b in zip(ts, ts[1:])):
+            raise ValueError(f'timesteps must start at step {T}, decrease strictly and end at 1 or above (0 is implied), got {ts[:4]}{"..." if len(ts) > 4 else ""}')
+        return ts
+    if steps is None:
+        return tuple(range(T, 0, -1))
+    K = int(steps)
+    if not 1 <= K <= T:
+        raise ValueError(f'steps must be between 1 and {T}, got {steps}')
+    return tuple((i * T + K // 2) // K for i in range(K, 0, -1))
+
+
+def _spec_timesteps(t_start, steps, timesteps):
+    """_LoopSpec.timesteps of sample(steps=, timesteps=) / optimize(...), in its one spelling: 0 where every step is visited, so that such a call IS the plain loop
+    (same graph key too), K for the evenly respaced K steps however they were asked for, the tuple for any other list."""
+    ts = respaced_steps(t_start, steps, timesteps)
+    if len(ts) == int(t_start):
+        return 0
+    return len(ts) if ts == respaced_steps(t_start, len(ts)) else ts
 
 
 def _graph_key(spec, inputs, token):
@@ -142,14 +175,31 @@ class FullDPM(_Derived, nn.Module):
                 mean=g(self.position_mean.flatten())))
         return self._host_sched[1]
 
-    def _step_params(self, t, sample_structure, sample_sequence, ppl_masked, optimize_mode=False):
+    def _stride(self, t, t_prev):
+        """(alpha', sigma) of the stride t -> t_prev of a respaced loop, in float64 from the fp32 alpha_bars buffer:
+        alpha' = abar_t / abar_u, sigma = sqrt((1 - abar_u) / (1 - abar_t) (1 - alpha')): the DDPM posterior of x_u given x_t and x_0."""
+        ab = self._sched_host()['alpha_bars']
+        a = ab[t] / ab[t_prev]
+        return a, math.sqrt((1.0 - ab[t_prev]) / (1.0 - ab[t]) * (1.0 - a))
+
+    def _step_params(self, t, sample_structure, sample_sequence, ppl_masked, optimize_mode=False, t_prev=None):
+        """The scalars of the step t -> t_prev (None: t - 1).  A unit stride reads every one of them from the buffers, as the reference does; a longer one
+        computes alpha', sigma and the IGSO(3) width of the stride (_stride) and rounds them once to fp32 -- alpha_bar and the two pred_x0 factors stay those of t."""
         h = self._sched_host()
+        u = t - 1 if t_prev is None else int(t_prev)
         sp = hip.StepParams()
-        sp.t = t
-        sp.alpha_clamped = max(h['alphas'][t], h['alphas'][-2])
-        sp.alpha_bar, sp.sigma = h['alpha_bars'][t], h['sigmas'][t]
+        sp.t, sp.t_prev = t, u
+        sp.alpha_bar = h['alpha_bars'][t]
         sp.sqrt_recip_abar, sp.sqrt_recipm1_abar = h['sr'][t], h['srm1'][t]
-        sp.igso3_std, sp.igso3_gaussian = h['std'][t], int(h['approx'][t])
+        if u == t - 1:
+            sp.alpha_clamped = max(h['alphas'][t], h['alphas'][-2])
+            sp.sigma = h['sigmas'][t]
+            sp.igso3_std, sp.igso3_gaussian = h['std'][t], int(h['approx'][t])
+        else:
+            a, sig = self._stride(t, u)
+            sp.alpha_clamped = max(a, h['alphas'][-2])
+            sp.sigma = sp.igso3_std = sig
+            sp.igso3_gaussian = int(sp.igso3_std <= ctypes.c_float(self.trans_rot.angular_distrib_inv.std_threshold).value)      # fp32 <= fp32, as approx_flag is built
         sp.position_scale = h['scale']
         for k in range(3):
             sp.position_mean[k] = h['mean'][k]
@@ -158,6 +208,17 @@ class FullDPM(_Derived, nn.Module):
         sp.dist_min, sp.dist_max = float(self.dist_min), float(self.dist_max)
         sp.ppl_masked = int(ppl_masked)
         return sp
+
+    @staticmethod
+    def _loop_steps(spec):
+        """[(t, t_prev), ...] of the loop, in the order it runs them: t_start first, 0 last."""
+        ts = respaced_steps(spec.t_start, spec.timesteps or None) if isinstance(spec.timesteps, int) else respaced_steps(spec.t_start, timesteps=spec.timesteps)
+        return list(zip(ts, ts[1:] + (0,)))
+
+    def _loop_tables(self, pairs):
+        """(X rows, cdf rows) of the inverse IGSO(3) histograms, one per step of _loop_steps: the trained rows for unit strides, device-built ones for the sigmas of
+        longer strides (RotationTransition.inverse_tables, cached per loop).  Whoever captures the loop keeps the result: the graph's nodes point into it."""
+        return self.trans_rot.inverse_tables([t if u == t - 1 else ctypes.c_float(self._stride(t, u)[1]).value for t, u in pairs])
 
     @staticmethod
     def _new_seed():
@@ -256,6 +317,8 @@ class FullDPM(_Derived, nn.Module):
         dev = res_feat.device
         N, L = mask_res.shape
         T0, Nc, use_bias_cache = spec.t_start, pair_feat.shape[0], spec.use_bias_cache
+        pairs = self._loop_steps(spec)
+        K = len(pairs)                                  # slot i of the trajectory buffers holds the state at tau_i: slot K the start, slot 0 the end (slot t in the full loop)
         group = N // Nc
         shared = group > 1
         if shared and not use_bias_cache:
@@ -263,56 +326,61 @@ class FullDPM(_Derived, nn.Module):
         if res_feat.shape[0] != N:
             res_feat = res_feat.repeat_interleave(group, dim=0)
         f32 = dict(dtype=torch.float32, device=dev)
-        tv = torch.empty(T0 + 1, N, L, 3, **f32)
-        tp = torch.empty(T0 + 1, N, L, 3, **f32)
-        ts = torch.empty(T0 + 1, N, L, dtype=torch.int64, device=dev)
-        tv[T0], tp[T0], ts[T0] = state
-        tpr = torch.zeros(T0 + 1, N, **f32) if self.abdock else None
-        tpp = torch.zeros(T0 + 1, N, **f32) if self.abdock else None
+        tv = torch.empty(K + 1, N, L, 3, **f32)
+        tp = torch.empty(K + 1, N, L, 3, **f32)
+        ts = torch.empty(K + 1, N, L, dtype=torch.int64, device=dev)
+        tv[K], tp[K], ts[K] = state
+        tpr = torch.zeros(K + 1, N, **f32) if self.abdock else None
+        tpp = torch.zeros(K + 1, N, **f32) if self.abdock else None
         ew = self.eps_net.packed_fp32() if range_safe else self.eps_net.packed()
         # pair_feat and the weights are constant over the loop: project the pair bias of all blocks once (dpm_full.py:274-283 feeds
         # the same pair_feat to every step); ~0.4 ms at N=32, L=256, outside nothing -- it is part of this call
         pbc = hip.pair_bias_cache(self.eps_net.encoder.packed_array(), len(self.eps_net.encoder.blocks), pair_feat) if use_bias_cache else None
         # ... and, where the 32-row block kernels will run, re-lay pair_feat once as the fp16 operands of their pair aggregation (hip.pair_terms; ~0.25 ms)
         pterms = hip.pair_terms(pair_feat) if (use_bias_cache and self._pair_terms_wanted(N, L, Nc, dev)) else None
-        inv = self.trans_rot.angular_distrib_inv
-        X, cdf = inv.X, (inv.cdf() if noise is None else None)
+        X, cdf = self._loop_tables(pairs)
         beta_rows = self.trans_pos.var_sched.betas[:T0 + 1, None].expand(T0 + 1, N).contiguous()    # beta_t per sample, one row per step
         net = dict(v_next=torch.empty(N, L, 3, **f32), R_next=torch.empty(N, L, 3, 3, **f32), eps_pos=torch.empty(N, L, 3, **f32),
                    c=torch.empty(N, L, 20, **f32), prmsd_logits=torch.empty(N, self.num_bins, **f32) if self.abdock else None)
         p_norm = torch.empty(N, L, 3, **f32)
-        it = range(T0, 0, -1)
+        it = enumerate(pairs)
         if pbar:
             from tqdm.auto import tqdm
-            it = tqdm(it, total=T0, desc='Sampling')
+            it = tqdm(it, total=K, desc='Sampling')
         # dpm_full.py:276: p_t = normalize(traj[t].p) -- here for the first step, afterwards written by the step kernel itself
-        torch.sub(tp[T0], self.position_mean, out=p_norm).div_(self.position_scale)
-        for t in it:
-            if spec.stop_after is not None and T0 - t >= spec.stop_after:
+        torch.sub(tp[K], self.position_mean, out=p_norm).div_(self.position_scale)
+        evals = 0
+        for j, (t, t_prev) in it:
+            if spec.stop_after is not None and j >= spec.stop_after:
                 break
-            hip.eps_net_forward(ew, tv[t], p_norm, ts[t], res_feat, pair_feat, beta_rows[t], mask_generate, mask_res,
+            i = K - j                                   # the slot of step t; the step writes slot i - 1, that of t_prev
+            # the network is conditioned on the trained beta_t whatever the stride
+            hip.eps_net_forward(ew, tv[i], p_norm, ts[i], res_feat, pair_feat, beta_rows[t], mask_generate, mask_res,
                                 self.abdock, self.num_bins, False, out=net, pair_bias_cache=pbc, pair_feat_shared=(group if shared else 0), pair_terms=pterms)
-            out = dict(v=tv[t - 1], p=tp[t - 1], s=ts[t - 1], p_norm=p_norm)
+            out = dict(v=tv[i - 1], p=tp[i - 1], s=ts[i - 1], p_norm=p_norm)
             if self.abdock:
-                out.update(prmsd=tpr[t - 1], ppl=tpp[t - 1])
-            hip.denoise_step(self._step_params(t, spec.sample_structure, spec.sample_sequence, spec.ppl_masked, spec.optimize_mode),
-                             noise[t] if noise is not None else None, seed, rng_offset, tv[t], tp[t], ts[t], net['v_next'], net['eps_pos'], net['c'],
-                             net['prmsd_logits'], mask_generate, X[t], cdf[t] if cdf is not None else None, self.num_bins, out, seed_dev=seed_dev,
+                out.update(prmsd=tpr[i - 1], ppl=tpp[i - 1])
+            hip.denoise_step(self._step_params(t, spec.sample_structure, spec.sample_sequence, spec.ppl_masked, spec.optimize_mode, t_prev),
+                             noise[t] if noise is not None else None, seed, rng_offset, tv[i], tp[i], ts[i], net['v_next'], net['eps_pos'], net['c'],
+                             net['prmsd_logits'], mask_generate, X[j], cdf[j] if noise is None else None, self.num_bins, out, seed_dev=seed_dev,
                              aa_allowed=aa_allowed)
-        self.last_run_info = dict(bias_cache=use_bias_cache, pair_terms=pterms is not None, shared_context=shared, graph=seed_dev is not None)
+            evals += 1
+        self.last_run_info = dict(bias_cache=use_bias_cache, pair_terms=pterms is not None, shared_context=shared, graph=seed_dev is not None, steps=evals)
         return tv, tp, ts, tpr, tpp
 
-    def _to_traj(self, T0, tv, tp, ts, tpr, tpp):
-        """Reference layout: dict t -> [v, p, s(, prmsd, ppl)], t>0 on the host, t=0 on the device."""
+    def _to_traj(self, T0, tv, tp, ts, tpr, tpp, timesteps=0):
+        """Reference layout: dict t -> [v, p, s(, prmsd, ppl)], t>0 on the host, t=0 on the device.  timesteps (a respaced loop's, _LoopSpec.timesteps): the buffers
+        hold the visited steps only, slot i the i-th of them from the end, and the dict has those keys."""
         hv, hp, hs = tv[1:].cpu(), tp[1:].cpu(), ts[1:].cpu()       # one bulk D2H each
         traj = {}
         if self.abdock:
             hpr, hpp = tpr.cpu(), tpp.cpu()
-        for t in range(T0, 0, -1):
-            e = [hv[t - 1], hp[t - 1], hs[t - 1]]
+        keys = (0,) + tuple(t for t, _ in reversed(self._loop_steps(_LoopSpec(T0, timesteps=timesteps))))        # slot -> step
+        for i in range(len(keys) - 1, 0, -1):
+            e = [hv[i - 1], hp[i - 1], hs[i - 1]]
             if self.abdock:         # dpm_full.py:269: the first entry carries zeros_like(s) / ones_like(s) in the two extra slots
-                e += [torch.zeros_like(e[2]), torch.ones_like(e[2])] if t == T0 else [hpr[t], hpp[t]]
-            traj[t] = e if self.abdock else tuple(e)
+                e += [torch.zeros_like(e[2]), torch.ones_like(e[2])] if i == len(keys) - 1 else [hpr[i], hpp[i]]
+            traj[keys[i]] = e if self.abdock else tuple(e)
         e0 = [tv[0].clone(), tp[0].clone(), ts[0].clone()]       # own storage: the buffers may be a captured graph's static ones
         if self.abdock:
             e0 += [hpr[0], hpp[0]]
@@ -321,25 +389,30 @@ class FullDPM(_Derived, nn.Module):
 
     @torch.no_grad()
     def sample(self, v, p, s, res_feat, pair_feat, mask_generate, mask_res, sample_structure=True, sample_sequence=True,
-               pbar=False, noise=None, seed=None, rng_offset=0, use_bias_cache=None, graph=None, aa_allowed=None, **kwargs):
+               pbar=False, noise=None, seed=None, rng_offset=0, use_bias_cache=None, graph=None, aa_allowed=None, steps=None, timesteps=None, **kwargs):
         """dpm_full.py:236-302.  `noise` (optional) = {'init': {q4,p,s}, t: {axis,bin,ubin,gauss,z,s_next}} replays
         recorded draws; otherwise a Philox stream seeded from torch's CPU generator is used.
         aa_allowed (optional; no reference counterpart): the residue types that may appear at each generated residue, (N, L) / (1, L) / (L,) int32 or int64 words with
-        bit k = type k (model.aa_allowed_mask builds them).  The initial state and every step draw from the allowed types only, so a forbidden type never enters s_t."""
+        bit k = type k (model.aa_allowed_mask builds them).  The initial state and every step draw from the allowed types only, so a forbidden type never enters s_t.
+        steps = K / timesteps = [...] (optional; no reference counterpart): denoise over a sub-sequence of the trained steps (respaced_steps) --
+        K network evaluations instead of num_steps; the trajectory holds the visited steps (and 0) only, and `noise` needs entries for those alone."""
         allowed = _checked_allowed(aa_allowed, mask_generate)
+        visited = _spec_timesteps(self.num_steps, steps, timesteps)
         seed, h = self._begin(seed)
         state = hip.sample_init(v.float(), p.float(), s, mask_generate, noise['init'] if noise is not None else None, seed, rng_offset,
                                 h['scale'], h['mean'], sample_structure, sample_sequence, aa_allowed=allowed)
         spec = _LoopSpec(self.num_steps, None, bool(sample_structure), bool(sample_sequence), ppl_masked=True, use_bias_cache=use_bias_cache,
-                         constrained=allowed is not None)
+                         constrained=allowed is not None, timesteps=visited)
         inputs = self._inputs(res_feat, pair_feat, mask_generate, mask_res, allowed)
-        return self._to_traj(spec.t_start, *_range_guarded(lambda safe: self._denoise(spec, state, inputs, noise, seed, rng_offset, pbar, graph, safe)))
+        return self._to_traj(spec.t_start, *_range_guarded(lambda safe: self._denoise(spec, state, inputs, noise, seed, rng_offset, pbar, graph, safe)), timesteps=visited)
 
     @torch.no_grad()
     def optimize(self, v, p, s, opt_step, res_feat, pair_feat, mask_generate, mask_res, sample_structure=True,
-                 sample_sequence=True, pbar=False, noise=None, seed=None, rng_offset=0, use_bias_cache=None, graph=None, aa_allowed=None):
-        """dpm_full.py:304-367: noise the input to step `opt_step`, then denoise.  aa_allowed: as in sample(); the forward noising draws from the allowed types too."""
+                 sample_sequence=True, pbar=False, noise=None, seed=None, rng_offset=0, use_bias_cache=None, graph=None, aa_allowed=None, steps=None, timesteps=None):
+        """dpm_full.py:304-367: noise the input to step `opt_step`, then denoise.  aa_allowed: as in sample(); the forward noising draws from the allowed types too.
+        steps = K / timesteps: as in sample(), over [0, opt_step] (K <= opt_step)."""
         allowed = _checked_allowed(aa_allowed, mask_generate)
+        visited = _spec_timesteps(opt_step, steps, timesteps)
         seed, h = self._begin(seed)
         N = v.shape[0]
         t = torch.full([N], opt_step, dtype=torch.long, device=res_feat.device)
@@ -352,10 +425,10 @@ class FullDPM(_Derived, nn.Module):
         # dpm_full.py:351-358: the loop feeds the net's third output to the position update as noise whatever `obj` is,
         # and averages the perplexity over all residues (calc_perplexity(logits) without a mask)
         spec = _LoopSpec(opt_step, None, bool(sample_structure), bool(sample_sequence), ppl_masked=False, optimize_mode=True, use_bias_cache=use_bias_cache,
-                         constrained=allowed is not None)
+                         constrained=allowed is not None, timesteps=visited)
         inputs = self._inputs(res_feat, pair_feat, mask_generate, mask_res, allowed)
         # same counters as add_noise, other sub-sequence tags (csrc/denoise.hip): a sample's stream position does not depend on the batch it sits in
-        traj = self._to_traj(opt_step, *_range_guarded(lambda safe: self._denoise(spec, state, inputs, noise, seed, rng_offset, pbar, graph, safe)))
+        traj = self._to_traj(opt_step, *_range_guarded(lambda safe: self._denoise(spec, state, inputs, noise, seed, rng_offset, pbar, graph, safe)), timesteps=visited)
         return {k: tuple(e) for k, e in traj.items()}
 
 
@@ -373,6 +446,7 @@ class _LoopGraph:
         self.res_feat, self.pair_feat, self.mask_generate, self.mask_res = static[:4]
         self.aa_allowed = static[4] if spec.constrained else None      # a constrained loop's mask is an input like mask_generate: refreshed before each replay
         self.seed_dev = torch.zeros(2, dtype=torch.int64, device=self.res_feat.device)
+        self.tables = dpm._loop_tables(dpm._loop_steps(spec))          # the IGSO(3) rows the captured steps read: the cache that built them may drop them, this graph may not
         run = lambda stop_after: dpm._run_eager(dataclasses.replace(spec, stop_after=stop_after), self.state, static, None, 0, 0, False, seed_dev=self.seed_dev)
         hip.prof_enable(False)
         run(1)                                                          # warm: kernel attributes, host-side caches, cdf tables

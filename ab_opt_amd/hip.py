@@ -13,7 +13,7 @@ import torch
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # ABOPT_LIB_PATH: developer override to load a variant build of the same ABI (csrc/Makefile VARIANT=...: A/B of two source trees)
 LIB_PATH = os.environ.get('ABOPT_LIB_PATH') or os.path.join(_HERE, 'libabopt_hip.so')
-ABI_VERSION = 44
+ABI_VERSION = 45
 
 c_f = C.c_void_p        # device float*
 c_i64 = C.c_void_p      # device int64*
@@ -65,7 +65,7 @@ class StepParams(C.Structure):
                 ('sqrt_recip_abar', C.c_float), ('sqrt_recipm1_abar', C.c_float), ('igso3_std', C.c_float),
                 ('igso3_gaussian', C.c_int), ('position_scale', C.c_float), ('position_mean', C.c_float * 3),
                 ('pred_x0', C.c_int), ('sample_structure', C.c_int), ('sample_sequence', C.c_int),
-                ('dist_min', C.c_float), ('dist_max', C.c_float), ('ppl_masked', C.c_int)]
+                ('dist_min', C.c_float), ('dist_max', C.c_float), ('ppl_masked', C.c_int), ('t_prev', C.c_int)]
 
 
 class AddNoiseNoise(C.Structure):
@@ -116,6 +116,7 @@ _SIGNATURES = {
                               [c_f, c_int, c_f, c_void_p, c_size_t, c_stream]),
     'abopt_denoise_step': (c_int, [POINTER(StepParams), POINTER(StepNoise), c_uint64, c_uint64, c_f, c_f, c_i64] + [c_f] * 4 + [c_u8, c_f, c_f, c_int, c_int] +
                            [c_f, c_f, c_i64] + [c_f] * 4 + [c_void_p, c_i32, c_int, c_int, c_stream]),
+    'abopt_igso3_tables': (c_int, [c_f, c_int, c_int, c_int, c_f, c_f, c_f, c_stream]),
     'abopt_sample_init': (c_int, [c_f, c_f, c_i64, c_u8, c_f, c_f, c_i64, c_uint64, c_uint64, c_float, c_void_p, c_int, c_int, c_f, c_f, c_i64, c_i32, c_int, c_int, c_stream]),
     'abopt_add_noise': (c_int, [c_i64, c_f, c_f, c_u8, c_f, c_f, c_int, c_int, POINTER(AddNoiseNoise), c_uint64, c_uint64, c_f, c_f, c_i64, c_u8, c_float, c_void_p, c_int, c_int, c_int,
                         c_f, c_f, c_i64, c_f, c_f, c_void_p, c_i32, c_int, c_int, c_stream]),
@@ -529,6 +530,17 @@ def denoise_step(sp, noise, seed, offset, v_t, p_t, s_t, v_net, p_net, c_net, pr
                                     ptr(out.get('ppl'), optional=True), ptr(post, optional=True), ptr(out.get('p_norm'), optional=True),
                                     ptr(seed_dev, torch.int64, optional=True), _allowed_ptr(aa_allowed, mask_generate), N, L, stream()))
     return post
+
+
+def igso3_tables(stddevs, bins=8192, iters=1024):
+    """stddevs: fp32 device tensor (rows,) -> (X (rows, bins), Y (rows, bins), cdf (rows, bins - 1)): the IGSO(3) angle histograms of ApproxAngularDistribution for
+    arbitrary standard deviations, built on the device (abopt_igso3_tables: factors and the sum over l in fp64)."""
+    stddevs = stddevs.contiguous()
+    rows = stddevs.numel()
+    f32 = dict(dtype=torch.float32, device=stddevs.device)
+    X, Y, cdf = torch.empty(rows, bins, **f32), torch.empty(rows, bins, **f32), torch.empty(rows, bins - 1, **f32)
+    _check(lib().abopt_igso3_tables(ptr(stddevs, torch.float32), rows, int(bins), int(iters), ptr(X), ptr(Y), ptr(cdf), stream()))
+    return X, Y, cdf
 
 
 def sample_init(v, p, s, mask_generate, init_noise, seed, offset, scale, mean, sample_structure, sample_sequence, aa_allowed=None):

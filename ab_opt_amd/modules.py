@@ -9,6 +9,7 @@ forward on the hot path is a call into libabopt_hip.so.  Reference files mirrore
   D/modules/common/so3.py:71-138      ApproxAngularDistribution D/modules/diffusion/transition.py  schedules / transitions
   D/modules/diffusion/dpm_full.py     EpsilonNet, FullDPM
 """
+import collections
 import math
 import ctypes as C
 import numpy as np
@@ -409,6 +410,9 @@ class PositionTransition(nn.Module):
         self.var_sched = VarianceSchedule(num_steps, **var_sched_opt)
 
 
+_IGSO3_DEVICE_ROWS = collections.OrderedDict()     # (sigmas, bins, iters, device) -> (X, cdf) built by hip.igso3_tables: the eight most recent (a row pair is 64 KB)
+
+
 class RotationTransition(nn.Module):
     def __init__(self, num_steps, var_sched_opt={}, angular_distrib_fwd_opt={}, angular_distrib_inv_opt={}):
         super().__init__()
@@ -417,6 +421,31 @@ class RotationTransition(nn.Module):
         self.angular_distrib_fwd = ApproxAngularDistribution(c1.tolist(), **angular_distrib_fwd_opt)
         self.angular_distrib_inv = ApproxAngularDistribution(self.var_sched.sigmas.tolist(), **angular_distrib_inv_opt)
         self.register_buffer('_dummy', torch.empty([0, ]))
+
+    def inverse_tables(self, sigmas):
+        """sigmas: one entry per step of a respaced loop (FullDPM._loop_tables) -- an int t for the step t -> t - 1, whose rows are the trained ones, or the fp32 standard
+        deviation of a longer stride (a float).  -> (X, cdf): lists of table rows in that order, as abopt_denoise_step reads them.  The trained steps reuse rows
+        X[t], cdf()[t] of angular_distrib_inv as they are; the others are built on the device in ONE launch (hip.igso3_tables) and cached per tuple of sigmas, so a
+        repeated call builds nothing and reads the same memory."""
+        inv = self.angular_distrib_inv
+        new = tuple(s for s in sigmas if not isinstance(s, int))
+        Xn = cn = None
+        if new:
+            key = (new, inv.num_bins, inv.num_iters, inv.X.device)
+            if key not in _IGSO3_DEVICE_ROWS:
+                while len(_IGSO3_DEVICE_ROWS) >= 8:
+                    _IGSO3_DEVICE_ROWS.popitem(last=False)
+                Xn, _, cn = hip.igso3_tables(torch.tensor(new, dtype=torch.float32).to(inv.X.device), inv.num_bins, inv.num_iters)
+                _IGSO3_DEVICE_ROWS[key] = (Xn, cn)
+            _IGSO3_DEVICE_ROWS.move_to_end(key)
+            Xn, cn = _IGSO3_DEVICE_ROWS[key]
+        cdf, fresh = inv.cdf(), iter(range(len(new)))
+        X, rows = [], []
+        for s in sigmas:
+            i = s if isinstance(s, int) else next(fresh)
+            X.append(inv.X[i] if isinstance(s, int) else Xn[i])
+            rows.append(cdf[i] if isinstance(s, int) else cn[i])
+        return X, rows
 
 
 class AminoacidCategoricalTransition(nn.Module):

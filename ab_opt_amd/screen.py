@@ -85,7 +85,8 @@ def _rebuild(pos, mask, traj0, lo, hi, aa, flag, one):
 
 @torch.no_grad()
 def optimize_antibody(dock_model, design_model, complex_, num_poses, designs_per_pose, redocks_per_design, design_flag=None, redock_flag=None,
-                      contig='', screened_per_pose=1, seed=0, poses_per_launch=8, group=None, screen_by='first', timings=None, allowed_aa=None):
+                      contig='', screened_per_pose=1, seed=0, poses_per_launch=8, group=None, screen_by='first', timings=None, allowed_aa=None,
+                      dock_steps=None, design_steps=None):
     """Dock -> redesign -> re-dock screen of one antibody-antigen complex (module docstring).
 
     complex_: batch dict with batch dim 1 (cropped, as sample_replicated takes it); its generate_flag marks the residues to dock.
@@ -96,6 +97,9 @@ def optimize_antibody(dock_model, design_model, complex_, num_poses, designs_per
     allowed_aa (optional, (L,) or (1, L) int32 / int64; default: complex_['aa_allowed'] if it has one): the residue types each redesigned residue may take, bit k of a
     word = type k (model.aa_allowed_mask).  It constrains the redesign stage alone -- the docking stages draw no types -- inside the sampler, so no design is thrown away:
     seqs, the re-docked designs and everything downstream hold allowed types only; aar still counts recovery of the input sequence.
+    dock_steps / design_steps (optional; default: every trained step): the network evaluations of every dock and re-dock trajectory / of every design trajectory,
+    over the evenly respaced sub-sequence of the model's steps (FullDPM.sample(steps=K)) -- the screen spends P + P S + P k D trajectories per
+    antibody, and this trades their depth for breadth.  Sample quality against K is unmeasured.
     timings (optional dict): receives the seconds each stage took on this rank (device-synchronised) and of the final gather.
 
     -> dict of device tensors in global pose order (P poses, S designs, k screened, D re-docks; n_* = residues in the mask):
@@ -129,7 +133,9 @@ def optimize_antibody(dock_model, design_model, complex_, num_poses, designs_per
     plan = launch_plan(P, poses_per_launch, world, rank)
     a, b = sampler.shard_range(P, world, rank)
     mine = b - a
-    rngs = lambda stage, lo: dict(seed=stage_seed(seed, stage), rng_offset=stage_rng_offset(stage, lo, L, S, k, D))
+    depth = dict(dock=dock_steps, design=design_steps, redock=dock_steps)
+    rngs = lambda stage, lo: dict(seed=stage_seed(seed, stage), rng_offset=stage_rng_offset(stage, lo, L, S, k, D),
+                                  **({} if depth[stage] is None else dict(steps=int(depth[stage]))))
     aa = one['aa'][0]
     f32 = dict(dtype=torch.float32, device=dev)
     clock = {}

@@ -23,7 +23,7 @@
 extern "C" {
 #endif
 
-#define ABOPT_ABI_VERSION 44
+#define ABOPT_ABI_VERSION 45
 
 enum { ABOPT_OK = 0, ABOPT_EINVAL = 1, ABOPT_EHIP = 2, ABOPT_EUNSUPPORTED = 3, ABOPT_EWORKSPACE = 4 };
 
@@ -226,9 +226,10 @@ int abopt_eps_net_forward(const abopt_eps_weights* w, const float* v_t, const fl
 /* ---- Per-step transitions: D/modules/diffusion/transition.py:42-50,80-101 (position), :146-160
  * (rotation), :202-245 (amino acid), D/modules/common/so3.py:111-146 (IGSO(3) draw),
  * dpm_full.py:284-300 (loop body after eps_net), :380-399 (perplexity), prmsd.py:31-47.
- * Schedule scalars of step t (host reads them from the var_sched buffers): */
+ * Schedule scalars of the step t -> t_prev.  For t_prev = t - 1 the host reads them from the var_sched buffers; for a longer stride of a respaced loop
+ * (ABI 45) alpha_clamped, sigma, igso3_std and igso3_gaussian are those of the stride, the rest stay those of t: */
 typedef struct {
-    int   t;                 /* current step, T..1 */
+    int   t;                 /* current step, T..1: the Philox tag of the step's draws */
     float alpha_clamped;     /* max(alphas[t], alphas[T-1])          transition.py:84-86 */
     float alpha_bar;         /* alpha_bars[t] */
     float sigma;             /* sigmas[t] */
@@ -243,6 +244,7 @@ typedef struct {
     int   sample_sequence;   /* dpm_full.py:296-297 */
     float dist_min, dist_max;/* prmsd bounds (prmsd.py:41) */
     int   ppl_masked;        /* 1: perplexity averaged over generated residues (sample, dpm_full.py:293); 0: over all L (optimize, :358) */
+    int   t_prev;            /* the step this one lands on, t - 1 in the full loop: no noise is added when it is 0 (the reference's t > 1, transition.py:94-98,155) */
 } abopt_step_params;
 
 /* Explicit draws for teacher-forced replay, reference draw order; all NULL => the
@@ -291,6 +293,15 @@ int abopt_denoise_step(const abopt_step_params* sp, const abopt_step_noise* nois
                                                           with a fresh stream position (the values are read at execution time) */,
                        const int32_t* aa_allowed /* optional [N,L]: allowed residue types, see above */,
                        int N, int L, abopt_stream stream);
+
+/* ---- IGSO(3) angle histograms for arbitrary standard deviations (ABI 45): the tables ApproxAngularDistribution builds on the host at construction
+ * (D/modules/common/so3.py:82-109), for the strides of a respaced loop, whose sigmas are chosen per call.  Row r, bin b at x_b = linspace(0, pi, bins)[b]:
+ *   Y[r,b] = max(0, nan_to_num(sum_{l < iters} c a_l b_l)),  c = (1 - cos x) / pi,  a_l = (2 l + 1) exp(-l (l + 1) std_r^2),
+ *   b_l = (sin((l + 1/2) x) + 1e-6) / (sin(x / 2) + 1e-6)
+ * with every factor evaluated in fp32 as the host builder does and the products summed over l in fp64 (one rounding to fp32 at the end);
+ * cdf[r,:] = cumsum(Y[r,:bins-1]) / sum(Y[r,:bins-1]) in fp64, rounded to fp32 (an all-zero row is divided by 1): what multinomial(Y[:, :-1]) samples.
+ * stddevs [rows] (device), X [rows,bins] (every row linspace(0, pi, bins); may be NULL), Y [rows,bins], cdf [rows,bins-1].  bins >= 2, iters >= 1. */
+int abopt_igso3_tables(const float* stddevs, int rows, int bins, int iters, float* X, float* Y, float* cdf, abopt_stream stream);
 
 /* Initial state of FullDPM.sample (dpm_full.py:255-269): q4 [N,L,4], pn [N,L,3], sr [N,L] are the
  * reference's three draws (NULL => Philox).  p in/out in Angstrom.  position_mean is a HOST pointer to 3 floats. */

@@ -1,7 +1,8 @@
 """The dock -> redesign -> re-dock screen (ab_opt_amd/screen.py) on a synthetic complex with hash-filled weights: prints the time of every
 stage and the designs the notebook's median filter keeps.
 
-    python tools/example_screen.py [--poses 16 --designs 8 --redocks 8 --screened 1 --steps 100 --per-launch 8 --contig 97-103 --exclude CM]
+    python tools/example_screen.py [--poses 16 --designs 8 --redocks 8 --screened 1 --steps 100 --per-launch 8 --contig 97-103 --exclude CM
+                                    --dock-steps 20 --design-steps 20]
 
 The weights are not a trained checkpoint, so the numbers say nothing about antibodies; the stage times are what a screen of this size costs.
 """
@@ -27,7 +28,9 @@ def main():
     ap.add_argument('--designs', type=int, default=8)
     ap.add_argument('--redocks', type=int, default=8)
     ap.add_argument('--screened', type=int, default=1)
-    ap.add_argument('--steps', type=int, default=100)
+    ap.add_argument('--steps', type=int, default=100, help='T, the steps the two models are built with')
+    ap.add_argument('--dock-steps', type=int, default=None, metavar='K', help='network evaluations per dock / re-dock trajectory (default: all T; respaced sampling)')
+    ap.add_argument('--design-steps', type=int, default=None, metavar='K', help='network evaluations per design trajectory (default: all T)')
     ap.add_argument('--per-launch', type=int, default=8)
     ap.add_argument('--contig', default='97-103')
     ap.add_argument('--seed', type=int, default=0)
@@ -43,8 +46,9 @@ def main():
     heavy = one['fragment_type'][0] == 1                                   # the re-dock labels the whole heavy chain (--label_heavy_as_cdr)
     kw = dict(num_poses=args.poses, designs_per_pose=args.designs, redocks_per_design=args.redocks, screened_per_pose=args.screened,
               contig=args.contig, seed=args.seed, poses_per_launch=args.per_launch, redock_flag=heavy,
+              dock_steps=args.dock_steps, design_steps=args.design_steps,
               allowed_aa=model.aa_allowed_mask(one['aa'].shape[1], exclude=args.exclude, device=dev) if args.exclude else None)
-    print(f'L={one["aa"].shape[1]} P={args.poses} S={args.designs} k={args.screened} D={args.redocks} T={args.steps} per_launch={args.per_launch} '
+    print(f'L={one["aa"].shape[1]} P={args.poses} S={args.designs} k={args.screened} D={args.redocks} T={args.steps} dock_steps={args.dock_steps or args.steps} design_steps={args.design_steps or args.steps} per_launch={args.per_launch} '
           f'contig={args.contig!r} device={torch.cuda.get_device_name(dev)}')
     t0 = time.perf_counter()
     screen.optimize_antibody(dock, design, one, **dict(kw, num_poses=2, designs_per_pose=2, redocks_per_design=2, screened_per_pose=1,
