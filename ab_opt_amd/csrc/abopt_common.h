@@ -112,10 +112,11 @@ __device__ __forceinline__ float relu_nan(float x) { return x < 0.f ? 0.f : x; }
 // Geometric epilogue of the three denoiser heads for ONE residue i (dpm_full.py:95-107): eps_pos = gen ? R eps_crd : 0;
 // R_next = R * U(eps_rot); v_next = gen ? log(R_next) : v_t; c = softmax(seq logits).  crd / rot / seq point at the row's head outputs
 // (global memory: heads_epilogue_kernel; LDS: the tail of heads_mlp_kernel).  seq == nullptr: training path, the softmax stays in autograd.
+// keep (optional, 26 floats): the row's v_next | eps_pos | c as well, for the transitions that follow in the same launch (heads.hip: step_tail_kernel).
 __device__ __forceinline__ void heads_epilogue_row(int64_t i, const float* __restrict__ R, const float* __restrict__ v_t, const float* crd, const float* rot,
                                                    const float* seq, const uint8_t* __restrict__ mask_generate, float* __restrict__ v_next,
                                                    float* __restrict__ R_next, float* __restrict__ eps_pos, float* __restrict__ c_den, int grad_mode,
-                                                   unsigned* __restrict__ nonfinite = nullptr) {
+                                                   unsigned* __restrict__ nonfinite = nullptr, float* keep = nullptr) {
     const bool gen = mask_generate[i] != 0;
     // Range guard (round 6): the dense layers multiply on two fp16 terms per operand, so an activation beyond 65504 becomes inf and reaches the heads'
     // outputs as inf / NaN through every path (LayerNorm, attention); a non-finite head output of ANY row raises the flag the host reads once per call
@@ -126,18 +127,20 @@ __device__ __forceinline__ void heads_epilogue_row(int64_t i, const float* __res
     for (int k = 0; k < 9; ++k) Rm.m[k] = R[i * 9 + k];
     const float cx = crd[0], cy = crd[1], cz = crd[2];
     // apply_rotation_to_vector = R p + 0 (geometry.py:116-117)
-    eps_pos[i * 3 + 0] = gen ? (Rm.m[0] * cx + Rm.m[1] * cy + Rm.m[2] * cz + 0.f) : 0.f;
-    eps_pos[i * 3 + 1] = gen ? (Rm.m[3] * cx + Rm.m[4] * cy + Rm.m[5] * cz + 0.f) : 0.f;
-    eps_pos[i * 3 + 2] = gen ? (Rm.m[6] * cx + Rm.m[7] * cy + Rm.m[8] * cz + 0.f) : 0.f;
+    const float e0 = gen ? (Rm.m[0] * cx + Rm.m[1] * cy + Rm.m[2] * cz + 0.f) : 0.f;
+    const float e1 = gen ? (Rm.m[3] * cx + Rm.m[4] * cy + Rm.m[5] * cz + 0.f) : 0.f;
+    const float e2 = gen ? (Rm.m[6] * cx + Rm.m[7] * cy + Rm.m[8] * cz + 0.f) : 0.f;
+    eps_pos[i * 3 + 0] = e0; eps_pos[i * 3 + 1] = e1; eps_pos[i * 3 + 2] = e2;
+    if (keep) { keep[3] = e0; keep[4] = e1; keep[5] = e2; }
     const Mat3 U = quat1ijk_to_rot(rot[0], rot[1], rot[2]);
     const Mat3 Rn = matmul3(Rm, U);
 #pragma unroll
     for (int k = 0; k < 9; ++k) R_next[i * 9 + k] = Rn.m[k];
     if (v_next) {
         const Vec3 w = so3_log(Rn, grad_mode != 0);
-        v_next[i * 3 + 0] = gen ? w.x : v_t[i * 3 + 0];
-        v_next[i * 3 + 1] = gen ? w.y : v_t[i * 3 + 1];
-        v_next[i * 3 + 2] = gen ? w.z : v_t[i * 3 + 2];
+        const float n0 = gen ? w.x : v_t[i * 3 + 0], n1 = gen ? w.y : v_t[i * 3 + 1], n2 = gen ? w.z : v_t[i * 3 + 2];
+        v_next[i * 3 + 0] = n0; v_next[i * 3 + 1] = n1; v_next[i * 3 + 2] = n2;
+        if (keep) { keep[0] = n0; keep[1] = n1; keep[2] = n2; }
     }
     if (!seq) return;
     float lgt[ABOPT_AA], mx = -INFINITY;
@@ -148,7 +151,7 @@ __device__ __forceinline__ void heads_epilogue_row(int64_t i, const float* __res
 #pragma unroll
     for (int k = 0; k < ABOPT_AA; ++k) { lgt[k] = expf(lgt[k] - mx); sm += lgt[k]; }
 #pragma unroll
-    for (int k = 0; k < ABOPT_AA; ++k) c_den[i * ABOPT_AA + k] = lgt[k] / sm;
+    for (int k = 0; k < ABOPT_AA; ++k) { const float c = lgt[k] / sm; c_den[i * ABOPT_AA + k] = c; if (keep) keep[6 + k] = c; }
 }
 
 // general quaternion (real first) -> R with normalisation, reference geometry.py:148-175.

@@ -75,12 +75,12 @@ static GaScratch carve_ga(Carver& cv, int64_t M, int N, int L) {
     return s;
 }
 
-// The five environment switches of the forward path, read once per C-ABI call (never cached: callers flip them between the calls of one process)
+// The six environment switches of the forward path, read once per C-ABI call (never cached: callers flip them between the calls of one process)
 static Switches read_switches() {
     const auto first = [](const char* name) { const char* e = getenv(name); return e ? e[0] : '\0'; };
     const char c32 = first("ABOPT_CORE32");
     return {c32 == '0' ? 0 : (c32 == '1' ? 1 : -1), getenv("ABOPT_CORE_NO_SPLIT") != nullptr, first("ABOPT_FUSE_TAIL") != '0', first("ABOPT_X_TERMS") != '0',
-            first("ABOPT_FUSE_HEADS") != '0'};
+            first("ABOPT_FUSE_HEADS") != '0', first("ABOPT_FUSE_STEP") != '0'};
 }
 
 // What every forward entry knows of its ForwardQuery (forward_plan.h): geometry, the CU count (asked once per entry), operands and scratch held, which blocks are
@@ -528,6 +528,11 @@ EpsScratch carve_eps(Carver& cv, int64_t M, int N, int L, int num_bins) {
     e.pr3 = cv.f((size_t)M * (size_t)(num_bins > 0 ? num_bins : 1));
     return e;
 }
+// what abopt_eps_net_step adds to a forward: the arguments of abopt_denoise_step that the forward does not have already, and the carry
+struct StepCall {
+    const abopt_step_params* sp; const abopt_step_noise* noise; uint64_t seed, offset; const float* p_angstrom; const float *igX, *igCdf; int bins, num_bins;
+    float *v_next, *p_next; int64_t* s_next; float *prmsd, *ppl, *post_out, *p_next_norm; const uint64_t* seed_dev; const int32_t* aa_allowed; int carry_in, carry_out;
+};
 }  // namespace
 
 extern "C" size_t abopt_eps_workspace_bytes(int N, int L, int Fd, int Cd) {
@@ -537,12 +542,13 @@ extern "C" size_t abopt_eps_workspace_bytes(int N, int L, int Fd, int Cd) {
     return cv.off;
 }
 
-extern "C" int abopt_eps_net_forward(const abopt_eps_weights* w, const float* v_t, const float* p_t, const int64_t* s_t,
-                                     const float* res_feat, const float* pair_feat, const float* beta,
-                                     const uint8_t* mask_generate, const uint8_t* mask_res,
-                                     float* v_next, float* R_next, float* eps_pos, float* c_denoised, float* prmsd_logits,
-                                     int N, int L, int Fd, int Cd, int grad_mode, const float* pair_bias_cache, int pair_feat_shared,
-                                     const float* pair_terms, void* ws, size_t ws_bytes, abopt_stream stream) {
+// EpsilonNet.forward and, sc given (abopt_eps_net_step), the step's transitions behind it -- as the plan says: the heads' launches + denoise_step, or the fused tail
+static int eps_forward(const abopt_eps_weights* w, const float* v_t, const float* p_t, const int64_t* s_t,
+                       const float* res_feat, const float* pair_feat, const float* beta,
+                       const uint8_t* mask_generate, const uint8_t* mask_res,
+                       float* v_next, float* R_next, float* eps_pos, float* c_denoised, float* prmsd_logits,
+                       int N, int L, int Fd, int Cd, int grad_mode, const float* pair_bias_cache, int pair_feat_shared,
+                       const float* pair_terms, void* ws, size_t ws_bytes, abopt_stream stream, const StepCall* sc) {
     int rc;
     if ((rc = check_dims(N, L, Fd, Cd))) return rc;
     ABOPT_CHECK_ARG(w && w->seq_embed && w->w_mix0 && w->b_mix0 && w->w_mix1 && w->b_mix1 && w->blocks && w->w_head1 && w->b_head1 &&
@@ -570,10 +576,18 @@ extern "C" int abopt_eps_net_forward(const abopt_eps_weights* w, const float* v_
     ForwardQuery q;
     if ((rc = forward_query(N, L, zg, e.ga, w->blocks, w->num_layers, pair_bias_cache, pair_terms, &q))) return rc;
     q.mix_frag = w->w_mix_frag && w->mix_table; q.heads_frag = w->w_heads_frag != nullptr; q.prmsd = has_prmsd;
+    abopt_step_noise nz{};
+    if (sc) {
+        ABOPT_CHECK_ARG(sc->p_angstrom && sc->v_next && sc->p_next && sc->s_next, "eps_net_step: NULL argument");
+        if ((rc = check_step_args(sc->sp, sc->noise, sc->igX, sc->igCdf, sc->bins, &nz))) return rc;
+        q.step = true; q.ppl = sc->ppl != nullptr; q.carry_in = sc->carry_in != 0; q.carry_out = sc->carry_out != 0;
+    }
     const NetPlan plan = plan_network(q);
 
     // dpm_full.py:86  R = exp(v_t)   and   dpm_full.py:89  res_feat_mixer([res_feat | Embedding(s_t)])
-    if (plan.mixer_kernel) {
+    if (!plan.mixer_launch) {
+        // carried in: the fused tail of the previous step wrote x, its terms and R for exactly this state into this workspace
+    } else if (plan.mixer_kernel) {
         if ((rc = launch_mixer(res_feat, s_t, w->w_mix_frag, w->mix_table, w->b_mix1, e.cat, M, st, v_t, e.R, plan.mixer_xt >= 0 ? e.ga.xt[plan.mixer_xt] : nullptr))) return rc;       // one launch for both
     } else {
         if ((rc = launch_so3_exp(v_t, e.R, M, st))) return rc;
@@ -585,6 +599,18 @@ extern "C" int abopt_eps_net_forward(const abopt_eps_weights* w, const float* v_
     if ((rc = ga_encoder(plan.enc, q, w->blocks, BlockArgs{e.R, p_t, e.cat, pair_feat, mask_res, e.xe, pair_bias_cache, pair_terms}, e.ga, e.pong, st))) return rc;
     // dpm_full.py:92-93 time features (the heads kernel takes them as an affine term: then only the prmsd head's LayerNorm'd copy is needed)
     if (plan.build_infeat && (rc = launch_build_infeat(e.xe, beta, e.infeat, w->prmsd_ln_gamma, w->prmsd_ln_beta, plan.prmsd ? e.infeat_ln : nullptr, N, L, st))) return rc;
+    if (plan.step_fused) {
+        // the heads, their epilogue, the step's transitions and (carry) the next evaluation's mixer in one launch (heads.hip: step_tail_kernel)
+        const HeadsEpilogue hep{e.R, v_t, mask_generate, v_next, R_next, eps_pos, c_denoised, grad_mode, nonfinite_flag_ptr()};
+        StepTail tl{*sc->sp, nz, sc->seed, sc->offset, sc->seed_dev, sc->p_angstrom, s_t, sc->aa_allowed, sc->igX, sc->igCdf, sc->bins,
+                    sc->v_next, sc->p_next, sc->s_next, sc->post_out, sc->p_next_norm, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+        if (plan.step_carry) {
+            tl.res_feat = res_feat; tl.mix_wfrag = w->w_mix_frag; tl.mix_table = w->mix_table; tl.mix_b1 = w->b_mix1;
+            tl.x_out = e.cat; tl.R_out = e.R; tl.xt_out = plan.mixer_xt >= 0 ? e.ga.xt[plan.mixer_xt] : nullptr;
+        }
+        return launch_step_tail(e.xe, beta, w->w_heads_frag, w->w_head1, FI, w->b_head1, w->b_crd2, w->b_rot2, w->b_seq2, w->b_crd3, w->b_rot3, w->b_seq3, e.out3, M, L,
+                                st, hep, tl);
+    }
     if (plan.heads_kernel) {
         // dpm_full.py:92-101: time features + the three heads in one launch (heads.hip) and, unless ABOPT_FUSE_HEADS=0 (A/B, tests), their geometric epilogue as its tail
         const HeadsEpilogue hep{e.R, v_t, mask_generate, v_next, R_next, eps_pos, c_denoised, grad_mode, nonfinite_flag_ptr()};
@@ -610,5 +636,34 @@ extern "C" int abopt_eps_net_forward(const abopt_eps_weights* w, const float* v_
         if ((rc = launch_linear(e.pr2, F, w->w_prmsd3, F, w->b_prmsd3, e.pr3, w->num_bins, (int)M, w->num_bins, F, false, st))) return rc;
         if ((rc = launch_mean_over_L(e.pr3, prmsd_logits, N, L, w->num_bins, st))) return rc;
     }
-    return ABOPT_OK;
+    if (!sc) return ABOPT_OK;
+    return abopt_denoise_step(sc->sp, sc->noise, sc->seed, sc->offset, v_t, sc->p_angstrom, s_t, v_next, eps_pos, c_denoised, prmsd_logits, mask_generate, sc->igX, sc->igCdf,
+                              sc->bins, sc->num_bins, sc->v_next, sc->p_next, sc->s_next, sc->prmsd, sc->ppl, sc->post_out, sc->p_next_norm, sc->seed_dev, sc->aa_allowed,
+                              N, L, stream);
+}
+
+extern "C" int abopt_eps_net_forward(const abopt_eps_weights* w, const float* v_t, const float* p_t, const int64_t* s_t,
+                                     const float* res_feat, const float* pair_feat, const float* beta,
+                                     const uint8_t* mask_generate, const uint8_t* mask_res,
+                                     float* v_next, float* R_next, float* eps_pos, float* c_denoised, float* prmsd_logits,
+                                     int N, int L, int Fd, int Cd, int grad_mode, const float* pair_bias_cache, int pair_feat_shared,
+                                     const float* pair_terms, void* ws, size_t ws_bytes, abopt_stream stream) {
+    return eps_forward(w, v_t, p_t, s_t, res_feat, pair_feat, beta, mask_generate, mask_res, v_next, R_next, eps_pos, c_denoised, prmsd_logits, N, L, Fd, Cd, grad_mode,
+                       pair_bias_cache, pair_feat_shared, pair_terms, ws, ws_bytes, stream, nullptr);
+}
+
+extern "C" int abopt_eps_net_step(const abopt_eps_weights* w, const float* v_t, const float* p_t, const int64_t* s_t,
+                                  const float* res_feat, const float* pair_feat, const float* beta,
+                                  const uint8_t* mask_generate, const uint8_t* mask_res,
+                                  float* v_net, float* R_net, float* eps_pos, float* c_denoised, float* prmsd_logits,
+                                  int N, int L, int Fd, int Cd, const float* pair_bias_cache, int pair_feat_shared,
+                                  const float* pair_terms, void* ws, size_t ws_bytes,
+                                  const abopt_step_params* sp, const abopt_step_noise* noise, uint64_t seed, uint64_t offset, const float* p_angstrom,
+                                  const float* igso3_X, const float* igso3_cdf, int igso3_bins, int num_bins,
+                                  float* v_next, float* p_next, int64_t* s_next, float* prmsd, float* perplexity, float* post_out, float* p_next_norm,
+                                  const uint64_t* seed_offset_dev, const int32_t* aa_allowed, int carry_in, int carry_out, abopt_stream stream) {
+    const StepCall sc{sp, noise, seed, offset, p_angstrom, igso3_X, igso3_cdf, igso3_bins, num_bins, v_next, p_next, s_next, prmsd, perplexity, post_out, p_next_norm,
+                      seed_offset_dev, aa_allowed, carry_in, carry_out};
+    return eps_forward(w, v_t, p_t, s_t, res_feat, pair_feat, beta, mask_generate, mask_res, v_net, R_net, eps_pos, c_denoised, prmsd_logits, N, L, Fd, Cd, 0,
+                       pair_bias_cache, pair_feat_shared, pair_terms, ws, ws_bytes, stream, &sc);
 }

@@ -325,6 +325,21 @@ __global__ __launch_bounds__(256) void commonness_grouped_kernel(const float* __
 
 using namespace abopt;
 
+// The step's checks, shared with abopt_eps_net_step (api.hip): nz = the injected draws, or all NULL for the device stream
+int abopt::check_step_args(const abopt_step_params* sp, const abopt_step_noise* noise, const float* igso3_X, const float* igso3_cdf, int igso3_bins, abopt_step_noise* nz) {
+    ABOPT_CHECK_ARG(sp, "denoise_step: NULL argument");
+    ABOPT_CHECK_ARG(igso3_X && igso3_bins >= 2, "denoise_step: IGSO(3) histogram row missing");
+    ABOPT_CHECK_ARG(sp->t_prev >= 0 && sp->t_prev < sp->t, "denoise_step: the step must land below where it starts (t=%d t_prev=%d)", sp->t, sp->t_prev);
+    *nz = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+    if (noise && noise->axis) {
+        ABOPT_CHECK_ARG(noise->bin && noise->ubin && noise->gauss && noise->z && noise->s_next, "denoise_step: injected noise must provide all six draws");
+        *nz = *noise;
+    } else {
+        ABOPT_CHECK_ARG(igso3_cdf, "denoise_step: device RNG path needs the CDF row");
+    }
+    return ABOPT_OK;
+}
+
 extern "C" int abopt_denoise_step(const abopt_step_params* sp, const abopt_step_noise* noise, uint64_t seed, uint64_t offset,
                                   const float* v_t, const float* p_t, const int64_t* s_t,
                                   const float* v_net, const float* p_net, const float* c_net, const float* prmsd_logits,
@@ -333,15 +348,8 @@ extern "C" int abopt_denoise_step(const abopt_step_params* sp, const abopt_step_
                                   float* post_out, float* p_next_norm, const uint64_t* seed_offset_dev, const int32_t* aa_allowed,
                                   int N, int L, abopt_stream stream) {
     ABOPT_CHECK_ARG(sp && v_t && p_t && s_t && v_net && p_net && c_net && mask_generate && v_next && p_next && s_next, "denoise_step: NULL argument");
-    ABOPT_CHECK_ARG(igso3_X && igso3_bins >= 2, "denoise_step: IGSO(3) histogram row missing");
-    ABOPT_CHECK_ARG(sp->t_prev >= 0 && sp->t_prev < sp->t, "denoise_step: the step must land below where it starts (t=%d t_prev=%d)", sp->t, sp->t_prev);
-    abopt_step_noise nz = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-    if (noise && noise->axis) {
-        ABOPT_CHECK_ARG(noise->bin && noise->ubin && noise->gauss && noise->z && noise->s_next, "denoise_step: injected noise must provide all six draws");
-        nz = *noise;
-    } else {
-        ABOPT_CHECK_ARG(igso3_cdf, "denoise_step: device RNG path needs the CDF row");
-    }
+    abopt_step_noise nz;
+    if (int rc = check_step_args(sp, noise, igso3_X, igso3_cdf, igso3_bins, &nz)) return rc;
     if (N == 0 || L == 0) return ABOPT_OK;
     hipLaunchKernelGGL(denoise_step_kernel, dim3(N), dim3(256), 0, (hipStream_t)stream, *sp, nz, seed, offset, seed_offset_dev, v_t, p_t, s_t, v_net, p_net, c_net,
                        prmsd_logits, mask_generate, igso3_X, igso3_cdf, igso3_bins, num_bins, v_next, p_next, s_next, prmsd, perplexity, post_out,

@@ -1,8 +1,8 @@
 // One residue of a denoising step (the loop body of FullDPM.sample after the network, dpm_full.py:284-297): the three transitions
 //   RotationTransition.denoise (transition.py:146-160, so3.py:111-146), PositionTransition.denoise / pred_noise_from_start (transition.py:42-50,80-101),
 //   AminoacidCategoricalTransition.denoise (transition.py:202-245), and the residue's perplexity term (dpm_full.py:392-396)
-// as ONE device function shared by denoise_step_kernel (denoise.hip: one workgroup per sample) and by the mixer kernel of the NEXT network evaluation
-// (heads.hip, round 5: the step's transitions run on an otherwise idle wave of that launch) -- the same arithmetic in the same order, bit for bit.
+// as device functions shared by denoise_step_kernel (denoise.hip: one workgroup per sample, the pieces back to back in denoise_row) and by the fused tail of a step
+// (heads.hip: step_tail_kernel runs the pieces on different waves of the heads' workgroup) -- the same arithmetic in the same order, bit for bit.
 //
 // Allowed residue types (include/abopt.h: aa_allowed): one int32 word per residue, bit k = type k may be drawn, read on generated residues only.  A disallowed
 // class leaves the categorical BEFORE it is normalised (its unnormalised product becomes 0), so post_out, the draw and the perplexity term all see the distribution
@@ -31,101 +31,109 @@ struct DenoiseRowIO {
     float* v_next; float* p_next; int64_t* s_next; float* post_out; float* p_next_norm;
 };
 
-// cdf_s: the CDF row staged in LDS (or nullptr: searched in global memory).  Returns the next orientation vector through (nvx, nvy, nvz) as well.
-__device__ __forceinline__ void denoise_row(int64_t i, const abopt_step_params& sp, const abopt_step_noise& nz, bool injected, const Philox& rng, uint64_t offset,
-                                            const DenoiseRowIO& io, const float* cdf_s, bool need_bin, int ppl_masked, float& ppl_num, float& ppl_den,
-                                            float& nvx_out, float& nvy_out, float& nvz_out) {
-    const uint8_t* mask_generate = io.mask_generate;
-    const float *v_t = io.v_t, *p_t = io.p_t, *v_net = io.v_net, *p_net = io.p_net, *c_net = io.c_net, *igX = io.igX, *igCdf = io.igCdf;
-    const int64_t* s_t = io.s_t;
-    float *v_next = io.v_next, *p_next = io.p_next, *post_out = io.post_out, *p_next_norm = io.p_next_norm;
-    int64_t* s_next = io.s_next;
-    const int bins = io.bins;
-    const bool cdf_lds = cdf_s != nullptr;
-    const bool gen = mask_generate[i] != 0;
-    // ---- draws
-    float ax, ay, az, ubin, gss, zx, zy, zz, useq;
-    int64_t bin = 0;
+// The row's chain in pieces, cut where a value is complete (a raw draw, a select, the result of an addition or a division: nothing hipcc could contract across the
+// cut): denoise_row below calls them back to back, the fused tail of a step (heads.hip: step_tail_kernel) runs them on different waves with LDS in between.
+// a product rounded to fp32 HERE, whatever follows it (the compiler may not contract it into an fma)
+__device__ __forceinline__ float rounded_mul(float a, float b) {
+#pragma clang fp contract(off)
+    return a * b;
+}
+struct RowDraws { float ax, ay, az, ubin, gss, zx, zy, zz, useq; int64_t bin; };
+
+// ---- draws.  cdf_s: the CDF row staged in LDS (or nullptr: searched in global memory, when need_bin)
+__device__ __forceinline__ RowDraws denoise_draws(int64_t i, const abopt_step_params& sp, const abopt_step_noise& nz, bool injected, const Philox& rng, uint64_t offset,
+                                                  const float* igCdf, int bins, const float* cdf_s, bool need_bin) {
+    RowDraws d;
+    d.bin = 0;
     if (injected) {
-        ax = nz.axis[i * 3]; ay = nz.axis[i * 3 + 1]; az = nz.axis[i * 3 + 2];
-        bin = nz.bin[i]; ubin = nz.ubin[i]; gss = nz.gauss[i];
-        zx = nz.z[i * 3]; zy = nz.z[i * 3 + 1]; zz = nz.z[i * 3 + 2];
-        useq = 0.f;
+        d.ax = nz.axis[i * 3]; d.ay = nz.axis[i * 3 + 1]; d.az = nz.axis[i * 3 + 2];
+        d.bin = nz.bin[i]; d.ubin = nz.ubin[i]; d.gss = nz.gauss[i];
+        d.zx = nz.z[i * 3]; d.zy = nz.z[i * 3 + 1]; d.zz = nz.z[i * 3 + 2];
+        d.useq = 0.f;
     } else {
         const uint64_t ctr = offset + (uint64_t)i;
         const uint4 r0 = rng(ctr, ((uint64_t)sp.t << 8) | 0u), r1 = rng(ctr, ((uint64_t)sp.t << 8) | 1u), r2 = rng(ctr, ((uint64_t)sp.t << 8) | 2u);
         float d0;
-        box_muller(r0.x, r0.y, ax, ay);
-        box_muller(r0.z, r0.w, az, gss);
-        box_muller(r1.x, r1.y, zx, zy);
-        box_muller(r1.z, r1.w, zz, d0);
-        ubin = u01(r2.x); useq = u01(r2.y);
+        box_muller(r0.x, r0.y, d.ax, d.ay);
+        box_muller(r0.z, r0.w, d.az, d.gss);
+        box_muller(r1.x, r1.y, d.zx, d.zy);
+        box_muller(r1.z, r1.w, d.zz, d0);
+        d.ubin = u01(r2.x); d.useq = u01(r2.y);
         const float ub = u01(r2.z);
         // inverse CDF over bins-1 histogram cells == multinomial(Y[t, :-1]) (so3.py:122)
         int lo = 0, hi = bins - 2;
-        if (cdf_lds) { while (lo < hi) { const int mid = (lo + hi) >> 1; if (cdf_s[mid] > ub) hi = mid; else lo = mid + 1; } }
+        if (cdf_s) { while (lo < hi) { const int mid = (lo + hi) >> 1; if (cdf_s[mid] > ub) hi = mid; else lo = mid + 1; } }
         else if (need_bin) { while (lo < hi) { const int mid = (lo + hi) >> 1; if (igCdf[mid] > ub) hi = mid; else lo = mid + 1; } }
-        bin = lo;
+        d.bin = lo;
     }
-    // ---- rotation (transition.py:146-160)
-    const float vx = v_t[i * 3], vy = v_t[i * 3 + 1], vz = v_t[i * 3 + 2];
-    float nvx = vx, nvy = vy, nvz = vz;
-    {
-        const float nrm = fmaxf(sqrtf(ax * ax + ay * ay + az * az), 1e-12f);
-        const float hist = igX[bin] + ubin * (igX[bin + 1] - igX[bin]);
-        const float gau = fmodf(fabsf(sp.igso3_std * 2.f + gss * sp.igso3_std), PI_F);
-        const float th = sp.igso3_gaussian ? gau : hist;
-        float ex = ax / nrm * th, ey = ay / nrm * th, ez = az / nrm * th;
-        if (!(sp.t_prev > 0)) { ex = 0.f; ey = 0.f; ez = 0.f; }       // no noise on the step that lands on 0 (the reference's t > 1: t_prev = t - 1 there)
-        const Mat3 E = so3_exp(ex, ey, ez);
-        const Mat3 Rn = matmul3(E, so3_exp(v_net[i * 3], v_net[i * 3 + 1], v_net[i * 3 + 2]));
-        const Vec3 w = so3_log(Rn, false);
-        if (gen) { nvx = w.x; nvy = w.y; nvz = w.z; }
-    }
-    // ---- position (transition.py:42-50, 80-101); state is kept in Angstrom like the reference traj
-    const float pa[3] = {p_t[i * 3], p_t[i * 3 + 1], p_t[i * 3 + 2]};
-    const float zn[3] = {zx, zy, zz};
-    float pn[3], pt[3];
-    {
-        const float c0 = 1.0f / sqrtf(sp.alpha_clamped + 1e-8f);
-        const float c1 = (1.f - sp.alpha_clamped) / sqrtf(1.f - sp.alpha_bar + 1e-8f);
+    return d;
+}
+
+// ---- rotation noise (transition.py:146-160, so3.py:111-146): the normalised axis times its IGSO(3) angle; 0 on the step that lands on 0
+__device__ __forceinline__ void denoise_rot_noise(const RowDraws& d, const abopt_step_params& sp, const float* igX, float& ex, float& ey, float& ez) {
+    const float ax = d.ax, ay = d.ay, az = d.az;
+    const float nrm = fmaxf(sqrtf(ax * ax + ay * ay + az * az), 1e-12f);
+    const float hist = igX[d.bin] + d.ubin * (igX[d.bin + 1] - igX[d.bin]);
+    const float gau = fmodf(fabsf(fmaf(d.gss, sp.igso3_std, sp.igso3_std * 2.f)), PI_F);      // std 2 + gss std: the doubling is exact, the one rounding is the fma's
+    const float th = sp.igso3_gaussian ? gau : hist;
+    ex = ax / nrm * th; ey = ay / nrm * th; ez = az / nrm * th;
+    if (!(sp.t_prev > 0)) { ex = 0.f; ey = 0.f; ez = 0.f; }       // no noise on the step that lands on 0 (the reference's t > 1: t_prev = t - 1 there)
+}
+
+// ---- rotation: log(exp(e) exp(v_net)) on generated residues.  vt / vn: the row's three values of v_t / v_net
+__device__ __forceinline__ void denoise_rotation(float ex, float ey, float ez, const float* vt, const float* vn, bool gen, float& nvx, float& nvy, float& nvz) {
+    nvx = vt[0]; nvy = vt[1]; nvz = vt[2];
+    const Mat3 E = so3_exp(ex, ey, ez);
+    const Mat3 Rn = matmul3(E, so3_exp(vn[0], vn[1], vn[2]));
+    const Vec3 w = so3_log(Rn, false);
+    if (gen) { nvx = w.x; nvy = w.y; nvz = w.z; }
+}
+
+// ---- position (transition.py:42-50, 80-101); state is kept in Angstrom like the reference traj.  pa / pnet / zn: the row's three values of p_t / p_net / the noise
+__device__ __forceinline__ void denoise_position(const abopt_step_params& sp, const float* pa, const float* pnet_row, const float* zn, bool gen, float* pn, float* pt) {
+    const float c0 = 1.0f / sqrtf(sp.alpha_clamped + 1e-8f);
+    const float c1 = (1.f - sp.alpha_clamped) / sqrtf(1.f - sp.alpha_bar + 1e-8f);
 #pragma unroll
-        for (int k = 0; k < 3; ++k) {
-            pt[k] = (pa[k] - sp.position_mean[k]) / sp.position_scale;
-            const float pnet = p_net[i * 3 + k];
-            float eps = pnet;
-            if (sp.pred_x0) eps = gen ? (sp.sqrt_recip_abar * pt[k] - pnet) / sp.sqrt_recipm1_abar : pt[k];
-            const float zk = (sp.t_prev > 0) ? zn[k] : 0.f;
-            const float nx = c0 * (pt[k] - c1 * eps) + sp.sigma * zk;
-            pn[k] = gen ? nx : pt[k];
-        }
+    for (int k = 0; k < 3; ++k) {
+        pt[k] = (pa[k] - sp.position_mean[k]) / sp.position_scale;
+        const float pnet = pnet_row[k];
+        float eps = pnet;
+        if (sp.pred_x0) eps = gen ? (sp.sqrt_recip_abar * pt[k] - pnet) / sp.sqrt_recipm1_abar : pt[k];
+        const float zk = (sp.t_prev > 0) ? zn[k] : 0.f;
+        // c0 (pt - c1 eps) + sigma z with the product that is rounded and the one that is fused spelled out: left to the compiler, the choice between the two
+        // contractions follows the operand order its passes leave, which differs between the kernels this function is inlined into
+        const float nx = fmaf(sp.sigma, zk, rounded_mul(c0, pt[k] - c1 * eps));
+        pn[k] = gen ? nx : pt[k];
     }
-    if (!sp.sample_structure) { nvx = vx; nvy = vy; nvz = vz; pn[0] = pt[0]; pn[1] = pt[1]; pn[2] = pt[2]; }
-    v_next[i * 3] = nvx; v_next[i * 3 + 1] = nvy; v_next[i * 3 + 2] = nvz;
+}
+
+// the row's next position in Angstrom and, normalised again, as the next step feeds the network (dpm_full.py:276 normalises the STORED Angstrom value): saves the host two launches per step
+__device__ __forceinline__ void denoise_store_position(int64_t i, const abopt_step_params& sp, const float* pn, float* p_next, float* p_next_norm) {
 #pragma unroll
     for (int k = 0; k < 3; ++k) {
         const float pa_next = pn[k] * sp.position_scale + sp.position_mean[k];
         p_next[i * 3 + k] = pa_next;
-        // what the next step feeds the network (dpm_full.py:276 normalises the STORED Angstrom value again): saves the host two launches per step
         if (p_next_norm) p_next_norm[i * 3 + k] = (pa_next - sp.position_mean[k]) / sp.position_scale;
     }
+}
 
-    // ---- sequence (transition.py:202-245): NOTE alpha_bar_t multiplies both factors (reference quirk)
-    const int64_t st = s_t[i];
+// ---- sequence (transition.py:202-245): NOTE alpha_bar_t multiplies both factors (reference quirk).  cn: the row's 20 values of c_net.  Leaves the posterior in post
+// (and post_out) and its maximum in pmax; returns what s_next takes
+__device__ __forceinline__ int64_t denoise_sequence(int64_t i, const abopt_step_params& sp, const abopt_step_noise& nz, bool injected, float useq, int64_t st, const float* cn,
+                                                    uint32_t allow, bool gen, float* post_out, float* post, float& pmax) {
     const bool st_ok = st >= 0 && st < KAA;
-    const uint32_t allow = aa_allowed_set(io.aa_allowed, i, gen);
     const bool draws = gen && allow != 0u;          // an empty set: the type is frozen, its posterior is onehot(s_t) like a context residue's (the structure above still moved)
-    float post[KAA], tot = 0.f;
+    float tot = 0.f;
     const float ab = sp.alpha_bar, unif = (1.f - ab) / (float)KAA;
 #pragma unroll
     for (int k = 0; k < KAA; ++k) {
         const float ct = (st_ok && st == k) ? 1.f : 0.f;
-        const float raw = ((ab * ct) + unif) * ((ab * c_net[i * KAA + k]) + unif);
+        const float raw = ((ab * ct) + unif) * ((ab * cn[k]) + unif);
         const bool ok = ((allow >> k) & 1u) != 0u;
         tot = ok ? tot + raw : tot;                 // `tot + raw` as the unconstrained code spells it: the compiler contracts it to the same fma
         post[k] = ok ? raw : 0.f;
     }
-    float pmax = -INFINITY;
+    pmax = -INFINITY;
 #pragma unroll
     for (int k = 0; k < KAA; ++k) {
         const float ct = (st_ok && st == k) ? 1.f : 0.f;
@@ -147,7 +155,28 @@ __device__ __forceinline__ void denoise_row(int64_t i, const abopt_step_params& 
             if (ok && cum > target) { sn = k; break; }
         }
     }
-    s_next[i] = (sp.sample_sequence && allow != 0u) ? sn : st;
+    return (sp.sample_sequence && allow != 0u) ? sn : st;
+}
+
+// cdf_s: the CDF row staged in LDS (or nullptr: searched in global memory).  Returns the next orientation vector through (nvx, nvy, nvz) as well.
+__device__ __forceinline__ void denoise_row(int64_t i, const abopt_step_params& sp, const abopt_step_noise& nz, bool injected, const Philox& rng, uint64_t offset,
+                                            const DenoiseRowIO& io, const float* cdf_s, bool need_bin, int ppl_masked, float& ppl_num, float& ppl_den,
+                                            float& nvx_out, float& nvy_out, float& nvz_out) {
+    const bool gen = io.mask_generate[i] != 0;
+    const RowDraws d = denoise_draws(i, sp, nz, injected, rng, offset, io.igCdf, io.bins, cdf_s, need_bin);
+    float ex, ey, ez, nvx, nvy, nvz;
+    denoise_rot_noise(d, sp, io.igX, ex, ey, ez);
+    denoise_rotation(ex, ey, ez, io.v_t + i * 3, io.v_net + i * 3, gen, nvx, nvy, nvz);
+    const float zn[3] = {d.zx, d.zy, d.zz};
+    float pn[3], pt[3];
+    denoise_position(sp, io.p_t + i * 3, io.p_net + i * 3, zn, gen, pn, pt);
+    if (!sp.sample_structure) { nvx = io.v_t[i * 3]; nvy = io.v_t[i * 3 + 1]; nvz = io.v_t[i * 3 + 2]; pn[0] = pt[0]; pn[1] = pt[1]; pn[2] = pt[2]; }
+    io.v_next[i * 3] = nvx; io.v_next[i * 3 + 1] = nvy; io.v_next[i * 3 + 2] = nvz;
+    denoise_store_position(i, sp, pn, io.p_next, io.p_next_norm);
+    const uint32_t allow = aa_allowed_set(io.aa_allowed, i, gen);
+    float post[KAA], pmax;
+    const int64_t st = io.s_t[i];
+    io.s_next[i] = denoise_sequence(i, sp, nz, injected, d.useq, st, io.c_net + i * KAA, allow, gen, io.post_out, post, pmax);
     // perplexity term: max softmax(post) (dpm_full.py:392-396)
     float se = 0.f;
 #pragma unroll

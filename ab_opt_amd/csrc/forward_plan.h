@@ -15,6 +15,7 @@ struct Switches {
     bool fuse_tail = true;          // ABOPT_FUSE_TAIL=0: core and tail as two launches where the 32-row core runs
     bool x_terms = true;            // ABOPT_X_TERMS=0: no kernel writes x as fp16 terms, every node_frags splits x for itself
     bool fuse_heads = true;         // ABOPT_FUSE_HEADS=0: the heads' geometric epilogue as a launch of its own
+    bool fuse_step = true;          // ABOPT_FUSE_STEP=0: a denoising step's transitions and the next evaluation's mixer as launches of their own (abopt_eps_net_step)
 };
 
 struct BlockWeights { bool node_frag, out_frag, mlp_frag, out_terms; };     // which packed operands of abopt_ga_weights are given
@@ -31,6 +32,9 @@ struct ForwardQuery {
     BlockWeights blocks[kMaxBlocks];
     bool mix_frag, heads_frag, prmsd;       // network only: w_mix_frag + mix_table, w_heads_frag, the prmsd head
     Switches sw;
+    // abopt_eps_net_step only: the forward is followed by the step's transitions; they report the perplexity; the workspace holds this evaluation's mixer output
+    // (carry_in: the previous call of the entry wrote it); the next evaluation's is wanted (carry_out)
+    bool step = false, ppl = false, carry_in = false, carry_out = false;
 };
 
 enum class NodeForm { Kernel, Gemm };               // node_frags | projection GEMM + ipa_frags
@@ -54,6 +58,9 @@ struct NetPlan {
     bool heads_kernel;              // the heads kernel | the GEMM chain
     bool heads_epilogue;            // the geometric epilogue rides in the heads kernel
     bool build_infeat, prmsd;       // build_infeat runs (GEMM heads, or the prmsd head's LayerNorm'd copy); the prmsd chain runs
+    bool step_fused;                // abopt_eps_net_step: heads, transitions (and the next mixer) as ONE launch (heads.hip: step_tail_kernel) | heads launch(es) + denoise_step
+    bool mixer_launch;              // the mixer step runs at the head of this call (false: carried in by the previous call's fused tail)
+    bool step_carry;                // the fused tail also writes the next evaluation's mixer output (x, its terms in slot mixer_xt, R) into the workspace
 };
 
 inline CoreQuery core_query(const ForwardQuery& q) {
@@ -97,12 +104,19 @@ inline NetPlan plan_network(const ForwardQuery& q) {
     NetPlan n{};
     n.mixer_kernel = q.mix_frag;
     n.mixer_xt = (q.mix_frag && q.sw.x_terms && q.num_blocks > 0 && q.blocks[0].node_frag) ? 1 : -1;     // slot 1: block 0 writes slot 0 after it has read this one
+    n.mixer_launch = true;
     n.enc = plan_encoder(q, n.mixer_xt);
     if (!n.enc.ok) return n;
     n.heads_kernel = q.heads_frag;
     n.heads_epilogue = q.heads_frag && q.sw.fuse_heads;
     n.build_infeat = !q.heads_frag || q.prmsd;
     n.prmsd = q.prmsd;
+    // The fused tail of a step.  The two per-sample scalars (prmsd, perplexity) need a reduction across the workgroups of a sample in a fixed order: a call that
+    // wants either keeps the launches of its own.  At the time the tail runs, the mixer's outputs are free: x (block 0 alone read it) and x-terms slot mixer_xt
+    // (slot 1: the last writer's reader, an even block's node_frags, is long done), R after the epilogue of the same rows has read it.
+    n.step_fused = q.step && n.mixer_kernel && n.heads_kernel && n.heads_epilogue && q.sw.fuse_step && !q.prmsd && !q.ppl;
+    n.mixer_launch = !(n.step_fused && q.carry_in);
+    n.step_carry = n.step_fused && q.carry_out;
     return n;
 }
 

@@ -74,6 +74,20 @@ int launch_heads_mlp(const float* xe, const float* beta, const float* wfrag, con
                      const float* b2r, const float* b2s, const float* b3c, const float* b3r, const float* b3s, float* out3, int64_t rows, int L,
                      hipStream_t st,
                      const HeadsEpilogue* ep = nullptr /* optional: the geometric epilogue of the same rows in the same launch */);
+// heads.hip: the tail of a denoising step in one launch -- the heads with their epilogue, the step's three transitions (denoise_row.h) and, with carry, the mixer of
+// the NEXT network evaluation on the state just sampled (x, its terms and R = exp(v_next) into the workspace that evaluation reads)
+struct StepTail {
+    abopt_step_params sp; abopt_step_noise nz; uint64_t seed, offset; const uint64_t* seed_dev;
+    const float* p_t /* Angstrom */; const int64_t* s_t; const int32_t* aa_allowed; const float *igX, *igCdf; int bins;
+    float *v_next, *p_next; int64_t* s_next; float *post_out, *p_next_norm;
+    // carry (all NULL: none): the mixer's operands and outputs (launch_mixer)
+    const float *res_feat, *mix_wfrag, *mix_table, *mix_b1; float *x_out, *R_out, *xt_out;
+};
+int launch_step_tail(const float* xe, const float* beta, const float* wfrag, const float* w1, int ld1, const float* b1, const float* b2c,
+                     const float* b2r, const float* b2s, const float* b3c, const float* b3r, const float* b3s, float* out3, int64_t rows, int L,
+                     hipStream_t st, const HeadsEpilogue& ep, const StepTail& tail);
+// denoise.hip: the argument checks of abopt_denoise_step; nz = the injected draws or all NULL (the device Philox stream)
+int check_step_args(const abopt_step_params* sp, const abopt_step_noise* noise, const float* igso3_X, const float* igso3_cdf, int igso3_bins, abopt_step_noise* nz);
 size_t out_wfrag_floats();
 size_t out_wterms_floats();
 int launch_out_frag_terms(const float* wof, float* wot, hipStream_t st);

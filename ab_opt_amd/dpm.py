@@ -308,7 +308,7 @@ class FullDPM(_Derived, nn.Module):
         return hip.pair_terms_bytes(n_pair, L) <= _free_bytes(dev) // 2
 
     def _run_eager(self, spec, state, inputs, noise, seed, rng_offset, pbar, seed_dev=None, range_safe=False):
-        """The loop itself, one C call per network evaluation and one per transition; spec.use_bias_cache is settled (_denoise).
+        """The loop itself, one C call per step (network evaluation + transitions: hip.eps_net_step); spec.use_bias_cache is settled (_denoise).
         seed_dev: device {seed, offset} (graph capture)."""
         res_feat, pair_feat, mask_generate, mask_res, *allowed = _loop_inputs(inputs)
         if spec.constrained != bool(allowed):
@@ -355,15 +355,17 @@ class FullDPM(_Derived, nn.Module):
                 break
             i = K - j                                   # the slot of step t; the step writes slot i - 1, that of t_prev
             # the network is conditioned on the trained beta_t whatever the stride
-            hip.eps_net_forward(ew, tv[i], p_norm, ts[i], res_feat, pair_feat, beta_rows[t], mask_generate, mask_res,
-                                self.abdock, self.num_bins, False, out=net, pair_bias_cache=pbc, pair_feat_shared=(group if shared else 0), pair_terms=pterms)
             out = dict(v=tv[i - 1], p=tp[i - 1], s=ts[i - 1], p_norm=p_norm)
             if self.abdock:
                 out.update(prmsd=tpr[i - 1], ppl=tpp[i - 1])
-            hip.denoise_step(self._step_params(t, spec.sample_structure, spec.sample_sequence, spec.ppl_masked, spec.optimize_mode, t_prev),
-                             noise[t] if noise is not None else None, seed, rng_offset, tv[i], tp[i], ts[i], net['v_next'], net['eps_pos'], net['c'],
-                             net['prmsd_logits'], mask_generate, X[j], cdf[j] if noise is None else None, self.num_bins, out, seed_dev=seed_dev,
-                             aa_allowed=aa_allowed)
+            # Network and transitions as one call: where the library fuses the step's tail, it also runs the mixer of the next evaluation there (carry_out: this call
+            # has a next step) and skips its own (carry_in: the previous step of this call left it in the workspace, which nothing else touches inside the loop)
+            more = j + 1 < K and (spec.stop_after is None or j + 1 < spec.stop_after)
+            hip.eps_net_step(ew, tv[i], p_norm, ts[i], res_feat, pair_feat, beta_rows[t], mask_generate, mask_res, self.num_bins, net,
+                             self._step_params(t, spec.sample_structure, spec.sample_sequence, spec.ppl_masked, spec.optimize_mode, t_prev),
+                             noise[t] if noise is not None else None, seed, rng_offset, tp[i], X[j], cdf[j] if noise is None else None, out,
+                             pair_bias_cache=pbc, pair_feat_shared=(group if shared else 0), pair_terms=pterms, seed_dev=seed_dev, aa_allowed=aa_allowed,
+                             carry_in=j > 0, carry_out=more)
             evals += 1
         self.last_run_info = dict(bias_cache=use_bias_cache, pair_terms=pterms is not None, shared_context=shared, graph=seed_dev is not None, steps=evals)
         return tv, tp, ts, tpr, tpp

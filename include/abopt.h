@@ -23,7 +23,7 @@
 extern "C" {
 #endif
 
-#define ABOPT_ABI_VERSION 45
+#define ABOPT_ABI_VERSION 46
 
 enum { ABOPT_OK = 0, ABOPT_EINVAL = 1, ABOPT_EHIP = 2, ABOPT_EUNSUPPORTED = 3, ABOPT_EWORKSPACE = 4 };
 
@@ -293,6 +293,27 @@ int abopt_denoise_step(const abopt_step_params* sp, const abopt_step_noise* nois
                                                           with a fresh stream position (the values are read at execution time) */,
                        const int32_t* aa_allowed /* optional [N,L]: allowed residue types, see above */,
                        int N, int L, abopt_stream stream);
+
+/* One whole loop iteration (ABI 46): abopt_eps_net_forward (grad_mode 0) followed by abopt_denoise_step on its outputs, as one call.  The arguments are those of the
+ * two functions, once each: v_t / s_t / mask_generate / N / L / stream are shared, p_t is the normalised position the network takes and p_angstrom the state the
+ * step moves, v_net / R_net / eps_pos / c_denoised / prmsd_logits are the network's outputs (written as by abopt_eps_net_forward, read as the step's v_net / p_net /
+ * c_net / prmsd_logits).  p_next_norm may be p_t itself.  Every output is bit-identical to the two calls in a row.
+ * Where the packed mixer and heads operands are given, neither prmsd nor perplexity is asked for (no prmsd head in w, perplexity NULL) and ABOPT_FUSE_STEP is not 0,
+ * the heads, the step's transitions and -- carry_out -- the mixer step of the NEXT evaluation on the state just sampled run as ONE launch behind the encoder;
+ * otherwise the call makes the launches of the two functions, in their order, and ignores the carry.
+ *   carry_out != 0: also leave the next evaluation's mixer output (for v_next / s_next and the same res_feat) in ws.
+ *   carry_in  != 0: ws already holds this evaluation's mixer output -- the previous call of this function, with carry_out set, on the same ws, N, L, w and res_feat,
+ *                   produced exactly this v_t / s_t, and nothing wrote ws in between.  The mixer launch is skipped. */
+int abopt_eps_net_step(const abopt_eps_weights* w, const float* v_t, const float* p_t, const int64_t* s_t,
+                       const float* res_feat, const float* pair_feat, const float* beta,
+                       const uint8_t* mask_generate, const uint8_t* mask_res,
+                       float* v_net, float* R_net, float* eps_pos, float* c_denoised, float* prmsd_logits,
+                       int N, int L, int F, int C,
+                       const float* pair_bias_cache, int pair_feat_shared, const float* pair_terms, void* ws, size_t ws_bytes,
+                       const abopt_step_params* sp, const abopt_step_noise* noise, uint64_t seed, uint64_t offset, const float* p_angstrom,
+                       const float* igso3_X, const float* igso3_cdf, int igso3_bins, int num_bins,
+                       float* v_next, float* p_next, int64_t* s_next, float* prmsd, float* perplexity, float* post_out, float* p_next_norm,
+                       const uint64_t* seed_offset_dev, const int32_t* aa_allowed, int carry_in, int carry_out, abopt_stream stream);
 
 /* ---- IGSO(3) angle histograms for arbitrary standard deviations (ABI 45): the tables ApproxAngularDistribution builds on the host at construction
  * (D/modules/common/so3.py:82-109), for the strides of a respaced loop, whose sigmas are chosen per call.  Row r, bin b at x_b = linspace(0, pi, bins)[b]:
