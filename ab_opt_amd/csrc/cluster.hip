@@ -1,0 +1,229 @@
+// Greedy clustering of docked poses on the device: the step every docking tool puts after its sampler -- near-duplicate
+// poses are merged into binding modes, each reported by one representative and its population.  Nothing in the reference is matched; the
+// definition is this project's own (include/abopt.h: abopt_cluster_poses_grouped):
+//   distance   RMSD over the n points WITHOUT superposition (commonness_kernel's distance: all poses of a complex live in the antigen's frame)
+//   neighbours ssd(a, b) = sum_k |a_k - b_k|^2 <= cutoff^2 n; the diagonal is always set
+//   greedy     the alive structure with the most alive neighbours (ties: lowest index) becomes a centre, its alive neighbours its members
+// Two launches: pose_adjacency_kernel writes the neighbour relation as a bit matrix (and every row's population), greedy_cluster_kernel walks it.
+#include <math.h>
+#include "abopt_common.h"
+#include "kernels.h"
+
+namespace abopt {
+
+constexpr int CL_MAX_S = 16384;            // structures per group: the greedy kernel's LDS state (4 S + S / 4 bytes) stays under 160 KB
+constexpr int CL_KC = 48;                  // coordinates (16 points) of 64 rows and 64 columns staged in LDS at a time: 24.3 KB, any n
+constexpr int CL_ROWS = 16;                // rows a wave carries at once: 4 waves x 16 = the 64-row tile
+constexpr int CL_THREADS = 1024;
+
+// bit (row a, column b) of group g = ssd(a, b) <= thr, or a == b.  Grid (64-row tile, group), 4 waves: a wave owns 16 rows of the tile and walks the
+// group's columns 64 at a time; lane j carries ssd(row, column 64 cb + j) of each of its rows as ONE fmaf chain over the 3 n coordinates in index order.
+// (x - y)^2 == (y - x)^2 in floating point and the order is the same for (a, b) and (b, a), so the relation and the optional rmsd matrix are symmetric
+// bit for bit.  The workgroup stages 48 coordinates of its 64 rows and of the 64 columns in LDS per step (coalesced loads, each column read once per
+// 64 rows; a short last chunk is zero-filled: fmaf(0, 0, s) == s, the chain's bits do not change); the row operand is a broadcast read, the column
+// operand is one read per 16 fmaf (stride 49: conflict-free).  __ballot IS the 64-bit word of the bit row (columns past S: 0); lane 0 stores it and, at
+// the end of the row, the row's population.
+__global__ __launch_bounds__(256) void pose_adjacency_kernel(const float* __restrict__ x_all, unsigned long long* __restrict__ bits_all,
+                                                             int32_t* __restrict__ pop_all, float* __restrict__ rmsd_all, int S, int n, float thr) {
+    __shared__ __attribute__((aligned(16))) float row_sh[64][CL_KC];
+    __shared__ float col_sh[64][CL_KC + 1];
+    const int g = blockIdx.y, tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+    const int W = (S + 63) >> 6, n3 = n * 3, r0 = blockIdx.x * 64;
+    const float* x = x_all + (int64_t)g * S * n3;
+    int pop[CL_ROWS];
+#pragma unroll
+    for (int q = 0; q < CL_ROWS; ++q) pop[q] = 0;
+    for (int cb = 0; cb < W; ++cb) {
+        float s[CL_ROWS];
+#pragma unroll
+        for (int q = 0; q < CL_ROWS; ++q) s[q] = 0.f;
+        for (int k0 = 0; k0 < n3; k0 += CL_KC) {
+            __syncthreads();                                                   // the previous chunk's reads are done
+            for (int idx = tid; idx < 64 * CL_KC; idx += 256) {
+                const int rr = idx / CL_KC, k = idx % CL_KC;
+                const bool in = k0 + k < n3;
+                const int r = min(r0 + rr, S - 1), c = min(cb * 64 + rr, S - 1);   // rows / columns past S read the last structure and are masked below
+                row_sh[rr][k] = in ? x[(int64_t)r * n3 + k0 + k] : 0.f;
+                col_sh[rr][k] = in ? x[(int64_t)c * n3 + k0 + k] : 0.f;
+            }
+            __syncthreads();
+#pragma unroll 4
+            for (int k = 0; k < CL_KC; ++k) {
+                const float c = col_sh[lane][k];
+#pragma unroll
+                for (int q = 0; q < CL_ROWS; ++q) { const float d = row_sh[wave * CL_ROWS + q][k] - c; s[q] = fmaf(d, d, s[q]); }
+            }
+        }
+        const int col = cb * 64 + lane;
+        const bool valid = col < S;
+#pragma unroll
+        for (int q = 0; q < CL_ROWS; ++q) {
+            const int r = r0 + wave * CL_ROWS + q;
+            if (r >= S) break;                                                  // wave-uniform
+            const unsigned long long word = __ballot(valid && (s[q] <= thr || col == r));
+            if (lane == 0) bits_all[((int64_t)g * S + r) * W + cb] = word;
+            pop[q] += __popcll(word);
+            if (rmsd_all && valid) rmsd_all[((int64_t)g * S + r) * S + col] = sqrtf(s[q] / (float)n);
+        }
+    }
+    if (lane == 0) {
+#pragma unroll
+        for (int q = 0; q < CL_ROWS; ++q) {
+            const int r = r0 + wave * CL_ROWS + q;
+            if (r < S) pop_all[(int64_t)g * S + r] = pop[q];
+        }
+    }
+}
+
+// 64-bit max over the workgroup's 16 waves; every thread gets the result.  red[16]; two barriers.
+__device__ __forceinline__ unsigned long long block_max_u64(unsigned long long v, unsigned long long* red) {
+    for (int off = 32; off > 0; off >>= 1) { const unsigned long long o = __shfl_xor(v, off, 64); v = o > v ? o : v; }
+    __syncthreads();                                                           // the previous round's reads of red[] are done
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
+    __syncthreads();
+    unsigned long long m = red[0];
+#pragma unroll
+    for (int w = 1; w < CL_THREADS / 64; ++w) m = red[w] > m ? red[w] : m;
+    return m;
+}
+
+// ONE 1024-thread workgroup per group.  LDS: cnt[S] (alive neighbours of every alive structure, itself included), alive[W], mem[W] (the members of
+// the cluster being cut out).  Per iteration:
+//   pick     max over the alive structures of the key (cnt << 32 | ~index): count descending, index ascending; S / 1024 keys per thread + one
+//            16-wave reduction.  Deterministic: integers.
+//   cut      mem = row(centre) & alive; alive &= ~mem; the cluster's size is cnt[centre] (the invariant above).
+//   update   INCREMENTAL: every member m is visited once (a wave per member, its bit row read ONCE in the whole call) and takes 1 off cnt[j] of every
+//            surviving neighbour j (row(m) & alive; the relation is symmetric, so these are the structures that counted m).  LDS integer atomics: the
+//            order does not matter.  Over the whole call that is one pass over the bit matrix (S W words) + one LDS atomic per (dying, surviving)
+//            neighbour pair, against S W words PER ITERATION for a recount.
+//   tail     once the largest count is 1 every structure left is a singleton: they are numbered in index order in ONE pass (a docking run's tail of
+//            isolated poses is most of the iterations otherwise).
+// An iteration costs 4 barriers, S / 1024 LDS reads per thread and W / 64 word loads per wave and member.
+__global__ __launch_bounds__(CL_THREADS) void greedy_cluster_kernel(const unsigned long long* __restrict__ bits_all, const int32_t* __restrict__ pop_all,
+                                                                    int32_t* __restrict__ label_all, int32_t* __restrict__ centre_all,
+                                                                    int32_t* __restrict__ size_all, int32_t* __restrict__ count_all, int S, int max_clusters) {
+    extern __shared__ unsigned long long cl_lds[];
+    const int g = blockIdx.x, tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+    const int W = (S + 63) >> 6;
+    unsigned long long* alive = cl_lds;                  // [W]
+    unsigned long long* mem = alive + W;                 // [W]
+    unsigned long long* red = mem + W;                   // [16]
+    int* cnt = (int*)(red + CL_THREADS / 64);            // [S]
+    const unsigned long long* bits = bits_all + (int64_t)g * S * W;
+    int32_t* label = label_all + (int64_t)g * S;
+    int32_t* centre = centre_all + (int64_t)g * S;
+    int32_t* size = size_all + (int64_t)g * S;
+    for (int i = tid; i < S; i += CL_THREADS) cnt[i] = pop_all[(int64_t)g * S + i];
+    for (int w = tid; w < W; w += CL_THREADS) alive[w] = (w * 64 + 64 <= S) ? ~0ull : ((1ull << (S - w * 64)) - 1ull);
+    __syncthreads();
+    const int cap = max_clusters > 0 ? min(max_clusters, S) : S;
+    int found = 0;
+    while (found < cap) {
+        unsigned long long key = 0ull;
+        for (int i = tid; i < S; i += CL_THREADS)
+            if ((alive[i >> 6] >> (i & 63)) & 1ull) {
+                const unsigned long long k = ((unsigned long long)(unsigned)cnt[i] << 32) | (unsigned long long)(0xffffffffu - (unsigned)i);
+                key = k > key ? k : key;
+            }
+        key = block_max_u64(key, red);
+        if (key == 0ull) break;                                                 // nobody alive (block-uniform)
+        if ((key >> 32) == 1ull) {
+            // the largest count is 1: nobody alive has an alive neighbour but itself, so the rest are singletons and the picks would take them in index order.
+            // One pass instead of one iteration each: cluster number = found + rank among the alive (a prefix sum over the words' populations, in mem[]).
+            for (int w = tid; w < W; w += CL_THREADS) mem[w] = (unsigned long long)__popcll(alive[w]);
+            __syncthreads();
+            if (tid == 0) {
+                unsigned long long run = 0ull;
+                for (int w = 0; w < W; ++w) { const unsigned long long t = mem[w]; mem[w] = run; run += t; }
+                red[0] = run;
+            }
+            __syncthreads();
+            const int rest = (int)red[0];
+            for (int i = tid; i < S; i += CL_THREADS) {
+                const unsigned long long a = alive[i >> 6];
+                if (!((a >> (i & 63)) & 1ull)) continue;
+                const int cl = found + (int)mem[i >> 6] + __popcll(a & ((1ull << (i & 63)) - 1ull));
+                label[i] = cl < cap ? cl : -1;                                  // past the cap: left over
+                if (cl < cap) { centre[cl] = i; size[cl] = 1; }
+            }
+            __syncthreads();
+            for (int w = tid; w < W; w += CL_THREADS) alive[w] = 0ull;
+            found = min(cap, found + rest);
+            __syncthreads();
+            break;
+        }
+        const int c = (int)(0xffffffffu - (unsigned)(key & 0xffffffffull));
+        if (tid == 0) { centre[found] = c; size[found] = (int)(key >> 32); }
+        for (int w = tid; w < W; w += CL_THREADS) {
+            const unsigned long long a = alive[w], m = bits[(int64_t)c * W + w] & a;
+            mem[w] = m;
+            alive[w] = a & ~m;
+        }
+        __syncthreads();
+        for (int w = wave; w < W; w += CL_THREADS / 64) {
+            unsigned long long mw = mem[w];                                     // wave-uniform
+            while (mw) {
+                const int m = w * 64 + __ffsll((long long)mw) - 1;
+                mw &= mw - 1ull;
+                if (lane == 0) label[m] = found;
+                const unsigned long long* mrow = bits + (int64_t)m * W;
+                for (int ww = lane; ww < W; ww += 64) {
+                    unsigned long long nb = mrow[ww] & alive[ww];
+                    while (nb) {
+                        const int j = ww * 64 + __ffsll((long long)nb) - 1;
+                        nb &= nb - 1ull;
+                        atomicSub(&cnt[j], 1);
+                    }
+                }
+            }
+        }
+        __syncthreads();
+        ++found;
+    }
+    // structures still alive at the cap keep label -1; centre / size are padded with -1 / 0
+    for (int i = tid; i < S; i += CL_THREADS) {
+        if ((alive[i >> 6] >> (i & 63)) & 1ull) label[i] = -1;
+        if (i >= found) { centre[i] = -1; size[i] = 0; }
+    }
+    if (tid == 0) count_all[g] = found;
+}
+
+static LdsConfig g_cluster_lds;
+
+}  // namespace abopt
+
+using namespace abopt;
+
+// bit matrix [G, S, ceil(S / 64)] of 8-byte words | populations [G, S] int32
+extern "C" size_t abopt_cluster_ws_bytes(int G, int S) {
+    if (G <= 0 || S <= 0 || S > CL_MAX_S) return 0;                             // nothing to do / unsupported: the call itself says which
+    const size_t W = ((size_t)S + 63) / 64;
+    return (size_t)G * S * W * 8 + (((size_t)G * S * 4 + 7) & ~(size_t)7);
+}
+
+extern "C" int abopt_cluster_poses_grouped(const float* structs, int G, int S, int n, float cutoff, int max_clusters, void* ws, size_t ws_bytes,
+                                           void* label, void* centre, void* size, void* count, float* rmsd, abopt_stream stream) {
+    ABOPT_CHECK_ARG(G >= 0 && S >= 1 && n >= 1 && max_clusters >= 0 && (int64_t)G * S <= 0x7fffffff && (int64_t)n * 3 <= 0x7fffffff,
+                    "cluster_poses_grouped: bad dims G=%d S=%d n=%d max_clusters=%d", G, S, n, max_clusters);
+    if (S > CL_MAX_S) { set_error("cluster_poses_grouped: S=%d structures per group exceed the greedy kernel's LDS state (max %d)", S, CL_MAX_S); return ABOPT_EUNSUPPORTED; }
+    ABOPT_CHECK_ARG(isfinite(cutoff) && cutoff >= 0.f, "cluster_poses_grouped: the cutoff must be finite and >= 0 (got %g)", (double)cutoff);
+    if (G == 0) return ABOPT_OK;
+    ABOPT_CHECK_ARG(G <= 65535, "cluster_poses_grouped: G=%d groups exceed one launch (max 65535)", G);
+    ABOPT_CHECK_ARG(structs && ws && label && centre && size && count, "cluster_poses_grouped: NULL argument");
+    ABOPT_CHECK_ARG(((uintptr_t)ws & 7) == 0, "cluster_poses_grouped: the workspace must be 8-byte aligned");
+    if (ws_bytes < abopt_cluster_ws_bytes(G, S)) { set_error("cluster_poses_grouped: workspace too small (%zu bytes given)", ws_bytes); return ABOPT_EWORKSPACE; }
+    hipStream_t st = (hipStream_t)stream;
+    const int W = (S + 63) / 64;
+    unsigned long long* bits = (unsigned long long*)ws;
+    int32_t* pop = (int32_t*)(bits + (size_t)G * S * W);
+    const float thr = (float)((double)cutoff * (double)cutoff * (double)n);      // +inf for a huge cutoff: every finite pair is a neighbour
+    const size_t lds = (size_t)(2 * W + CL_THREADS / 64) * 8 + (size_t)S * 4;
+    int rc = ensure_dynamic_lds((const void*)greedy_cluster_kernel, lds, g_cluster_lds);
+    if (rc != ABOPT_OK) return rc;
+    hipLaunchKernelGGL(pose_adjacency_kernel, dim3((unsigned)W, (unsigned)G), dim3(256), 0, st, structs, bits, pop, rmsd, S, n, thr);
+    ABOPT_LAUNCH_CHECK();
+    hipLaunchKernelGGL(greedy_cluster_kernel, dim3((unsigned)G), dim3(CL_THREADS), lds, st, (const unsigned long long*)bits, (const int32_t*)pop,
+                       (int32_t*)label, (int32_t*)centre, (int32_t*)size, (int32_t*)count, S, max_clusters);
+    ABOPT_LAUNCH_CHECK();
+    return ABOPT_OK;
+}

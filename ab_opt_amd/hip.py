@@ -13,7 +13,7 @@ import torch
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # ABOPT_LIB_PATH: developer override to load a variant build of the same ABI (csrc/Makefile VARIANT=...: A/B of two source trees)
 LIB_PATH = os.environ.get('ABOPT_LIB_PATH') or os.path.join(_HERE, 'libabopt_hip.so')
-ABI_VERSION = 46
+ABI_VERSION = 47
 
 c_f = C.c_void_p        # device float*
 c_i64 = C.c_void_p      # device int64*
@@ -158,6 +158,8 @@ _SIGNATURES = {
     'abopt_adam_step': (c_int, [c_int] + [c_void_p] * 5 + [c_double] * 6 + [c_i64, c_f, c_size_t, c_f, c_void_p, c_stream]),
     'abopt_commonness_score': (c_int, [c_f, c_f, c_int, c_int, c_stream]),
     'abopt_commonness_score_grouped': (c_int, [c_f, c_f, c_int, c_int, c_int, c_stream]),
+    'abopt_cluster_ws_bytes': (c_size_t, [c_int, c_int]),
+    'abopt_cluster_poses_grouped': (c_int, [c_f, c_int, c_int, c_int, c_float, c_int, c_void_p, c_size_t] + [c_void_p] * 4 + [c_f, c_stream]),
     'abopt_prof_enable': (c_int, [c_int]),
     'abopt_prof_spans_reset': (c_int, [c_stream]),
     'abopt_prof_spans': (c_int, [POINTER(c_int), POINTER(c_double)]),
@@ -634,6 +636,40 @@ def commonness_score_grouped(structs, group_size):
     score = torch.empty(B, device=structs.device)
     _check(lib().abopt_commonness_score_grouped(ptr(structs), ptr(score), B // S, S, n, stream()))
     return score
+
+
+def check_cluster_cutoff(name, cutoff):
+    """float(cutoff), or ValueError for a negative or non-finite one (the check abopt_cluster_poses_grouped makes, ahead of any device work)."""
+    import math
+    c = float(cutoff)
+    if not math.isfinite(c) or c < 0.0:
+        raise ValueError(f'{name} must be finite and >= 0 (got {cutoff!r})')
+    return c
+
+
+def cluster_poses_grouped(structs, group_size, cutoff, max_clusters=0, want_rmsd=False):
+    """Greedy clustering of every group of S = group_size structures (include/abopt.h: abopt_cluster_poses_grouped).
+    structs (G*S, n, 3); cutoff in Angstrom (RMSD without superposition); max_clusters 0 = no cap.
+    -> dict of device tensors: label (G*S,) int32 (-1: left over at the cap), centre (G, S) int32 (indices within the group, -1 padded),
+    size (G, S) int32 (0 padded), count (G,) int32 [, rmsd (G, S, S) fp32, symmetric bit for bit].  Two stream-ordered launches, no host synchronisation."""
+    structs = structs.contiguous().float()
+    B, n, _ = structs.shape
+    S, M = int(group_size), int(max_clusters)
+    if S < 1 or B % S or n < 1 or structs.shape[2] != 3:
+        raise ValueError(f'cluster_poses_grouped: {tuple(structs.shape)} structures are not whole groups of {S} >= 1 structures (n, 3)')
+    if M < 0:
+        raise ValueError(f'cluster_poses_grouped: max_clusters must be >= 0 (0 = no cap), got {max_clusters!r}')
+    cutoff = check_cluster_cutoff('cluster_poses_grouped: cutoff', cutoff)
+    ptr(structs)                                                    # a CPU tensor is refused here, before anything is allocated
+    G, dev = B // S, structs.device
+    i32 = dict(dtype=torch.int32, device=dev)
+    out = dict(label=torch.empty(B, **i32), centre=torch.empty(G, S, **i32), size=torch.empty(G, S, **i32), count=torch.empty(G, **i32))
+    if want_rmsd:
+        out['rmsd'] = torch.empty(G, S, S, dtype=torch.float32, device=dev)
+    buf = Workspace.get(max(8, lib().abopt_cluster_ws_bytes(G, S)), dev)
+    _check(lib().abopt_cluster_poses_grouped(ptr(structs), G, S, n, cutoff, M, ptr(buf), buf.numel(), ptr(out['label']), ptr(out['centre']), ptr(out['size']),
+                                             ptr(out['count']), ptr(out.get('rmsd'), optional=True), stream()))
+    return out
 
 
 def pair_bias_cache_layers(w_pair_bias_list, pair_feat):

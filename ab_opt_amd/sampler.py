@@ -63,6 +63,25 @@ def rank_commoness(structs, k, score_fn=None):
     return torch.topk(commonness_score(structs, score_fn), k=k, largest=False)[1]
 
 
+def cluster_poses(ca, cutoff, max_clusters=None):
+    """Greedy clustering of P docked poses on the device (include/abopt.h: abopt_cluster_poses_grouped): what a docking tool hands
+    back instead of a flat list -- one representative per binding mode with its population.  ca (P, n, 3): the poses' CA (all in one frame: the
+    distance is the RMSD WITHOUT superposition, as in `commonness_score`); cutoff in Angstrom: a and b are neighbours iff RMSD(a, b) <= cutoff.
+    The pose with the most unassigned neighbours (ties: lowest index) becomes a centre, its unassigned neighbours its members; repeat until every
+    pose is assigned or max_clusters (optional, >= 1) clusters exist.
+    -> dict(label (P,) cluster of every pose (-1: left over at the cap), centre (C,) pose index of every centre, size (C,) members per cluster), int64 on
+    the device, in order of discovery (not sorted).  Costs one host read (the number of clusters C).  Raises on CPU tensors (no fallback)."""
+    from . import hip
+    cutoff = hip.check_cluster_cutoff('cluster_poses: cutoff', cutoff)
+    if max_clusters is not None and int(max_clusters) < 1:
+        raise ValueError(f'cluster_poses: max_clusters must be >= 1 or None (got {max_clusters!r})')
+    if ca.dim() != 3 or ca.shape[0] < 1 or ca.shape[1] < 1 or ca.shape[2] != 3:
+        raise ValueError(f'cluster_poses: expected (P, n, 3) poses with P, n >= 1, got {tuple(ca.shape)}')
+    out = hip.cluster_poses_grouped(ca, ca.shape[0], cutoff, int(max_clusters or 0))
+    C = int(out['count'][0])
+    return dict(label=out['label'].long(), centre=out['centre'][0, :C].long(), size=out['size'][0, :C].long())
+
+
 def dockq_scores(model_pos, model_mask, native_pos, native_mask, fragment_type=None, group=None):
     """DockQ of candidate structures against the native complex, on the device (the reference writes every candidate to a PDB
     file and shells out: AbDock/src/tools/runner/design_for_pdb.py:316-321, AbDock/DockQ/DockQ.py:98-385).

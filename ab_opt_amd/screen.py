@@ -19,6 +19,15 @@ Randomness: stage k draws from Philox seed `stage_seed(seed, k)`, and sample i o
 therefore do not depend on `poses_per_launch` or on the number of ranks (bit for bit where the launches of different sizes take the same
 kernel forms: DESIGN.md section 3.1b).  Multi-GPU: rank r owns the poses `sampler.shard_range(P, world, r)` through all three stages;
 one tensor all_gather per result field at the end.
+
+Pose clustering (optional, off by default): a docking sampler returns a few binding modes many times over, and the two expensive
+stages spend P S + P k D trajectories on those near-duplicates.  With `cluster_cutoff` the P poses are clustered on the device after stage 1
+(`sampler.cluster_poses`: greedy, RMSD of the docked residues' CA without superposition -- the distance of the commonness score) and stages 2 and 3 run on
+the C cluster centres only, in cluster order: cluster c takes the place pose c has above for `launch_plan`, `sampler.shard_range(C, world, rank)` and the
+Philox layout (global sample index c S + design, ...).  With several ranks the poses and their rebuilt coordinates are gathered before the clustering, so
+every rank clusters the same array and owns the centres of its shard.  With `redock_cutoff` the D re-docks of every screened design are clustered as well
+(ONE grouped launch pair per chunk, hip.cluster_poses_grouped): the largest cluster's share of D is the convergence measure DockQ_std approximates.
+How many clusters trained weights produce, and what a cutoff costs in hit rate, is unmeasured: no trained checkpoint exists here.
 """
 import time
 
@@ -86,7 +95,7 @@ def _rebuild(pos, mask, traj0, lo, hi, aa, flag, one):
 @torch.no_grad()
 def optimize_antibody(dock_model, design_model, complex_, num_poses, designs_per_pose, redocks_per_design, design_flag=None, redock_flag=None,
                       contig='', screened_per_pose=1, seed=0, poses_per_launch=8, group=None, screen_by='first', timings=None, allowed_aa=None,
-                      dock_steps=None, design_steps=None):
+                      dock_steps=None, design_steps=None, cluster_cutoff=None, max_clusters=None, redock_cutoff=None):
     """Dock -> redesign -> re-dock screen of one antibody-antigen complex (module docstring).
 
     complex_: batch dict with batch dim 1 (cropped, as sample_replicated takes it); its generate_flag marks the residues to dock.
@@ -100,9 +109,18 @@ def optimize_antibody(dock_model, design_model, complex_, num_poses, designs_per
     dock_steps / design_steps (optional; default: every trained step): the network evaluations of every dock and re-dock trajectory / of every design trajectory,
     over the evenly respaced sub-sequence of the model's steps (FullDPM.sample(steps=K)) -- the screen spends P + P S + P k D trajectories per
     antibody, and this trades their depth for breadth.  Sample quality against K is unmeasured.
-    timings (optional dict): receives the seconds each stage took on this rank (device-synchronised) and of the final gather.
+    cluster_cutoff (optional, Angstrom; default None: every pose goes on, nothing below changes): cluster the P poses after stage 1 and run stages 2 and 3 on the
+    C cluster centres only (module docstring); max_clusters (optional, >= 1; needs cluster_cutoff) caps C -- poses left over at the cap keep label -1 and
+    are not screened.  The result gains cluster_label (P,), cluster_centre (C,) (pose indices) and cluster_size (C,), all int64; pose_ca / pose_score
+    stay (P, ...), and every field of stages 2 and 3 below has leading dimension C instead of P: row c belongs to pose cluster_centre[c].  Costs one host read
+    (C) between stage 1 and stage 2.
+    redock_cutoff (optional, Angstrom): cluster the D re-docks of every screened design; the result gains redock_cluster_frac (., k) fp32, the largest cluster's
+    share of D, and redock_clusters (., k) int64, the number of clusters.
+    timings (optional dict): receives the seconds each stage took on this rank (device-synchronised) and of the final gather ('cluster': the gather and
+    clustering between stage 1 and stage 2, with cluster_cutoff).
 
     -> dict of device tensors in global pose order (P poses, S designs, k screened, D re-docks; n_* = residues in the mask):
+      (with cluster_cutoff: C cluster centres in place of the P poses in every field from seqs on, see above)
       pose_ca (P, n_dock, 3), pose_score (P,)           CA of the docked residues of every pose, its commonness among the P poses
       seqs (P, S, n_design) int64, aar (P, S), ppl (P, S)  designed residues, recovery of the input sequence on them, perplexity
       chosen (P, k) int64                                 the designs that were re-docked
@@ -119,6 +137,12 @@ def optimize_antibody(dock_model, design_model, complex_, num_poses, designs_per
                          f'(got P={P}, S={S}, k={k}, D={D})')
     if screen_by not in ('first', 'ppl'):
         raise ValueError(f"screen_by must be 'first' or 'ppl', not {screen_by!r}")
+    if cluster_cutoff is not None:
+        cluster_cutoff = hip.check_cluster_cutoff('optimize_antibody: cluster_cutoff', cluster_cutoff)
+    if redock_cutoff is not None:
+        redock_cutoff = hip.check_cluster_cutoff('optimize_antibody: redock_cutoff', redock_cutoff)
+    if max_clusters is not None and (cluster_cutoff is None or int(max_clusters) < 1):
+        raise ValueError(f'optimize_antibody: max_clusters must be >= 1 and needs cluster_cutoff (got max_clusters={max_clusters!r}, cluster_cutoff={cluster_cutoff!r})')
     L = int(one['aa'].shape[1])
     dev = one['aa'].device
     given = one.pop('aa_allowed', None)
@@ -160,6 +184,26 @@ def optimize_antibody(dock_model, design_model, complex_, num_poses, designs_per
         pose_ca[lo - a:hi - a] = traj[0][1][:, gen]
     t0 = tick('dock', t0)
 
+    # ---- optional: cluster the P poses (every rank the same gathered array); from here on "pose" c is the centre of cluster c, and a / mine / plan are the
+    # shard and launches of this rank over the C centres
+    pose_counts = [e - s_ for s_, e in (sampler.shard_range(P, world, r) for r in range(world))]
+    clusters = None
+    if cluster_cutoff is not None:
+        if world > 1:
+            pose_ca = sampler.all_gather_candidates(pose_ca, pose_counts, group)
+            pose_pos = sampler.all_gather_candidates(pose_pos, pose_counts, group)
+            pose_mask = sampler.all_gather_candidates(pose_mask.to(torch.uint8), pose_counts, group).bool()
+        clusters = sampler.cluster_poses(pose_ca, cluster_cutoff, max_clusters)
+        Q = int(clusters['centre'].shape[0])
+        plan = launch_plan(Q, poses_per_launch, world, rank)
+        a, b = sampler.shard_range(Q, world, rank)
+        mine = b - a
+        own = clusters['centre'][a:b]
+        pose_pos, pose_mask = pose_pos[own], pose_mask[own]
+        t0 = tick('cluster', t0)
+    else:
+        Q = P
+
     # ---- stage 2: S designs per pose on the fixed pose backbone, each pose encoded once, its designs share its pair features
     seqs = torch.empty(mine, S, n_design, dtype=torch.int64, device=dev)
     aar, ppl = torch.empty(mine, S, **f32), torch.empty(mine, S, **f32)
@@ -196,6 +240,7 @@ def optimize_antibody(dock_model, design_model, complex_, num_poses, designs_per
     # ---- stage 3: D re-docks of every screened design, one grouped DockQ + one grouped commonness launch per chunk
     dockq = torch.empty(mine, k, D, 4, **f32)
     prmsd, redock_score = torch.empty(mine, k, D, **f32), torch.empty(mine, k, D, **f32)
+    redock_frac, redock_clusters = torch.empty(mine, k, **f32), torch.empty(mine, k, dtype=torch.int64, device=dev)
     grp = chain_groups(one['fragment_type'][0])
     for lo, hi in plan:
         Gk = (hi - lo) * k
@@ -209,12 +254,22 @@ def optimize_antibody(dock_model, design_model, complex_, num_poses, designs_per
         prmsd[lo - a:hi - a] = traj[0][3].to(dev).view(hi - lo, k, D)
         ca = traj[0][1][:, rflag].contiguous()                                          # (Gk*D, n_redock, 3)
         redock_score[lo - a:hi - a] = hip.commonness_score_grouped(ca, D).view(hi - lo, k, D)
+        if redock_cutoff is not None:
+            cl = hip.cluster_poses_grouped(ca, D, redock_cutoff)
+            redock_frac[lo - a:hi - a] = (cl['size'].amax(1).float() / D).view(hi - lo, k)
+            redock_clusters[lo - a:hi - a] = cl['count'].long().view(hi - lo, k)
     t0 = tick('redock', t0)
 
     res = dict(pose_ca=pose_ca, seqs=seqs, aar=aar, ppl=ppl, chosen=chosen, dockq=dockq, prmsd=prmsd, redock_score=redock_score)
+    if redock_cutoff is not None:
+        res.update(redock_cluster_frac=redock_frac, redock_clusters=redock_clusters)
     if world > 1:
-        counts = [e - s_ for s_, e in (sampler.shard_range(P, world, r) for r in range(world))]
-        res = {name: sampler.all_gather_candidates(t, counts, group) for name, t in res.items()}
+        counts = [e - s_ for s_, e in (sampler.shard_range(Q, world, r) for r in range(world))]
+        gathered = {} if clusters is None else dict(pose_ca=res.pop('pose_ca'))          # the clustered poses were gathered before stage 2
+        res = {name: sampler.all_gather_candidates(t, pose_counts if name == 'pose_ca' else counts, group) for name, t in res.items()}
+        res.update(gathered)
+    if clusters is not None:
+        res.update(cluster_label=clusters['label'], cluster_centre=clusters['centre'], cluster_size=clusters['size'])
     res['pose_score'] = hip.commonness_score(res['pose_ca'])
     q, pr = res['dockq'][..., 3], res['prmsd']
     res.update(dockq_mean=q.mean(-1), dockq_std=q.std(-1, unbiased=False), prmsd_mean=pr.mean(-1), prmsd_std=pr.std(-1, unbiased=False))

@@ -23,7 +23,7 @@
 extern "C" {
 #endif
 
-#define ABOPT_ABI_VERSION 46
+#define ABOPT_ABI_VERSION 47
 
 enum { ABOPT_OK = 0, ABOPT_EINVAL = 1, ABOPT_EHIP = 2, ABOPT_EUNSUPPORTED = 3, ABOPT_EWORKSPACE = 4 };
 
@@ -605,6 +605,29 @@ int abopt_commonness_score(const float* structs, float* score, int B, int n, abo
  * design_for_pdb.py:326-345 ranks one run's candidates): structs [G*S,n,3] -> score [G*S], each score the commonness within its own group
  * of S, bit-identical to abopt_commonness_score called on that group.  S >= 2. */
 int abopt_commonness_score_grouped(const float* structs, float* score, int G, int S, int n, abopt_stream stream);
+
+/* ---- Pose clustering (ABI 47): the step a docking workflow puts between its sampler and everything expensive.  A docking sampler returns a few binding
+ * modes many times over; this merges the near-duplicates so that the redesign and re-dock stages of the screen (AbDock/optimize_ab.py:12-98) run on ONE
+ * representative per mode, and reports every mode's population -- for the D re-docks of a design, the share of the largest mode is the convergence
+ * measure.  Nothing in the reference is matched; the definition is this library's own, per group of S structures [n,3]:
+ *   distance    ssd(a, b) = sum_k |a_k - b_k|^2 over the n points WITHOUT superposition (abopt_commonness_score's distance), accumulated in fp32 as one
+ *               fma chain over the 3 n coordinates in index order -- the same for (a, b) and (b, a), so the relation below is symmetric bit for bit
+ *   neighbours  a ~ b iff ssd(a, b) <= cutoff^2 n, and a ~ a always (a structure holding a NaN is a neighbour of itself alone)
+ *   greedy      all structures start alive; repeat: the alive structure with the most alive neighbours (ties: the lowest index) is the centre of the
+ *               next cluster, its alive neighbours (itself included) are the members, which get the cluster's number as label and die; stop when nobody
+ *               is alive or max_clusters clusters exist (0: no cap).  Structures still alive at the cap keep label -1.  Clusters are numbered in order
+ *               of discovery and are NOT sorted.
+ *   structs [G*S,n,3] -> label [G*S] (cluster of every structure, within its group), centre [G*S] (per group: the centres' indices WITHIN the group,
+ *   -1 padded to S), size [G*S] (per group: members per cluster, 0 padded), count [G] (clusters per group); all four are DEVICE int32 arrays (spelled
+ *   void* here: this header names no mutable int32 pointer type).  rmsd (optional, [G,S,S] fp32): sqrt(ssd / n) of every pair, symmetric bit for bit.
+ *   ws: abopt_cluster_ws_bytes(G, S) bytes, 8-byte aligned (a bit matrix of S x ceil(S / 64) 8-byte words per group + one int32 per structure;
+ *   0 for G = 0 and for an S the call refuses).
+ * Two stream-ordered launches, nothing allocated, no host synchronisation.  1 <= S <= 16384 (beyond: ABOPT_EUNSUPPORTED), n >= 1, G S <= 2^31 - 1,
+ * G <= 65535, G = 0 is a no-op, cutoff finite and >= 0; every check precedes the first launch.  A group's result is bit-identical to a call on that
+ * group alone. */
+size_t abopt_cluster_ws_bytes(int G, int S);
+int abopt_cluster_poses_grouped(const float* structs, int G, int S, int n, float cutoff, int max_clusters, void* ws, size_t ws_bytes,
+                                void* label, void* centre, void* size, void* count, float* rmsd, abopt_stream stream);
 
 /* ---- Measurement hook (bench.py's roofline leg).  When enabled, every launch of the IPA-core kernel is bracketed
  * by hipEvents on the stream it is launched on; abopt_prof_collect synchronises those events and returns the number

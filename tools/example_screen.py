@@ -2,7 +2,10 @@
 stage and the designs the notebook's median filter keeps.
 
     python tools/example_screen.py [--poses 16 --designs 8 --redocks 8 --screened 1 --steps 100 --per-launch 8 --contig 97-103 --exclude CM
-                                    --dock-steps 20 --design-steps 20]
+                                    --dock-steps 20 --design-steps 20 --cluster-cutoff 2.0 --max-clusters 4 --redock-cutoff 2.0]
+
+--cluster-cutoff clusters the docked poses on the device and screens one centre per cluster: the run prints the number of clusters C,
+their sizes and the stage times.  How many clusters a trained model's poses fall into is unmeasured.
 
 The weights are not a trained checkpoint, so the numbers say nothing about antibodies; the stage times are what a screen of this size costs.
 """
@@ -35,6 +38,9 @@ def main():
     ap.add_argument('--contig', default='97-103')
     ap.add_argument('--seed', type=int, default=0)
     ap.add_argument('--exclude', default='', metavar='LETTERS', help='residue types no design may contain, e.g. CM (constrains the sampler itself)')
+    ap.add_argument('--cluster-cutoff', type=float, default=None, metavar='A', help='cluster the poses at this RMSD (no superposition) and screen the cluster centres only')
+    ap.add_argument('--max-clusters', type=int, default=None, metavar='M', help='at most M clusters (needs --cluster-cutoff)')
+    ap.add_argument('--redock-cutoff', type=float, default=None, metavar='A', help="cluster every design's re-docks at this RMSD: share of the largest cluster, cluster count")
     args = ap.parse_args()
     dev = torch.device('cuda:0')
     dock = synth.build_model(args.steps, 3, device=dev)                     # dock_cdr.yml: AbDock, full heavy atoms
@@ -47,6 +53,7 @@ def main():
     kw = dict(num_poses=args.poses, designs_per_pose=args.designs, redocks_per_design=args.redocks, screened_per_pose=args.screened,
               contig=args.contig, seed=args.seed, poses_per_launch=args.per_launch, redock_flag=heavy,
               dock_steps=args.dock_steps, design_steps=args.design_steps,
+              cluster_cutoff=args.cluster_cutoff, max_clusters=args.max_clusters, redock_cutoff=args.redock_cutoff,
               allowed_aa=model.aa_allowed_mask(one['aa'].shape[1], exclude=args.exclude, device=dev) if args.exclude else None)
     print(f'L={one["aa"].shape[1]} P={args.poses} S={args.designs} k={args.screened} D={args.redocks} T={args.steps} dock_steps={args.dock_steps or args.steps} design_steps={args.design_steps or args.steps} per_launch={args.per_launch} '
           f'contig={args.contig!r} device={torch.cuda.get_device_name(dev)}')
@@ -62,6 +69,12 @@ def main():
         torch.cuda.synchronize()
         total = time.perf_counter() - t0
         print(f'run {run}: ' + '  '.join(f'{k} {v:.3f} s' for k, v in times.items()) + f'  total {total:.3f} s')
+    if args.cluster_cutoff is not None:
+        print(f'{res["cluster_centre"].numel()} clusters of {args.poses} poses at {args.cluster_cutoff} A: sizes {res["cluster_size"].tolist()} centres {res["cluster_centre"].tolist()} '
+              f'(rows below: cluster c = pose cluster_centre[c])')
+    if args.redock_cutoff is not None:
+        print(f're-docks at {args.redock_cutoff} A: largest cluster share {[round(v, 3) for v in res["redock_cluster_frac"].flatten().tolist()]} '
+              f'clusters {res["redock_clusters"].flatten().tolist()}')
     keep = screen.screen_filter(res)
     print(f'{int(keep.sum())} of {keep.numel()} screened designs pass the median filter')
     print(f'{"pose":>4} {"design":>6} {"seq":>9} {"AAR":>6} {"PPL":>7} {"DockQ_avg":>9} {"DockQ_std":>9} {"prmsd_avg":>9} {"prmsd_std":>9}')
