@@ -60,14 +60,24 @@ struct Carver {
 constexpr int F = 128, FI = F + 4;
 constexpr int OUT_KSPLIT = 2;     // out_transform (K = 1824, N = 128) has only M/64 * 2 tiles: split K so it fills the chip
 
-struct GaScratch { float *proj, *feat, *u, *kvf, *qf, *split; size_t split_floats; float* xt[2]; };
+// kvf / qf [0]: the fragment pair of its own; [1]: a second pair for carried fragments (forward_plan.h: frag_slot), aliased onto proj | feat -- carved back to back,
+// and idle while carried fragments are live: their producer and their consumer both run node_frags + the fused block kernel, which touch neither (15.3 KB per
+// row against 9.2 KB of fragments per padded row: it fits from L = 32 on; frag2 says whether it does, and no workspace size grows)
+struct GaScratch { float *proj, *feat, *u, *kvf[2], *qf[2], *split; size_t split_floats; float* xt[2]; bool frag2; };
 static GaScratch carve_ga(Carver& cv, int64_t M, int N, int L) {
     GaScratch s;
+    const size_t off0 = cv.off;
     s.proj = cv.f((size_t)M * NP);
     s.feat = cv.f((size_t)M * ABOPT_IPA_FEAT);
+    {
+        Carver alias(s.proj, cv.off - off0);                                // over proj | feat, with the same 256-byte carves (a size query: no base, no pointers)
+        s.frag2 = plan_frag2_fits((size_t)M * NP, (size_t)M * ABOPT_IPA_FEAT, ipa_kvfrag_floats(N, L), ipa_qfrag_floats(N, L));
+        s.kvf[1] = s.frag2 ? alias.f(ipa_kvfrag_floats(N, L)) : nullptr;
+        s.qf[1] = s.frag2 ? alias.f(ipa_qfrag_floats(N, L)) : nullptr;
+    }
     s.u = cv.f((size_t)M * F * OUT_KSPLIT);
-    s.kvf = cv.f(ipa_kvfrag_floats(N, L));
-    s.qf = cv.f(ipa_qfrag_floats(N, L));
+    s.kvf[0] = cv.f(ipa_kvfrag_floats(N, L));
+    s.qf[0] = cv.f(ipa_qfrag_floats(N, L));
     s.split_floats = ipa_split_ws_floats(N, L);
     s.split = s.split_floats ? cv.f(s.split_floats) : nullptr;
     s.xt[0] = cv.f((size_t)M * F);          // node features as two fp16 terms, ping-pong between blocks (written by the tail / mixer, read by node_frags)
@@ -75,12 +85,12 @@ static GaScratch carve_ga(Carver& cv, int64_t M, int N, int L) {
     return s;
 }
 
-// The six environment switches of the forward path, read once per C-ABI call (never cached: callers flip them between the calls of one process)
+// The seven environment switches of the forward path, read once per C-ABI call (never cached: callers flip them between the calls of one process)
 static Switches read_switches() {
     const auto first = [](const char* name) { const char* e = getenv(name); return e ? e[0] : '\0'; };
     const char c32 = first("ABOPT_CORE32");
     return {c32 == '0' ? 0 : (c32 == '1' ? 1 : -1), getenv("ABOPT_CORE_NO_SPLIT") != nullptr, first("ABOPT_FUSE_TAIL") != '0', first("ABOPT_X_TERMS") != '0',
-            first("ABOPT_FUSE_HEADS") != '0', first("ABOPT_FUSE_STEP") != '0'};
+            first("ABOPT_FUSE_HEADS") != '0', first("ABOPT_FUSE_STEP") != '0', first("ABOPT_FUSE_NODE") != '0'};
 }
 
 // What every forward entry knows of its ForwardQuery (forward_plan.h): geometry, the CU count (asked once per entry), operands and scratch held, which blocks are
@@ -92,6 +102,7 @@ static int forward_query(int N, int L, int z_shared, const GaScratch& s, const a
     q->N = N; q->L = L; q->z_shared = z_shared;
     q->cache = pbc != nullptr; q->terms = pbc && pair_terms;
     q->split_ws = s.split != nullptr; q->split_ws_floats = s.split_floats;
+    q->frag2 = s.frag2;
     q->num_blocks = num_blocks;
     for (int i = 0; i < num_blocks; ++i) q->blocks[i] = {blocks[i].w_node_frag != nullptr, blocks[i].w_out_frag != nullptr, blocks[i].w_mlp_frag != nullptr, blocks[i].w_out_terms != nullptr};
     q->sw = read_switches();
@@ -101,25 +112,33 @@ static int forward_query(int N, int L, int z_shared, const GaScratch& s, const a
 // what one block runs on, besides its plan, its weights and the scratch
 struct BlockArgs { const float *R, *t, *x, *z; const uint8_t* mask; float* x_out; const float *pbc = nullptr, *pair_terms = nullptr; const abopt_ga_debug* dbg = nullptr; float* feat_out = nullptr; };
 
-static int ga_block(const BlockPlan& p, const ForwardQuery& q, const abopt_ga_weights* w, const BlockArgs& a, const GaScratch& s, hipStream_t st) {
+// wnext: the next block's weights where the plan has this block write that block's fragments (carry_next), into the other fragment pair
+static int ga_block(const BlockPlan& p, const ForwardQuery& q, const abopt_ga_weights* w, const BlockArgs& a, const GaScratch& s, hipStream_t st,
+                    const abopt_ga_weights* wnext = nullptr, int next_qk_terms = 0) {
     const int N = q.N, L = q.L;
+    float *const qf = s.qf[p.frag_slot], *const kvf = s.kvf[p.frag_slot];
+    ABOPT_CHECK_ARG(qf && kvf && (!p.carry_next || (wnext && s.qf[1 - p.frag_slot])), "ga_block: the plan carries fragments the workspace or the weight list cannot hold");
     const int64_t M = (int64_t)N * L;
     const float* pair_terms = p.qk_terms ? a.pair_terms : nullptr;          // the term forms go together: q / k term fragments only for the core that reads pair terms
     float* xt_out = p.xt_write >= 0 ? s.xt[p.xt_write] : nullptr;
     int rc;
     // node projections q|k|v|qp|kp|vp, points to the global frame, MFMA fragment layout: one fused kernel when the packed weights are given
-    if (p.node == NodeForm::Kernel) {
-        if ((rc = launch_node_frags(a.x, w->w_node_frag, a.R, a.t, w->spatial_coef, s.qf, s.kvf, N, L, st, q.cus, p.qk_terms, p.xt_read >= 0 ? s.xt[p.xt_read] : nullptr))) return rc;
+    if (p.carried) {
+        // the previous block's fused kernel wrote them as its last phase
+    } else if (p.node == NodeForm::Kernel) {
+        if ((rc = launch_node_frags(a.x, w->w_node_frag, a.R, a.t, w->spatial_coef, qf, kvf, N, L, st, q.cus, p.qk_terms, p.xt_read >= 0 ? s.xt[p.xt_read] : nullptr))) return rc;
     } else {
         if ((rc = launch_linear(a.x, F, w->w_node, F, nullptr, s.proj, NP, (int)M, ABOPT_NODE_PROJ, F, false, st))) return rc;
-        if ((rc = launch_ipa_frags(s.proj, a.R, a.t, w->spatial_coef, s.qf, s.kvf, N, L, st))) return rc;
+        if ((rc = launch_ipa_frags(s.proj, a.R, a.t, w->spatial_coef, qf, kvf, N, L, st))) return rc;
     }
     // core + tail as one kernel (feat stays on the chip); bit-identical to the two launches below
-    if (p.tail == TailForm::InCore)
-        return launch_ipa_block_fused(p.core, s.qf, s.kvf, a.z, a.mask, a.R, a.t, a.pbc, N, L, st, q.z_shared, w->w_out_terms, w->w_mlp_frag, a.x, w->b_out, w->ln1_gamma,
-                                      w->ln1_beta, w->b_mlp0, w->b_mlp1, w->b_mlp2, w->ln2_gamma, w->ln2_beta, a.x_out, pair_terms, xt_out);
+    if (p.tail == TailForm::InCore) {
+        const NodeCarryArgs nc{wnext ? wnext->w_node_frag : nullptr, wnext ? wnext->spatial_coef : nullptr, s.qf[1 - p.frag_slot], s.kvf[1 - p.frag_slot], next_qk_terms};
+        return launch_ipa_block_fused(p.core, qf, kvf, a.z, a.mask, a.R, a.t, a.pbc, N, L, st, q.z_shared, w->w_out_terms, w->w_mlp_frag, a.x, w->b_out, w->ln1_gamma,
+                                      w->ln1_beta, w->b_mlp0, w->b_mlp1, w->b_mlp2, w->ln2_gamma, w->ln2_beta, a.x_out, pair_terms, xt_out, p.carry_next ? &nc : nullptr);
+    }
     float* feat = (a.dbg && a.dbg->feat) ? a.dbg->feat : (a.feat_out ? a.feat_out : s.feat);
-    if ((rc = launch_ipa_core(p.core, s.qf, s.kvf, a.z, a.mask, a.R, a.t, w->w_pair_bias, feat, a.dbg ? a.dbg->logits : nullptr, a.dbg ? a.dbg->alpha : nullptr, a.pbc,
+    if ((rc = launch_ipa_core(p.core, qf, kvf, a.z, a.mask, a.R, a.t, w->w_pair_bias, feat, a.dbg ? a.dbg->logits : nullptr, a.dbg ? a.dbg->alpha : nullptr, a.pbc,
                               N, L, st, q.z_shared, s.split, pair_terms))) return rc;
     // out_transform -> mask -> +x -> LN1 -> MLP -> +res -> LN2
     if (p.tail == TailForm::OutLnMlp)
@@ -442,7 +461,8 @@ static int ga_encoder(const EncoderPlan& e, const ForwardQuery& q, const abopt_g
     for (int i = 0; i < e.num_blocks; ++i) {            // a plan that ends in an Unsupported core ends here with that core's error
         a.x_out = ((q.num_blocks - 1 - i) % 2 == 0) ? x_out : pong;
         a.pbc = pbc ? pbc + (size_t)i * pair_bias_layer_floats(q.z_shared ? q.N / q.z_shared : q.N, q.L) : nullptr;
-        if (int rc = ga_block(e.blocks[i], q, &blocks[i], a, s, st)) return rc;
+        const bool carry = e.blocks[i].carry_next;                          // (then block i + 1 is planned: its fragments take the form its own plan asks for)
+        if (int rc = ga_block(e.blocks[i], q, &blocks[i], a, s, st, carry ? &blocks[i + 1] : nullptr, carry ? (int)e.blocks[i + 1].qk_terms : 0)) return rc;
         a.x = a.x_out;
     }
     if (q.num_blocks == 0) ABOPT_HIP(hipMemcpyAsync(x_out, a.x, (size_t)q.N * q.L * F * sizeof(float), hipMemcpyDeviceToDevice, st));

@@ -1,6 +1,7 @@
 // Which launches a denoiser forward is made of: the ONE place that decides (api.hip reads the switches once per entry, builds a ForwardQuery and walks the plan;
 // the launchers of ipa_core.hip / ipa.hip take the CorePlan they are handed).  plan_ipa_core (ipa_plan.h) is called from here and from nowhere else on the
-// forward path.  Plain host C++17, no HIP: tests/forward_plan_table.cpp tabulates the functions without a device (tests/test_forward_plan.py).
+// forward path.  Plain host C++17, no HIP: tests/forward_plan_table.cpp and tests/forward_plan_carry_table.cpp tabulate the functions without a device
+// (tests/test_forward_plan.py, tests/test_forward_plan_carry.py).
 #pragma once
 #include "ipa_plan.h"
 
@@ -16,6 +17,7 @@ struct Switches {
     bool x_terms = true;            // ABOPT_X_TERMS=0: no kernel writes x as fp16 terms, every node_frags splits x for itself
     bool fuse_heads = true;         // ABOPT_FUSE_HEADS=0: the heads' geometric epilogue as a launch of its own
     bool fuse_step = true;          // ABOPT_FUSE_STEP=0: a denoising step's transitions and the next evaluation's mixer as launches of their own (abopt_eps_net_step)
+    bool fuse_node = true;          // ABOPT_FUSE_NODE=0: every block's node_frags as a launch of its own (no block writes its successor's fragments)
 };
 
 struct BlockWeights { bool node_frag, out_frag, mlp_frag, out_terms; };     // which packed operands of abopt_ga_weights are given
@@ -35,6 +37,7 @@ struct ForwardQuery {
     // abopt_eps_net_step only: the forward is followed by the step's transitions; they report the perplexity; the workspace holds this evaluation's mixer output
     // (carry_in: the previous call of the entry wrote it); the next evaluation's is wanted (carry_out)
     bool step = false, ppl = false, carry_in = false, carry_out = false;
+    bool frag2 = false;             // the workspace holds a second fragment pair (api.hip: carve_ga aliases it onto proj | feat where it fits)
 };
 
 enum class NodeForm { Kernel, Gemm };               // node_frags | projection GEMM + ipa_frags
@@ -45,6 +48,10 @@ struct BlockPlan {
     CorePlan core;
     TailForm tail;
     int xt_read, xt_write;          // slot of the workspace's x-terms pair that node_frags reads / the tail writes; -1: none
+    // Carried fragments (plan_encoder): the fused kernel of block i (ipa_core32_kernel<true, *, true>) ends by writing block i + 1's fragments from the rows it holds
+    bool carry_next = false;        // this block's fused kernel also writes the next block's fragments
+    bool carried = false;           // this block's fragments were written by its predecessor: no node_frags launch
+    int frag_slot = 0;              // which of the workspace's fragment pairs the block's core reads (and its own node_frags, if it runs, writes)
 };
 struct EncoderPlan {
     bool ok;                        // false: the last planned block's core is Unsupported and nothing is planned after it
@@ -62,6 +69,12 @@ struct NetPlan {
     bool mixer_launch;              // the mixer step runs at the head of this call (false: carried in by the previous call's fused tail)
     bool step_carry;                // the fused tail also writes the next evaluation's mixer output (x, its terms in slot mixer_xt, R) into the workspace
 };
+
+// Whether a second fragment pair fits over proj | feat as the workspace carves them (256-byte carves; api.hip: carve_ga sets ForwardQuery::frag2 from this)
+inline bool plan_frag2_fits(size_t proj_floats, size_t feat_floats, size_t kvfrag_floats, size_t qfrag_floats) {
+    const auto carve = [](size_t nfloat) { return (nfloat * sizeof(float) + 255) & ~(size_t)255; };
+    return carve(kvfrag_floats) + carve(qfrag_floats) <= carve(proj_floats) + carve(feat_floats);
+}
 
 inline CoreQuery core_query(const ForwardQuery& q) {
     return {q.N, q.L, q.z_shared, q.cus, q.cache, q.dump, q.split_ws, q.split_ws_floats, q.sw.core32_override, q.sw.no_split};
@@ -89,13 +102,30 @@ inline BlockPlan plan_block(const ForwardQuery& q, int i, int produced = -1, int
     return p;
 }
 
-// The blocks of an encoder: block 0's producer wrote `produced` (the mixer; -1: nobody), block i writes slot i & 1
+// The blocks of an encoder: block 0's producer wrote `produced` (the mixer; -1: nobody), block i writes slot i & 1.
+// Carried fragments: block i + 1 is carried iff block i's tail is InCore (its workgroups end holding their 32 finished rows), block i + 1's node step is the kernel
+// (packed weights) and its tail is InCore too (the second fragment pair aliases proj | feat, which only Gemm node steps and out-of-core tails touch), the switch
+// is on, the workspace has the second pair and nobody debugs.  A carried block reads the slot its producer wrote, which is NEVER the slot the producer's own
+// core reads: other workgroups of the sample are still in their key loops on that one when the first workgroup starts writing.  So slots alternate along a
+// chain; block 0 and every uncarried block use slot 0 (their own node_frags writes it behind a launch boundary).
+// One round: measured, not structural.  The phase costs a workgroup about 18 us for its 32 rows whatever the batch (the next block's 1.18 MB of weights come from L2 per
+// workgroup), the launch keeps its weights in LDS and costs 24 us per 256 workgroups' worth of rows.  Where the fused kernel's workgroups fit the CUs in ONE round (the bench
+// shape: 256 on 256) the phase wins by the launch's ramp and boundary; carried over several rounds it lost (N = 64 x L = 256: 2.05 -> 2.23 ms per step, N = 1000 x L = 48:
+// 3.70 -> 3.87; profiles/node_carry_shapes.txt), so such a forward is not carried.  DESIGN.md section 3.3 has what is and is not known about the cause.
 inline EncoderPlan plan_encoder(const ForwardQuery& q, int produced = -1) {
     EncoderPlan e{true, 0, {}};
     for (int i = 0; i < q.num_blocks && e.ok; ++i) {
         const BlockPlan& p = e.blocks[e.num_blocks++] = plan_block(q, i, produced, i & 1);
         produced = p.xt_write;
         e.ok = p.core.form != CoreForm::Unsupported;
+    }
+    if (!e.ok || !q.sw.fuse_node || !q.frag2 || q.dbg) return e;
+    for (int i = 0; i + 1 < e.num_blocks; ++i) {
+        BlockPlan &a = e.blocks[i], &b = e.blocks[i + 1];
+        if (a.tail != TailForm::InCore || b.node != NodeForm::Kernel || b.tail != TailForm::InCore) continue;
+        if (a.core.grid > (unsigned)q.cus) continue;                        // more than one round of workgroups: node_frags as a launch is the faster form (see above)
+        a.carry_next = b.carried = true;
+        b.frag_slot = 1 - a.frag_slot;
     }
     return e;
 }

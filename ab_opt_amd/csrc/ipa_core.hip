@@ -25,6 +25,7 @@
 #include <cstdlib>
 #include <type_traits>
 #include "tail_common.h"
+#include "node_task.h"
 #include "kernels.h"
 
 // Layout of a layer's slab of the pair-bias cache: chunk-major, [chunk][row of the batch][12 x 16].  The workgroups of a launch read the same
@@ -860,6 +861,9 @@ struct TailArgs {
     float* out;
     unsigned* xt;           // optional: the output rows as two fp16 terms as well (tail_common.h: tail_p2_run)
 };
+// the kernel's tail arguments: NF adds the operands of the carried projections behind them, every other instantiation keeps TailArgs' layout
+template <bool NF> struct TailArgsT : TailArgs {};
+template <> struct TailArgsT<true> : TailArgs { NodeCarryArgs nc; };
 constexpr int C32_LOOP_LDS_FLOATS = 3 * 32 * SROW + 2 * 32 * SCLD + 32 * SCLD + 32 * 32;      // sp | scl | lsum | mlr (then the key mask)
 __host__ __device__ constexpr size_t core32_lds_bytes(int nchunk) { return sizeof(float) * C32_LOOP_LDS_FLOATS + (size_t)nchunk * JC; }     // ipa_core32_kernel<false, ZT>
 constexpr int C32F_PTS_OFF = ((C32_LOOP_LDS_FLOATS * 4 + 2048 + 255) / 256) * 256;               // aggregated points [32][12][24] fp32, behind the key mask of L <= 2048
@@ -888,6 +892,36 @@ __device__ __forceinline__ void stage_put4(char* buf, int row, int col, float v0
     *reinterpret_cast<uint2*>(d + OT_PLANE) = make_uint2(l0, l1);
 }
 
+// NF: the NEXT block's node projections as the last phase of the fused kernel (forward_plan.h: carry_next).  tail_p2_run has left the fp16 terms of the workgroup's
+// 32 finished rows in an LDS tile (the u tile: dead since phase 2's first barrier) -- exactly one row-tile pair of node_frags.  The 24 (head, half) tasks of the pair
+// go three to a wave (wave w: half w & 1 of heads w >> 1, + 4, + 8: 3 x 144 MFMAs for every wave), with the next block's weight fragments streamed from L2
+// NF_CARRY_WD - 1 steps ahead (node_task.h) and the fragments stored where node_frags would store them, in the OTHER fragment pair of the workspace: the rest of
+// the sample's workgroups may still be in their key loops on this launch's own pair.  Inlined into the kernel: as a noinline function (persist_point_epilogue is one) it
+// needs most of the register file, whose upper part is callee-saved, and cost the kernel 392 bytes of scratch per lane; inlined the kernel keeps 254 VGPRs and no
+// scratch, at the price of a scalar register allocation that differs from the two-argument kernel's from the prologue on.  R and t are the
+// launch's own (ga.py:190-193: every block of an encoder has the same frames).
+constexpr int NF_CARRY_WD = 9;
+static_assert(2 * H == 3 * (NTH2 / 64), "three (head, half) tasks per wave");
+static_assert(MR * NF_XLDS_STRIDE * 4 <= MR * XLD * 4, "the x-term tile takes the place of the u tile");
+__device__ __forceinline__ void node_carry_phase(NfLdsTerms xt, NodeCarryArgs nc, const float* __restrict__ R, const float* __restrict__ t, int L, int nchunk,
+                                                           int n, int ib, int tid) {
+    const int lane = tid & 63, fm = lane & 15, kq = lane >> 4;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int tile0 = n * nchunk + 2 * ib, tiles_end = (n + 1) * nchunk;    // the second row tile is skipped where it lies past the sample's last chunk
+    const float winv = nc.w_node_frag[(int64_t)H * NF_HEAD_VEC * 4 + 1];      // 1 / S behind the packed weights
+#pragma unroll 1
+    for (int k = 0; k < 3; ++k) {
+        const int h = __builtin_amdgcn_readfirstlane((wave >> 1) + 4 * k);
+        const float sc = nc.spatial_coef[h];
+        const float gamma = (sc > 20.f) ? sc : log1pf(expf(sc));                 // as node_frags_kernel
+        const float ch_ = (-1.f * gamma * 0.16666666666666666f) / 2.f;
+        const float m2c = -2.f * ch_;
+        const u32x4* wg = reinterpret_cast<const u32x4*>(nc.w_node_frag) + (int64_t)h * NF_HEAD_VEC + (wave & 1) * NF_LDS_VEC;
+        if (wave & 1) nf_task<1, NfX::LdsTerms, NF_CARRY_WD>(nullptr, xt, wg, R, t, nc.qfrag, nc.kvfrag, L, nchunk, tiles_end, tile0, h, ch_, m2c, winv, lane, fm, kq, nc.qk_terms, ib * BI2);
+        else          nf_task<0, NfX::LdsTerms, NF_CARRY_WD>(nullptr, xt, wg, R, t, nc.qfrag, nc.kvfrag, L, nchunk, tiles_end, tile0, h, ch_, m2c, winv, lane, fm, kq, nc.qk_terms, ib * BI2);
+    }
+}
+
 // ZT (round 6): the pair aggregation sum_j P z on the fp16 matrix instructions.  z arrives PRE-SPLIT (`zt`, pair_terms_kernel: once per sample() call,
 // like the bias cache) as two fp16 terms of S_ic z packed along K -- per (query row, chunk, channel tile) a lane's 16 bytes are {h(keys 4 kq .. + 3),
 // l(same keys)} of channel 4 fm + tile: exactly one A operand of v_mfma_f32_16x16x32_f16, and the same 4 bytes per value the fp32 stream has.  The lane's own
@@ -895,11 +929,12 @@ __device__ __forceinline__ void stage_put4(char* buf, int row, int col, float v0
 // B operand {P_h, P_h}: one 16-cycle MFMA per channel tile gives P_h z_h + P_h z_l, a K = 16 MFMA P_l z_h -- 8 MFMAs of 16 cycles per row-chunk instead
 // of 16 of 32 (P_l z_l <= 2^-22 relative is dropped, as in ipa_common.h).  S_ic is a power of two per (query row, channel) (max_j |z[i,j,c]| S_ic in [2^13, 2^14)),
 // 2^-14 / S_ic (`zsc`, [rows][64]) leaves through the final normalisation: exact.  P itself, its row sums and everything the C waves compute are those of the fp32 form, bit for bit.  Measured (profiles/r06_a_*): -7 % of the replayed step.
-template <bool FUSE, bool ZT>
+template <bool FUSE, bool ZT, bool NF = false>
 __global__ __launch_bounds__(NTH2) void ipa_core32_kernel(const float* __restrict__ qfrag, const float* __restrict__ kvfrag, const float* __restrict__ z,
                                                           const uint8_t* __restrict__ mask, const float* __restrict__ R, const float* __restrict__ t,
                                                           float* __restrict__ feat, const float* __restrict__ pbc, int L, int nib2, int xcd_remap, int z_shared,
-                                                          TailArgs ta, int prof_slot, const float* __restrict__ zt, const float* __restrict__ zsc) {
+                                                          TailArgsT<NF> ta, int prof_slot, const float* __restrict__ zt, const float* __restrict__ zsc) {
+    static_assert(FUSE || !NF, "the carried projections follow the fused tail");
     extern __shared__ __attribute__((aligned(16))) char smem_raw[];
     float* sp = reinterpret_cast<float*>(smem_raw);                     // [3][BI2][SROW]
     float* scl = sp + 3 * BI2 * SROW;                                   // [2][BI2][SCLD]
@@ -1577,7 +1612,12 @@ __global__ __launch_bounds__(NTH2) void ipa_core32_kernel(const float* __restric
         const float (*us)[XLD] = reinterpret_cast<const float (*)[XLD]>(smem_raw + C32F_U_OFF);
         auto get_u = [&](int rl) { return *reinterpret_cast<const float2*>(&us[rl][2 * lane]); };
         tail_p2_run<NTH2 / 64, false>(pre, get_u, reinterpret_cast<float (*)[XLD]>(smem_raw + C32F_YS_OFF), bias, smem_raw + C32F_APA_OFF,
-                                      smem_raw + C32F_PTS_OFF, ta.wmf, ta.g2, ta.be2, ta.out, nullptr, 0, row0, row_end, wave, lane, ta.xt);
+                                      smem_raw + C32F_PTS_OFF, ta.wmf, ta.g2, ta.be2, ta.out, nullptr, 0, row0, row_end, wave, lane, ta.xt,
+                                      NF ? reinterpret_cast<unsigned*>(smem_raw + C32F_U_OFF) : nullptr, NF_XLDS_STRIDE);
+        if constexpr (NF) {
+            __syncthreads();                                                // the x terms of the 32 rows are in LDS
+            node_carry_phase((NfLdsTerms)(smem_raw + C32F_U_OFF), ta.nc, R, t, L, nchunk, n, ib, tid);
+        }
     }
     if (blockIdx.x == 0 && tid == 0) { g_clock_probe[0] = clock64() - probe_c0; g_clock_probe[1] = wall_clock64() - probe_w0; }
     if (prof_slot >= 0 && tid == 0) atomicMax(&g_prof_span[prof_slot][1], (unsigned long long)wall_clock64());
@@ -1787,17 +1827,17 @@ static int launch_core_variant(const CorePlan& plan, const float* qfrag, const f
 }
 
 // ipa_core32_kernel<FUSE, ZT> from a Core32 plan: the core alone into `feat`, or (FUSE) core + tail with `ta`.  ZT: `pair_terms` is given.
-template <bool FUSE, bool ZT>
+template <bool FUSE, bool ZT, bool NF = false>
 static int launch_core32(const CorePlan& plan, const float* qfrag, const float* kvfrag, const float* z, const uint8_t* mask, const float* R, const float* t, float* feat,
-                         const float* pbc, int N, int L, hipStream_t st, int z_shared, const TailArgs& ta, const float* pair_terms) {
+                         const float* pbc, int N, int L, hipStream_t st, int z_shared, const TailArgsT<NF>& ta, const float* pair_terms) {
     const int nib2 = (L + BI2 - 1) / BI2, nchunk = (L + JC - 1) / JC;
     const size_t lds = FUSE ? (size_t)C32F_LDS_BYTES : core32_lds_bytes(nchunk);
     ABOPT_CHECK_ARG(lds <= 160 * 1024, "ipa_core: L=%d needs %zu bytes of LDS for the key mask (max 163840)", L, lds);
     static LdsConfig lds_cfg;                                               // per instantiation
-    if (int rc = ensure_dynamic_lds(reinterpret_cast<const void*>(ipa_core32_kernel<FUSE, ZT>), lds, lds_cfg)) return rc;
+    if (int rc = ensure_dynamic_lds(reinterpret_cast<const void*>(ipa_core32_kernel<FUSE, ZT, NF>), lds, lds_cfg)) return rc;
     const float* zsc = ZT ? pair_terms + pair_terms_floats(z_shared ? N / z_shared : N, L) : nullptr;
     prof::begin(st);
-    hipLaunchKernelGGL((ipa_core32_kernel<FUSE, ZT>), dim3(plan.grid), dim3(NTH2), lds, st, qfrag, kvfrag, z, mask, R, t, feat, pbc, L, nib2, plan.remap, z_shared, ta,
+    hipLaunchKernelGGL((ipa_core32_kernel<FUSE, ZT, NF>), dim3(plan.grid), dim3(NTH2), lds, st, qfrag, kvfrag, z, mask, R, t, feat, pbc, L, nib2, plan.remap, z_shared, ta,
                        prof::next_span_slot(), ZT ? pair_terms : nullptr, zsc);
     prof::end(st);
     ABOPT_LAUNCH_CHECK();
@@ -1809,9 +1849,20 @@ static int launch_core32(const CorePlan& plan, const float* qfrag, const float* 
 int launch_ipa_block_fused(const CorePlan& plan, const float* qfrag, const float* kvfrag, const float* z, const uint8_t* mask, const float* R, const float* t,
                            const float* pair_bias_cache, int N, int L, hipStream_t st, int z_shared, const float* wot, const float* wmf, const float* x,
                            const float* ubias, const float* g1, const float* be1, const float* b0, const float* b1, const float* b2, const float* g2,
-                           const float* be2, float* out, const float* pair_terms, float* xt_out) {
+                           const float* be2, float* out, const float* pair_terms, float* xt_out, const NodeCarryArgs* carry) {
     ABOPT_CHECK_ARG(plan.form == CoreForm::Core32 && pair_bias_cache && wot && wmf, "ipa_block_fused: not a 32-row plan with a cache and packed tail weights");
-    const TailArgs ta{wot, wmf, x, ubias, g1, be1, b0, b1, b2, g2, be2, out, reinterpret_cast<unsigned*>(xt_out)};
+    const TailArgs ta0{wot, wmf, x, ubias, g1, be1, b0, b1, b2, g2, be2, out, reinterpret_cast<unsigned*>(xt_out)};
+    if (carry) {
+        ABOPT_CHECK_ARG(carry->w_node_frag && carry->spatial_coef && carry->qfrag && carry->kvfrag && carry->qfrag != qfrag && carry->kvfrag != kvfrag,
+                        "ipa_block_fused: the next block's fragments need its packed weights and a fragment pair this launch does not read");
+        TailArgsT<true> tn;
+        static_cast<TailArgs&>(tn) = ta0;
+        tn.nc = *carry;
+        return pair_terms ? launch_core32<true, true, true>(plan, qfrag, kvfrag, z, mask, R, t, nullptr, pair_bias_cache, N, L, st, z_shared, tn, pair_terms)
+                          : launch_core32<true, false, true>(plan, qfrag, kvfrag, z, mask, R, t, nullptr, pair_bias_cache, N, L, st, z_shared, tn, nullptr);
+    }
+    TailArgsT<false> ta;
+    static_cast<TailArgs&>(ta) = ta0;
     return pair_terms ? launch_core32<true, true>(plan, qfrag, kvfrag, z, mask, R, t, nullptr, pair_bias_cache, N, L, st, z_shared, ta, pair_terms)
                       : launch_core32<true, false>(plan, qfrag, kvfrag, z, mask, R, t, nullptr, pair_bias_cache, N, L, st, z_shared, ta, nullptr);
 }
@@ -1853,8 +1904,8 @@ int launch_ipa_core_kernel(const CorePlan& plan, const float* qfrag, const float
         set_error("ipa_core: the logits dump reads a pair-bias cache through 32-bit offsets and this one (%d x %d rows) is 4 GB or more per layer; pass none", N, L);
         return ABOPT_EUNSUPPORTED;
     case CoreForm::Core32:
-        return pair_terms ? launch_core32<false, true>(plan, qfrag, kvfrag, z, mask, R, t, feat, pair_bias_cache, N, L, st, z_shared, TailArgs{}, pair_terms)
-                          : launch_core32<false, false>(plan, qfrag, kvfrag, z, mask, R, t, feat, pair_bias_cache, N, L, st, z_shared, TailArgs{}, nullptr);
+        return pair_terms ? launch_core32<false, true>(plan, qfrag, kvfrag, z, mask, R, t, feat, pair_bias_cache, N, L, st, z_shared, TailArgsT<false>{}, pair_terms)
+                          : launch_core32<false, false>(plan, qfrag, kvfrag, z, mask, R, t, feat, pair_bias_cache, N, L, st, z_shared, TailArgsT<false>{}, nullptr);
     case CoreForm::Persist: {
         const size_t lds = persist_lds_bytes(nchunk);
         ABOPT_CHECK_ARG(lds <= 160 * 1024, "ipa_core: L=%d needs %zu bytes of LDS for the key masks (max 163840)", L, lds);

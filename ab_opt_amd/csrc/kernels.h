@@ -34,11 +34,15 @@ int launch_ipa_core(const CorePlan& plan, const float* qfrag, const float* kvfra
                     float* split_ws = nullptr /* scratch of the key-split form (small batches), ipa_split_ws_floats(N, L) */,
                     const float* pair_terms = nullptr /* abopt_pair_terms blob of the same pair_feat: the 32-row kernels then aggregate on the fp16 matrix instructions */);
 
+// What the fused block kernel needs to write the NEXT block's fragments as its last phase (forward_plan.h: carry_next): that block's packed projection weights and
+// spatial coefficients, the form of its q / k slots, and the fragment pair to write -- never the pair the launch itself reads
+struct NodeCarryArgs { const float *w_node_frag, *spatial_coef; float *qfrag, *kvfrag; int qk_terms; };
 // ipa_core.hip: core + tail of a block in one launch, from a Core32 plan
 int launch_ipa_block_fused(const CorePlan& plan, const float* qfrag, const float* kvfrag, const float* z, const uint8_t* mask, const float* R, const float* t,
                            const float* pair_bias_cache, int N, int L, hipStream_t st, int z_shared, const float* wot /* W_out as bf16 terms */, const float* wmf, const float* x,
                            const float* ubias, const float* g1, const float* be1, const float* b0, const float* b1, const float* b2, const float* g2,
-                           const float* be2, float* out, const float* pair_terms = nullptr, float* xt_out = nullptr);
+                           const float* be2, float* out, const float* pair_terms = nullptr, float* xt_out = nullptr,
+                           const NodeCarryArgs* carry = nullptr /* the next block's fragments are written too (ipa_core32_kernel<true, *, true>) */);
 
 // node_frags.hip: x [N*L,128] -> qfrag / kvfrag directly (projection GEMM + frame transform + fragment layout in one kernel)
 size_t node_wfrag_floats();

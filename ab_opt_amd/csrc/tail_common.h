@@ -201,7 +201,7 @@ template <int NW, bool DUMP, class GetU>
 __device__ __forceinline__ void tail_p2_run(TailP2Pre<NW>& pre, GetU&& get_u, float (*ys)[XLD], float (*bias)[F], char* apA, char* apB,
                                             const float* __restrict__ wmf, const float* __restrict__ g2, const float* __restrict__ be2,
                                             float* __restrict__ out, float* __restrict__ dump, int64_t slab, int64_t row0, int64_t row_end,
-                                            int wave, int lane, unsigned* __restrict__ xt_out = nullptr) {
+                                            int wave, int lane, unsigned* __restrict__ xt_out = nullptr, unsigned* xt_lds = nullptr, int xt_lds_stride = 0) {
     constexpr int RW = MR / NW;
     const int fm = lane & 15, kq = lane >> 4;
     const bool mlpw = wave < 8;                                                                          // waves 0..7 own the eight 16-column tiles
@@ -292,7 +292,12 @@ __device__ __forceinline__ void tail_p2_run(TailP2Pre<NW>& pre, GetU&& get_u, fl
                 reinterpret_cast<float2*>(out + row * F)[lane] = make_float2(o0, o1);
                 // round 6: the same row as two fp16 terms ([64 words of high terms | 64 words of low terms], split_pair2) for the NEXT block's node_frags, whose 24
                 // (head, half) workgroups would otherwise each split these values again
-                if (xt_out) { unsigned h_, l_; split_pair2(o0, o1, h_, l_); xt_out[row * F + lane] = h_; xt_out[row * F + 64 + lane] = l_; }
+                // (xt_lds: the same two words into an LDS tile [MR rows][xt_lds_stride words] as well -- the fused block kernel's last phase projects them for the next block)
+                if (xt_out || xt_lds) {
+                    unsigned h_, l_; split_pair2(o0, o1, h_, l_);
+                    if (xt_out) { xt_out[row * F + lane] = h_; xt_out[row * F + 64 + lane] = l_; }
+                    if (xt_lds) { xt_lds[(wave * RW + rr) * xt_lds_stride + lane] = h_; xt_lds[(wave * RW + rr) * xt_lds_stride + 64 + lane] = l_; }
+                }
             }
         }
     }
