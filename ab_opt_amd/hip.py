@@ -13,7 +13,7 @@ import torch
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # ABOPT_LIB_PATH: developer override to load a variant build of the same ABI (csrc/Makefile VARIANT=...: A/B of two source trees)
 LIB_PATH = os.environ.get('ABOPT_LIB_PATH') or os.path.join(_HERE, 'libabopt_hip.so')
-ABI_VERSION = 47
+ABI_VERSION = 48
 
 c_f = C.c_void_p        # device float*
 c_i64 = C.c_void_p      # device int64*
@@ -160,6 +160,8 @@ _SIGNATURES = {
     'abopt_commonness_score_grouped': (c_int, [c_f, c_f, c_int, c_int, c_int, c_stream]),
     'abopt_cluster_ws_bytes': (c_size_t, [c_int, c_int]),
     'abopt_cluster_poses_grouped': (c_int, [c_f, c_int, c_int, c_int, c_float, c_int, c_void_p, c_size_t] + [c_void_p] * 4 + [c_f, c_stream]),
+    'abopt_interface_geometry_ws_bytes': (c_size_t, [c_int, c_int, c_int]),
+    'abopt_interface_geometry_grouped': (c_int, [c_f, c_u8, c_int, c_i32, c_u8] + [c_int] * 4 + [c_float] * 3 + [c_void_p] * 3 + [c_size_t, c_stream]),
     'abopt_prof_enable': (c_int, [c_int]),
     'abopt_prof_spans_reset': (c_int, [c_stream]),
     'abopt_prof_spans': (c_int, [POINTER(c_int), POINTER(c_double)]),
@@ -670,6 +672,57 @@ def cluster_poses_grouped(structs, group_size, cutoff, max_clusters=0, want_rmsd
     _check(lib().abopt_cluster_poses_grouped(ptr(structs), G, S, n, cutoff, M, ptr(buf), buf.numel(), ptr(out['label']), ptr(out['centre']), ptr(out['size']),
                                              ptr(out['count']), ptr(out.get('rmsd'), optional=True), stream()))
     return out
+
+
+def check_distance_cutoff(name, v):
+    """float(v), or ValueError for a negative or non-finite one (the check abopt_interface_geometry_grouped makes on its cutoffs, ahead of any device work)."""
+    import math
+    c = float(v)
+    if not math.isfinite(c) or c < 0.0:
+        raise ValueError(f'{name} must be finite and >= 0 (got {v!r})')
+    return c
+
+
+def interface_geometry_grouped(pos, mask, group, clash_cutoff=3.0, contact_cutoff=5.0, link=None, bond_max=None, want_freq=False):
+    """Clashes, contacts, interface residues and chain breaks of G*S candidates in G groups (include/abopt.h: abopt_interface_geometry_grouped; DESIGN.md
+    section 6.3).  pos (G*S,L,A,3); mask (G*S,L,A), or (G,L,A) shared by the S candidates of a group; group (G,L) int: 1 and 2 name the two sides, anything else
+    takes no part; link (optional, (G,L) bool): residue r is peptide-bonded to r + 1 -- bonded neighbours are not compared, and with bond_max (Angstrom; None:
+    breaks are not counted) a link whose C-N distance exceeds it is a break.  Cutoffs in Angstrom: clash d < clash_cutoff per atom pair, contact
+    min d <= contact_cutoff per residue pair.
+    -> dict of device tensors: clash, contacts, iface1, iface2, breaks (G*S,) int32 [, freq (G,L) int32 with want_freq: in how many of the group's candidates
+    each residue is in a contact].  Stream-ordered, no host synchronisation."""
+    if group.dim() != 2 or pos.dim() != 4 or mask.dim() != 3:
+        raise ValueError(f'interface_geometry_grouped: expected pos (G*S, L, A, 3), mask (G*S or G, L, A) and group (G, L), got {tuple(pos.shape)}, '
+                         f'{tuple(mask.shape)} and {tuple(group.shape)}')
+    G, L = group.shape
+    N, A = pos.shape[0], pos.shape[2]
+    if L < 1 or tuple(pos.shape[1:]) != (L, A, 3) or (N % G if G else N):
+        raise ValueError(f'interface_geometry_grouped: {tuple(pos.shape)} candidates are not whole groups of the {G} rows of group {tuple(group.shape)}')
+    if not 1 <= A <= 15:
+        raise ValueError(f'interface_geometry_grouped: A={A} atoms per residue, expected 1 .. 15')
+    S = N // G if G else 0
+    shared = mask.shape[0] != N or S == 1
+    if tuple(mask.shape) != ((G if shared else N), L, A):
+        raise ValueError(f'interface_geometry_grouped: mask {tuple(mask.shape)} is neither per candidate nor per group')
+    if link is not None and (tuple(link.shape) != (G, L) or A < 3):
+        raise ValueError(f'interface_geometry_grouped: link {tuple(link.shape)} must be (G, L) = {(G, L)} and needs the backbone atoms (A >= 3, got {A})')
+    clash = check_distance_cutoff('interface_geometry_grouped: clash_cutoff', clash_cutoff)
+    contact = check_distance_cutoff('interface_geometry_grouped: contact_cutoff', contact_cutoff)
+    bond = -1.0 if bond_max is None else check_distance_cutoff('interface_geometry_grouped: bond_max', bond_max)
+    ptr(pos, strided=True)                                          # a CPU tensor is refused here, before anything is allocated
+    pos, mask = _contig(pos.float(), mask if mask.dtype in (torch.bool, torch.uint8) else mask.bool())
+    group = group.to(torch.int32).contiguous()
+    link = None if link is None else link.bool().contiguous()
+    dev = pos.device
+    out = torch.empty(N, 5, dtype=torch.int32, device=dev)
+    freq = (torch.empty if N else torch.zeros)(G, L, dtype=torch.int32, device=dev) if want_freq else None      # an empty call launches nothing
+    buf = Workspace.get(max(8, lib().abopt_interface_geometry_ws_bytes(G, S, L)), dev)
+    _check(lib().abopt_interface_geometry_grouped(ptr(pos, torch.float32), ptr(mask), int(shared), ptr(group, torch.int32), ptr(link, optional=True), G, S, L, A,
+                                                  clash, contact, bond, ptr(out), ptr(freq, optional=True), ptr(buf), buf.numel(), stream()))
+    res = dict(zip(('clash', 'contacts', 'iface1', 'iface2', 'breaks'), out.unbind(1)))
+    if want_freq:
+        res['freq'] = freq
+    return res
 
 
 def pair_bias_cache_layers(w_pair_bias_list, pair_feat):

@@ -82,6 +82,35 @@ def cluster_poses(ca, cutoff, max_clusters=None):
     return dict(label=out['label'].long(), centre=out['centre'][0, :C].long(), size=out['size'][0, :C].long())
 
 
+def backbone_links(chain_nb, res_nb):
+    """(..., L) bool: residue r is peptide-bonded to r + 1 as far as the numbering says -- same chain and consecutive residue numbers; the last entry is False.
+    Pure torch, any device."""
+    link = torch.zeros_like(chain_nb, dtype=torch.bool)
+    link[..., :-1] = (chain_nb[..., :-1] == chain_nb[..., 1:]) & (res_nb[..., 1:] == res_nb[..., :-1] + 1)
+    return link
+
+
+def interface_geometry(batch, pos, mask, groups='chains', **cutoffs):
+    """Clashes, contacts, interface residues and chain breaks of candidate structures of the complexes of `batch` (hip.interface_geometry_grouped; DESIGN.md
+    section 6.3).  batch: G complexes (fragment_type, chain_nb, res_nb, generate_flag (G, L)); pos (G*S, L, A, 3), mask (G*S, L, A) or (G, L, A): S candidates of
+    each, candidate c belongs to complex c // S.
+    groups='chains': antibody (side 1) against antigen (side 2), as DockQ sees them (screen.chain_groups); 'generated': the generated residues (side 1) against
+    every other real residue (side 2), bonded neighbours excluded.  cutoffs: clash_cutoff, contact_cutoff, bond_max, want_freq of hip.interface_geometry_grouped;
+    the links are those of `backbone_links` (passed with 'generated', and whenever bond_max asks for the breaks)."""
+    from . import hip, screen
+    ft = batch['fragment_type']
+    if groups == 'chains':
+        grp = screen.chain_groups(ft)
+    elif groups == 'generated':
+        grp = torch.where(batch['generate_flag'].bool(), 1, torch.where(ft > 0, 2, 0))
+    else:
+        raise ValueError(f"interface_geometry: groups must be 'chains' or 'generated', not {groups!r}")
+    link = None
+    if groups == 'generated' or cutoffs.get('bond_max') is not None:
+        link = backbone_links(batch['chain_nb'], batch['res_nb'])
+    return hip.interface_geometry_grouped(pos, mask, grp, link=link, **cutoffs)
+
+
 def dockq_scores(model_pos, model_mask, native_pos, native_mask, fragment_type=None, group=None):
     """DockQ of candidate structures against the native complex, on the device (the reference writes every candidate to a PDB
     file and shells out: AbDock/src/tools/runner/design_for_pdb.py:316-321, AbDock/DockQ/DockQ.py:98-385).

@@ -28,6 +28,13 @@ Philox layout (global sample index c S + design, ...).  With several ranks the p
 every rank clusters the same array and owns the centres of its shard.  With `redock_cutoff` the D re-docks of every screened design are clustered as well
 (ONE grouped launch pair per chunk, hip.cluster_poses_grouped): the largest cluster's share of D is the convergence measure DockQ_std approximates.
 How many clusters trained weights produce, and what a cutoff costs in hit rate, is unmeasured: no trained checkpoint exists here.
+
+Interface geometry (optional, off by default): without a relax stage nothing above looks at whether a pose is physically possible.  With any
+of `clash_cutoff`, `contact_cutoff`, `bond_max` every pose (per chunk, right after it is rebuilt) and every re-dock (ONE grouped call per chunk,
+hip.interface_geometry_grouped, beside the grouped DockQ and commonness calls) is scored for steric clashes and contacts between antibody and antigen
+(`chain_groups`) and for broken peptide bonds, and the D re-docks of a design give the share of them that contacts each residue: the consensus epitope.
+The counts steer nothing and draw nothing; `screen_filter(max_clashes=, min_contacts=)` can use them afterwards.  3.0 / 5.0 / 2.0 A are conventional values,
+not tuned ones, and the distribution of the counts for trained weights is unmeasured.
 """
 import time
 
@@ -95,7 +102,8 @@ def _rebuild(pos, mask, traj0, lo, hi, aa, flag, one):
 @torch.no_grad()
 def optimize_antibody(dock_model, design_model, complex_, num_poses, designs_per_pose, redocks_per_design, design_flag=None, redock_flag=None,
                       contig='', screened_per_pose=1, seed=0, poses_per_launch=8, group=None, screen_by='first', timings=None, allowed_aa=None,
-                      dock_steps=None, design_steps=None, cluster_cutoff=None, max_clusters=None, redock_cutoff=None):
+                      dock_steps=None, design_steps=None, cluster_cutoff=None, max_clusters=None, redock_cutoff=None, clash_cutoff=None, contact_cutoff=None,
+                      bond_max=None):
     """Dock -> redesign -> re-dock screen of one antibody-antigen complex (module docstring).
 
     complex_: batch dict with batch dim 1 (cropped, as sample_replicated takes it); its generate_flag marks the residues to dock.
@@ -116,6 +124,10 @@ def optimize_antibody(dock_model, design_model, complex_, num_poses, designs_per
     (C) between stage 1 and stage 2.
     redock_cutoff (optional, Angstrom): cluster the D re-docks of every screened design; the result gains redock_cluster_frac (., k) fp32, the largest cluster's
     share of D, and redock_clusters (., k) int64, the number of clusters.
+    clash_cutoff / contact_cutoff / bond_max (optional, Angstrom; default None: nothing below changes, bit for bit): if any is given, score the interface geometry
+    of every pose and every re-dock (module docstring; the others default to 3.0, 5.0 and "breaks are not counted").  The result gains pose_geom (P, 5) int64 --
+    always P rows, like pose_score --, redock_geom (., k, D, 5) int64 (columns: clash, contacts, iface1, iface2, breaks of hip.interface_geometry_grouped; side 1 =
+    antibody, side 2 = antigen) and epitope_freq (., k, L) fp32: the share of a design's D re-docks in which each residue is in a contact.
     timings (optional dict): receives the seconds each stage took on this rank (device-synchronised) and of the final gather ('cluster': the gather and
     clustering between stage 1 and stage 2, with cluster_cutoff).
 
@@ -141,6 +153,11 @@ def optimize_antibody(dock_model, design_model, complex_, num_poses, designs_per
         cluster_cutoff = hip.check_cluster_cutoff('optimize_antibody: cluster_cutoff', cluster_cutoff)
     if redock_cutoff is not None:
         redock_cutoff = hip.check_cluster_cutoff('optimize_antibody: redock_cutoff', redock_cutoff)
+    geom = None
+    if clash_cutoff is not None or contact_cutoff is not None or bond_max is not None:
+        geom = dict(clash_cutoff=hip.check_distance_cutoff('optimize_antibody: clash_cutoff', 3.0 if clash_cutoff is None else clash_cutoff),
+                    contact_cutoff=hip.check_distance_cutoff('optimize_antibody: contact_cutoff', 5.0 if contact_cutoff is None else contact_cutoff),
+                    bond_max=None if bond_max is None else hip.check_distance_cutoff('optimize_antibody: bond_max', bond_max))
     if max_clusters is not None and (cluster_cutoff is None or int(max_clusters) < 1):
         raise ValueError(f'optimize_antibody: max_clusters must be >= 1 and needs cluster_cutoff (got max_clusters={max_clusters!r}, cluster_cutoff={cluster_cutoff!r})')
     L = int(one['aa'].shape[1])
@@ -175,6 +192,10 @@ def optimize_antibody(dock_model, design_model, complex_, num_poses, designs_per
     pose_pos = torch.empty(mine, L, *one['pos_heavyatom'].shape[2:], **f32)
     pose_mask = torch.empty(mine, L, one['mask_heavyatom'].shape[2], dtype=torch.bool, device=dev)
     pose_ca = torch.empty(mine, n_dock, 3, **f32)
+    pose_geom = torch.empty(mine, 5, dtype=torch.int64, device=dev) if geom is not None else None
+    grp = chain_groups(one['fragment_type'][0])
+    links = sampler.backbone_links(one['chain_nb'], one['res_nb']) if geom is not None and geom['bond_max'] is not None else None       # (1, L)
+    geom_cols = ('clash', 'contacts', 'iface1', 'iface2', 'breaks')
     for lo, hi in plan:
         n = hi - lo
         traj = sampler.sample_replicated(dock_model, one, n, dict(sample_structure=True, sample_sequence=False, **rngs('dock', lo)))
@@ -182,6 +203,9 @@ def optimize_antibody(dock_model, design_model, complex_, num_poses, designs_per
         pos, mask = _rebuild(rep(one['pos_heavyatom']), rep(one['mask_heavyatom']), traj[0], 0, n, rep(one['aa']), gen, one)
         pose_pos[lo - a:hi - a], pose_mask[lo - a:hi - a] = pos, mask
         pose_ca[lo - a:hi - a] = traj[0][1][:, gen]
+        if geom is not None:                                                             # the chunk's poses: one group of n candidates of the complex
+            ig = hip.interface_geometry_grouped(pos, mask, grp[None], link=links, **geom)
+            pose_geom[lo - a:hi - a] = torch.stack([ig[c] for c in geom_cols], 1).long()
     t0 = tick('dock', t0)
 
     # ---- optional: cluster the P poses (every rank the same gathered array); from here on "pose" c is the centre of cluster c, and a / mine / plan are the
@@ -193,6 +217,8 @@ def optimize_antibody(dock_model, design_model, complex_, num_poses, designs_per
             pose_ca = sampler.all_gather_candidates(pose_ca, pose_counts, group)
             pose_pos = sampler.all_gather_candidates(pose_pos, pose_counts, group)
             pose_mask = sampler.all_gather_candidates(pose_mask.to(torch.uint8), pose_counts, group).bool()
+            if geom is not None:
+                pose_geom = sampler.all_gather_candidates(pose_geom, pose_counts, group)
         clusters = sampler.cluster_poses(pose_ca, cluster_cutoff, max_clusters)
         Q = int(clusters['centre'].shape[0])
         plan = launch_plan(Q, poses_per_launch, world, rank)
@@ -241,7 +267,9 @@ def optimize_antibody(dock_model, design_model, complex_, num_poses, designs_per
     dockq = torch.empty(mine, k, D, 4, **f32)
     prmsd, redock_score = torch.empty(mine, k, D, **f32), torch.empty(mine, k, D, **f32)
     redock_frac, redock_clusters = torch.empty(mine, k, **f32), torch.empty(mine, k, dtype=torch.int64, device=dev)
-    grp = chain_groups(one['fragment_type'][0])
+    if geom is not None:
+        redock_geom = torch.empty(mine, k, D, 5, dtype=torch.int64, device=dev)
+        epitope_freq = torch.empty(mine, k, L, **f32)
     for lo, hi in plan:
         Gk = (hi - lo) * k
         npos, nmask, naa = (t[lo - a:hi - a].reshape(Gk, *t.shape[2:]) for t in (des_pos, des_mask, des_aa))
@@ -258,15 +286,22 @@ def optimize_antibody(dock_model, design_model, complex_, num_poses, designs_per
             cl = hip.cluster_poses_grouped(ca, D, redock_cutoff)
             redock_frac[lo - a:hi - a] = (cl['size'].amax(1).float() / D).view(hi - lo, k)
             redock_clusters[lo - a:hi - a] = cl['count'].long().view(hi - lo, k)
+        if geom is not None:
+            ig = hip.interface_geometry_grouped(pos, mask, grp[None].expand(Gk, L), link=None if links is None else links.expand(Gk, L), want_freq=True, **geom)
+            redock_geom[lo - a:hi - a] = torch.stack([ig[c] for c in geom_cols], 1).long().view(hi - lo, k, D, 5)
+            epitope_freq[lo - a:hi - a] = (ig['freq'].float() / D).view(hi - lo, k, L)
     t0 = tick('redock', t0)
 
     res = dict(pose_ca=pose_ca, seqs=seqs, aar=aar, ppl=ppl, chosen=chosen, dockq=dockq, prmsd=prmsd, redock_score=redock_score)
     if redock_cutoff is not None:
         res.update(redock_cluster_frac=redock_frac, redock_clusters=redock_clusters)
+    if geom is not None:
+        res.update(pose_geom=pose_geom, redock_geom=redock_geom, epitope_freq=epitope_freq)
+    pose_fields = ('pose_ca', 'pose_geom')                                               # P rows whatever the clustering does
     if world > 1:
         counts = [e - s_ for s_, e in (sampler.shard_range(Q, world, r) for r in range(world))]
-        gathered = {} if clusters is None else dict(pose_ca=res.pop('pose_ca'))          # the clustered poses were gathered before stage 2
-        res = {name: sampler.all_gather_candidates(t, pose_counts if name == 'pose_ca' else counts, group) for name, t in res.items()}
+        gathered = {} if clusters is None else {name: res.pop(name) for name in pose_fields if name in res}     # the clustered poses were gathered before stage 2
+        res = {name: sampler.all_gather_candidates(t, pose_counts if name in pose_fields else counts, group) for name, t in res.items()}
         res.update(gathered)
     if clusters is not None:
         res.update(cluster_label=clusters['label'], cluster_centre=clusters['centre'], cluster_size=clusters['size'])
@@ -280,13 +315,23 @@ def optimize_antibody(dock_model, design_model, complex_, num_poses, designs_per
     return res
 
 
-def screen_filter(res):
+def screen_filter(res, max_clashes=None, min_contacts=None):
     """The notebook's median rule (ab_opt_analysis_4mutations.ipynb, cell 7): keep the designs whose DockQ_std, prmsd_std and prmsd_avg
     are each at or below the median over all screened designs (pandas' quantile(0.5): the mean of the two middle values for an even count).
+    max_clashes / min_contacts (optional; need the redock_geom of optimize_antibody(clash_cutoff=...)): additionally require, per design, that the MEDIAN over
+    its D re-docks (the same quantile) of the clash count is <= max_clashes and of the contact count is >= min_contacts.
     -> bool (P, k)."""
     med = lambda t: torch.quantile(t.reshape(-1).double(), 0.5)
     keep = torch.ones_like(res['dockq_std'], dtype=torch.bool)
     for name in ('dockq_std', 'prmsd_std', 'prmsd_mean'):
         t = res[name]
         keep &= t.double() <= med(t)
+    if max_clashes is not None or min_contacts is not None:
+        if 'redock_geom' not in res:
+            raise ValueError('screen_filter: max_clashes / min_contacts need redock_geom (run optimize_antibody with clash_cutoff, contact_cutoff or bond_max)')
+        over_d = torch.quantile(res['redock_geom'].double(), 0.5, dim=2)                  # (., k, 5)
+        if max_clashes is not None:
+            keep &= over_d[..., 0] <= float(max_clashes)
+        if min_contacts is not None:
+            keep &= over_d[..., 1] >= float(min_contacts)
     return keep

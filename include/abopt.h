@@ -23,7 +23,7 @@
 extern "C" {
 #endif
 
-#define ABOPT_ABI_VERSION 47
+#define ABOPT_ABI_VERSION 48
 
 enum { ABOPT_OK = 0, ABOPT_EINVAL = 1, ABOPT_EHIP = 2, ABOPT_EUNSUPPORTED = 3, ABOPT_EWORKSPACE = 4 };
 
@@ -628,6 +628,37 @@ int abopt_commonness_score_grouped(const float* structs, float* score, int G, in
 size_t abopt_cluster_ws_bytes(int G, int S);
 int abopt_cluster_poses_grouped(const float* structs, int G, int S, int n, float cutoff, int max_clusters, void* ws, size_t ws_bytes,
                                 void* label, void* centre, void* size, void* count, float* rmsd, abopt_stream stream);
+
+/* ---- Interface geometry (ABI 48): the physical sanity check of a docked pose that every structure-generation pipeline reports -- steric clashes across the
+ * interface, the size of the interface in contacts, broken peptide bonds -- and, per group, how often each residue is contacted across the group's candidates
+ * (for the D re-docks of a design: the consensus epitope).  Nothing in the reference is matched (its relax stage is its only physical check); the definition is
+ * this library's own.  G groups of S candidates, conventions of abopt_dockq_lite_grouped:
+ *   pos [G*S,L,A,3] fp32; mask [G*S,L,A], or [G,L,A] shared by the S candidates of a group (mask_shared != 0); group [G,L] int32: 1 and 2 name the two sides,
+ *   any other value takes no part; link (optional) [G,L]: link[r] != 0 = residue r is peptide-bonded to r + 1 (the last entry is ignored);
+ *   clash_d, contact_d, bond_max in Angstrom: finite, clash_d and contact_d >= 0, a negative bond_max = breaks are not counted.
+ *   distance    atoms p, q in fp32: dx = x_p - x_q (dy, dz likewise), d2(p, q) = fmaf(dz, dz, fmaf(dy, dy, dx dx)), every step rounded once: symmetric bit for
+ *               bit.  The thresholds are clash_d clash_d, contact_d contact_d and bond_max bond_max, each rounded once in fp32.
+ *   pairs       a residue pair (a, b) takes part iff group[a] == 1 and group[b] == 2 and, with link, the two are not bonded neighbours (b == a + 1 with link[a],
+ *               or a == b + 1 with link[b]: a caller may put the generated residues on side 1 and the rest of their own chain on side 2 without counting every
+ *               peptide bond as a clash).  An atom takes part iff its mask byte is set.
+ *   out [G*S,5] int32 (DEVICE, spelled void*: this header names no mutable int32 pointer type), per candidate:
+ *     0 clash     atom pairs of participating residue pairs with d2 < clash_d^2 (strict)
+ *     1 contacts  participating residue pairs whose minimum d2 over their masked atom pairs is <= contact_d^2 (the <= of fnat.c); a residue without atoms
+ *                 contacts nobody
+ *     2 iface1    side-1 residues in at least one contact          3 iface2    the same for side 2
+ *     4 breaks    r < L - 1 with link[r], atom 2 (C) of r and atom 0 (N) of r + 1 both masked, and NOT d2(C_r, N_r+1) <= bond_max^2: a NaN coordinate counts as a
+ *                 break, a link with a missing atom does not; 0 without link or with bond_max < 0
+ *     A NaN coordinate never clashes and never contacts: every comparison is false.
+ *   freq (optional, [G,L] int32, DEVICE): freq[g,r] = the number of the group's S candidates in which residue r, of either side, is in at least one contact;
+ *     cleared by the call in stream order, accumulated with integer atomics (deterministic).
+ *   ws: abopt_interface_geometry_ws_bytes(G, S, L) bytes, 4-byte aligned (per candidate one bit per residue + four int32; 0 for an empty call).
+ * Stream-ordered (three launches in one chain, no memset node: capturable into a hipGraph), nothing allocated, no host synchronisation.  L >= 1, 1 <= A <= 15, link needs
+ * A >= 3, G S <= 2^31 - 1, G <= 65535, G = 0 or S = 0 is a no-op; every check precedes the first launch (ABOPT_EINVAL).  Residue pairs are pruned by bounding
+ * spheres before their atoms are compared; the prune is conservative in fp32 and never changes a count.  A group's result is that of a call on the group alone. */
+size_t abopt_interface_geometry_ws_bytes(int G, int S, int L);
+int abopt_interface_geometry_grouped(const float* pos, const uint8_t* mask, int mask_shared, const int32_t* group, const uint8_t* link,
+                                     int G, int S, int L, int A, float clash_d, float contact_d, float bond_max, void* out, void* freq,
+                                     void* ws, size_t ws_bytes, abopt_stream stream);
 
 /* ---- Measurement hook (bench.py's roofline leg).  When enabled, every launch of the IPA-core kernel is bracketed
  * by hipEvents on the stream it is launched on; abopt_prof_collect synchronises those events and returns the number

@@ -2,10 +2,16 @@
 stage and the designs the notebook's median filter keeps.
 
     python tools/example_screen.py [--poses 16 --designs 8 --redocks 8 --screened 1 --steps 100 --per-launch 8 --contig 97-103 --exclude CM
-                                    --dock-steps 20 --design-steps 20 --cluster-cutoff 2.0 --max-clusters 4 --redock-cutoff 2.0]
+                                    --dock-steps 20 --design-steps 20 --cluster-cutoff 2.0 --max-clusters 4 --redock-cutoff 2.0
+                                    --clash-cutoff 3.0 --contact-cutoff 5.0 --bond-max 2.0]
 
 --cluster-cutoff clusters the docked poses on the device and screens one centre per cluster: the run prints the number of clusters C,
 their sizes and the stage times.  How many clusters a trained model's poses fall into is unmeasured.
+
+--clash-cutoff / --contact-cutoff / --bond-max (any of them; the others default to 3.0 A, 5.0 A and "breaks are not counted") score the interface geometry of every
+pose and re-dock on the device: the run prints, per design, the medians over its re-docks of the clashes, contacts and chain breaks, and the
+antigen residues at least half of its re-docks contact.  3.0 / 5.0 / 2.0 A are conventional values, not tuned ones; the distribution of these counts for trained
+weights is unmeasured.
 
 The weights are not a trained checkpoint, so the numbers say nothing about antibodies; the stage times are what a screen of this size costs.
 """
@@ -41,6 +47,9 @@ def main():
     ap.add_argument('--cluster-cutoff', type=float, default=None, metavar='A', help='cluster the poses at this RMSD (no superposition) and screen the cluster centres only')
     ap.add_argument('--max-clusters', type=int, default=None, metavar='M', help='at most M clusters (needs --cluster-cutoff)')
     ap.add_argument('--redock-cutoff', type=float, default=None, metavar='A', help="cluster every design's re-docks at this RMSD: share of the largest cluster, cluster count")
+    ap.add_argument('--clash-cutoff', type=float, default=None, metavar='A', help='count atom pairs across the interface closer than this (3.0 with the other two flags)')
+    ap.add_argument('--contact-cutoff', type=float, default=None, metavar='A', help='count residue pairs across the interface within this (5.0 with the other two flags)')
+    ap.add_argument('--bond-max', type=float, default=None, metavar='A', help='count peptide bonds whose C-N distance exceeds this (default: not counted)')
     args = ap.parse_args()
     dev = torch.device('cuda:0')
     dock = synth.build_model(args.steps, 3, device=dev)                     # dock_cdr.yml: AbDock, full heavy atoms
@@ -54,6 +63,7 @@ def main():
               contig=args.contig, seed=args.seed, poses_per_launch=args.per_launch, redock_flag=heavy,
               dock_steps=args.dock_steps, design_steps=args.design_steps,
               cluster_cutoff=args.cluster_cutoff, max_clusters=args.max_clusters, redock_cutoff=args.redock_cutoff,
+              clash_cutoff=args.clash_cutoff, contact_cutoff=args.contact_cutoff, bond_max=args.bond_max,
               allowed_aa=model.aa_allowed_mask(one['aa'].shape[1], exclude=args.exclude, device=dev) if args.exclude else None)
     print(f'L={one["aa"].shape[1]} P={args.poses} S={args.designs} k={args.screened} D={args.redocks} T={args.steps} dock_steps={args.dock_steps or args.steps} design_steps={args.design_steps or args.steps} per_launch={args.per_launch} '
           f'contig={args.contig!r} device={torch.cuda.get_device_name(dev)}')
@@ -75,6 +85,15 @@ def main():
     if args.redock_cutoff is not None:
         print(f're-docks at {args.redock_cutoff} A: largest cluster share {[round(v, 3) for v in res["redock_cluster_frac"].flatten().tolist()]} '
               f'clusters {res["redock_clusters"].flatten().tolist()}')
+    if 'redock_geom' in res:
+        med = torch.quantile(res['redock_geom'].double(), 0.5, dim=2)                 # (., k, 5): over the D re-docks
+        antigen = one['fragment_type'][0] == 3
+        print(f'poses: clashes {res["pose_geom"][:, 0].tolist()} contacts {res["pose_geom"][:, 1].tolist()} breaks {res["pose_geom"][:, 4].tolist()}')
+        print(f'{"pose":>4} {"design":>6} {"clash_med":>9} {"cont_med":>8} {"break_med":>9}  antigen residues (0-based) contacted by >= half of the re-docks')
+        for p in range(med.shape[0]):
+            for j in range(med.shape[1]):
+                epi = ((res['epitope_freq'][p, j] >= 0.5) & antigen).nonzero().flatten().tolist()
+                print(f'{p:>4} {int(res["chosen"][p, j]):>6} {med[p, j, 0].item():9.1f} {med[p, j, 1].item():8.1f} {med[p, j, 4].item():9.1f}  {epi}')
     keep = screen.screen_filter(res)
     print(f'{int(keep.sum())} of {keep.numel()} screened designs pass the median filter')
     print(f'{"pose":>4} {"design":>6} {"seq":>9} {"AAR":>6} {"PPL":>7} {"DockQ_avg":>9} {"DockQ_std":>9} {"prmsd_avg":>9} {"prmsd_std":>9}')
