@@ -5,6 +5,8 @@
 //   neighbours ssd(a, b) = sum_k |a_k - b_k|^2 <= cutoff^2 n; the diagonal is always set
 //   greedy     the alive structure with the most alive neighbours (ties: lowest index) becomes a centre, its alive neighbours its members
 // Two launches: pose_adjacency_kernel writes the neighbour relation as a bit matrix (and every row's population), greedy_cluster_kernel walks it.
+// Designed sequences are clustered by the same walk over the Hamming relation of seq_adjacency_kernel, and sequence_profile_kernel counts a group's
+// per-position composition (abopt_cluster_sequences_grouped, abopt_sequence_profile_grouped).
 #include <math.h>
 #include "abopt_common.h"
 #include "kernels.h"
@@ -188,7 +190,122 @@ __global__ __launch_bounds__(CL_THREADS) void greedy_cluster_kernel(const unsign
     if (tid == 0) count_all[g] = found;
 }
 
+// ---- Sequence clustering: the same greedy walk over another relation.
+//   distance   d(a, b) = number of positions whose bytes differ (Hamming; the bytes are compared for equality only)
+//   neighbours d(a, b) <= max_mismatch; the diagonal is always set
+constexpr int SQ_KW = 16;                  // 4-byte words (64 residues) of 64 rows and 64 columns staged in LDS at a time: 8.3 KB, any n
+
+// number of non-zero bytes of x: bit 7 of every byte of ((x & 0x7f..) + 0x7f..) | x is set iff the byte is non-zero (no carry leaves a byte)
+__device__ __forceinline__ int nonzero_bytes(unsigned x) {
+    return __popc((((x & 0x7f7f7f7fu) + 0x7f7f7f7fu) | x) & 0x80808080u);
+}
+
+// 4 consecutive residues of a sequence as one word; positions past n read as 0 on both sides of every comparison, so the padding adds no mismatch
+__device__ __forceinline__ unsigned seq_word(const uint8_t* __restrict__ row, int k, int n) {
+    unsigned w = 0u;
+#pragma unroll
+    for (int b = 0; b < 4; ++b)
+        if (k + b < n) w |= (unsigned)row[k + b] << (8 * b);
+    return w;
+}
+
+// The sequence twin of pose_adjacency_kernel: the same grid (64-row tile, group), the same 4 waves x 16 rows, lane j = column 64 cb + j, the same outputs
+// (bit rows through __ballot, row populations, every word written once by lane 0).  The workgroup stages 64 residues of its 64 rows and of the 64 columns per
+// step as 16 packed words each (lane-adjacent byte loads; a short last chunk only stages and walks the words it has); the row operand is a broadcast read,
+// the column operand one read per 16 comparisons (stride 17: conflict-free).  A comparison is XOR + nonzero_bytes: 4 residues per 5 integer instructions.
+// Integers only: d is exact and d(a, b) == d(b, a), so the relation and the optional dist matrix are symmetric.
+__global__ __launch_bounds__(256) void seq_adjacency_kernel(const uint8_t* __restrict__ seq_all, unsigned long long* __restrict__ bits_all,
+                                                            int32_t* __restrict__ pop_all, int32_t* __restrict__ dist_all, int S, int n, int max_mismatch) {
+    __shared__ unsigned row_sh[64][SQ_KW];
+    __shared__ unsigned col_sh[64][SQ_KW + 1];
+    const int g = blockIdx.y, tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+    const int W = (S + 63) >> 6, r0 = blockIdx.x * 64;
+    const uint8_t* x = seq_all + (int64_t)g * S * n;
+    int pop[CL_ROWS];
+#pragma unroll
+    for (int q = 0; q < CL_ROWS; ++q) pop[q] = 0;
+    for (int cb = 0; cb < W; ++cb) {
+        int d[CL_ROWS];
+#pragma unroll
+        for (int q = 0; q < CL_ROWS; ++q) d[q] = 0;
+        for (int k0 = 0; k0 < n; k0 += 4 * SQ_KW) {
+            const int kw = min(SQ_KW, (n - k0 + 3) >> 2);                      // words this chunk holds (block-uniform)
+            __syncthreads();                                                   // the previous chunk's reads are done
+            for (int idx = tid; idx < 64 * kw; idx += 256) {
+                const int rr = idx / kw, w = idx % kw;
+                const int r = min(r0 + rr, S - 1), c = min(cb * 64 + rr, S - 1);   // rows / columns past S read the last sequence and are masked below
+                row_sh[rr][w] = seq_word(x + (int64_t)r * n, k0 + 4 * w, n);
+                col_sh[rr][w] = seq_word(x + (int64_t)c * n, k0 + 4 * w, n);
+            }
+            __syncthreads();
+            for (int w = 0; w < kw; ++w) {
+                const unsigned c = col_sh[lane][w];
+#pragma unroll
+                for (int q = 0; q < CL_ROWS; ++q) d[q] += nonzero_bytes(row_sh[wave * CL_ROWS + q][w] ^ c);
+            }
+        }
+        const int col = cb * 64 + lane;
+        const bool valid = col < S;
+#pragma unroll
+        for (int q = 0; q < CL_ROWS; ++q) {
+            const int r = r0 + wave * CL_ROWS + q;
+            if (r >= S) break;                                                  // wave-uniform
+            const unsigned long long word = __ballot(valid && (d[q] <= max_mismatch || col == r));
+            if (lane == 0) bits_all[((int64_t)g * S + r) * W + cb] = word;
+            pop[q] += __popcll(word);
+            if (dist_all && valid) dist_all[((int64_t)g * S + r) * S + col] = d[q];
+        }
+    }
+    if (lane == 0) {
+#pragma unroll
+        for (int q = 0; q < CL_ROWS; ++q) {
+            const int r = r0 + wave * CL_ROWS + q;
+            if (r < S) pop_all[(int64_t)g * S + r] = pop[q];
+        }
+    }
+}
+
+constexpr int PF_TILE = 64;                // positions a workgroup owns
+constexpr int PF_BINS = 21;                // the 20 residue types + everything else
+
+// counts[g, p, t] = how many of the group's S sequences hold type t at position p (bin 20: every byte >= 20).  Grid (64-position tile, group), 256 threads:
+// the workgroup walks its S x tile bytes in index order -- lane-adjacent bytes along n, whole rows back to back when the tile holds all of n -- and counts
+// into an LDS histogram with LDS integer atomics; the tile's counts are one contiguous run of the output and leave by plain stores.
+__global__ __launch_bounds__(256) void sequence_profile_kernel(const uint8_t* __restrict__ seq_all, int32_t* __restrict__ counts_all, int S, int n) {
+    __shared__ int hist[PF_TILE * PF_BINS];
+    const int g = blockIdx.y, tid = threadIdx.x, p0 = blockIdx.x * PF_TILE;
+    const int tl = min(PF_TILE, n - p0);
+    const uint8_t* x = seq_all + (int64_t)g * S * n + p0;
+    for (int i = tid; i < tl * PF_BINS; i += 256) hist[i] = 0;
+    __syncthreads();
+    const int64_t total = (int64_t)S * tl;
+    for (int64_t e = tid; e < total; e += 256) {
+        const int s = (int)(e / tl), p = (int)(e - (int64_t)s * tl);
+        const int t = min((int)x[(int64_t)s * n + p], PF_BINS - 1);
+        atomicAdd(&hist[p * PF_BINS + t], 1);
+    }
+    __syncthreads();
+    int32_t* out = counts_all + ((int64_t)g * n + p0) * PF_BINS;
+    for (int i = tid; i < tl * PF_BINS; i += 256) out[i] = hist[i];
+}
+
 static LdsConfig g_cluster_lds;
+
+// The greedy kernel's dynamic LDS for groups of S, made available before anything is launched ...
+static int greedy_prepare(int S, size_t* lds) {
+    const int W = (S + 63) / 64;
+    *lds = (size_t)(2 * W + CL_THREADS / 64) * 8 + (size_t)S * 4;
+    return ensure_dynamic_lds((const void*)greedy_cluster_kernel, *lds, g_cluster_lds);
+}
+
+// ... and its launch on a neighbour relation (bit matrix + populations) some adjacency kernel has written to the workspace: both entries end here
+static int greedy_launch(const unsigned long long* bits, const int32_t* pop, void* label, void* centre, void* size, void* count, int G, int S, int max_clusters,
+                         size_t lds, hipStream_t st) {
+    hipLaunchKernelGGL(greedy_cluster_kernel, dim3((unsigned)G), dim3(CL_THREADS), lds, st, bits, pop, (int32_t*)label, (int32_t*)centre, (int32_t*)size,
+                       (int32_t*)count, S, max_clusters);
+    ABOPT_LAUNCH_CHECK();
+    return ABOPT_OK;
+}
 
 }  // namespace abopt
 
@@ -217,13 +334,44 @@ extern "C" int abopt_cluster_poses_grouped(const float* structs, int G, int S, i
     unsigned long long* bits = (unsigned long long*)ws;
     int32_t* pop = (int32_t*)(bits + (size_t)G * S * W);
     const float thr = (float)((double)cutoff * (double)cutoff * (double)n);      // +inf for a huge cutoff: every finite pair is a neighbour
-    const size_t lds = (size_t)(2 * W + CL_THREADS / 64) * 8 + (size_t)S * 4;
-    int rc = ensure_dynamic_lds((const void*)greedy_cluster_kernel, lds, g_cluster_lds);
+    size_t lds;
+    int rc = greedy_prepare(S, &lds);
     if (rc != ABOPT_OK) return rc;
     hipLaunchKernelGGL(pose_adjacency_kernel, dim3((unsigned)W, (unsigned)G), dim3(256), 0, st, structs, bits, pop, rmsd, S, n, thr);
     ABOPT_LAUNCH_CHECK();
-    hipLaunchKernelGGL(greedy_cluster_kernel, dim3((unsigned)G), dim3(CL_THREADS), lds, st, (const unsigned long long*)bits, (const int32_t*)pop,
-                       (int32_t*)label, (int32_t*)centre, (int32_t*)size, (int32_t*)count, S, max_clusters);
+    return greedy_launch(bits, pop, label, centre, size, count, G, S, max_clusters, lds, st);
+}
+
+extern "C" int abopt_cluster_sequences_grouped(const uint8_t* seqs, int G, int S, int n, int max_mismatch, int max_clusters, void* ws, size_t ws_bytes,
+                                               void* label, void* centre, void* size, void* count, void* dist, abopt_stream stream) {
+    ABOPT_CHECK_ARG(G >= 0 && S >= 1 && n >= 1 && max_clusters >= 0 && (int64_t)G * S <= 0x7fffffff,
+                    "cluster_sequences_grouped: bad dims G=%d S=%d n=%d max_clusters=%d", G, S, n, max_clusters);
+    if (S > CL_MAX_S) { set_error("cluster_sequences_grouped: S=%d sequences per group exceed the greedy kernel's LDS state (max %d)", S, CL_MAX_S); return ABOPT_EUNSUPPORTED; }
+    ABOPT_CHECK_ARG(max_mismatch >= 0, "cluster_sequences_grouped: max_mismatch must be >= 0 (got %d)", max_mismatch);
+    if (G == 0) return ABOPT_OK;
+    ABOPT_CHECK_ARG(G <= 65535, "cluster_sequences_grouped: G=%d groups exceed one launch (max 65535)", G);
+    ABOPT_CHECK_ARG(seqs && ws && label && centre && size && count, "cluster_sequences_grouped: NULL argument");
+    ABOPT_CHECK_ARG(((uintptr_t)ws & 7) == 0, "cluster_sequences_grouped: the workspace must be 8-byte aligned");
+    if (ws_bytes < abopt_cluster_ws_bytes(G, S)) { set_error("cluster_sequences_grouped: workspace too small (%zu bytes given)", ws_bytes); return ABOPT_EWORKSPACE; }
+    hipStream_t st = (hipStream_t)stream;
+    const int W = (S + 63) / 64;
+    unsigned long long* bits = (unsigned long long*)ws;
+    int32_t* pop = (int32_t*)(bits + (size_t)G * S * W);
+    size_t lds;
+    int rc = greedy_prepare(S, &lds);
+    if (rc != ABOPT_OK) return rc;
+    hipLaunchKernelGGL(seq_adjacency_kernel, dim3((unsigned)W, (unsigned)G), dim3(256), 0, st, seqs, bits, pop, (int32_t*)dist, S, n, max_mismatch);
+    ABOPT_LAUNCH_CHECK();
+    return greedy_launch(bits, pop, label, centre, size, count, G, S, max_clusters, lds, st);
+}
+
+extern "C" int abopt_sequence_profile_grouped(const uint8_t* seqs, int G, int S, int n, void* counts, abopt_stream stream) {
+    ABOPT_CHECK_ARG(G >= 0 && S >= 1 && n >= 1 && (int64_t)G * n * PF_BINS <= 0x7fffffff, "sequence_profile_grouped: bad dims G=%d S=%d n=%d", G, S, n);
+    if (G == 0) return ABOPT_OK;
+    ABOPT_CHECK_ARG(G <= 65535, "sequence_profile_grouped: G=%d groups exceed one launch (max 65535)", G);
+    ABOPT_CHECK_ARG(seqs && counts, "sequence_profile_grouped: NULL argument");
+    hipLaunchKernelGGL(sequence_profile_kernel, dim3((unsigned)((n + PF_TILE - 1) / PF_TILE), (unsigned)G), dim3(256), 0, (hipStream_t)stream, seqs,
+                       (int32_t*)counts, S, n);
     ABOPT_LAUNCH_CHECK();
     return ABOPT_OK;
 }

@@ -13,7 +13,7 @@ import torch
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # ABOPT_LIB_PATH: developer override to load a variant build of the same ABI (csrc/Makefile VARIANT=...: A/B of two source trees)
 LIB_PATH = os.environ.get('ABOPT_LIB_PATH') or os.path.join(_HERE, 'libabopt_hip.so')
-ABI_VERSION = 48
+ABI_VERSION = 49
 
 c_f = C.c_void_p        # device float*
 c_i64 = C.c_void_p      # device int64*
@@ -160,6 +160,8 @@ _SIGNATURES = {
     'abopt_commonness_score_grouped': (c_int, [c_f, c_f, c_int, c_int, c_int, c_stream]),
     'abopt_cluster_ws_bytes': (c_size_t, [c_int, c_int]),
     'abopt_cluster_poses_grouped': (c_int, [c_f, c_int, c_int, c_int, c_float, c_int, c_void_p, c_size_t] + [c_void_p] * 4 + [c_f, c_stream]),
+    'abopt_cluster_sequences_grouped': (c_int, [c_u8, c_int, c_int, c_int, c_int, c_int, c_void_p, c_size_t] + [c_void_p] * 5 + [c_stream]),
+    'abopt_sequence_profile_grouped': (c_int, [c_u8, c_int, c_int, c_int, c_void_p, c_stream]),
     'abopt_interface_geometry_ws_bytes': (c_size_t, [c_int, c_int, c_int]),
     'abopt_interface_geometry_grouped': (c_int, [c_f, c_u8, c_int, c_i32, c_u8] + [c_int] * 4 + [c_float] * 3 + [c_void_p] * 3 + [c_size_t, c_stream]),
     'abopt_prof_enable': (c_int, [c_int]),
@@ -672,6 +674,56 @@ def cluster_poses_grouped(structs, group_size, cutoff, max_clusters=0, want_rmsd
     _check(lib().abopt_cluster_poses_grouped(ptr(structs), G, S, n, cutoff, M, ptr(buf), buf.numel(), ptr(out['label']), ptr(out['centre']), ptr(out['size']),
                                              ptr(out['count']), ptr(out.get('rmsd'), optional=True), stream()))
     return out
+
+
+def check_max_mismatch(name, m):
+    """int(m), or ValueError for a negative one (the check abopt_cluster_sequences_grouped makes, ahead of any device work)."""
+    if isinstance(m, bool) or int(m) != m or int(m) < 0:
+        raise ValueError(f'{name} must be an integer >= 0 (got {m!r})')
+    return int(m)
+
+
+def _seq_bytes(name, seqs, group_size):
+    """(G*S, n) integer sequences on the device -> (uint8 bytes (G*S, n), G, S, n).  Values are brought into 0..255 by clamping, on the device (no host read):
+    the kernels take one byte per residue type, and a value outside 0..255 saturates instead of wrapping onto a type."""
+    S = int(group_size)
+    if seqs.dim() != 2 or S < 1 or seqs.shape[0] % S or seqs.shape[1] < 1 or seqs.dtype.is_floating_point or seqs.dtype.is_complex:
+        raise ValueError(f'{name}: {tuple(seqs.shape)} {seqs.dtype} sequences are not whole groups of {S} >= 1 integer sequences (n,)')
+    ptr(seqs, strided=True)                                         # a CPU tensor is refused here, before anything is allocated
+    b = seqs if seqs.dtype == torch.uint8 else (seqs.to(torch.uint8) if seqs.dtype == torch.bool else seqs.clamp(0, 255).to(torch.uint8))
+    return b.contiguous(), seqs.shape[0] // S, S, seqs.shape[1]
+
+
+def cluster_sequences_grouped(seqs, group_size, max_mismatch, max_clusters=0, want_dist=False):
+    """Greedy clustering of every group of S = group_size sequences (include/abopt.h: abopt_cluster_sequences_grouped).
+    seqs (G*S, n), any integer dtype, one residue type per entry (clamped into 0..255); a and b are neighbours iff they differ at no more than max_mismatch
+    positions; max_clusters 0 = no cap.
+    -> dict of device tensors: label (G*S,) int32 (-1: left over at the cap), centre (G, S) int32 (indices within the group, -1 padded),
+    size (G, S) int32 (0 padded), count (G,) int32 [, dist (G, S, S) int32, symmetric].  Two stream-ordered launches, no host synchronisation."""
+    M = int(max_clusters)
+    if M < 0:
+        raise ValueError(f'cluster_sequences_grouped: max_clusters must be >= 0 (0 = no cap), got {max_clusters!r}')
+    m = check_max_mismatch('cluster_sequences_grouped: max_mismatch', max_mismatch)
+    seqs, G, S, n = _seq_bytes('cluster_sequences_grouped', seqs, group_size)
+    dev = seqs.device
+    i32 = dict(dtype=torch.int32, device=dev)
+    out = dict(label=torch.empty(G * S, **i32), centre=torch.empty(G, S, **i32), size=torch.empty(G, S, **i32), count=torch.empty(G, **i32))
+    if want_dist:
+        out['dist'] = torch.empty(G, S, S, **i32)
+    buf = Workspace.get(max(8, lib().abopt_cluster_ws_bytes(G, S)), dev)
+    _check(lib().abopt_cluster_sequences_grouped(ptr(seqs), G, S, n, min(m, 0x7fffffff), M, ptr(buf), buf.numel(), ptr(out['label']), ptr(out['centre']),
+                                                 ptr(out['size']), ptr(out['count']), ptr(out.get('dist'), optional=True), stream()))
+    return out
+
+
+def sequence_profile_grouped(seqs, group_size):
+    """Per-position composition of every group of S = group_size sequences (include/abopt.h: abopt_sequence_profile_grouped).
+    seqs (G*S, n) as for cluster_sequences_grouped -> counts (G, n, 21) int32 on the device: bin t < 20 counts type t, bin 20 everything else; every position
+    sums to S.  One stream-ordered launch."""
+    seqs, G, S, n = _seq_bytes('sequence_profile_grouped', seqs, group_size)
+    counts = torch.empty(G, n, 21, dtype=torch.int32, device=seqs.device)
+    _check(lib().abopt_sequence_profile_grouped(ptr(seqs), G, S, n, ptr(counts), stream()))
+    return counts
 
 
 def check_distance_cutoff(name, v):

@@ -82,6 +82,49 @@ def cluster_poses(ca, cutoff, max_clusters=None):
     return dict(label=out['label'].long(), centre=out['centre'][0, :C].long(), size=out['size'][0, :C].long())
 
 
+def cluster_sequences(seqs, max_mismatch, max_clusters=None):
+    """Greedy clustering of S designed sequences on the device (include/abopt.h: abopt_cluster_sequences_grouped): the single-group form
+    of `cluster_poses` on the sequence side.  seqs (S, n), any integer dtype, one residue type per entry; a and b are neighbours iff they differ at no more
+    than max_mismatch positions (0: identical sequences only).  The sequence with the most unassigned neighbours (ties: lowest index) becomes a centre, its
+    unassigned neighbours its members; repeat until every sequence is assigned or max_clusters (optional, >= 1) clusters exist.
+    -> dict(label (S,) (-1: left over at the cap), centre (C,), size (C,)), int64 on the device, in order of discovery.  Costs one host read (C).  Raises on
+    CPU tensors (no fallback)."""
+    from . import hip
+    m = hip.check_max_mismatch('cluster_sequences: max_mismatch', max_mismatch)
+    if max_clusters is not None and int(max_clusters) < 1:
+        raise ValueError(f'cluster_sequences: max_clusters must be >= 1 or None (got {max_clusters!r})')
+    if seqs.dim() != 2 or seqs.shape[0] < 1 or seqs.shape[1] < 1:
+        raise ValueError(f'cluster_sequences: expected (S, n) sequences with S, n >= 1, got {tuple(seqs.shape)}')
+    out = hip.cluster_sequences_grouped(seqs, seqs.shape[0], m, int(max_clusters or 0))
+    C = int(out['count'][0])
+    return dict(label=out['label'].long(), centre=out['centre'][0, :C].long(), size=out['size'][0, :C].long())
+
+
+def profile_summary(counts):
+    """counts (..., n, 21) of hip.sequence_profile_grouped -> (consensus (..., n) int64: the most frequent of the 20 types, lowest type on a tie;
+    entropy (..., n) fp32: -sum p ln p over the 21 bins, p = counts / S, computed in float64).  Pure torch, no host read."""
+    # argmax does not promise the first maximum: take the lowest type that reaches the largest count instead
+    top = counts[..., :20].amax(-1, keepdim=True)
+    types = torch.arange(20, device=counts.device).expand_as(counts[..., :20])
+    consensus = torch.where(counts[..., :20] == top, types, 20).amin(-1)
+    c = counts.double()
+    p = c / c.sum(-1, keepdim=True)
+    entropy = -(torch.where(p > 0, p * torch.log(p.clamp_min(1e-300)), torch.zeros_like(p))).sum(-1)
+    return consensus, entropy.float()
+
+
+def sequence_profile(seqs):
+    """Per-position composition of S designed sequences (include/abopt.h: abopt_sequence_profile_grouped).  seqs (S, n), any integer dtype.
+    -> dict(counts (n, 21) int32: bin t < 20 counts type t, bin 20 everything else; consensus (n,) int64 and entropy (n,) fp32 of `profile_summary`), on the
+    device, no host read.  Raises on CPU tensors (no fallback)."""
+    from . import hip
+    if seqs.dim() != 2 or seqs.shape[0] < 1 or seqs.shape[1] < 1:
+        raise ValueError(f'sequence_profile: expected (S, n) sequences with S, n >= 1, got {tuple(seqs.shape)}')
+    counts = hip.sequence_profile_grouped(seqs, seqs.shape[0])[0]
+    consensus, entropy = profile_summary(counts)
+    return dict(counts=counts, consensus=consensus, entropy=entropy)
+
+
 def backbone_links(chain_nb, res_nb):
     """(..., L) bool: residue r is peptide-bonded to r + 1 as far as the numbering says -- same chain and consecutive residue numbers; the last entry is False.
     Pure torch, any device."""

@@ -35,6 +35,11 @@ hip.interface_geometry_grouped, beside the grouped DockQ and commonness calls) i
 (`chain_groups`) and for broken peptide bonds, and the D re-docks of a design give the share of them that contacts each residue: the consensus epitope.
 The counts steer nothing and draw nothing; `screen_filter(max_clashes=, min_contacts=)` can use them afterwards.  3.0 / 5.0 / 2.0 A are conventional values,
 not tuned ones, and the distribution of the counts for trained weights is unmeasured.
+
+Sequence clustering (optional, off by default): the sequence side of the same waste.  With `seq_mismatch` the S designs of every pose are
+clustered by the number of differing positions and their composition is counted (two grouped calls per design launch); `screen_by='diverse'` re-docks one design per
+family instead of k near-copies, and `share_redocks` re-docks every distinct chosen sequence once, whichever poses chose it.  How many duplicates trained weights
+produce is unmeasured.
 """
 import time
 
@@ -82,6 +87,19 @@ def chain_groups(fragment_type):
     return torch.where(fragment_type == 3, 2, torch.where(fragment_type > 0, 1, 0))
 
 
+def diverse_choice(centre, k):
+    """The k designs of every pose that screen_by='diverse' re-docks, from centre (G, S) of hip.cluster_sequences_grouped (cluster order, -1 padded): the centres
+    of the pose's first min(k, clusters) sequence clusters in the kernel's discovery order, then -- a pose with fewer than k clusters -- the designs of lowest
+    index not yet chosen, ascending.  -> (G, k) int64.  Pure torch, no host read: design i sorts by its cluster's number if it is one of the first k centres,
+    by S + i otherwise."""
+    G, S = centre.shape
+    dev = centre.device
+    key = (S + torch.arange(S + 1, device=dev)).repeat(G, 1)                             # column S takes the writes of the padding
+    cen = centre[:, :k].long()
+    key.scatter_(1, torch.where(cen >= 0, cen, S), torch.arange(cen.shape[1], device=dev).expand(G, -1))
+    return torch.sort(key[:, :S], dim=1, stable=True)[1][:, :k]
+
+
 def _with(one, **kw):
     out = dict(one)
     out.update(kw)
@@ -103,14 +121,14 @@ def _rebuild(pos, mask, traj0, lo, hi, aa, flag, one):
 def optimize_antibody(dock_model, design_model, complex_, num_poses, designs_per_pose, redocks_per_design, design_flag=None, redock_flag=None,
                       contig='', screened_per_pose=1, seed=0, poses_per_launch=8, group=None, screen_by='first', timings=None, allowed_aa=None,
                       dock_steps=None, design_steps=None, cluster_cutoff=None, max_clusters=None, redock_cutoff=None, clash_cutoff=None, contact_cutoff=None,
-                      bond_max=None):
+                      bond_max=None, seq_mismatch=None, share_redocks=False):
     """Dock -> redesign -> re-dock screen of one antibody-antigen complex (module docstring).
 
     complex_: batch dict with batch dim 1 (cropped, as sample_replicated takes it); its generate_flag marks the residues to dock.
     design_flag / redock_flag (L,) or (1, L) bool: residues to redesign / re-dock (default: generate_flag; the reference's
     --label_heavy_as_cdr re-dock corresponds to every heavy-chain residue).  contig limits design_flag ('start-end', 1-based).
     screened_per_pose k designs of every pose go on to the re-dock: the first k (screen_by='first', as the reference takes 0000.pdb) or the
-    k of lowest PPL (screen_by='ppl', stable order).  num_poses >= 2 and redocks_per_design >= 2 (commonness needs two structures).
+    k of lowest PPL (screen_by='ppl', stable order), or one per sequence cluster (screen_by='diverse', below).  num_poses >= 2 and redocks_per_design >= 2 (commonness needs two structures).
     allowed_aa (optional, (L,) or (1, L) int32 / int64; default: complex_['aa_allowed'] if it has one): the residue types each redesigned residue may take, bit k of a
     word = type k (model.aa_allowed_mask).  It constrains the redesign stage alone -- the docking stages draw no types -- inside the sampler, so no design is thrown away:
     seqs, the re-docked designs and everything downstream hold allowed types only; aar still counts recovery of the input sequence.
@@ -128,8 +146,20 @@ def optimize_antibody(dock_model, design_model, complex_, num_poses, designs_per
     of every pose and every re-dock (module docstring; the others default to 3.0, 5.0 and "breaks are not counted").  The result gains pose_geom (P, 5) int64 --
     always P rows, like pose_score --, redock_geom (., k, D, 5) int64 (columns: clash, contacts, iface1, iface2, breaks of hip.interface_geometry_grouped; side 1 =
     antibody, side 2 = antigen) and epitope_freq (., k, L) fp32: the share of a design's D re-docks in which each residue is in a contact.
+    seq_mismatch (optional, int >= 0; default None: nothing below exists): after every design launch cluster the S designs of each pose (two
+    designs are neighbours iff they differ at no more than seq_mismatch positions; hip.cluster_sequences_grouped) and count their composition
+    (hip.sequence_profile_grouped).  The result gains seq_label (., S), seq_centre (., S) (-1 padded), seq_size (., S) (0 padded), seq_clusters (.,) and
+    seq_counts (., n_design, 21), all int64.  screen_by='diverse' (needs seq_mismatch): the k re-docked designs of a pose are the centres of its first
+    min(k, clusters) sequence clusters in order of discovery, then the designs of lowest index not yet chosen (`diverse_choice`).
+    share_redocks (default False; needs redock_flag to cover generate_flag and P k <= 16384): the chosen designs of ALL poses are clustered by identity after stage 2
+    (one group, gathered over ranks first) and every distinct sequence -- a unit -- is re-docked once, from its lowest-index owner's complex: with the docked residues
+    regenerated and their input structure hidden from the network, the re-dock trajectories of a design do not depend on the pose it was designed on.  Stage 3 runs
+    over the U units as it runs over poses with one screened design each (launches, shards, Philox: global sample index unit D + re-dock); prmsd, redock_score and
+    the optional re-dock cluster / geometry / epitope fields are computed per unit and copied to every owner (pose, slot), dockq is computed for every owner against
+    its own design complex.  Every field keeps its shape; the result gains design_unit (., k), unit_owner (U,) (flat index pose k + slot of the unit's centre) and
+    unit_size (U,), int64.  Costs one host read (the units) between stage 2 and stage 3.
     timings (optional dict): receives the seconds each stage took on this rank (device-synchronised) and of the final gather ('cluster': the gather and
-    clustering between stage 1 and stage 2, with cluster_cutoff).
+    clustering between stage 1 and stage 2, with cluster_cutoff; 'units': the gather and clustering between stage 2 and stage 3, with share_redocks).
 
     -> dict of device tensors in global pose order (P poses, S designs, k screened, D re-docks; n_* = residues in the mask):
       (with cluster_cutoff: C cluster centres in place of the P poses in every field from seqs on, see above)
@@ -147,8 +177,14 @@ def optimize_antibody(dock_model, design_model, complex_, num_poses, designs_per
     if P < 2 or D < 2 or S < 1 or not 1 <= k <= S:
         raise ValueError(f'optimize_antibody: need num_poses >= 2, redocks_per_design >= 2 and 1 <= screened_per_pose <= designs_per_pose '
                          f'(got P={P}, S={S}, k={k}, D={D})')
-    if screen_by not in ('first', 'ppl'):
-        raise ValueError(f"screen_by must be 'first' or 'ppl', not {screen_by!r}")
+    if screen_by not in ('first', 'ppl', 'diverse'):
+        raise ValueError(f"screen_by must be 'first', 'ppl' or 'diverse', not {screen_by!r}")
+    if seq_mismatch is not None:
+        seq_mismatch = hip.check_max_mismatch('optimize_antibody: seq_mismatch', seq_mismatch)
+    if screen_by == 'diverse' and seq_mismatch is None:
+        raise ValueError("optimize_antibody: screen_by='diverse' re-docks the centres of the sequence clusters and needs seq_mismatch")
+    if share_redocks and P * k > 16384:
+        raise ValueError(f'optimize_antibody: share_redocks clusters the P k chosen designs as one group of at most 16384 (got P={P}, k={k})')
     if cluster_cutoff is not None:
         cluster_cutoff = hip.check_cluster_cutoff('optimize_antibody: cluster_cutoff', cluster_cutoff)
     if redock_cutoff is not None:
@@ -171,12 +207,15 @@ def optimize_antibody(dock_model, design_model, complex_, num_poses, designs_per
     n_dock, n_design, n_redock = int(gen.sum()), int(dflag.sum()), int(rflag.sum())
     if min(n_dock, n_design, n_redock) == 0:
         raise ValueError('optimize_antibody: the dock, design and re-dock masks must each select at least one residue')
+    if share_redocks and bool((gen & ~rflag).any()):
+        raise ValueError('optimize_antibody: share_redocks needs redock_flag to cover every docked residue (generate_flag): a docked residue that is not '
+                         're-docked keeps the coordinates of its own pose in the re-dock input, so designs of different poses would no longer share trajectories')
     plan = launch_plan(P, poses_per_launch, world, rank)
     a, b = sampler.shard_range(P, world, rank)
     mine = b - a
     depth = dict(dock=dock_steps, design=design_steps, redock=dock_steps)
-    rngs = lambda stage, lo: dict(seed=stage_seed(seed, stage), rng_offset=stage_rng_offset(stage, lo, L, S, k, D),
-                                  **({} if depth[stage] is None else dict(steps=int(depth[stage]))))
+    rngs = lambda stage, lo, kk=k: dict(seed=stage_seed(seed, stage), rng_offset=stage_rng_offset(stage, lo, L, S, kk, D),
+                                        **({} if depth[stage] is None else dict(steps=int(depth[stage]))))
     aa = one['aa'][0]
     f32 = dict(dtype=torch.float32, device=dev)
     clock = {}
@@ -238,6 +277,10 @@ def optimize_antibody(dock_model, design_model, complex_, num_poses, designs_per
     des_mask = torch.empty(mine, k, *pose_mask.shape[1:], dtype=torch.bool, device=dev)
     des_aa = torch.empty(mine, k, L, dtype=torch.int64, device=dev)
     native = aa[dflag]
+    if seq_mismatch is not None:
+        i64 = dict(dtype=torch.int64, device=dev)
+        seq_label, seq_centre, seq_size = torch.empty(mine, S, **i64), torch.empty(mine, S, **i64), torch.empty(mine, S, **i64)
+        seq_clusters, seq_counts = torch.empty(mine, **i64), torch.empty(mine, n_design, 21, **i64)
     for lo, hi in plan:
         G = hi - lo
         cx = [_with(one, pos_heavyatom=pose_pos[i - a:i - a + 1], mask_heavyatom=pose_mask[i - a:i - a + 1], generate_flag=dflag[None], **design_extra)
@@ -249,8 +292,15 @@ def optimize_antibody(dock_model, design_model, complex_, num_poses, designs_per
         aar[lo - a:hi - a] = ((sq == native).sum(-1).float() / n_design).view(G, S)
         pp = traj[0][4].to(dev).view(G, S)
         ppl[lo - a:hi - a] = pp
+        if seq_mismatch is not None:                                                     # the launch's poses: G groups of S designs, two grouped calls
+            cl = hip.cluster_sequences_grouped(sq, S, seq_mismatch)
+            seq_label[lo - a:hi - a], seq_centre[lo - a:hi - a] = cl['label'].view(G, S).long(), cl['centre'].long()
+            seq_size[lo - a:hi - a], seq_clusters[lo - a:hi - a] = cl['size'].long(), cl['count'].long()
+            seq_counts[lo - a:hi - a] = hip.sequence_profile_grouped(sq, S).long()
         if screen_by == 'first':
             ch = torch.arange(k, device=dev).expand(G, k)
+        elif screen_by == 'diverse':
+            ch = diverse_choice(cl['centre'], k)
         else:
             ch = torch.sort(pp, dim=1, stable=True)[1][:, :k]
         chosen[lo - a:hi - a] = ch
@@ -263,46 +313,98 @@ def optimize_antibody(dock_model, design_model, complex_, num_poses, designs_per
         des_aa[lo - a:hi - a] = torch.where(dflag, sub[2], aa).view(G, k, L)
     t0 = tick('design', t0)
 
+    def redock(npos, nmask, naa, rng):
+        """D re-docks of each of the n given design complexes -> their rebuilt coordinates and everything that depends on the trajectories alone."""
+        n = npos.shape[0]
+        cx = [_with(one, pos_heavyatom=npos[i:i + 1], mask_heavyatom=nmask[i:i + 1], aa=naa[i:i + 1], generate_flag=rflag[None]) for i in range(n)]
+        traj = sampler.sample_grouped(dock_model, cx, D, dict(sample_structure=True, sample_sequence=False, **rng), pad_to=L)
+        rep = lambda t: t.repeat_interleave(D, dim=0)
+        pos, mask = _rebuild(rep(npos), rep(nmask), traj[0], 0, n * D, rep(naa), rflag, one)
+        out = dict(pos=pos, mask=mask, prmsd=traj[0][3].to(dev).view(n, D))
+        ca = traj[0][1][:, rflag].contiguous()                                          # (n*D, n_redock, 3)
+        out['redock_score'] = hip.commonness_score_grouped(ca, D).view(n, D)
+        if redock_cutoff is not None:
+            cl = hip.cluster_poses_grouped(ca, D, redock_cutoff)
+            out['redock_cluster_frac'] = cl['size'].amax(1).float() / D
+            out['redock_clusters'] = cl['count'].long()
+        if geom is not None:
+            ig = hip.interface_geometry_grouped(pos, mask, grp[None].expand(n, L), link=None if links is None else links.expand(n, L), want_freq=True, **geom)
+            out['redock_geom'] = torch.stack([ig[c] for c in geom_cols], 1).long().view(n, D, 5)
+            out['epitope_freq'] = ig['freq'].float() / D
+        return out
+
+    unit_fields = ('prmsd', 'redock_score') + (('redock_cluster_frac', 'redock_clusters') if redock_cutoff is not None else ()) + \
+                  (('redock_geom', 'epitope_freq') if geom is not None else ())
+    tail = dict(dockq=(D, 4), prmsd=(D,), redock_score=(D,), redock_cluster_frac=(), redock_clusters=(), redock_geom=(D, 5), epitope_freq=(L,))     # per design
+    kind = dict(redock_clusters=torch.int64, redock_geom=torch.int64)
+    counts = [e - s_ for s_, e in (sampler.shard_range(Q, world, r) for r in range(world))]
+    shared = None
+    # ---- optional: the chosen designs of all poses fall into units of identical sequence; a unit is re-docked once, from its lowest-index member's complex
+    if share_redocks:
+        all_pos, all_mask, all_aa = des_pos, des_mask, des_aa
+        if world > 1:
+            all_pos = sampler.all_gather_candidates(des_pos, counts, group)
+            all_mask = sampler.all_gather_candidates(des_mask.to(torch.uint8), counts, group).bool()
+            all_aa = sampler.all_gather_candidates(des_aa, counts, group)
+        all_pos, all_mask, all_aa = (t.reshape(Q * k, *t.shape[2:]) for t in (all_pos, all_mask, all_aa))
+        units = sampler.cluster_sequences(all_aa[:, dflag], 0)                          # identity is an equivalence: a unit's centre is its lowest-index member
+        U = int(units['centre'].shape[0])
+        owners = [[] for _ in range(U)]
+        for i, u in enumerate(units['label'].tolist()):                                 # every rank holds the same gathered array: the same units everywhere
+            owners[u].append(i)
+        t0 = tick('units', t0)
+
+        # ---- stage 3 over the U units: unit u takes the place of pose u with ONE screened design (launches, shards, Philox: global sample index u D + re-dock)
+        got = {name: [] for name in unit_fields + ('dockq',)}
+        for lo, hi in launch_plan(U, poses_per_launch, world, rank):
+            own = units['centre'][lo:hi]
+            r = redock(all_pos[own], all_mask[own], all_aa[own], rngs('redock', lo, 1))
+            for name in unit_fields:
+                got[name].append(r[name])
+            # DockQ of every owner against its own design complex, from its unit's D re-docks: groups = owners, unit-major, owners ascending
+            ow = torch.tensor([i for u in range(lo, hi) for i in owners[u]], dtype=torch.int64, device=dev)
+            src = torch.tensor([u - lo for u in range(lo, hi) for _ in owners[u]], dtype=torch.int64, device=dev)
+            rows = (src[:, None] * D + torch.arange(D, device=dev)).reshape(-1)
+            out = hip.dockq_lite_grouped(r['pos'][rows], r['mask'][rows], all_pos[ow], all_mask[ow], grp[None].expand(ow.numel(), L), check=False)
+            got['dockq'].append(out.view(ow.numel(), D, 4))
+        got = {name: (torch.cat(v, 0) if v else torch.empty(0, *tail[name], dtype=kind.get(name, torch.float32), device=dev)) for name, v in got.items()}
+        if world > 1:
+            ucounts = [e - s_ for s_, e in (sampler.shard_range(U, world, r) for r in range(world))]
+            ocounts = [sum(len(owners[u]) for u in range(*sampler.shard_range(U, world, r))) for r in range(world)]
+            got = {name: sampler.all_gather_candidates(t, ocounts if name == 'dockq' else ucounts, group) for name, t in got.items()}
+        order = torch.tensor([i for u in range(U) for i in owners[u]], dtype=torch.int64, device=dev)
+        shared = {name: got[name][units['label']].view(Q, k, *got[name].shape[1:]) for name in unit_fields}      # a unit's rows, copied to every owner (pose, slot)
+        shared['dockq'] = torch.empty(Q * k, D, 4, **f32).index_copy_(0, order, got['dockq']).view(Q, k, D, 4)
+        shared.update(design_unit=units['label'].view(Q, k), unit_owner=units['centre'], unit_size=units['size'])
+        plan = []                                                                        # stage 3 is done
+
     # ---- stage 3: D re-docks of every screened design, one grouped DockQ + one grouped commonness launch per chunk
     dockq = torch.empty(mine, k, D, 4, **f32)
-    prmsd, redock_score = torch.empty(mine, k, D, **f32), torch.empty(mine, k, D, **f32)
-    redock_frac, redock_clusters = torch.empty(mine, k, **f32), torch.empty(mine, k, dtype=torch.int64, device=dev)
-    if geom is not None:
-        redock_geom = torch.empty(mine, k, D, 5, dtype=torch.int64, device=dev)
-        epitope_freq = torch.empty(mine, k, L, **f32)
+    stage3 = {name: torch.empty(mine, k, *tail[name], dtype=kind.get(name, torch.float32), device=dev) for name in unit_fields}
     for lo, hi in plan:
         Gk = (hi - lo) * k
         npos, nmask, naa = (t[lo - a:hi - a].reshape(Gk, *t.shape[2:]) for t in (des_pos, des_mask, des_aa))
-        cx = [_with(one, pos_heavyatom=npos[i:i + 1], mask_heavyatom=nmask[i:i + 1], aa=naa[i:i + 1], generate_flag=rflag[None]) for i in range(Gk)]
-        traj = sampler.sample_grouped(dock_model, cx, D, dict(sample_structure=True, sample_sequence=False, **rngs('redock', lo)), pad_to=L)
-        rep = lambda t: t.repeat_interleave(D, dim=0)
-        pos, mask = _rebuild(rep(npos), rep(nmask), traj[0], 0, Gk * D, rep(naa), rflag, one)
-        out = hip.dockq_lite_grouped(pos, mask, npos, nmask, grp[None].expand(Gk, L), check=False)
+        r = redock(npos, nmask, naa, rngs('redock', lo))
+        out = hip.dockq_lite_grouped(r['pos'], r['mask'], npos, nmask, grp[None].expand(Gk, L), check=False)
         dockq[lo - a:hi - a] = out.view(hi - lo, k, D, 4)
-        prmsd[lo - a:hi - a] = traj[0][3].to(dev).view(hi - lo, k, D)
-        ca = traj[0][1][:, rflag].contiguous()                                          # (Gk*D, n_redock, 3)
-        redock_score[lo - a:hi - a] = hip.commonness_score_grouped(ca, D).view(hi - lo, k, D)
-        if redock_cutoff is not None:
-            cl = hip.cluster_poses_grouped(ca, D, redock_cutoff)
-            redock_frac[lo - a:hi - a] = (cl['size'].amax(1).float() / D).view(hi - lo, k)
-            redock_clusters[lo - a:hi - a] = cl['count'].long().view(hi - lo, k)
-        if geom is not None:
-            ig = hip.interface_geometry_grouped(pos, mask, grp[None].expand(Gk, L), link=None if links is None else links.expand(Gk, L), want_freq=True, **geom)
-            redock_geom[lo - a:hi - a] = torch.stack([ig[c] for c in geom_cols], 1).long().view(hi - lo, k, D, 5)
-            epitope_freq[lo - a:hi - a] = (ig['freq'].float() / D).view(hi - lo, k, L)
+        for name in unit_fields:
+            stage3[name][lo - a:hi - a] = r[name].view(hi - lo, k, *r[name].shape[1:])
     t0 = tick('redock', t0)
 
-    res = dict(pose_ca=pose_ca, seqs=seqs, aar=aar, ppl=ppl, chosen=chosen, dockq=dockq, prmsd=prmsd, redock_score=redock_score)
-    if redock_cutoff is not None:
-        res.update(redock_cluster_frac=redock_frac, redock_clusters=redock_clusters)
+    res = dict(pose_ca=pose_ca, seqs=seqs, aar=aar, ppl=ppl, chosen=chosen)
+    if shared is None:
+        res.update(dockq=dockq, **stage3)
     if geom is not None:
-        res.update(pose_geom=pose_geom, redock_geom=redock_geom, epitope_freq=epitope_freq)
+        res.update(pose_geom=pose_geom)
+    if seq_mismatch is not None:
+        res.update(seq_label=seq_label, seq_centre=seq_centre, seq_size=seq_size, seq_clusters=seq_clusters, seq_counts=seq_counts)
     pose_fields = ('pose_ca', 'pose_geom')                                               # P rows whatever the clustering does
     if world > 1:
-        counts = [e - s_ for s_, e in (sampler.shard_range(Q, world, r) for r in range(world))]
         gathered = {} if clusters is None else {name: res.pop(name) for name in pose_fields if name in res}     # the clustered poses were gathered before stage 2
         res = {name: sampler.all_gather_candidates(t, pose_counts if name in pose_fields else counts, group) for name, t in res.items()}
         res.update(gathered)
+    if shared is not None:                                                               # gathered over the units' ranks above
+        res.update(shared)
     if clusters is not None:
         res.update(cluster_label=clusters['label'], cluster_centre=clusters['centre'], cluster_size=clusters['size'])
     res['pose_score'] = hip.commonness_score(res['pose_ca'])

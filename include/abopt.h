@@ -23,7 +23,7 @@
 extern "C" {
 #endif
 
-#define ABOPT_ABI_VERSION 48
+#define ABOPT_ABI_VERSION 49
 
 enum { ABOPT_OK = 0, ABOPT_EINVAL = 1, ABOPT_EHIP = 2, ABOPT_EUNSUPPORTED = 3, ABOPT_EWORKSPACE = 4 };
 
@@ -628,6 +628,26 @@ int abopt_commonness_score_grouped(const float* structs, float* score, int G, in
 size_t abopt_cluster_ws_bytes(int G, int S);
 int abopt_cluster_poses_grouped(const float* structs, int G, int S, int n, float cutoff, int max_clusters, void* ws, size_t ws_bytes,
                                 void* label, void* centre, void* size, void* count, float* rmsd, abopt_stream stream);
+
+/* ---- Sequence clustering and composition (ABI 49): the sequence side of the same question.  A sequence-design model sampling S times on one backbone
+ * returns near-identical designs many times over; this groups them so that the screen re-docks one design per family (and identical designs once), and
+ * counts what every position holds.  Nothing in the reference is matched (its notebooks summarise designs on the host); the definition is this library's
+ * own, per group of S sequences [n] of one byte per residue type (any byte value; bytes are compared for equality only):
+ *   distance    d(a, b) = the number of positions k with a_k != b_k: an integer, exact, d(a, b) == d(b, a)
+ *   neighbours  a ~ b iff d(a, b) <= max_mismatch, and a ~ a always; max_mismatch >= n puts every sequence of a group into one cluster
+ *   greedy      exactly as abopt_cluster_poses_grouped above (the same kernel walks the relation): most alive neighbours first, ties to the lowest index,
+ *               clusters numbered in order of discovery, max_clusters 0 = no cap, sequences still alive at the cap keep label -1
+ *   seqs [G*S,n] uint8 -> label [G*S], centre [G*S], size [G*S], count [G]: DEVICE int32 arrays laid out as above.  dist (optional, [G,S,S] DEVICE
+ *   int32): d of every pair, symmetric.  ws: abopt_cluster_ws_bytes(G, S) bytes, 8-byte aligned.
+ * Two stream-ordered launches, nothing allocated, no host synchronisation, no floating point.  1 <= S <= 16384 (beyond: ABOPT_EUNSUPPORTED), n >= 1,
+ * G S <= 2^31 - 1, G <= 65535, G = 0 is a no-op, max_mismatch >= 0; every check precedes the first launch.  A group's result is identical to a call on
+ * that group alone.
+ * abopt_sequence_profile_grouped: counts [G,n,21] DEVICE int32, counts[g][k][t] = how many of group g's S sequences hold type t < 20 at position k;
+ * bin 20 counts every other byte (UNK, padding), so every position sums to S.  One launch; S >= 1, n >= 1, G n 21 <= 2^31 - 1, G <= 65535, G = 0 is a
+ * no-op. */
+int abopt_cluster_sequences_grouped(const uint8_t* seqs, int G, int S, int n, int max_mismatch, int max_clusters, void* ws, size_t ws_bytes,
+                                    void* label, void* centre, void* size, void* count, void* dist, abopt_stream stream);
+int abopt_sequence_profile_grouped(const uint8_t* seqs, int G, int S, int n, void* counts, abopt_stream stream);
 
 /* ---- Interface geometry (ABI 48): the physical sanity check of a docked pose that every structure-generation pipeline reports -- steric clashes across the
  * interface, the size of the interface in contacts, broken peptide bonds -- and, per group, how often each residue is contacted across the group's candidates

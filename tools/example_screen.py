@@ -3,7 +3,8 @@ stage and the designs the notebook's median filter keeps.
 
     python tools/example_screen.py [--poses 16 --designs 8 --redocks 8 --screened 1 --steps 100 --per-launch 8 --contig 97-103 --exclude CM
                                     --dock-steps 20 --design-steps 20 --cluster-cutoff 2.0 --max-clusters 4 --redock-cutoff 2.0
-                                    --clash-cutoff 3.0 --contact-cutoff 5.0 --bond-max 2.0]
+                                    --clash-cutoff 3.0 --contact-cutoff 5.0 --bond-max 2.0
+                                    --seq-mismatch 2 --screen-by diverse --share-redocks --allow A,G,S,T,AV,LK,DE]
 
 --cluster-cutoff clusters the docked poses on the device and screens one centre per cluster: the run prints the number of clusters C,
 their sizes and the stage times.  How many clusters a trained model's poses fall into is unmeasured.
@@ -12,6 +13,12 @@ their sizes and the stage times.  How many clusters a trained model's poses fall
 pose and re-dock on the device: the run prints, per design, the medians over its re-docks of the clashes, contacts and chain breaks, and the
 antigen residues at least half of its re-docks contact.  3.0 / 5.0 / 2.0 A are conventional values, not tuned ones; the distribution of these counts for trained
 weights is unmeasured.
+
+--seq-mismatch M clusters the S designs of every pose on the device (two sequences are neighbours if they differ at no more than M positions) and counts their
+composition: the run prints the distinct designs and families per pose and the consensus.  --screen-by diverse re-docks one design per
+family instead of the first / the lowest-PPL ones.  --share-redocks re-docks every distinct chosen sequence ONCE, whichever poses chose it, and prints the number
+of units; --allow narrows the types per contig position (comma-separated letter sets, in contig order) so that a hash-filled model produces duplicates at all.
+How many duplicates trained weights produce, and so what sharing saves in practice, is unmeasured.
 
 The weights are not a trained checkpoint, so the numbers say nothing about antibodies; the stage times are what a screen of this size costs.
 """
@@ -50,6 +57,10 @@ def main():
     ap.add_argument('--clash-cutoff', type=float, default=None, metavar='A', help='count atom pairs across the interface closer than this (3.0 with the other two flags)')
     ap.add_argument('--contact-cutoff', type=float, default=None, metavar='A', help='count residue pairs across the interface within this (5.0 with the other two flags)')
     ap.add_argument('--bond-max', type=float, default=None, metavar='A', help='count peptide bonds whose C-N distance exceeds this (default: not counted)')
+    ap.add_argument('--seq-mismatch', type=int, default=None, metavar='M', help="cluster every pose's designs: neighbours differ at <= M positions; also counts the composition")
+    ap.add_argument('--screen-by', choices=('first', 'ppl', 'diverse'), default='first', help="the designs that are re-docked ('diverse': one per sequence cluster; needs --seq-mismatch)")
+    ap.add_argument('--share-redocks', action='store_true', help='re-dock every distinct chosen sequence once (the re-dock must cover the docked residues: it does here)')
+    ap.add_argument('--allow', default='', metavar='SETS', help='allowed types per contig position, comma-separated in contig order, e.g. A,G,S,T,AV,LK,DE')
     args = ap.parse_args()
     dev = torch.device('cuda:0')
     dock = synth.build_model(args.steps, 3, device=dev)                     # dock_cdr.yml: AbDock, full heavy atoms
@@ -59,12 +70,17 @@ def main():
     gen[94:106] = True                                                      # CDR-H3 of LAYOUT_256
     one['generate_flag'] = gen[None]
     heavy = one['fragment_type'][0] == 1                                   # the re-dock labels the whole heavy chain (--label_heavy_as_cdr)
+    allowed = None
+    if args.exclude or args.allow:
+        first = int(args.contig.split('-')[0])
+        at = {first + i: letters for i, letters in enumerate(args.allow.split(','))} if args.allow else None
+        allowed = model.aa_allowed_mask(one['aa'].shape[1], exclude=args.exclude, at=at, device=dev)
     kw = dict(num_poses=args.poses, designs_per_pose=args.designs, redocks_per_design=args.redocks, screened_per_pose=args.screened,
               contig=args.contig, seed=args.seed, poses_per_launch=args.per_launch, redock_flag=heavy,
               dock_steps=args.dock_steps, design_steps=args.design_steps,
               cluster_cutoff=args.cluster_cutoff, max_clusters=args.max_clusters, redock_cutoff=args.redock_cutoff,
               clash_cutoff=args.clash_cutoff, contact_cutoff=args.contact_cutoff, bond_max=args.bond_max,
-              allowed_aa=model.aa_allowed_mask(one['aa'].shape[1], exclude=args.exclude, device=dev) if args.exclude else None)
+              allowed_aa=allowed, seq_mismatch=args.seq_mismatch, screen_by=args.screen_by, share_redocks=args.share_redocks)
     print(f'L={one["aa"].shape[1]} P={args.poses} S={args.designs} k={args.screened} D={args.redocks} T={args.steps} dock_steps={args.dock_steps or args.steps} design_steps={args.design_steps or args.steps} per_launch={args.per_launch} '
           f'contig={args.contig!r} device={torch.cuda.get_device_name(dev)}')
     t0 = time.perf_counter()
@@ -82,6 +98,15 @@ def main():
     if args.cluster_cutoff is not None:
         print(f'{res["cluster_centre"].numel()} clusters of {args.poses} poses at {args.cluster_cutoff} A: sizes {res["cluster_size"].tolist()} centres {res["cluster_centre"].tolist()} '
               f'(rows below: cluster c = pose cluster_centre[c])')
+    if args.seq_mismatch is not None:
+        distinct = [len({tuple(r) for r in pose.tolist()}) for pose in res['seqs']]
+        print(f'designs per pose: {args.designs}; distinct {distinct}; families at <= {args.seq_mismatch} mismatches {res["seq_clusters"].tolist()} '
+              f'(largest {res["seq_size"].amax(1).tolist()})')
+        consensus = res['seq_counts'][..., :20].argmax(-1)
+        print('consensus per pose: ' + ' '.join(''.join(AA[int(a)] for a in row) for row in consensus))
+    if args.share_redocks:
+        print(f'{res["unit_owner"].numel()} units for {res["design_unit"].numel()} chosen designs: sizes {res["unit_size"].tolist()} '
+              f'(re-docked from pose * k + slot = {res["unit_owner"].tolist()})')
     if args.redock_cutoff is not None:
         print(f're-docks at {args.redock_cutoff} A: largest cluster share {[round(v, 3) for v in res["redock_cluster_frac"].flatten().tolist()]} '
               f'clusters {res["redock_clusters"].flatten().tolist()}')
