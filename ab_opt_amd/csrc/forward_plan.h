@@ -1,7 +1,7 @@
 // Which launches a denoiser forward is made of: the ONE place that decides (api.hip reads the switches once per entry, builds a ForwardQuery and walks the plan;
 // the launchers of ipa_core.hip / ipa.hip take the CorePlan they are handed).  plan_ipa_core (ipa_plan.h) is called from here and from nowhere else on the
-// forward path.  Plain host C++17, no HIP: tests/forward_plan_table.cpp and tests/forward_plan_carry_table.cpp tabulate the functions without a device
-// (tests/test_forward_plan.py, tests/test_forward_plan_carry.py).
+// forward path.  Plain host C++17, no HIP: tests/forward_plan_table.cpp, tests/forward_plan_carry_table.cpp and tests/forward_plan_rows_table.cpp tabulate the
+// functions without a device (tests/test_forward_plan.py, tests/test_forward_plan_carry.py, tests/test_forward_plan_rows.py).
 #pragma once
 #include "ipa_plan.h"
 
@@ -18,6 +18,7 @@ struct Switches {
     bool fuse_heads = true;         // ABOPT_FUSE_HEADS=0: the heads' geometric epilogue as a launch of its own
     bool fuse_step = true;          // ABOPT_FUSE_STEP=0: a denoising step's transitions and the next evaluation's mixer as launches of their own (abopt_eps_net_step)
     bool fuse_node = true;          // ABOPT_FUSE_NODE=0: every block's node_frags as a launch of its own (no block writes its successor's fragments)
+    bool step_rows = true;          // ABOPT_STEP_ROWS=0: the last block of a step streams pair data for every query row, wanted or not (query_rows_masked)
 };
 
 struct BlockWeights { bool node_frag, out_frag, mlp_frag, out_terms; };     // which packed operands of abopt_ga_weights are given
@@ -38,6 +39,7 @@ struct ForwardQuery {
     // (carry_in: the previous call of the entry wrote it); the next evaluation's is wanted (carry_out)
     bool step = false, ppl = false, carry_in = false, carry_out = false;
     bool frag2 = false;             // the workspace holds a second fragment pair (api.hip: carve_ga aliases it onto proj | feat where it fits)
+    bool context_unused = false;    // abopt_eps_net_step_rows: the caller reads nothing of the network's outputs on rows that are not generated
 };
 
 enum class NodeForm { Kernel, Gemm };               // node_frags | projection GEMM + ipa_frags
@@ -52,6 +54,9 @@ struct BlockPlan {
     bool carry_next = false;        // this block's fused kernel also writes the next block's fragments
     bool carried = false;           // this block's fragments were written by its predecessor: no node_frags launch
     int frag_slot = 0;              // which of the workspace's fragment pairs the block's core reads (and its own node_frags, if it runs, writes)
+    // Masked query rows (plan_encoder): the block's output is read on generated rows only, so its fused kernel (ipa_core32_kernel<true, *, false, true>) streams pair
+    // data and bias for those rows alone; the other rows of its output are finite and otherwise unspecified
+    bool query_rows_masked = false;
 };
 struct EncoderPlan {
     bool ok;                        // false: the last planned block's core is Unsupported and nothing is planned after it
@@ -85,6 +90,12 @@ inline bool plan_pair_terms_used(int N, int L, int z_shared, int cus, const Swit
     return plan_is_core32({N, L, z_shared, cus, true, false, false, 0, sw.core32_override, sw.no_split});
 }
 
+// Whether a step's tail runs as one launch (NetPlan::step_fused).  The two per-sample scalars (prmsd, perplexity) need a reduction across the workgroups of a sample
+// in a fixed order: a call that wants either keeps the launches of its own.
+inline bool plan_step_fused(const ForwardQuery& q) {
+    return q.step && q.mix_frag && q.heads_frag && q.sw.fuse_heads && q.sw.fuse_step && !q.prmsd && !q.ppl;
+}
+
 // Block i of the query.  x as fp16 terms travels with x: the block reads the slot its producer wrote (`produced`; -1: none) if its node step is the kernel, and
 // writes `next_slot` for a successor whose node step is the kernel -- from one of the two term-writing tails, never the slot it reads
 inline BlockPlan plan_block(const ForwardQuery& q, int i, int produced = -1, int next_slot = -1) {
@@ -112,12 +123,20 @@ inline BlockPlan plan_block(const ForwardQuery& q, int i, int produced = -1, int
 // workgroup), the launch keeps its weights in LDS and costs 24 us per 256 workgroups' worth of rows.  Where the fused kernel's workgroups fit the CUs in ONE round (the bench
 // shape: 256 on 256) the phase wins by the launch's ramp and boundary; carried over several rounds it lost (N = 64 x L = 256: 2.05 -> 2.23 ms per step, N = 1000 x L = 48:
 // 3.70 -> 3.87; profiles/node_carry_shapes.txt), so such a forward is not carried.  DESIGN.md section 3.3 has what is and is not known about the cause.
+// Masked query rows: the LAST block's output x feeds the heads and nothing else, and in a step whose tail is fused (plan_step_fused: the heads' outputs go straight
+// into the transitions, which keep the old state on every row that is not generated, and no per-sample reduction over all rows -- prmsd, perplexity -- is formed)
+// a caller who says it reads none of the network's outputs on those rows (context_unused) cannot tell what x was there.  The block must be the fused 32-row
+// kernel on a pair-bias cache that carries nothing (the last block never does).
 inline EncoderPlan plan_encoder(const ForwardQuery& q, int produced = -1) {
     EncoderPlan e{true, 0, {}};
     for (int i = 0; i < q.num_blocks && e.ok; ++i) {
         const BlockPlan& p = e.blocks[e.num_blocks++] = plan_block(q, i, produced, i & 1);
         produced = p.xt_write;
         e.ok = p.core.form != CoreForm::Unsupported;
+    }
+    if (e.ok && e.num_blocks > 0 && q.context_unused && q.sw.step_rows && plan_step_fused(q) && !q.dbg) {
+        BlockPlan& last = e.blocks[e.num_blocks - 1];
+        last.query_rows_masked = last.core.form == CoreForm::Core32 && q.cache && last.tail == TailForm::InCore && !last.carry_next;
     }
     if (!e.ok || !q.sw.fuse_node || !q.frag2 || q.dbg) return e;
     for (int i = 0; i + 1 < e.num_blocks; ++i) {
@@ -141,10 +160,9 @@ inline NetPlan plan_network(const ForwardQuery& q) {
     n.heads_epilogue = q.heads_frag && q.sw.fuse_heads;
     n.build_infeat = !q.heads_frag || q.prmsd;
     n.prmsd = q.prmsd;
-    // The fused tail of a step.  The two per-sample scalars (prmsd, perplexity) need a reduction across the workgroups of a sample in a fixed order: a call that
-    // wants either keeps the launches of its own.  At the time the tail runs, the mixer's outputs are free: x (block 0 alone read it) and x-terms slot mixer_xt
+    // The fused tail of a step (plan_step_fused).  At the time the tail runs, the mixer's outputs are free: x (block 0 alone read it) and x-terms slot mixer_xt
     // (slot 1: the last writer's reader, an even block's node_frags, is long done), R after the epilogue of the same rows has read it.
-    n.step_fused = q.step && n.mixer_kernel && n.heads_kernel && n.heads_epilogue && q.sw.fuse_step && !q.prmsd && !q.ppl;
+    n.step_fused = plan_step_fused(q);
     n.mixer_launch = !(n.step_fused && q.carry_in);
     n.step_carry = n.step_fused && q.carry_out;
     return n;

@@ -862,8 +862,10 @@ struct TailArgs {
     unsigned* xt;           // optional: the output rows as two fp16 terms as well (tail_common.h: tail_p2_run)
 };
 // the kernel's tail arguments: NF adds the operands of the carried projections behind them, every other instantiation keeps TailArgs' layout
-template <bool NF> struct TailArgsT : TailArgs {};
-template <> struct TailArgsT<true> : TailArgs { NodeCarryArgs nc; };
+// (QR: the per-row "query row wanted" bytes of ipa_core32_kernel<true, *, false, true>, behind them as well)
+template <bool NF, bool QR = false> struct TailArgsT : TailArgs {};
+template <> struct TailArgsT<true, false> : TailArgs { NodeCarryArgs nc; };
+template <> struct TailArgsT<false, true> : TailArgs { const uint8_t* qrows; };
 constexpr int C32_LOOP_LDS_FLOATS = 3 * 32 * SROW + 2 * 32 * SCLD + 32 * SCLD + 32 * 32;      // sp | scl | lsum | mlr (then the key mask)
 __host__ __device__ constexpr size_t core32_lds_bytes(int nchunk) { return sizeof(float) * C32_LOOP_LDS_FLOATS + (size_t)nchunk * JC; }     // ipa_core32_kernel<false, ZT>
 constexpr int C32F_PTS_OFF = ((C32_LOOP_LDS_FLOATS * 4 + 2048 + 255) / 256) * 256;               // aggregated points [32][12][24] fp32, behind the key mask of L <= 2048
@@ -929,12 +931,21 @@ __device__ __forceinline__ void node_carry_phase(NfLdsTerms xt, NodeCarryArgs nc
 // B operand {P_h, P_h}: one 16-cycle MFMA per channel tile gives P_h z_h + P_h z_l, a K = 16 MFMA P_l z_h -- 8 MFMAs of 16 cycles per row-chunk instead
 // of 16 of 32 (P_l z_l <= 2^-22 relative is dropped, as in ipa_common.h).  S_ic is a power of two per (query row, channel) (max_j |z[i,j,c]| S_ic in [2^13, 2^14)),
 // 2^-14 / S_ic (`zsc`, [rows][64]) leaves through the final normalisation: exact.  P itself, its row sums and everything the C waves compute are those of the fp32 form, bit for bit.  Measured (profiles/r06_a_*): -7 % of the replayed step.
-template <bool FUSE, bool ZT, bool NF = false>
+//
+// QROWS (forward_plan.h: query_rows_masked): the caller reads the block's output on the query rows marked in ta.qrows [N L] only (the last block of a sampling step,
+// whose only reader -- the heads and the step's transitions -- keeps the old state on context rows whatever the network says there).  Same grid, same roles, same
+// instruction stream per row; the one difference is the buffer descriptor a row's z / term and bias requests go through: a row nobody reads takes one of ZERO
+// records, so every request of it fails the range check (the scalar row offset is not part of that check on this target, the record count is), returns zeros and
+// fetches nothing -- and still counts in vmcnt, so the ring, the software pipeline and every wait stay as they are.  Such a row's softmax sees S alone, its pair
+// features are 0 x the real 1 / S_ic, everything it leaves is finite, and nothing of it reaches another row (attention, out-transform, LayerNorm and MLP are per row).
+// A marked row computes what ipa_core32_kernel<true, ZT> computes, bit for bit.
+template <bool FUSE, bool ZT, bool NF = false, bool QROWS = false>
 __global__ __launch_bounds__(NTH2) void ipa_core32_kernel(const float* __restrict__ qfrag, const float* __restrict__ kvfrag, const float* __restrict__ z,
                                                           const uint8_t* __restrict__ mask, const float* __restrict__ R, const float* __restrict__ t,
                                                           float* __restrict__ feat, const float* __restrict__ pbc, int L, int nib2, int xcd_remap, int z_shared,
-                                                          TailArgsT<NF> ta, int prof_slot, const float* __restrict__ zt, const float* __restrict__ zsc) {
+                                                          TailArgsT<NF, QROWS> ta, int prof_slot, const float* __restrict__ zt, const float* __restrict__ zsc) {
     static_assert(FUSE || !NF, "the carried projections follow the fused tail");
+    static_assert(!QROWS || (FUSE && !NF), "query rows are masked in the block nobody follows");
     extern __shared__ __attribute__((aligned(16))) char smem_raw[];
     float* sp = reinterpret_cast<float*>(smem_raw);                     // [3][BI2][SROW]
     float* scl = sp + 3 * BI2 * SROW;                                   // [2][BI2][SCLD]
@@ -1059,9 +1070,28 @@ __global__ __launch_bounds__(NTH2) void ipa_core32_kernel(const float* __restric
         // the row's byte offset (an SGPR, added by the hardware) and the lane's offset inside a row (a VGPR that lives for a whole chunk)
         // (ZT: the same bytes per row-chunk, 4 KB, in the term layout [chunk][channel tile][lane]: every request is 1 KB contiguous, chunks past L are zero-padded)
         const int rows_tot_ = ((int)gridDim.x / nib2 / (z_shared ? z_shared : 1)) * L;          // rows of the terms buffer (distinct samples x L)
-        const __amdgpu_buffer_rsrc_t zrs = ZT ? __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(zt), 0, (unsigned)rows_tot_ * (unsigned)nchunk * (JC * C * 4), 0x00020000)
-                                              : __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(z + zbase * (int64_t)L * C), 0, L * L * C * 4, 0x00020000);
-        const __amdgpu_buffer_rsrc_t brs = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(pbc), 0, (unsigned)rows_tot_ * (unsigned)nchunk * (H * JC * 4), 0x00020000);
+        // one spelling of both descriptors: base, no stride, NUM records (bytes), the flags word
+        const float* const zsrc_ = ZT ? zt : z + zbase * (int64_t)L * C;
+        const unsigned znum_ = ZT ? (unsigned)rows_tot_ * (unsigned)nchunk * (JC * C * 4) : (unsigned)(L * L * C * 4), bnum_ = (unsigned)rows_tot_ * (unsigned)nchunk * (H * JC * 4);
+#define P2_RSRC(PTR, NUM) __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(PTR), 0, (NUM), 0x00020000)
+        const __amdgpu_buffer_rsrc_t zrs = P2_RSRC(zsrc_, znum_), brs = P2_RSRC(pbc, bnum_);
+        // QROWS: bit ii = row ii of this wave is read by somebody (wave-uniform, loaded once); the requests of the other rows see a record count of zero --
+        // the descriptor is assembled per request from the same base and flags, so the select lands on its record count alone
+        unsigned qneed_ = 0xffu;
+        if constexpr (QROWS) {
+            qneed_ = 0u;
+#pragma unroll
+            for (int ii = 0; ii < RPW2; ++ii) {
+                const int row = i0 + wave * RPW2 + ii;
+                if (row < L && ta.qrows[rowbase + row]) qneed_ |= 1u << ii;
+            }
+            qneed_ = __builtin_amdgcn_readfirstlane(qneed_);
+        }
+#define P2_ZRS(II) (QROWS ? P2_RSRC(zsrc_, ((qneed_ >> (II)) & 1u) ? znum_ : 0u) : zrs)
+#define P2_BRS(II) (QROWS ? P2_RSRC(pbc, ((qneed_ >> (II)) & 1u) ? bnum_ : 0u) : brs)
+        // (the flags are opaque to the compiler from chunk to chunk: else it selects all sixteen descriptors of a wave ahead of the key loop and keeps them in
+        // scalar registers the kernel does not have -- 97 of them spilled to lanes, two requests' worth of lane reads per row)
+#define P2_QNEED_FENCE() if constexpr (QROWS) asm volatile("" : "+s"(qneed_));
         int zrow[RPW2], pbrow[RPW2];
 #pragma unroll
         for (int ii = 0; ii < RPW2; ++ii) {
@@ -1083,8 +1113,8 @@ __global__ __launch_bounds__(NTH2) void ipa_core32_kernel(const float* __restric
 #define P2_BOFF(CH) boff_ = (unsigned)min((CH), nchunk - 1) * ((unsigned)rows_tot_ * (unsigned)(H * JC * 4)) + pb_lane;
 #define P2_ISSUE_Z(SLOT, II)                                                                                            \
         _Pragma("unroll") for (int r_ = 0; r_ < 4; ++r_)                                                                \
-            ring[SLOT][r_] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(zrs, koff_[r_], zrow[II], 2));   /* aux 2 = nt, as ZLOAD */
-#define P2_ISSUE_B(SLOT, II) ringb[SLOT] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(brs, boff_, pbrow[II], 2));
+            ring[SLOT][r_] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(P2_ZRS(II), koff_[r_], zrow[II], 2));   /* aux 2 = nt, as ZLOAD */
+#define P2_ISSUE_B(SLOT, II) ringb[SLOT] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(P2_BRS(II), boff_, pbrow[II], 2));
         P2_KOFF(0) P2_BOFF(0)
         P2_ISSUE_B(0, 0) P2_ISSUE_Z(0, 0) P2_ISSUE_B(1, 1) P2_ISSUE_Z(1, 1) P2_ISSUE_B(2, 2)
         fill_mask();
@@ -1286,6 +1316,7 @@ __global__ __launch_bounds__(NTH2) void ipa_core32_kernel(const float* __restric
         float mterm_[4];                                                    /* x k + (0 | -1e5 log2 e) in one fma: the values of the 16-row kernels' (mask ? x k : x k - 1e5 log2 e), whose second form the compiler contracts to the same fma */ \
         _Pragma("unroll") for (int r_ = 0; r_ < 4; ++r_) mterm_[r_] = ((mk4_ >> (8 * r_)) & 0xffu) ? 0.f : -kMask2;      \
         const int CHPAR = (CH) & 1;                                                                                      \
+        P2_QNEED_FENCE()                                                                                                 \
         f32x4 pvn_; float scn_;                                                                                                  \
         P2_SM(0, K)                                                                                                      \
         _Pragma("unroll") for (int mt_ = 0; mt_ < 4; ++mt_) accP[0][mt_] *= scn_;                                         \
@@ -1300,6 +1331,7 @@ __global__ __launch_bounds__(NTH2) void ipa_core32_kernel(const float* __restric
         float mterm_[4];                                                    /* x k + (0 | -1e5 log2 e) in one fma: the values of the 16-row kernels' (mask ? x k : x k - 1e5 log2 e), whose second form the compiler contracts to the same fma */ \
         _Pragma("unroll") for (int r_ = 0; r_ < 4; ++r_) mterm_[r_] = ((mk4_ >> (8 * r_)) & 0xffu) ? 0.f : -kMask2;      \
         const int CHPAR = (CH) & 1;                                                                                      \
+        P2_QNEED_FENCE()                                                                                                 \
         u32x4 pkn_; float scn_;                                                                                                  \
         P2H_SM(0, K)                                                                                                      \
         _Pragma("unroll") for (int mt_ = 0; mt_ < 4; ++mt_) accP[0][mt_] *= scn_;                                         \
@@ -1336,6 +1368,10 @@ __global__ __launch_bounds__(NTH2) void ipa_core32_kernel(const float* __restric
 #undef P2_SM
 #undef P2_ISSUE_Z
 #undef P2_ISSUE_B
+#undef P2_ZRS
+#undef P2_BRS
+#undef P2_RSRC
+#undef P2_QNEED_FENCE
 #undef P2_KOFF
 #undef P2_BOFF
         // alpha = P / l, zero for masked queries (ga.py:24-25); pair features out
@@ -1827,17 +1863,17 @@ static int launch_core_variant(const CorePlan& plan, const float* qfrag, const f
 }
 
 // ipa_core32_kernel<FUSE, ZT> from a Core32 plan: the core alone into `feat`, or (FUSE) core + tail with `ta`.  ZT: `pair_terms` is given.
-template <bool FUSE, bool ZT, bool NF = false>
+template <bool FUSE, bool ZT, bool NF = false, bool QROWS = false>
 static int launch_core32(const CorePlan& plan, const float* qfrag, const float* kvfrag, const float* z, const uint8_t* mask, const float* R, const float* t, float* feat,
-                         const float* pbc, int N, int L, hipStream_t st, int z_shared, const TailArgsT<NF>& ta, const float* pair_terms) {
+                         const float* pbc, int N, int L, hipStream_t st, int z_shared, const TailArgsT<NF, QROWS>& ta, const float* pair_terms) {
     const int nib2 = (L + BI2 - 1) / BI2, nchunk = (L + JC - 1) / JC;
     const size_t lds = FUSE ? (size_t)C32F_LDS_BYTES : core32_lds_bytes(nchunk);
     ABOPT_CHECK_ARG(lds <= 160 * 1024, "ipa_core: L=%d needs %zu bytes of LDS for the key mask (max 163840)", L, lds);
     static LdsConfig lds_cfg;                                               // per instantiation
-    if (int rc = ensure_dynamic_lds(reinterpret_cast<const void*>(ipa_core32_kernel<FUSE, ZT, NF>), lds, lds_cfg)) return rc;
+    if (int rc = ensure_dynamic_lds(reinterpret_cast<const void*>(ipa_core32_kernel<FUSE, ZT, NF, QROWS>), lds, lds_cfg)) return rc;
     const float* zsc = ZT ? pair_terms + pair_terms_floats(z_shared ? N / z_shared : N, L) : nullptr;
     prof::begin(st);
-    hipLaunchKernelGGL((ipa_core32_kernel<FUSE, ZT, NF>), dim3(plan.grid), dim3(NTH2), lds, st, qfrag, kvfrag, z, mask, R, t, feat, pbc, L, nib2, plan.remap, z_shared, ta,
+    hipLaunchKernelGGL((ipa_core32_kernel<FUSE, ZT, NF, QROWS>), dim3(plan.grid), dim3(NTH2), lds, st, qfrag, kvfrag, z, mask, R, t, feat, pbc, L, nib2, plan.remap, z_shared, ta,
                        prof::next_span_slot(), ZT ? pair_terms : nullptr, zsc);
     prof::end(st);
     ABOPT_LAUNCH_CHECK();
@@ -1849,8 +1885,9 @@ static int launch_core32(const CorePlan& plan, const float* qfrag, const float* 
 int launch_ipa_block_fused(const CorePlan& plan, const float* qfrag, const float* kvfrag, const float* z, const uint8_t* mask, const float* R, const float* t,
                            const float* pair_bias_cache, int N, int L, hipStream_t st, int z_shared, const float* wot, const float* wmf, const float* x,
                            const float* ubias, const float* g1, const float* be1, const float* b0, const float* b1, const float* b2, const float* g2,
-                           const float* be2, float* out, const float* pair_terms, float* xt_out, const NodeCarryArgs* carry) {
+                           const float* be2, float* out, const float* pair_terms, float* xt_out, const NodeCarryArgs* carry, const uint8_t* query_rows) {
     ABOPT_CHECK_ARG(plan.form == CoreForm::Core32 && pair_bias_cache && wot && wmf, "ipa_block_fused: not a 32-row plan with a cache and packed tail weights");
+    ABOPT_CHECK_ARG(!query_rows || !carry, "ipa_block_fused: a block with masked query rows carries nothing");
     const TailArgs ta0{wot, wmf, x, ubias, g1, be1, b0, b1, b2, g2, be2, out, reinterpret_cast<unsigned*>(xt_out)};
     if (carry) {
         ABOPT_CHECK_ARG(carry->w_node_frag && carry->spatial_coef && carry->qfrag && carry->kvfrag && carry->qfrag != qfrag && carry->kvfrag != kvfrag,
@@ -1860,6 +1897,13 @@ int launch_ipa_block_fused(const CorePlan& plan, const float* qfrag, const float
         tn.nc = *carry;
         return pair_terms ? launch_core32<true, true, true>(plan, qfrag, kvfrag, z, mask, R, t, nullptr, pair_bias_cache, N, L, st, z_shared, tn, pair_terms)
                           : launch_core32<true, false, true>(plan, qfrag, kvfrag, z, mask, R, t, nullptr, pair_bias_cache, N, L, st, z_shared, tn, nullptr);
+    }
+    if (query_rows) {
+        TailArgsT<false, true> tq;
+        static_cast<TailArgs&>(tq) = ta0;
+        tq.qrows = query_rows;
+        return pair_terms ? launch_core32<true, true, false, true>(plan, qfrag, kvfrag, z, mask, R, t, nullptr, pair_bias_cache, N, L, st, z_shared, tq, pair_terms)
+                          : launch_core32<true, false, false, true>(plan, qfrag, kvfrag, z, mask, R, t, nullptr, pair_bias_cache, N, L, st, z_shared, tq, nullptr);
     }
     TailArgsT<false> ta;
     static_cast<TailArgs&>(ta) = ta0;

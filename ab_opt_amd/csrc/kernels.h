@@ -42,7 +42,9 @@ int launch_ipa_block_fused(const CorePlan& plan, const float* qfrag, const float
                            const float* pair_bias_cache, int N, int L, hipStream_t st, int z_shared, const float* wot /* W_out as bf16 terms */, const float* wmf, const float* x,
                            const float* ubias, const float* g1, const float* be1, const float* b0, const float* b1, const float* b2, const float* g2,
                            const float* be2, float* out, const float* pair_terms = nullptr, float* xt_out = nullptr,
-                           const NodeCarryArgs* carry = nullptr /* the next block's fragments are written too (ipa_core32_kernel<true, *, true>) */);
+                           const NodeCarryArgs* carry = nullptr /* the next block's fragments are written too (ipa_core32_kernel<true, *, true>) */,
+                           const uint8_t* query_rows = nullptr /* [N L], forward_plan.h: query_rows_masked -- `out` is read on the rows marked here only: the others stream
+                                                                  neither pair data nor bias and leave finite, unspecified rows (ipa_core32_kernel<true, *, false, true>) */);
 
 // node_frags.hip: x [N*L,128] -> qfrag / kvfrag directly (projection GEMM + frame transform + fragment layout in one kernel)
 size_t node_wfrag_floats();

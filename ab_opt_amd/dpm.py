@@ -361,11 +361,13 @@ class FullDPM(_Derived, nn.Module):
             # Network and transitions as one call: where the library fuses the step's tail, it also runs the mixer of the next evaluation there (carry_out: this call
             # has a next step) and skips its own (carry_in: the previous step of this call left it in the workspace, which nothing else touches inside the loop)
             more = j + 1 < K and (spec.stop_after is None or j + 1 < spec.stop_after)
+            # `net` never leaves this function and the transitions keep the old state on context residues: the library may leave it unspecified there
+            # (context_outputs_unused; it does where the step's tail is fused, so never with the prmsd head and the perplexity of abdock)
             hip.eps_net_step(ew, tv[i], p_norm, ts[i], res_feat, pair_feat, beta_rows[t], mask_generate, mask_res, self.num_bins, net,
                              self._step_params(t, spec.sample_structure, spec.sample_sequence, spec.ppl_masked, spec.optimize_mode, t_prev),
                              noise[t] if noise is not None else None, seed, rng_offset, tp[i], X[j], cdf[j] if noise is None else None, out,
                              pair_bias_cache=pbc, pair_feat_shared=(group if shared else 0), pair_terms=pterms, seed_dev=seed_dev, aa_allowed=aa_allowed,
-                             carry_in=j > 0, carry_out=more)
+                             carry_in=j > 0, carry_out=more, context_outputs_unused=True)
             evals += 1
         self.last_run_info = dict(bias_cache=use_bias_cache, pair_terms=pterms is not None, shared_context=shared, graph=seed_dev is not None, steps=evals)
         return tv, tp, ts, tpr, tpp

@@ -23,7 +23,7 @@
 extern "C" {
 #endif
 
-#define ABOPT_ABI_VERSION 49
+#define ABOPT_ABI_VERSION 50
 
 enum { ABOPT_OK = 0, ABOPT_EINVAL = 1, ABOPT_EHIP = 2, ABOPT_EUNSUPPORTED = 3, ABOPT_EWORKSPACE = 4 };
 
@@ -314,6 +314,24 @@ int abopt_eps_net_step(const abopt_eps_weights* w, const float* v_t, const float
                        const float* igso3_X, const float* igso3_cdf, int igso3_bins, int num_bins,
                        float* v_next, float* p_next, int64_t* s_next, float* prmsd, float* perplexity, float* post_out, float* p_next_norm,
                        const uint64_t* seed_offset_dev, const int32_t* aa_allowed, int carry_in, int carry_out, abopt_stream stream);
+
+/* The same call from a loop that reads the network's outputs on generated residues only (ABI 50).  context_outputs_unused = 0: abopt_eps_net_step, bit for bit.
+ * context_outputs_unused != 0: v_next, p_next, s_next, post_out and p_next_norm are still bit-identical to abopt_eps_net_step's -- the transitions keep the old state
+ * wherever mask_generate is 0, whatever the network says there -- and so are v_net, R_net, eps_pos and c_denoised on residues with mask_generate set; on the other
+ * residues those four are finite but unspecified, and abopt_nonfinite_flag does not rise because of them.  What the library does with the freedom: where the step's
+ * tail is fused (see above: packed operands, no prmsd head, perplexity NULL) and the last block of the encoder is the fused 32-row kernel on a pair-bias cache, that
+ * block streams pair features and pair bias for generated query rows only.  Every other call runs exactly as abopt_eps_net_step does; ABOPT_STEP_ROWS=0 makes all do. */
+int abopt_eps_net_step_rows(const abopt_eps_weights* w, const float* v_t, const float* p_t, const int64_t* s_t,
+                            const float* res_feat, const float* pair_feat, const float* beta,
+                            const uint8_t* mask_generate, const uint8_t* mask_res,
+                            float* v_net, float* R_net, float* eps_pos, float* c_denoised, float* prmsd_logits,
+                            int N, int L, int F, int C,
+                            const float* pair_bias_cache, int pair_feat_shared, const float* pair_terms, void* ws, size_t ws_bytes,
+                            const abopt_step_params* sp, const abopt_step_noise* noise, uint64_t seed, uint64_t offset, const float* p_angstrom,
+                            const float* igso3_X, const float* igso3_cdf, int igso3_bins, int num_bins,
+                            float* v_next, float* p_next, int64_t* s_next, float* prmsd, float* perplexity, float* post_out, float* p_next_norm,
+                            const uint64_t* seed_offset_dev, const int32_t* aa_allowed, int carry_in, int carry_out, int context_outputs_unused,
+                            abopt_stream stream);
 
 /* ---- IGSO(3) angle histograms for arbitrary standard deviations (ABI 45): the tables ApproxAngularDistribution builds on the host at construction
  * (D/modules/common/so3.py:82-109), for the strides of a respaced loop, whose sigmas are chosen per call.  Row r, bin b at x_b = linspace(0, pi, bins)[b]:

@@ -1,0 +1,223 @@
+"""The last IPA block of a sampling step on generated query rows only (csrc/forward_plan.h: query_rows_masked; csrc/ipa_core.hip: ipa_core32_kernel<true, *, false, true>;
+include/abopt.h: abopt_eps_net_step_rows).  With the caller's word that it reads the network's outputs on generated residues only, the last
+block's pair waves send the z / term and bias requests of every other query row through a descriptor of zero records: zeros come back, nothing is fetched.  What the
+step hands on -- v_next, p_next, s_next, the posterior, p_next_norm -- and the network's outputs on generated rows are torch.equal to the same call without the word;
+the network's outputs on the other rows are finite and the range guard stays down.  ABOPT_CORE32=1 so that the small shapes take the 32-row kernels; that these shapes
+do mask on a 256-CU device is pinned without a device in tests/test_forward_plan_rows.py::test_shapes_of_the_gpu_test_are_masked."""
+import pytest
+import torch
+
+from ab_opt_amd import hip
+from ab_opt_amd.dpm import FullDPM, _LoopSpec
+from ab_opt_amd.utils import synth
+
+pytestmark = pytest.mark.gpu
+
+DEV = torch.device('cuda:0')
+T = 3
+NET = ('v_next', 'R_next', 'eps_pos', 'c')
+OUT = ('v', 'p', 's', 'p_norm')
+
+
+@pytest.fixture(scope='module')
+def design():
+    m = FullDPM(128, 64, num_steps=T, eps_net_opt=dict(num_layers=3), _abdesign=True).eval()
+    return synth.fill_module_(m, seed=5).to(DEV)
+
+
+@pytest.fixture(autouse=True)
+def core32(monkeypatch):
+    monkeypatch.setenv('ABOPT_CORE32', '1')
+    monkeypatch.setenv('ABOPT_CORE_NO_SPLIT', '1')
+    monkeypatch.delenv('ABOPT_STEP_ROWS', raising=False)
+    monkeypatch.delenv('ABOPT_PAIR_TERMS', raising=False)
+
+
+# N, L, lengths, samples per shared pair_feat entry (0: distinct)
+SHAPES = {
+    'three_row_blocks_last_partial_five_chunks': (2, 80, [80, 73], 0),     # workgroups own rows 0..31, 32..63, 64..79; five key chunks (5 % 3 = 2: both loop remainders)
+    'shared_pair_features': (3, 64, [64, 64, 50], 3),                      # one pair_feat entry for the batch: the descriptors' bases and row offsets of the shared form
+}
+
+
+def _scattered(N, L):
+    """Generated rows by (workgroup of 32 rows, pair wave of 8 rows).  Sample 0: workgroup 0 scattered -- row 0, wave 1 owns exactly one generated row (11), wave 2 none,
+    wave 3 two -- workgroup 1 none at all, the last workgroup all of its rows (row L - 1 among them).  Sample 1: workgroup 0 all, workgroup 1 one row in one wave, the last
+    one its first and last row.  Further samples: nothing in workgroup 0, every fifth row behind it."""
+    g = torch.zeros(N, L, dtype=torch.bool)
+    last0 = 32 * ((L - 1) // 32)
+    g[0, [0, 3, 11, 25, 30]] = True
+    g[0, last0:] = True
+    g[1, :32] = True
+    g[1, 45] = True
+    g[1, [last0, L - 1]] = True
+    g[2:, 32::5] = True
+    return g
+
+
+MASKS = {'scattered': _scattered, 'all_ones': lambda N, L: torch.ones(N, L, dtype=torch.bool), 'all_zeros': lambda N, L: torch.zeros(N, L, dtype=torch.bool)}
+
+
+def _inputs(shape, mask, salt=1200):
+    N, L, lengths, group = SHAPES[shape]
+    v, p, s, res_feat, pair_feat, _, _, mres = [a.to(DEV) for a in synth.eps_inputs(N, L, lengths, [], salt=salt, num_steps=T, t=2)]
+    gen = MASKS[mask](N, L).to(DEV)
+    if mask == 'scattered':
+        assert gen[0, 0] and gen[0, L - 1] and mres[0, L - 1]                                          # rows 0 and L - 1 are generated
+        full = gen[:, :32 * (L // 32)].view(N, -1, 32).sum(2)
+        assert (full == 0).any() and (full == 32).any() and gen[0, 32 * ((L - 1) // 32):].all()         # a workgroup with none, one with all (the partial one too)
+        assert (gen[0, :32].view(4, 8).sum(1) == 1).any()                                                 # a pair wave that owns exactly one generated row
+    gen &= mres
+    if group:
+        pair_feat = pair_feat[:N // group].contiguous()
+    return dict(N=N, L=L, group=group, v=v, p=p * 10.0, s=s, res_feat=res_feat, pair_feat=pair_feat, gen=gen, mres=mres)
+
+
+def _steps(d, inp, unused, nsteps, terms, pbc, pterms):
+    """nsteps calls of the step entry from t = T down, the mixer carried from call to call; every call has network and output buffers of its own"""
+    N, L = inp['N'], inp['L']
+    f32 = dict(dtype=torch.float32, device=DEV)
+    ew = d.eps_net.packed()
+    X, cdf = d._loop_tables(d._loop_steps(_LoopSpec(T)))
+    v, p, s = inp['v'], inp['p'], inp['s']
+    p_norm = ((p - d.position_mean) / d.position_scale).contiguous()
+    res = []
+    for j in range(nsteps):
+        t = T - j
+        net = dict(v_next=torch.empty(N, L, 3, **f32), R_next=torch.empty(N, L, 3, 3, **f32), eps_pos=torch.empty(N, L, 3, **f32), c=torch.empty(N, L, 20, **f32),
+                   prmsd_logits=None)
+        out = dict(v=torch.empty(N, L, 3, **f32), p=torch.empty(N, L, 3, **f32), s=torch.empty(N, L, dtype=torch.int64, device=DEV), p_norm=torch.empty(N, L, 3, **f32))
+        beta = d.trans_pos.var_sched.betas[t].expand(N).contiguous()
+        post = hip.eps_net_step(ew, v, p_norm, s, inp['res_feat'], inp['pair_feat'], beta, inp['gen'], inp['mres'], d.num_bins, net,
+                                d._step_params(t, True, True, True, False, t - 1), None, 11, 4096, p, X[j], cdf[j], out, pair_bias_cache=pbc,
+                                pair_feat_shared=inp['group'], pair_terms=pterms if terms else None, want_post=True, carry_in=j > 0, carry_out=j + 1 < nsteps,
+                                context_outputs_unused=unused)
+        res.append(dict(net=net, out=out, post=post))
+        v, p, s, p_norm = out['v'], out['p'], out['s'], out['p_norm']
+    return res
+
+
+def _run(d, inp, unused, nsteps, terms, replays=0):
+    """eagerly (replays = 0), or captured once and replayed `replays` times: the results of the last replay"""
+    pf = inp['pair_feat']
+    pbc = hip.pair_bias_cache(d.eps_net.encoder.packed_array(), len(d.eps_net.encoder.blocks), pf)
+    pterms = hip.pair_terms(pf)
+    hip.nonfinite_flag(reset=True)
+    if not replays:
+        res = _steps(d, inp, unused, nsteps, terms, pbc, pterms)
+    else:
+        hip.prof_enable(False)
+        _steps(d, inp, unused, 1, terms, pbc, pterms)                       # warm: kernel attributes, host-side caches
+        torch.cuda.synchronize()
+        before = set(hip.Workspace._bufs)
+        g = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(g):
+            res = _steps(d, inp, unused, nsteps, terms, pbc, pterms)
+        keep = [hip.Workspace._bufs.pop(k) for k in set(hip.Workspace._bufs) - before]       # the slab the capture allocated lives in the graph's pool
+        for _ in range(replays):
+            for r in res:
+                for a in list(r['net'].values()) + list(r['out'].values()) + [r['post']]:
+                    if a is not None:
+                        a.fill_(7)                                            # a replay that wrote nothing would be seen
+            g.replay()
+        torch.cuda.synchronize()
+        clone = lambda d_: {k: (a.clone() if a is not None else None) for k, a in d_.items()}
+        res = [dict(net=clone(r['net']), out=clone(r['out']), post=r['post'].clone()) for r in res]      # own storage: the buffers are the graph's static ones
+        del keep, g
+    torch.cuda.synchronize()
+    flag = hip.nonfinite_flag(reset=True)
+    return res, flag
+
+
+def _check(got, flag_got, ref, flag_ref, gen, everything):
+    assert not flag_ref and not flag_got                                    # abopt_nonfinite_flag reads 0
+    assert len(got) == len(ref)
+    for a, b in zip(got, ref):
+        for k in OUT:
+            assert torch.equal(a['out'][k], b['out'][k]), (k, int((a['out'][k] != b['out'][k]).sum()))
+        assert torch.equal(a['post'], b['post'])
+        for k in NET:
+            assert torch.isfinite(a['net'][k]).all() and torch.isfinite(b['net'][k]).all(), k
+            assert torch.equal(a['net'][k][gen], b['net'][k][gen]), (k, int((a['net'][k][gen] != b['net'][k][gen]).sum()))
+            if everything:
+                assert torch.equal(a['net'][k], b['net'][k]), k
+
+
+@pytest.fixture(scope='module')
+def reference():
+    """flag off, computed once per (shape, mask, terms, steps) and shared"""
+    return {}
+
+
+def _ref(reference, d, shape, mask, terms, nsteps):
+    key = (shape, mask, terms, nsteps)
+    if key not in reference:
+        inp = _inputs(shape, mask)
+        reference[key] = (inp,) + _run(d, inp, False, nsteps, terms)
+    return reference[key]
+
+
+@pytest.mark.parametrize('terms', [True, False], ids=['pair_terms', 'fp32_stream'])
+@pytest.mark.parametrize('mask', list(MASKS))
+@pytest.mark.parametrize('shape', list(SHAPES))
+def test_one_step(design, reference, monkeypatch, shape, mask, terms):
+    if not terms:
+        monkeypatch.setenv('ABOPT_PAIR_TERMS', '0')
+    inp, ref, fr = _ref(reference, design, shape, mask, terms, 1)
+    got, fg = _run(design, inp, True, 1, terms)
+    _check(got, fg, ref, fr, inp['gen'], everything=mask == 'all_ones')
+    if mask == 'scattered':
+        assert not torch.equal(got[0]['out']['s'], inp['s'])               # the step moved the generated residues
+
+
+@pytest.mark.parametrize('terms', [True, False], ids=['pair_terms', 'fp32_stream'])
+@pytest.mark.parametrize('mask', list(MASKS))
+@pytest.mark.parametrize('shape', list(SHAPES))
+def test_three_steps_carried_eager_and_replayed_twice(design, reference, monkeypatch, shape, mask, terms):
+    if not terms:
+        monkeypatch.setenv('ABOPT_PAIR_TERMS', '0')
+    inp, ref, fr = _ref(reference, design, shape, mask, terms, 3)
+    got, fg = _run(design, inp, True, 3, terms)
+    _check(got, fg, ref, fr, inp['gen'], everything=mask == 'all_ones')
+    rep, fp = _run(design, inp, True, 3, terms, replays=2)
+    _check(rep, fp, ref, fr, inp['gen'], everything=mask == 'all_ones')
+
+
+def test_switch_restores_the_full_stream(design, monkeypatch):
+    """ABOPT_STEP_ROWS=0: the call with the word runs what the call without it runs -- every output equal, context rows of the network's included"""
+    inp = _inputs('three_row_blocks_last_partial_five_chunks', 'scattered')
+    ref, fr = _run(design, inp, False, 1, True)
+    monkeypatch.setenv('ABOPT_STEP_ROWS', '0')
+    got, fg = _run(design, inp, True, 1, True)
+    _check(got, fg, ref, fr, inp['gen'], everything=True)
+
+
+def test_context_rows_do_differ(design):
+    """the comparisons above prove nothing if the plan refused: with the word, a context row's c_denoised is another finite number (its pair features were zeros)"""
+    inp = _inputs('three_row_blocks_last_partial_five_chunks', 'scattered')
+    ref, _ = _run(design, inp, False, 1, True)
+    got, _ = _run(design, inp, True, 1, True)
+    ctx = inp['mres'] & ~inp['gen']
+    assert not torch.equal(got[0]['net']['c'][ctx], ref[0]['net']['c'][ctx])
+
+
+@pytest.mark.parametrize('graph', [False, True], ids=['eager', 'graph'])
+def test_loop_trajectories(design, monkeypatch, graph):
+    """FullDPM._run for three steps at N = 2, L = 80: the trajectories with ABOPT_STEP_ROWS=0 and without it"""
+    inp = _inputs('three_row_blocks_last_partial_five_chunks', 'scattered')
+
+    def loop(rows):
+        if rows:
+            monkeypatch.delenv('ABOPT_STEP_ROWS', raising=False)
+        else:
+            monkeypatch.setenv('ABOPT_STEP_ROWS', '0')
+        design.clear_graphs()
+        out = design._run((inp['v'], inp['p'], inp['s']), T, inp['res_feat'], inp['pair_feat'], inp['gen'], inp['mres'], True, True, True, None, 11, 4096, False, graph=graph)
+        torch.cuda.synchronize()
+        assert design.last_run_info['steps'] == T and design.last_run_info['pair_terms'] and bool(design.last_run_info['graph']) == graph
+        res = [a.clone() for a in out if a is not None]
+        design.clear_graphs()
+        return res
+    ref, got = loop(False), loop(True)
+    assert len(got) == len(ref) == 3 and all(torch.equal(a, b) for a, b in zip(got, ref)), [int((a != b).sum()) for a, b in zip(got, ref)]
+    assert not torch.equal(ref[0][0], ref[0][-1])                           # the loop moved the state
