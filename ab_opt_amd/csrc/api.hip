@@ -710,3 +710,39 @@ extern "C" int abopt_eps_net_step_rows(const abopt_eps_weights* w, const float* 
     return eps_forward(w, v_t, p_t, s_t, res_feat, pair_feat, beta, mask_generate, mask_res, v_net, R_net, eps_pos, c_denoised, prmsd_logits, N, L, Fd, Cd, 0,
                        pair_bias_cache, pair_feat_shared, pair_terms, ws, ws_bytes, stream, &sc);
 }
+
+// ---- lDDT-CA (kernels: lddt.hip).  Every check precedes the first launch.
+extern "C" size_t abopt_lddt_ws_bytes(int G, int S, int L) { return lddt_ws_bytes(G, S, L); }
+
+static int lddt_check(const char* name, bool ensemble, const void* pos, const void* mask, int G, int S, int L, int A, float cutoff, const void* num, const void* den,
+                      const void* ws, size_t ws_bytes) {
+    ABOPT_CHECK_ARG(G >= 0 && S >= 0 && L >= 1 && A >= 2 && (int64_t)G * S <= 0x7fffffff, "%s: bad dims G=%d S=%d L=%d A=%d (atom slot 1 is the CA: A >= 2)", name, G, S, L, A);
+    ABOPT_CHECK_ARG(A <= 15, "%s: A=%d atoms per residue exceed the maximum of 15", name, A);
+    ABOPT_CHECK_ARG(std::isfinite(cutoff) && cutoff > 0.f, "%s: the cutoff must be finite and > 0 (got %g)", name, (double)cutoff);
+    if (L > 16384) { set_error("%s: L=%d residues exceed the maximum of 16384 (4 L^2 has to fit an int32)", name, L); return ABOPT_EUNSUPPORTED; }
+    if (ensemble && S > 16384) { set_error("%s: S=%d candidates per group exceed the maximum of 16384", name, S); return ABOPT_EUNSUPPORTED; }
+    ABOPT_CHECK_ARG(!ensemble || (int64_t)G * S * S <= 0x7fffffff, "%s: G S S = %lld entries exceed 2^31 - 1", name, (long long)G * S * S);
+    if (G == 0 || S == 0) return ABOPT_OK;
+    ABOPT_CHECK_ARG(G <= 65535, "%s: G=%d groups exceed one launch (max 65535)", name, G);
+    ABOPT_CHECK_ARG(pos && mask && num && den && ws, "%s: NULL argument", name);
+    ABOPT_CHECK_ARG(((uintptr_t)ws & 15) == 0 && ((uintptr_t)num & 3) == 0 && ((uintptr_t)den & 3) == 0, "%s: the workspace must be 16-byte aligned, num and den 4-byte aligned", name);
+    const size_t need = lddt_ws_bytes(G, S, L);
+    if (ws_bytes < need) { set_error("%s: workspace too small (%zu bytes given, %zu needed)", name, ws_bytes, need); return ABOPT_EWORKSPACE; }
+    return ABOPT_OK;
+}
+
+extern "C" int abopt_lddt_ca_grouped(const float* pos, const uint8_t* mask, int mask_shared, const float* ref_pos, const uint8_t* ref_mask, const uint8_t* rows,
+                                     const int32_t* group, int G, int S, int L, int A, float cutoff, void* num, void* den, void* ws, size_t ws_bytes,
+                                     abopt_stream stream) {
+    const int rc = lddt_check("lddt_ca_grouped", false, pos, mask, G, S, L, A, cutoff, num, den, ws, ws_bytes);
+    if (rc != ABOPT_OK || G == 0 || S == 0) return rc;
+    ABOPT_CHECK_ARG(ref_pos && ref_mask, "lddt_ca_grouped: NULL argument");
+    return launch_lddt(pos, mask, mask_shared, ref_pos, ref_mask, rows, group, G, S, L, A, cutoff, (int32_t*)num, (int32_t*)den, ws, (hipStream_t)stream);
+}
+
+extern "C" int abopt_lddt_ca_ensemble(const float* pos, const uint8_t* mask, int mask_shared, const uint8_t* rows, const int32_t* group, int G, int S, int L, int A,
+                                      float cutoff, void* num, void* den, void* ws, size_t ws_bytes, abopt_stream stream) {
+    const int rc = lddt_check("lddt_ca_ensemble", true, pos, mask, G, S, L, A, cutoff, num, den, ws, ws_bytes);
+    if (rc != ABOPT_OK || G == 0 || S == 0) return rc;
+    return launch_lddt(pos, mask, mask_shared, nullptr, nullptr, rows, group, G, S, L, A, cutoff, (int32_t*)num, (int32_t*)den, ws, (hipStream_t)stream);
+}

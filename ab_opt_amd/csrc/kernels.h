@@ -157,4 +157,11 @@ int launch_reconstruct_backbone(const float* pos_ctx, const float* R_new, const 
                                 const int64_t* res_nb, const uint8_t* mask_atoms, const uint8_t* mask_recons, const float* bb_table,
                                 const float* o_table, float* pos_new, uint8_t* mask_new, int N, int L, int A, hipStream_t st);
 
+// lddt.hip ------------------------------------------------------------------------------------
+// lDDT-CA counts (include/abopt.h: abopt_lddt_ca_grouped / abopt_lddt_ca_ensemble).  ref_pos == nullptr: the ensemble form, num / den [G][S][S]; else the
+// grouped form, num / den [G S][L].  ws: lddt_ws_bytes(G, S, L) bytes, 16-byte aligned.  The callers have checked every argument.
+size_t lddt_ws_bytes(int G, int S, int L);
+int launch_lddt(const float* pos, const uint8_t* mask, int mask_shared, const float* ref_pos, const uint8_t* ref_mask, const uint8_t* rows,
+                const int32_t* group, int G, int S, int L, int A, float cutoff, int32_t* num, int32_t* den, void* ws, hipStream_t st);
+
 }  // namespace abopt

@@ -13,7 +13,7 @@ import torch
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # ABOPT_LIB_PATH: developer override to load a variant build of the same ABI (csrc/Makefile VARIANT=...: A/B of two source trees)
 LIB_PATH = os.environ.get('ABOPT_LIB_PATH') or os.path.join(_HERE, 'libabopt_hip.so')
-ABI_VERSION = 50
+ABI_VERSION = 51
 
 c_f = C.c_void_p        # device float*
 c_i64 = C.c_void_p      # device int64*
@@ -167,6 +167,9 @@ _SIGNATURES = {
     'abopt_sequence_profile_grouped': (c_int, [c_u8, c_int, c_int, c_int, c_void_p, c_stream]),
     'abopt_interface_geometry_ws_bytes': (c_size_t, [c_int, c_int, c_int]),
     'abopt_interface_geometry_grouped': (c_int, [c_f, c_u8, c_int, c_i32, c_u8] + [c_int] * 4 + [c_float] * 3 + [c_void_p] * 3 + [c_size_t, c_stream]),
+    'abopt_lddt_ws_bytes': (c_size_t, [c_int, c_int, c_int]),
+    'abopt_lddt_ca_grouped': (c_int, [c_f, c_u8, c_int, c_f, c_u8, c_u8, c_i32] + [c_int] * 4 + [c_float, c_void_p, c_void_p, c_void_p, c_size_t, c_stream]),
+    'abopt_lddt_ca_ensemble': (c_int, [c_f, c_u8, c_int, c_u8, c_i32] + [c_int] * 4 + [c_float, c_void_p, c_void_p, c_void_p, c_size_t, c_stream]),
     'abopt_prof_enable': (c_int, [c_int]),
     'abopt_prof_spans_reset': (c_int, [c_stream]),
     'abopt_prof_spans': (c_int, [POINTER(c_int), POINTER(c_double)]),
@@ -781,6 +784,106 @@ def interface_geometry_grouped(pos, mask, group, clash_cutoff=3.0, contact_cutof
     if want_freq:
         res['freq'] = freq
     return res
+
+
+def check_lddt_cutoff(name, v):
+    """float(v), or ValueError unless it is finite and > 0 (the check abopt_lddt_ca_grouped / abopt_lddt_ca_ensemble make on their cutoff, ahead of any device work)."""
+    import math
+    c = float(v)
+    if not math.isfinite(c) or c <= 0.0:
+        raise ValueError(f'{name} must be finite and > 0 (got {v!r})')
+    return c
+
+
+def lddt_ratio(num, den):
+    """num / (4 den) in float64, rounded to fp32 once; -1 where den == 0 (the reference's lddt() returns eps / eps = 1.0 there: DESIGN.md section 6.5).  Pure torch,
+    no host read."""
+    d = den.double()
+    return torch.where(den > 0, num.double() / (4.0 * d.clamp_min(1.0)), -1.0).float()
+
+
+def _lddt_args(name, pos, mask, G, rows, group, cutoff):
+    """Shape checks shared by the two lDDT calls (no device work) -> (S, L, A, shared, cutoff)."""
+    if pos.dim() != 4 or mask.dim() != 3 or pos.shape[3] != 3:
+        raise ValueError(f'{name}: expected pos (G*S, L, A, 3) and mask (G*S or G, L, A), got {tuple(pos.shape)} and {tuple(mask.shape)}')
+    N, L, A = pos.shape[:3]
+    if L < 1 or L > 16384 or (N % G if G else N):
+        raise ValueError(f'{name}: {tuple(pos.shape)} candidates are not whole groups of {G} with 1 <= L <= 16384')
+    if not 2 <= A <= 15:
+        raise ValueError(f'{name}: A={A} atoms per residue, expected 2 .. 15 (atom slot 1 is the CA)')
+    S = N // G if G else 0
+    shared = mask.shape[0] != N or S == 1
+    if tuple(mask.shape) != ((G if shared else N), L, A):
+        raise ValueError(f'{name}: mask {tuple(mask.shape)} is neither per candidate nor per group')
+    for what, t in (('rows', rows), ('group', group)):
+        if t is not None and tuple(t.shape) != (G, L):
+            raise ValueError(f'{name}: {what} {tuple(t.shape)} must be (G, L) = {(G, L)}')
+    return S, L, A, shared, check_lddt_cutoff(f'{name}: cutoff', cutoff)
+
+
+def _lddt_tensors(pos, mask, rows, group):
+    pos, mask = _contig(pos.float(), mask if mask.dtype in (torch.bool, torch.uint8) else mask.bool())
+    rows = None if rows is None else (rows if rows.dtype in (torch.bool, torch.uint8) else rows != 0).contiguous()
+    group = None if group is None else group.to(torch.int32).contiguous()
+    return pos, mask, rows, group
+
+
+def lddt_ca_grouped(pos, mask, ref_pos, ref_mask, rows=None, group=None, cutoff=15.0):
+    """lDDT-CA of G*S candidates against the G references of their groups, per residue and pooled (include/abopt.h: abopt_lddt_ca_grouped).
+    pos (G*S,L,A,3); mask (G*S,L,A), or (G,L,A) shared by the S candidates of a group; ref_pos (G,L,A,3), ref_mask (G,L,A); atom slot 1 is the CA.  rows
+    (optional, (G,L) bool): the residues that are scored; group (optional, (G,L) int): the interface form, only pairs with one residue of side 1 and one of side 2
+    count; cutoff in Angstrom on the reference's CA-CA distance.
+    -> dict of device tensors: num, den (G*S,L) int32 (hits of the four thresholds, scored pairs), lddt_res (G*S,L) fp32 = num / (4 den) and lddt (G*S,) fp32 =
+    sum num / (4 sum den), both computed in float64 and rounded once, -1 where den == 0.  Stream-ordered, no host synchronisation."""
+    name = 'lddt_ca_grouped'
+    if ref_pos.dim() != 4 or ref_mask.dim() != 3:
+        raise ValueError(f'{name}: expected ref_pos (G, L, A, 3) and ref_mask (G, L, A), got {tuple(ref_pos.shape)} and {tuple(ref_mask.shape)}')
+    G = ref_pos.shape[0]
+    S, L, A, shared, cut = _lddt_args(name, pos, mask, G, rows, group, cutoff)
+    if tuple(ref_pos.shape) != (G, L, A, 3) or tuple(ref_mask.shape) != (G, L, A):
+        raise ValueError(f'{name}: ref_pos {tuple(ref_pos.shape)} / ref_mask {tuple(ref_mask.shape)} do not match the candidates {tuple(pos.shape)}')
+    ptr(pos, strided=True)                                          # a CPU tensor is refused here, before anything is allocated
+    ptr(ref_pos, strided=True)
+    pos, mask, rows, group = _lddt_tensors(pos, mask, rows, group)
+    ref_pos, ref_mask, _, _ = _lddt_tensors(ref_pos, ref_mask, None, None)
+    dev = pos.device
+    num, den = torch.empty(G * S, L, dtype=torch.int32, device=dev), torch.empty(G * S, L, dtype=torch.int32, device=dev)
+    buf = Workspace.get(max(16, lib().abopt_lddt_ws_bytes(G, S, L)), dev)
+    _check(lib().abopt_lddt_ca_grouped(ptr(pos, torch.float32), ptr(mask), int(shared), ptr(ref_pos, torch.float32), ptr(ref_mask), ptr(rows, optional=True),
+                                       ptr(group, torch.int32, optional=True), G, S, L, A, cut, ptr(num), ptr(den), ptr(buf), buf.numel(), stream()))
+    return dict(num=num, den=den, lddt_res=lddt_ratio(num, den), lddt=lddt_ratio(num.sum(1, dtype=torch.int64), den.sum(1, dtype=torch.int64)))
+
+
+def lddt_ca_ensemble(pos, mask, group_size, rows=None, group=None, cutoff=15.0):
+    """lDDT-CA of every candidate of a group against every other one, pooled over the residues (include/abopt.h: abopt_lddt_ca_ensemble).
+    pos (G*S,L,A,3) with S = group_size; mask (G*S,L,A) or (G,L,A); rows, group, cutoff as for lddt_ca_grouped.
+    -> dict of device tensors: num, den (G,S,S) int32, entry (g, a, b) = candidate a as the reference, b as the model; lddt (G,S,S) fp32 = num / (4 den), -1 where
+    den == 0 (the diagonal is 1 wherever it has a scored pair); consistency (G,S) fp32: for candidate b the mean of lddt(a, b) over the a != b with den > 0 (in
+    float64, rounded once), -1 if there is none.  Stream-ordered, no host synchronisation."""
+    name = 'lddt_ca_ensemble'
+    S = int(group_size)
+    if S < 1 and pos.shape[0]:
+        raise ValueError(f'{name}: group_size must be >= 1 (got {group_size!r})')
+    if S > 16384:
+        raise ValueError(f'{name}: group_size {S} exceeds the maximum of 16384')
+    G = pos.shape[0] // S if S else 0
+    if G * S != pos.shape[0]:
+        raise ValueError(f'{name}: {tuple(pos.shape)} candidates are not whole groups of {S}')
+    _, L, A, shared, cut = _lddt_args(name, pos, mask, G, rows, group, cutoff)
+    if G * S * S > 2 ** 31 - 1:
+        raise ValueError(f'{name}: G S S = {G * S * S} entries exceed 2^31 - 1')
+    ptr(pos, strided=True)                                          # a CPU tensor is refused here, before anything is allocated
+    pos, mask, rows, group = _lddt_tensors(pos, mask, rows, group)
+    dev = pos.device
+    num, den = torch.empty(G, S, S, dtype=torch.int32, device=dev), torch.empty(G, S, S, dtype=torch.int32, device=dev)
+    buf = Workspace.get(max(16, lib().abopt_lddt_ws_bytes(G, S, L)), dev)
+    _check(lib().abopt_lddt_ca_ensemble(ptr(pos, torch.float32), ptr(mask), int(shared), ptr(rows, optional=True), ptr(group, torch.int32, optional=True),
+                                        G, S, L, A, cut, ptr(num), ptr(den), ptr(buf), buf.numel(), stream()))
+    peer = (den > 0) & ~torch.eye(S, dtype=torch.bool, device=dev)
+    ratio = torch.where(peer, num.double() / (4.0 * den.double().clamp_min(1.0)), 0.0)
+    cnt = peer.sum(1)
+    consistency = torch.where(cnt > 0, ratio.sum(1) / cnt.clamp_min(1), -1.0).float()
+    return dict(num=num, den=den, lddt=lddt_ratio(num, den), consistency=consistency)
 
 
 def pair_bias_cache_layers(w_pair_bias_list, pair_feat):

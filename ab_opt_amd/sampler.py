@@ -154,6 +154,44 @@ def interface_geometry(batch, pos, mask, groups='chains', **cutoffs):
     return hip.interface_geometry_grouped(pos, mask, grp, link=link, **cutoffs)
 
 
+def _lddt_group(name, fragment_type, interface, G):
+    """group (G, L) of the interface form from fragment_type (G, L) or (L,) (screen.chain_groups), or None."""
+    from . import screen
+    if not interface:
+        return None
+    if fragment_type is None:
+        raise ValueError(f'{name}: interface=True takes the two sides from fragment_type')
+    ft = fragment_type if fragment_type.dim() == 2 else fragment_type[None]
+    return screen.chain_groups(ft.expand(G, ft.shape[1]))
+
+
+def lddt_scores(model_pos, model_mask, ref_pos, ref_mask, rows=None, fragment_type=None, interface=False, cutoff=15.0):
+    """lDDT-CA of candidate structures against reference structures, per residue and pooled (hip.lddt_ca_grouped): bounded in [0, 1],
+    no superposition.  model_pos (G*S, L, A, 3), model_mask (G*S, L, A) or (G, L, A): S candidates of each of G references ref_pos (G, L, A, 3) / ref_mask
+    (G, L, A) (or one reference (L, A, 3) / (L, A)); candidate c belongs to reference c // S.  rows (optional, (G, L) or (L,) bool): the residues that are
+    scored.  interface=True: only pairs across the interface count, antibody against antigen as DockQ sees them (screen.chain_groups of fragment_type (G, L) or
+    (L,)).  -> dict(num, den, lddt_res (G*S, L), lddt (G*S,)); -1 where nothing was scored (the reference's lddt() gives 1.0 there)."""
+    from . import hip
+    if ref_pos.dim() == 3:
+        ref_pos, ref_mask = ref_pos[None], ref_mask[None]
+    G = ref_pos.shape[0]
+    if rows is not None and rows.dim() == 1:
+        rows = rows[None].expand(G, -1)
+    return hip.lddt_ca_grouped(model_pos, model_mask, ref_pos, ref_mask, rows=rows, group=_lddt_group('lddt_scores', fragment_type, interface, G), cutoff=cutoff)
+
+
+def lddt_consistency(pos, mask, group_size, rows=None, fragment_type=None, interface=False, cutoff=15.0):
+    """How well the S = group_size structures of each group agree with each other (hip.lddt_ca_ensemble): the lDDT counterpart of
+    `commonness_score`.  pos (G*S, L, A, 3), mask (G*S, L, A) or (G, L, A); rows / fragment_type / interface / cutoff as for `lddt_scores`.
+    -> dict(num, den, lddt (G, S, S): structure a as the reference, b as the model; consistency (G, S): the mean lDDT of each structure against its peers)."""
+    from . import hip
+    S = int(group_size)
+    G = pos.shape[0] // S if S > 0 else 0
+    if rows is not None and rows.dim() == 1:
+        rows = rows[None].expand(G, -1)
+    return hip.lddt_ca_ensemble(pos, mask, S, rows=rows, group=_lddt_group('lddt_consistency', fragment_type, interface, G), cutoff=cutoff)
+
+
 def dockq_scores(model_pos, model_mask, native_pos, native_mask, fragment_type=None, group=None):
     """DockQ of candidate structures against the native complex, on the device (the reference writes every candidate to a PDB
     file and shells out: AbDock/src/tools/runner/design_for_pdb.py:316-321, AbDock/DockQ/DockQ.py:98-385).

@@ -40,6 +40,12 @@ Sequence clustering (optional, off by default): the seque
 clustered by the number of differing positions and their composition is counted (two grouped calls per design launch); `screen_by='diverse'` re-docks one design per
 family instead of k near-copies, and `share_redocks` re-docks every distinct chosen sequence once, whichever poses chose it.  How many duplicates trained weights
 produce is unmeasured.
+
+lDDT-CA (optional, off by default): DockQ, commonness and prmsd say how well the D re-docks of a design agree, not WHERE they disagree.  With
+`lddt_cutoff` every re-dock is scored by the lDDT-CA of its re-docked residues against its design complex, per residue and pooled (ONE hip.lddt_ca_grouped call per
+chunk, with the groups of the grouped DockQ call), and among the D re-docks of its design (ONE hip.lddt_ca_ensemble call per chunk): bounded in [0, 1], no
+superposition, -1 where nothing is scored.  The scores steer nothing and draw nothing; `screen_filter(min_lddt=)` can use them afterwards.  What values trained
+weights produce is unmeasured.
 """
 import time
 
@@ -117,11 +123,24 @@ def _rebuild(pos, mask, traj0, lo, hi, aa, flag, one):
                                                    mask, gen)
 
 
+def _scored_mean_std(t, dim):
+    """Mean and population standard deviation of the lDDT values t along `dim`, over the entries that were scored (>= 0; -1 marks "no scored pair"), computed in
+    float64 and rounded to fp32 once; -1 where no entry was scored.  Pure torch, no host read."""
+    ok = t >= 0
+    cnt = ok.sum(dim)
+    div = cnt.clamp_min(1).double()
+    v = torch.where(ok, t.double(), 0.0)
+    mean = v.sum(dim) / div
+    var = (torch.where(ok, (t.double() - mean.unsqueeze(dim)) ** 2, 0.0)).sum(dim) / div
+    none = cnt == 0
+    return torch.where(none, -1.0, mean).float(), torch.where(none, -1.0, var.sqrt()).float()
+
+
 @torch.no_grad()
 def optimize_antibody(dock_model, design_model, complex_, num_poses, designs_per_pose, redocks_per_design, design_flag=None, redock_flag=None,
                       contig='', screened_per_pose=1, seed=0, poses_per_launch=8, group=None, screen_by='first', timings=None, allowed_aa=None,
                       dock_steps=None, design_steps=None, cluster_cutoff=None, max_clusters=None, redock_cutoff=None, clash_cutoff=None, contact_cutoff=None,
-                      bond_max=None, seq_mismatch=None, share_redocks=False):
+                      bond_max=None, seq_mismatch=None, share_redocks=False, lddt_cutoff=None):
     """Dock -> redesign -> re-dock screen of one antibody-antigen complex (module docstring).
 
     complex_: batch dict with batch dim 1 (cropped, as sample_replicated takes it); its generate_flag marks the residues to dock.
@@ -158,6 +177,14 @@ def optimize_antibody(dock_model, design_model, complex_, num_poses, designs_per
     the optional re-dock cluster / geometry / epitope fields are computed per unit and copied to every owner (pose, slot), dockq is computed for every owner against
     its own design complex.  Every field keeps its shape; the result gains design_unit (., k), unit_owner (U,) (flat index pose k + slot of the unit's centre) and
     unit_size (U,), int64.  Costs one host read (the units) between stage 2 and stage 3.
+    lddt_cutoff (optional, Angstrom, 15.0 is the reference's; default None: nothing below exists, no other field changes): score every re-dock
+    by lDDT-CA of the re-docked residues (rows = redock_flag, pairs with every residue of the complex within lddt_cutoff in the design) -- against its design complex
+    (ONE hip.lddt_ca_grouped call per chunk, beside the grouped DockQ call and with its groups) and among the D re-docks of its design (ONE hip.lddt_ca_ensemble call
+    per chunk).  The result gains redock_lddt (., k, D) fp32, the pooled lDDT of each re-dock against its design; redock_lddt_res (., k, D, n_redock) fp32, the same per
+    re-docked residue; lddt_mean / lddt_std (., k) over the D re-docks and lddt_res_mean (., k, n_redock), the per-residue "where do they disagree" answer, each
+    ignoring the -1 of a re-dock or residue without a scored pair (-1 if all are); redock_consistency (., k, D) fp32, the mean lDDT of each re-dock against its D - 1
+    peers.  Leading dimension, gathering and cluster_cutoff as for dockq; with share_redocks the versus-design fields follow dockq (per owner) and
+    redock_consistency follows redock_score (per unit, copied to every owner).  The scores steer nothing and draw nothing.
     timings (optional dict): receives the seconds each stage took on this rank (device-synchronised) and of the final gather ('cluster': the gather and
     clustering between stage 1 and stage 2, with cluster_cutoff; 'units': the gather and clustering between stage 2 and stage 3, with share_redocks).
 
@@ -194,6 +221,8 @@ def optimize_antibody(dock_model, design_model, complex_, num_poses, designs_per
         geom = dict(clash_cutoff=hip.check_distance_cutoff('optimize_antibody: clash_cutoff', 3.0 if clash_cutoff is None else clash_cutoff),
                     contact_cutoff=hip.check_distance_cutoff('optimize_antibody: contact_cutoff', 5.0 if contact_cutoff is None else contact_cutoff),
                     bond_max=None if bond_max is None else hip.check_distance_cutoff('optimize_antibody: bond_max', bond_max))
+    if lddt_cutoff is not None:
+        lddt_cutoff = hip.check_lddt_cutoff('optimize_antibody: lddt_cutoff', lddt_cutoff)
     if max_clusters is not None and (cluster_cutoff is None or int(max_clusters) < 1):
         raise ValueError(f'optimize_antibody: max_clusters must be >= 1 and needs cluster_cutoff (got max_clusters={max_clusters!r}, cluster_cutoff={cluster_cutoff!r})')
     L = int(one['aa'].shape[1])
@@ -331,11 +360,25 @@ def optimize_antibody(dock_model, design_model, complex_, num_poses, designs_per
             ig = hip.interface_geometry_grouped(pos, mask, grp[None].expand(n, L), link=None if links is None else links.expand(n, L), want_freq=True, **geom)
             out['redock_geom'] = torch.stack([ig[c] for c in geom_cols], 1).long().view(n, D, 5)
             out['epitope_freq'] = ig['freq'].float() / D
+        if lddt_cutoff is not None:                                                      # the D re-docks of every design among each other
+            out['redock_consistency'] = hip.lddt_ca_ensemble(pos, mask, D, rows=rflag[None].expand(n, L), cutoff=lddt_cutoff)['consistency']
+        return out
+
+    def versus_design(rpos, rmask, dpos, dmask):
+        """The D re-docks of each of n owners against the owner's design complex: one grouped DockQ launch [+ one grouped lDDT call] -> the owner fields."""
+        n = dpos.shape[0]
+        out = dict(dockq=hip.dockq_lite_grouped(rpos, rmask, dpos, dmask, grp[None].expand(n, L), check=False).view(n, D, 4))
+        if lddt_cutoff is not None:
+            ld = hip.lddt_ca_grouped(rpos, rmask, dpos, dmask, rows=rflag[None].expand(n, L), cutoff=lddt_cutoff)
+            out['redock_lddt'] = ld['lddt'].view(n, D)
+            out['redock_lddt_res'] = ld['lddt_res'][:, rflag].view(n, D, n_redock)
         return out
 
     unit_fields = ('prmsd', 'redock_score') + (('redock_cluster_frac', 'redock_clusters') if redock_cutoff is not None else ()) + \
-                  (('redock_geom', 'epitope_freq') if geom is not None else ())
-    tail = dict(dockq=(D, 4), prmsd=(D,), redock_score=(D,), redock_cluster_frac=(), redock_clusters=(), redock_geom=(D, 5), epitope_freq=(L,))     # per design
+                  (('redock_geom', 'epitope_freq') if geom is not None else ()) + (('redock_consistency',) if lddt_cutoff is not None else ())
+    owner_fields = ('dockq',) + (('redock_lddt', 'redock_lddt_res') if lddt_cutoff is not None else ())      # scored against the owner's own design complex
+    tail = dict(dockq=(D, 4), prmsd=(D,), redock_score=(D,), redock_cluster_frac=(), redock_clusters=(), redock_geom=(D, 5), epitope_freq=(L,),
+                redock_consistency=(D,), redock_lddt=(D,), redock_lddt_res=(D, n_redock))                     # per design
     kind = dict(redock_clusters=torch.int64, redock_geom=torch.int64)
     counts = [e - s_ for s_, e in (sampler.shard_range(Q, world, r) for r in range(world))]
     shared = None
@@ -355,7 +398,7 @@ def optimize_antibody(dock_model, design_model, complex_, num_poses, designs_per
         t0 = tick('units', t0)
 
         # ---- stage 3 over the U units: unit u takes the place of pose u with ONE screened design (launches, shards, Philox: global sample index u D + re-dock)
-        got = {name: [] for name in unit_fields + ('dockq',)}
+        got = {name: [] for name in unit_fields + owner_fields}
         for lo, hi in launch_plan(U, poses_per_launch, world, rank):
             own = units['centre'][lo:hi]
             r = redock(all_pos[own], all_mask[own], all_aa[own], rngs('redock', lo, 1))
@@ -365,35 +408,38 @@ def optimize_antibody(dock_model, design_model, complex_, num_poses, designs_per
             ow = torch.tensor([i for u in range(lo, hi) for i in owners[u]], dtype=torch.int64, device=dev)
             src = torch.tensor([u - lo for u in range(lo, hi) for _ in owners[u]], dtype=torch.int64, device=dev)
             rows = (src[:, None] * D + torch.arange(D, device=dev)).reshape(-1)
-            out = hip.dockq_lite_grouped(r['pos'][rows], r['mask'][rows], all_pos[ow], all_mask[ow], grp[None].expand(ow.numel(), L), check=False)
-            got['dockq'].append(out.view(ow.numel(), D, 4))
+            vs = versus_design(r['pos'][rows], r['mask'][rows], all_pos[ow], all_mask[ow])
+            for name in owner_fields:
+                got[name].append(vs[name])
         got = {name: (torch.cat(v, 0) if v else torch.empty(0, *tail[name], dtype=kind.get(name, torch.float32), device=dev)) for name, v in got.items()}
         if world > 1:
             ucounts = [e - s_ for s_, e in (sampler.shard_range(U, world, r) for r in range(world))]
             ocounts = [sum(len(owners[u]) for u in range(*sampler.shard_range(U, world, r))) for r in range(world)]
-            got = {name: sampler.all_gather_candidates(t, ocounts if name == 'dockq' else ucounts, group) for name, t in got.items()}
+            got = {name: sampler.all_gather_candidates(t, ocounts if name in owner_fields else ucounts, group) for name, t in got.items()}
         order = torch.tensor([i for u in range(U) for i in owners[u]], dtype=torch.int64, device=dev)
         shared = {name: got[name][units['label']].view(Q, k, *got[name].shape[1:]) for name in unit_fields}      # a unit's rows, copied to every owner (pose, slot)
-        shared['dockq'] = torch.empty(Q * k, D, 4, **f32).index_copy_(0, order, got['dockq']).view(Q, k, D, 4)
+        for name in owner_fields:
+            shared[name] = torch.empty(Q * k, *tail[name], **f32).index_copy_(0, order, got[name]).view(Q, k, *tail[name])
         shared.update(design_unit=units['label'].view(Q, k), unit_owner=units['centre'], unit_size=units['size'])
         plan = []                                                                        # stage 3 is done
 
     # ---- stage 3: D re-docks of every screened design, one grouped DockQ + one grouped commonness launch per chunk
-    dockq = torch.empty(mine, k, D, 4, **f32)
+    owner3 = {name: torch.empty(mine, k, *tail[name], **f32) for name in owner_fields}
     stage3 = {name: torch.empty(mine, k, *tail[name], dtype=kind.get(name, torch.float32), device=dev) for name in unit_fields}
     for lo, hi in plan:
         Gk = (hi - lo) * k
         npos, nmask, naa = (t[lo - a:hi - a].reshape(Gk, *t.shape[2:]) for t in (des_pos, des_mask, des_aa))
         r = redock(npos, nmask, naa, rngs('redock', lo))
-        out = hip.dockq_lite_grouped(r['pos'], r['mask'], npos, nmask, grp[None].expand(Gk, L), check=False)
-        dockq[lo - a:hi - a] = out.view(hi - lo, k, D, 4)
+        vs = versus_design(r['pos'], r['mask'], npos, nmask)
+        for name in owner_fields:
+            owner3[name][lo - a:hi - a] = vs[name].view(hi - lo, k, *tail[name])
         for name in unit_fields:
             stage3[name][lo - a:hi - a] = r[name].view(hi - lo, k, *r[name].shape[1:])
     t0 = tick('redock', t0)
 
     res = dict(pose_ca=pose_ca, seqs=seqs, aar=aar, ppl=ppl, chosen=chosen)
     if shared is None:
-        res.update(dockq=dockq, **stage3)
+        res.update(**owner3, **stage3)
     if geom is not None:
         res.update(pose_geom=pose_geom)
     if seq_mismatch is not None:
@@ -410,6 +456,9 @@ def optimize_antibody(dock_model, design_model, complex_, num_poses, designs_per
     res['pose_score'] = hip.commonness_score(res['pose_ca'])
     q, pr = res['dockq'][..., 3], res['prmsd']
     res.update(dockq_mean=q.mean(-1), dockq_std=q.std(-1, unbiased=False), prmsd_mean=pr.mean(-1), prmsd_std=pr.std(-1, unbiased=False))
+    if lddt_cutoff is not None:
+        res['lddt_mean'], res['lddt_std'] = _scored_mean_std(res['redock_lddt'], -1)
+        res['lddt_res_mean'] = _scored_mean_std(res['redock_lddt_res'], 2)[0]
     tick('gather', t0)
     if timings is not None:
         clock.pop('start', None)
@@ -417,11 +466,13 @@ def optimize_antibody(dock_model, design_model, complex_, num_poses, designs_per
     return res
 
 
-def screen_filter(res, max_clashes=None, min_contacts=None):
+def screen_filter(res, max_clashes=None, min_contacts=None, min_lddt=None):
     """The notebook's median rule (ab_opt_analysis_4mutations.ipynb, cell 7): keep the designs whose DockQ_std, prmsd_std and prmsd_avg
     are each at or below the median over all screened designs (pandas' quantile(0.5): the mean of the two middle values for an even count).
     max_clashes / min_contacts (optional; need the redock_geom of optimize_antibody(clash_cutoff=...)): additionally require, per design, that the MEDIAN over
     its D re-docks (the same quantile) of the clash count is <= max_clashes and of the contact count is >= min_contacts.
+    min_lddt (optional; needs the redock_lddt of optimize_antibody(lddt_cutoff=...)): additionally require that the MEDIAN over a design's D re-docks of the pooled
+    lDDT against the design is >= min_lddt (a re-dock without a scored pair enters with its -1).
     -> bool (P, k)."""
     med = lambda t: torch.quantile(t.reshape(-1).double(), 0.5)
     keep = torch.ones_like(res['dockq_std'], dtype=torch.bool)
@@ -436,4 +487,8 @@ def screen_filter(res, max_clashes=None, min_contacts=None):
             keep &= over_d[..., 0] <= float(max_clashes)
         if min_contacts is not None:
             keep &= over_d[..., 1] >= float(min_contacts)
+    if min_lddt is not None:
+        if 'redock_lddt' not in res:
+            raise ValueError('screen_filter: min_lddt needs redock_lddt (run optimize_antibody with lddt_cutoff)')
+        keep &= torch.quantile(res['redock_lddt'].double(), 0.5, dim=-1) >= float(min_lddt)
     return keep

@@ -23,7 +23,7 @@
 extern "C" {
 #endif
 
-#define ABOPT_ABI_VERSION 50
+#define ABOPT_ABI_VERSION 51
 
 enum { ABOPT_OK = 0, ABOPT_EINVAL = 1, ABOPT_EHIP = 2, ABOPT_EUNSUPPORTED = 3, ABOPT_EWORKSPACE = 4 };
 
@@ -697,6 +697,37 @@ size_t abopt_interface_geometry_ws_bytes(int G, int S, int L);
 int abopt_interface_geometry_grouped(const float* pos, const uint8_t* mask, int mask_shared, const int32_t* group, const uint8_t* link,
                                      int G, int S, int L, int A, float clash_d, float contact_d, float bond_max, void* out, void* freq,
                                      void* ws, size_t ws_bytes, abopt_stream stream);
+
+/* ---- lDDT-CA (ABI 51): the superposition-free, bounded agreement score of two structures of one chain set, per residue -- where do a design's re-docks
+ * disagree with the design, and with each other.  The reference carries the score as lddt() of D/modules/common/plddt.py:41-94 (CA, cutoff 15, the four
+ * thresholds 0.5 / 1 / 2 / 4); this is that function as integer counts, with two deliberate differences: no eps inside the root, and a residue or pair set
+ * without any scored pair is reported by den = 0 (Python: -1) where the reference returns eps / eps = 1.0.  G groups of S
+ * candidates, conventions of abopt_dockq_lite_grouped and abopt_interface_geometry_grouped:
+ *   pos [G*S,L,A,3] fp32; mask [G*S,L,A], or [G,L,A] shared by the S candidates of a group (mask_shared != 0); atom slot 1 is the CA, so A >= 2;
+ *   rows (optional) [G,L] uint8: the residues i that are scored (NULL: all); group (optional) [G,L] int32, the interface form: a pair (i, j) takes part only
+ *   if {group[i], group[j]} == {1, 2}; cutoff in Angstrom, finite and > 0 (15.0 in the reference).
+ *   distance    d2(p, q) = fmaf(dz, dz, fmaf(dy, dy, dx dx)) with dx = __fsub_rn(x_p, x_q) and dx dx = __fmul_rn: the spelling of
+ *               abopt_interface_geometry_grouped, every step rounded once; d = __fsqrt_rn(d2).  No eps inside the root.
+ *   abopt_lddt_ca_grouped: candidate c of group g against ref_pos [G,L,A,3] / ref_mask [G,L,A].  Residue i is valid iff its CA byte is set in both the
+ *     candidate's mask and the reference's.  For a valid i selected by rows, every valid j != i that passes the group test is a pair; dt is the CA-CA distance in
+ *     the reference, dp in the candidate.  The pair is scored iff dt < cutoff (strict; a NaN dt is never scored).  A scored pair adds 1 to den[c,i] and
+ *     [e < 0.5] + [e < 1] + [e < 2] + [e < 4] to num[c,i], e = |__fsub_rn(dt, dp)|: a NaN dp scores no hit, and the pair still counts in den.
+ *     num, den [G*S,L] int32 (DEVICE, spelled void*: this header names no mutable int32 pointer type); every row that is not scored holds 0.
+ *   abopt_lddt_ca_ensemble: no separate reference.  Entry (g, a, b) of num, den [G,S,S] int32 is the sum over i of the counts above with candidate a of the
+ *     group as the reference and candidate b as the model, validity from both candidates' masks; the diagonal is computed like any other entry (num = 4 den).
+ *     It equals, bit for bit, the sum over L of an abopt_lddt_ca_grouped call that is handed candidate a as ref_pos.
+ *   The scores a caller derives: lddt_res = num / (4 den) per residue, lddt = sum_i num / (4 sum_i den) pooled (the reference's per_residue=False).
+ *   ws: abopt_lddt_ws_bytes(G, S, L) bytes, 16-byte aligned (the CA of every structure as float4, the compacted rows; 0 for an empty call).
+ * Stream-ordered (two launches in one chain, outputs and workspace cleared by a kernel: capturable into a hipGraph), nothing allocated, no host
+ * synchronisation, no LDS.  1 <= L <= 16384 (4 L^2 fits an int32; beyond: ABOPT_EUNSUPPORTED), 2 <= A <= 15, G <= 65535, G S <= 2^31 - 1; the ensemble form:
+ * S <= 16384 (beyond: ABOPT_EUNSUPPORTED) and G S S <= 2^31 - 1; G = 0 or S = 0 is a no-op; every check precedes the first launch.  The results are
+ * integers: no order of the additions changes them, and a group's result is that of a call on the group alone. */
+size_t abopt_lddt_ws_bytes(int G, int S, int L);
+int abopt_lddt_ca_grouped(const float* pos, const uint8_t* mask, int mask_shared, const float* ref_pos, const uint8_t* ref_mask, const uint8_t* rows,
+                          const int32_t* group, int G, int S, int L, int A, float cutoff, void* num, void* den, void* ws, size_t ws_bytes,
+                          abopt_stream stream);
+int abopt_lddt_ca_ensemble(const float* pos, const uint8_t* mask, int mask_shared, const uint8_t* rows, const int32_t* group, int G, int S, int L, int A,
+                           float cutoff, void* num, void* den, void* ws, size_t ws_bytes, abopt_stream stream);
 
 /* ---- Measurement hook (bench.py's roofline leg).  When enabled, every launch of the IPA-core kernel is bracketed
  * by hipEvents on the stream it is launched on; abopt_prof_collect synchronises those events and returns the number
