@@ -85,12 +85,12 @@ static GaScratch carve_ga(Carver& cv, int64_t M, int N, int L) {
     return s;
 }
 
-// The eight environment switches of the forward path, read once per C-ABI call (never cached: callers flip them between the calls of one process)
+// The nine environment switches of the forward path, read once per C-ABI call (never cached: callers flip them between the calls of one process)
 static Switches read_switches() {
     const auto first = [](const char* name) { const char* e = getenv(name); return e ? e[0] : '\0'; };
     const char c32 = first("ABOPT_CORE32");
     return {c32 == '0' ? 0 : (c32 == '1' ? 1 : -1), getenv("ABOPT_CORE_NO_SPLIT") != nullptr, first("ABOPT_FUSE_TAIL") != '0', first("ABOPT_X_TERMS") != '0',
-            first("ABOPT_FUSE_HEADS") != '0', first("ABOPT_FUSE_STEP") != '0', first("ABOPT_FUSE_NODE") != '0', first("ABOPT_STEP_ROWS") != '0'};
+            first("ABOPT_FUSE_HEADS") != '0', first("ABOPT_FUSE_STEP") != '0', first("ABOPT_FUSE_NODE") != '0', first("ABOPT_STEP_ROWS") != '0', first("ABOPT_STEP_COMPACT") != '0'};
 }
 
 // What every forward entry knows of its ForwardQuery (forward_plan.h): geometry, the CU count (asked once per entry), operands and scratch held, which blocks are
@@ -111,7 +111,8 @@ static int forward_query(int N, int L, int z_shared, const GaScratch& s, const a
 
 // what one block runs on, besides its plan, its weights and the scratch
 struct BlockArgs { const float *R, *t, *x, *z; const uint8_t* mask; float* x_out; const float *pbc = nullptr, *pair_terms = nullptr; const abopt_ga_debug* dbg = nullptr; float* feat_out = nullptr;
-                   const uint8_t* query_rows = nullptr; /* [N L]: the rows on which the LAST block's output is read, for a plan with query_rows_masked */ };
+                   const uint8_t* query_rows = nullptr; /* [N L]: the rows on which the LAST block's output is read, for a plan with query_rows_masked */
+                   const int32_t* query_row_list = nullptr; /* the same rows as abopt_query_row_list lists them, for a plan with query_rows_compact */ };
 
 // wnext: the next block's weights where the plan has this block write that block's fragments (carry_next), into the other fragment pair
 static int ga_block(const BlockPlan& p, const ForwardQuery& q, const abopt_ga_weights* w, const BlockArgs& a, const GaScratch& s, hipStream_t st,
@@ -119,6 +120,7 @@ static int ga_block(const BlockPlan& p, const ForwardQuery& q, const abopt_ga_we
     const int N = q.N, L = q.L;
     float *const qf = s.qf[p.frag_slot], *const kvf = s.kvf[p.frag_slot];
     ABOPT_CHECK_ARG(!p.query_rows_masked || (a.query_rows && p.tail == TailForm::InCore), "ga_block: the plan masks query rows the call does not name");
+    ABOPT_CHECK_ARG(!p.query_rows_compact || (p.query_rows_masked && a.query_row_list), "ga_block: the plan gathers query rows the call does not list");
     ABOPT_CHECK_ARG(qf && kvf && (!p.carry_next || (wnext && s.qf[1 - p.frag_slot])), "ga_block: the plan carries fragments the workspace or the weight list cannot hold");
     const int64_t M = (int64_t)N * L;
     const float* pair_terms = p.qk_terms ? a.pair_terms : nullptr;          // the term forms go together: q / k term fragments only for the core that reads pair terms
@@ -138,7 +140,7 @@ static int ga_block(const BlockPlan& p, const ForwardQuery& q, const abopt_ga_we
         const NodeCarryArgs nc{wnext ? wnext->w_node_frag : nullptr, wnext ? wnext->spatial_coef : nullptr, s.qf[1 - p.frag_slot], s.kvf[1 - p.frag_slot], next_qk_terms};
         return launch_ipa_block_fused(p.core, qf, kvf, a.z, a.mask, a.R, a.t, a.pbc, N, L, st, q.z_shared, w->w_out_terms, w->w_mlp_frag, a.x, w->b_out, w->ln1_gamma,
                                       w->ln1_beta, w->b_mlp0, w->b_mlp1, w->b_mlp2, w->ln2_gamma, w->ln2_beta, a.x_out, pair_terms, xt_out, p.carry_next ? &nc : nullptr,
-                                      p.query_rows_masked ? a.query_rows : nullptr);
+                                      p.query_rows_masked ? a.query_rows : nullptr, p.query_rows_compact ? a.query_row_list : nullptr, p.query_rows_compact);
     }
     float* feat = (a.dbg && a.dbg->feat) ? a.dbg->feat : (a.feat_out ? a.feat_out : s.feat);
     if ((rc = launch_ipa_core(p.core, qf, kvf, a.z, a.mask, a.R, a.t, w->w_pair_bias, feat, a.dbg ? a.dbg->logits : nullptr, a.dbg ? a.dbg->alpha : nullptr, a.pbc,
@@ -555,6 +557,7 @@ EpsScratch carve_eps(Carver& cv, int64_t M, int N, int L, int num_bins) {
 struct StepCall {
     const abopt_step_params* sp; const abopt_step_noise* noise; uint64_t seed, offset; const float* p_angstrom; const float *igX, *igCdf; int bins, num_bins;
     float *v_next, *p_next; int64_t* s_next; float *prmsd, *ppl, *post_out, *p_next_norm; const uint64_t* seed_dev; const int32_t* aa_allowed; int carry_in, carry_out, context_unused;
+    const int32_t* query_row_list = nullptr; int query_row_tiles = 0;      // abopt_eps_net_step_rows_compact
 };
 }  // namespace
 
@@ -605,6 +608,7 @@ static int eps_forward(const abopt_eps_weights* w, const float* v_t, const float
         if ((rc = check_step_args(sc->sp, sc->noise, sc->igX, sc->igCdf, sc->bins, &nz))) return rc;
         q.step = true; q.ppl = sc->ppl != nullptr; q.carry_in = sc->carry_in != 0; q.carry_out = sc->carry_out != 0;
         q.context_unused = sc->context_unused != 0;
+        q.query_row_tiles = sc->context_unused ? sc->query_row_tiles : 0;
     }
     const NetPlan plan = plan_network(q);
 
@@ -622,6 +626,7 @@ static int eps_forward(const abopt_eps_weights* w, const float* v_t, const float
     // dpm_full.py:90  encoder
     BlockArgs ba{e.R, p_t, e.cat, pair_feat, mask_res, e.xe, pair_bias_cache, pair_terms};
     ba.query_rows = mask_generate;                                          // read where the plan masks the last block's query rows (a step that says context_unused)
+    ba.query_row_list = sc ? sc->query_row_list : nullptr;                  // ... and where it gathers them
     if ((rc = ga_encoder(plan.enc, q, w->blocks, ba, e.ga, e.pong, st))) return rc;
     // dpm_full.py:92-93 time features (the heads kernel takes them as an affine term: then only the prmsd head's LayerNorm'd copy is needed)
     if (plan.build_infeat && (rc = launch_build_infeat(e.xe, beta, e.infeat, w->prmsd_ln_gamma, w->prmsd_ln_beta, plan.prmsd ? e.infeat_ln : nullptr, N, L, st))) return rc;
@@ -707,6 +712,32 @@ extern "C" int abopt_eps_net_step_rows(const abopt_eps_weights* w, const float* 
                                        abopt_stream stream) {
     const StepCall sc{sp, noise, seed, offset, p_angstrom, igso3_X, igso3_cdf, igso3_bins, num_bins, v_next, p_next, s_next, prmsd, perplexity, post_out, p_next_norm,
                       seed_offset_dev, aa_allowed, carry_in, carry_out, context_outputs_unused};
+    return eps_forward(w, v_t, p_t, s_t, res_feat, pair_feat, beta, mask_generate, mask_res, v_net, R_net, eps_pos, c_denoised, prmsd_logits, N, L, Fd, Cd, 0,
+                       pair_bias_cache, pair_feat_shared, pair_terms, ws, ws_bytes, stream, &sc);
+}
+
+extern "C" int abopt_query_row_list(const uint8_t* mask_generate, int N, int L, void* rows, void* count, abopt_stream stream) {
+    ABOPT_CHECK_ARG(N >= 0 && L >= 0 && (int64_t)N * (L + 15) < (1ll << 31), "query_row_list: bad dims N=%d L=%d", N, L);
+    if (N == 0) return ABOPT_OK;
+    ABOPT_CHECK_ARG(mask_generate && rows && count, "query_row_list: NULL argument");
+    return launch_query_row_list(mask_generate, N, L, (int32_t*)rows, (int32_t*)count, (hipStream_t)stream);
+}
+
+extern "C" int abopt_eps_net_step_rows_compact(const abopt_eps_weights* w, const float* v_t, const float* p_t, const int64_t* s_t,
+                                               const float* res_feat, const float* pair_feat, const float* beta,
+                                               const uint8_t* mask_generate, const uint8_t* mask_res,
+                                               float* v_net, float* R_net, float* eps_pos, float* c_denoised, float* prmsd_logits,
+                                               int N, int L, int Fd, int Cd, const float* pair_bias_cache, int pair_feat_shared,
+                                               const float* pair_terms, void* ws, size_t ws_bytes,
+                                               const abopt_step_params* sp, const abopt_step_noise* noise, uint64_t seed, uint64_t offset, const float* p_angstrom,
+                                               const float* igso3_X, const float* igso3_cdf, int igso3_bins, int num_bins,
+                                               float* v_next, float* p_next, int64_t* s_next, float* prmsd, float* perplexity, float* post_out, float* p_next_norm,
+                                               const uint64_t* seed_offset_dev, const int32_t* aa_allowed, int carry_in, int carry_out,
+                                               const int32_t* query_rows, const int32_t* query_row_count, int query_row_tiles, abopt_stream stream) {
+    ABOPT_CHECK_ARG(query_row_tiles >= 0 && (query_row_tiles == 0 || (query_rows && query_row_count)), "eps_net_step_rows_compact: %d tiles of a row list that is not given", query_row_tiles);
+    StepCall sc{sp, noise, seed, offset, p_angstrom, igso3_X, igso3_cdf, igso3_bins, num_bins, v_next, p_next, s_next, prmsd, perplexity, post_out, p_next_norm,
+                seed_offset_dev, aa_allowed, carry_in, carry_out, 1};
+    sc.query_row_list = query_rows; sc.query_row_tiles = query_row_tiles;
     return eps_forward(w, v_t, p_t, s_t, res_feat, pair_feat, beta, mask_generate, mask_res, v_net, R_net, eps_pos, c_denoised, prmsd_logits, N, L, Fd, Cd, 0,
                        pair_bias_cache, pair_feat_shared, pair_terms, ws, ws_bytes, stream, &sc);
 }

@@ -1,7 +1,7 @@
 // Which launches a denoiser forward is made of: the ONE place that decides (api.hip reads the switches once per entry, builds a ForwardQuery and walks the plan;
 // the launchers of ipa_core.hip / ipa.hip take the CorePlan they are handed).  plan_ipa_core (ipa_plan.h) is called from here and from nowhere else on the
-// forward path.  Plain host C++17, no HIP: tests/forward_plan_table.cpp, tests/forward_plan_carry_table.cpp and tests/forward_plan_rows_table.cpp tabulate the
-// functions without a device (tests/test_forward_plan.py, tests/test_forward_plan_carry.py, tests/test_forward_plan_rows.py).
+// forward path.  Plain host C++17, no HIP: tests/forward_plan_table.cpp, tests/forward_plan_carry_table.cpp, tests/forward_plan_rows_table.cpp and tests/forward_plan_compact_table.cpp
+// tabulate the functions without a device (tests/test_forward_plan.py, tests/test_forward_plan_carry.py, tests/test_forward_plan_rows.py, tests/test_forward_plan_compact.py).
 #pragma once
 #include "ipa_plan.h"
 
@@ -19,6 +19,7 @@ struct Switches {
     bool fuse_step = true;          // ABOPT_FUSE_STEP=0: a denoising step's transitions and the next evaluation's mixer as launches of their own (abopt_eps_net_step)
     bool fuse_node = true;          // ABOPT_FUSE_NODE=0: every block's node_frags as a launch of its own (no block writes its successor's fragments)
     bool step_rows = true;          // ABOPT_STEP_ROWS=0: the last block of a step streams pair data for every query row, wanted or not (query_rows_masked)
+    bool step_compact = true;       // ABOPT_STEP_COMPACT=0: the last block of a step keeps one workgroup per 32 rows, generated or not (query_rows_compact)
 };
 
 struct BlockWeights { bool node_frag, out_frag, mlp_frag, out_terms; };     // which packed operands of abopt_ga_weights are given
@@ -40,6 +41,7 @@ struct ForwardQuery {
     bool step = false, ppl = false, carry_in = false, carry_out = false;
     bool frag2 = false;             // the workspace holds a second fragment pair (api.hip: carve_ga aliases it onto proj | feat where it fits)
     bool context_unused = false;    // abopt_eps_net_step_rows: the caller reads nothing of the network's outputs on rows that are not generated
+    int query_row_tiles = 0;        // abopt_eps_net_step_rows_compact: the caller's list of generated rows fills at most this many 16-row tiles per sample; 0: no list
 };
 
 enum class NodeForm { Kernel, Gemm };               // node_frags | projection GEMM + ipa_frags
@@ -57,6 +59,10 @@ struct BlockPlan {
     // Masked query rows (plan_encoder): the block's output is read on generated rows only, so its fused kernel (ipa_core32_kernel<true, *, false, true>) streams pair
     // data and bias for those rows alone; the other rows of its output are finite and otherwise unspecified
     bool query_rows_masked = false;
+    // Gathered query rows (plan_encoder): on top of query_rows_masked, the caller's row list packs the generated rows of a sample into 16-row tiles and the fused
+    // kernel (ipa_core32_kernel<true, *, false, true, true>) runs one workgroup per tile -- compact_grid = N tiles of them -- and writes generated rows only
+    int query_rows_compact = 0;     // tiles per sample; 0: one workgroup per 32 rows (core.grid)
+    unsigned compact_grid = 0;
 };
 struct EncoderPlan {
     bool ok;                        // false: the last planned block's core is Unsupported and nothing is planned after it
@@ -113,6 +119,21 @@ inline BlockPlan plan_block(const ForwardQuery& q, int i, int produced = -1, int
     return p;
 }
 
+// Gathered query rows (BlockPlan::query_rows_compact), where the last block's query rows are masked already.  The fused kernel's instruction stream is that of 32
+// rows however few of them are wanted; with the generated rows of a sample packed into 16-row tiles a workgroup runs one row tile of the A and C roles and two
+// of its four pair waves.  The rule:
+//   the caller gave a row list (query_row_tiles > 0) and ABOPT_STEP_COMPACT is not 0;
+//   N tiles <= CUs: one round, as the 32-row grid of the same launch would be where it pays most;
+//   tiles <= ceil(L / 32): at most half the rows are generated -- from there on the gathered form has as many workgroups as the plain one, each with half
+//     the rows (the initial rule: no measured point has moved it yet);
+//   three blocks or more: the gathered form writes generated rows only, and the heads read every row of the encoder's output.  Blocks alternate between two
+//     output buffers and the last one writes the caller's, so with three blocks or more block num_blocks - 3 of the SAME forward wrote every row of it (finite
+//     wherever the forward is); a one- or two-block net would leave the heads whatever the buffer held before the call.
+inline bool plan_rows_compact(const ForwardQuery& q, int num_blocks) {
+    const int t = q.query_row_tiles;
+    return t > 0 && q.sw.step_compact && (int64_t)q.N * t <= q.cus && t <= (q.L + BI2 - 1) / BI2 && num_blocks >= 3;
+}
+
 // The blocks of an encoder: block 0's producer wrote `produced` (the mixer; -1: nobody), block i writes slot i & 1.
 // Carried fragments: block i + 1 is carried iff block i's tail is InCore (its workgroups end holding their 32 finished rows), block i + 1's node step is the kernel
 // (packed weights) and its tail is InCore too (the second fragment pair aliases proj | feat, which only Gemm node steps and out-of-core tails touch), the switch
@@ -137,6 +158,10 @@ inline EncoderPlan plan_encoder(const ForwardQuery& q, int produced = -1) {
     if (e.ok && e.num_blocks > 0 && q.context_unused && q.sw.step_rows && plan_step_fused(q) && !q.dbg) {
         BlockPlan& last = e.blocks[e.num_blocks - 1];
         last.query_rows_masked = last.core.form == CoreForm::Core32 && q.cache && last.tail == TailForm::InCore && !last.carry_next;
+        if (last.query_rows_masked && plan_rows_compact(q, e.num_blocks)) {
+            last.query_rows_compact = q.query_row_tiles;
+            last.compact_grid = (unsigned)q.N * (unsigned)q.query_row_tiles;
+        }
     }
     if (!e.ok || !q.sw.fuse_node || !q.frag2 || q.dbg) return e;
     for (int i = 0; i + 1 < e.num_blocks; ++i) {

@@ -863,9 +863,19 @@ struct TailArgs {
 };
 // the kernel's tail arguments: NF adds the operands of the carried projections behind them, every other instantiation keeps TailArgs' layout
 // (QR: the per-row "query row wanted" bytes of ipa_core32_kernel<true, *, false, true>, behind them as well)
-template <bool NF, bool QR = false> struct TailArgsT : TailArgs {};
-template <> struct TailArgsT<true, false> : TailArgs { NodeCarryArgs nc; };
-template <> struct TailArgsT<false, true> : TailArgs { const uint8_t* qrows; };
+// (QC: the list of gathered query rows of ipa_core32_kernel<true, *, false, true, true> in their place)
+template <bool NF, bool QR = false, bool QC = false> struct TailArgsT : TailArgs {};
+template <> struct TailArgsT<true, false, false> : TailArgs { NodeCarryArgs nc; };
+template <> struct TailArgsT<false, true, false> : TailArgs { const uint8_t* qrows; };
+template <> struct TailArgsT<false, true, true> : TailArgs { const int32_t* qlist; };
+// QC: the 16 rows of a workgroup, read from its tile of the sample's row list (abopt_query_row_list: ascending generated rows, then -1); local rows 16..31 of the
+// 32-row structures are nobody's.  Also the tail's row map (tail_common.h)
+struct GatherRows {
+    const int32_t* ql; int64_t rowbase; int L;
+    __device__ __forceinline__ int at(int il) const { const int r = il < 16 ? ql[il & 15] : -1; return (unsigned)r < (unsigned)L ? r : -1; }
+    __device__ __forceinline__ int64_t load(int rl) const { return rowbase + max(at(rl), 0); }
+    __device__ __forceinline__ int64_t store(int rl) const { const int r = at(rl); return r < 0 ? (int64_t)-1 : rowbase + r; }
+};
 constexpr int C32_LOOP_LDS_FLOATS = 3 * 32 * SROW + 2 * 32 * SCLD + 32 * SCLD + 32 * 32;      // sp | scl | lsum | mlr (then the key mask)
 __host__ __device__ constexpr size_t core32_lds_bytes(int nchunk) { return sizeof(float) * C32_LOOP_LDS_FLOATS + (size_t)nchunk * JC; }     // ipa_core32_kernel<false, ZT>
 constexpr int C32F_PTS_OFF = ((C32_LOOP_LDS_FLOATS * 4 + 2048 + 255) / 256) * 256;               // aggregated points [32][12][24] fp32, behind the key mask of L <= 2048
@@ -939,13 +949,23 @@ __device__ __forceinline__ void node_carry_phase(NfLdsTerms xt, NodeCarryArgs nc
 // fetches nothing -- and still counts in vmcnt, so the ring, the software pipeline and every wait stay as they are.  Such a row's softmax sees S alone, its pair
 // features are 0 x the real 1 / S_ic, everything it leaves is finite, and nothing of it reaches another row (attention, out-transform, LayerNorm and MLP are per row).
 // A marked row computes what ipa_core32_kernel<true, ZT> computes, bit for bit.
-template <bool FUSE, bool ZT, bool NF = false, bool QROWS = false>
+//
+// QC (forward_plan.h: query_rows_compact): the marked rows of a sample arrive as a LIST, and a workgroup owns the 16 of them in tile ib of
+// that list instead of rows i0 .. i0 + 31 -- the grid is N x tiles, `nib2` carries the tile count.  Attention, out-transform, LayerNorm and MLP are per query row, so
+// a row may sit at any tile position of any workgroup: the list enters at the load and store ADDRESSES only (the pair waves' row offsets and descriptors, the
+// gathered q' fragments, R / t / x / 1 / S_ic of a row, the row the tail stores) and the arithmetic of a row is that of QROWS, bit for bit.  Local rows 16..31 of the
+// 32-row structures are nobody's: pair waves 2 and 3 skip the key loop (they keep the barrier count and run the producer role on zero accumulators), the A and C
+// waves run ONE row tile, the second half of the epilogue tile carries zeros, and nothing of it -- or of a -1 pad entry, which reads row 0 through the descriptor
+// of zero records -- is stored.  Rows that are not in the list are NOT written: the caller's buffer keeps what it held.
+template <bool FUSE, bool ZT, bool NF = false, bool QROWS = false, bool QC = false>
 __global__ __launch_bounds__(NTH2) void ipa_core32_kernel(const float* __restrict__ qfrag, const float* __restrict__ kvfrag, const float* __restrict__ z,
                                                           const uint8_t* __restrict__ mask, const float* __restrict__ R, const float* __restrict__ t,
                                                           float* __restrict__ feat, const float* __restrict__ pbc, int L, int nib2, int xcd_remap, int z_shared,
-                                                          TailArgsT<NF, QROWS> ta, int prof_slot, const float* __restrict__ zt, const float* __restrict__ zsc) {
+                                                          TailArgsT<NF, QROWS, QC> ta, int prof_slot, const float* __restrict__ zt, const float* __restrict__ zsc) {
     static_assert(FUSE || !NF, "the carried projections follow the fused tail");
     static_assert(!QROWS || (FUSE && !NF), "query rows are masked in the block nobody follows");
+    static_assert(!QC || QROWS, "gathered rows are masked rows");
+    constexpr int NRT = QC ? 1 : 2;                                     // row tiles of the A and C waves' key loops
     extern __shared__ __attribute__((aligned(16))) char smem_raw[];
     float* sp = reinterpret_cast<float*>(smem_raw);                     // [3][BI2][SROW]
     float* scl = sp + 3 * BI2 * SROW;                                   // [2][BI2][SCLD]
@@ -972,6 +992,8 @@ __global__ __launch_bounds__(NTH2) void ipa_core32_kernel(const float* __restric
     const int i0 = ib * BI2;
     const int64_t rowbase = (int64_t)n * L;
     const int64_t zbase = z_shared ? (int64_t)(n / z_shared) * L : rowbase;
+    GatherRows qg_{nullptr, rowbase, L};
+    if constexpr (QC) qg_.ql = ta.qlist + ((int64_t)n * nib16 + ib) * 16;          // [N][nib16 x 16]; ib < tiles <= nib16
     auto fill_mask = [&]() { for (int e = tid; e < nchunk * JC; e += NTH2) mk[e] = (e < L) ? mask[rowbase + e] : 0; };
     // ---- fused tail (FUSE): LDS views valid after barrier F1, and the consumer role (A and C waves after their loops)
     char* const stage = smem_raw;                                               // [2][3][32][OT_SROW]: aliases the S/P tile
@@ -1078,7 +1100,16 @@ __global__ __launch_bounds__(NTH2) void ipa_core32_kernel(const float* __restric
         // QROWS: bit ii = row ii of this wave is read by somebody (wave-uniform, loaded once); the requests of the other rows see a record count of zero --
         // the descriptor is assembled per request from the same base and flags, so the select lands on its record count alone
         unsigned qneed_ = 0xffu;
-        if constexpr (QROWS) {
+        int qr_[RPW2];                                                      // QC: this wave's rows (wave-uniform), -1: nobody's
+        const bool stream_ = !QC || wave < 2;                               // QC: pair waves 2 and 3 own no row
+        if constexpr (QC) {
+            qneed_ = 0u;
+#pragma unroll
+            for (int ii = 0; ii < RPW2; ++ii) {
+                qr_[ii] = __builtin_amdgcn_readfirstlane(qg_.at(il0 + ii));
+                if (qr_[ii] >= 0) qneed_ |= 1u << ii;
+            }
+        } else if constexpr (QROWS) {
             qneed_ = 0u;
 #pragma unroll
             for (int ii = 0; ii < RPW2; ++ii) {
@@ -1095,7 +1126,8 @@ __global__ __launch_bounds__(NTH2) void ipa_core32_kernel(const float* __restric
         int zrow[RPW2], pbrow[RPW2];
 #pragma unroll
         for (int ii = 0; ii < RPW2; ++ii) {
-            const int row = min(i0 + il0 + ii, L - 1);
+            int row;
+            if constexpr (QC) row = max(qr_[ii], 0); else row = min(i0 + il0 + ii, L - 1);
             zrow[ii] = ZT ? ((int)zbase + row) * (JC * C * 4) : row * L * (C * 4);
             pbrow[ii] = ((int)zbase + row) * (H * JC * 4);
         }
@@ -1115,8 +1147,10 @@ __global__ __launch_bounds__(NTH2) void ipa_core32_kernel(const float* __restric
         _Pragma("unroll") for (int r_ = 0; r_ < 4; ++r_)                                                                \
             ring[SLOT][r_] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(P2_ZRS(II), koff_[r_], zrow[II], 2));   /* aux 2 = nt, as ZLOAD */
 #define P2_ISSUE_B(SLOT, II) ringb[SLOT] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(P2_BRS(II), boff_, pbrow[II], 2));
+        if (stream_) {
         P2_KOFF(0) P2_BOFF(0)
         P2_ISSUE_B(0, 0) P2_ISSUE_Z(0, 0) P2_ISSUE_B(1, 1) P2_ISSUE_Z(1, 1) P2_ISSUE_B(2, 2)
+        }
         fill_mask();
         f32x4 accP[RPW2][4];
         float* mlw = mlr + (il0 * 16 + fm) * 2;                             // this wave's rows; all four key groups of a lane column keep the same value
@@ -1341,7 +1375,9 @@ __global__ __launch_bounds__(NTH2) void ipa_core32_kernel(const float* __restric
         __syncthreads();                                                    /* barrier #(CH + 1) */                      \
     }
         int ch = 0;
-        if constexpr (ZT) {
+        if (!stream_) {
+            for (; ch < nchunk; ++ch) __syncthreads();                      // barrier #(ch + 1), nothing between them
+        } else if constexpr (ZT) {
         for (; ch + 3 <= nchunk; ch += 3) { P2H_CHUNK(0, ch) P2H_CHUNK(1, ch + 1) P2H_CHUNK(2, ch + 2) }
         if (ch < nchunk) {
             P2H_CHUNK(0, ch)
@@ -1409,15 +1445,17 @@ __global__ __launch_bounds__(NTH2) void ipa_core32_kernel(const float* __restric
         float rinv[RPW2];
 #pragma unroll
         for (int ii = 0; ii < RPW2; ++ii) {
-            const int i = i0 + il0 + ii;
-            const bool mi = (i < L) && mk[min(i, L - 1)] != 0;
+            bool mi;
+            if constexpr (QC) mi = qr_[ii] >= 0 && mk[max(qr_[ii], 0)] != 0;
+            else { const int i = i0 + il0 + ii; mi = (i < L) && mk[min(i, L - 1)] != 0; }
             rinv[ii] = mi ? 1.f / mlw[ii * 32 + 1] : 0.f;
         }
         // this thread's share of the point chunks: row prow, eighth psub of the columns
         const int ptid = wave * 64 + lane, prow = ptid >> 3, psub = ptid & 7;
         float rr_[9], tt_[3];
         {
-            const int64_t grow = rowbase + min(i0 + prow, L - 1);
+            int64_t grow;
+            if constexpr (QC) grow = qg_.load(prow); else grow = rowbase + min(i0 + prow, L - 1);
 #pragma unroll
             for (int q = 0; q < 9; ++q) rr_[q] = R[grow * 9 + q];
 #pragma unroll
@@ -1456,7 +1494,9 @@ __global__ __launch_bounds__(NTH2) void ipa_core32_kernel(const float* __restric
 #pragma unroll
                         for (int ii = 0; ii < RPW2; ++ii) {
                             if constexpr (ZT) {                                         // 1 / S_ic of channels 16 kq + 4 c .. + 3 of row ii (powers of two: the products with rinv are exact)
-                                const f32x4 zs = *reinterpret_cast<const f32x4*>(zsc + (zbase + min(i0 + il0 + ii, L - 1)) * C + kq * 16 + c * 4);
+                                int zr_;
+                                if constexpr (QC) zr_ = max(qr_[ii], 0); else zr_ = min(i0 + il0 + ii, L - 1);
+                                const f32x4 zs = *reinterpret_cast<const f32x4*>(zsc + (zbase + zr_) * C + kq * 16 + c * 4);
                                 stage_put4(buf, il0 + ii, fm * 16 + kq * 4, mul_rn(accP[ii][0][c], rinv[ii] * zs[0]), mul_rn(accP[ii][1][c], rinv[ii] * zs[1]),
                                            mul_rn(accP[ii][2][c], rinv[ii] * zs[2]), mul_rn(accP[ii][3][c], rinv[ii] * zs[3]));
                             } else
@@ -1486,12 +1526,17 @@ __global__ __launch_bounds__(NTH2) void ipa_core32_kernel(const float* __restric
         // =========================================================================================== A waves: S(t + 1), 6 heads x 2 row tiles
         const int h0 = (wave - NPW2) * HPW;
         const f32x4* kvn = reinterpret_cast<const f32x4*>(kvfrag) + (int64_t)n * nchunk * H * 512;
-        f32x4 qr[HPW][2][4];                                                // q' of this wave's heads, both row tiles: stays in registers
+        f32x4 qr[HPW][NRT][4];                                              // q' of this wave's heads, both row tiles: stays in registers
+        // QC: gathered -- a lane's 16 bytes of a fragment slot depend on its own residue and kq only (node_task.h: accumulator column fm = residue, the point norm is a
+        // sum over the kq lanes of that column), so lane (fm, kq) takes them from where its row's tile holds them: tile row >> 4, lane (row & 15, kq)
+        const int qrow_ = QC ? max(qg_.at(fm), 0) : 0;
 #pragma unroll
         for (int hh = 0; hh < HPW; ++hh)
 #pragma unroll
-            for (int rt = 0; rt < 2; ++rt) {
-                const f32x4* qg = reinterpret_cast<const f32x4*>(qfrag) + (((int64_t)n * nib16 + min(2 * ib + rt, nib16 - 1)) * H + h0 + hh) * (4 * 64) + lane;
+            for (int rt = 0; rt < NRT; ++rt) {
+                const f32x4* qg;
+                if constexpr (QC) qg = reinterpret_cast<const f32x4*>(qfrag) + (((int64_t)n * nib16 + (qrow_ >> 4)) * H + h0 + hh) * (4 * 64) + kq * 16 + (qrow_ & 15);
+                else qg = reinterpret_cast<const f32x4*>(qfrag) + (((int64_t)n * nib16 + min(2 * ib + rt, nib16 - 1)) * H + h0 + hh) * (4 * 64) + lane;
 #pragma unroll
                 for (int s_ = 0; s_ < 4; ++s_) qr[hh][rt][s_] = qg[s_ * 64];
             }
@@ -1504,7 +1549,7 @@ __global__ __launch_bounds__(NTH2) void ipa_core32_kernel(const float* __restric
                 const int h = h0 + hh;
                 if (hh + 1 < HPW) { if (hh & 1) A2_ISSUE(0, hh + 1, c) else A2_ISSUE(1, hh + 1, c) } else A2_ISSUE(0, 0, c + 1)
 #pragma unroll
-                for (int rt = 0; rt < 2; ++rt) {
+                for (int rt = 0; rt < NRT; ++rt) {
                     const f32x4 q0 = qr[hh][rt][0], q1 = qr[hh][rt][1], q2 = qr[hh][rt][2], q3 = qr[hh][rt][3];
                     f32x4 acc0 = (f32x4){0.f, 0.f, 0.f, 0.f}, acc1 = acc0;
                     if constexpr (ZT) {
@@ -1575,7 +1620,7 @@ __global__ __launch_bounds__(NTH2) void ipa_core32_kernel(const float* __restric
                 const int h = h0 + hh;
                 if (hh + 1 < HPW) { if (hh & 1) C2_ISSUE(0, hh + 1, c) else C2_ISSUE(1, hh + 1, c) } else C2_ISSUE(0, 0, c + 1)
 #pragma unroll
-                for (int rt = 0; rt < 2; ++rt) {
+                for (int rt = 0; rt < NRT; ++rt) {                          // (QC: the second tile's accumulators stay the zeros they start as)
                     const float sc = scl[(par * BI2 + rt * 16 + fm) * SCLD + h];
                     const f32x4 pa = *reinterpret_cast<const f32x4*>(sp + (buf * BI2 + rt * 16 + fm) * SROW + sp_off(h, kq));
                     // lazy rescale (FUSE only, see above): all 16 rows of the tile kept their running maximum of this head -- factors exactly 1, nothing to rescale
@@ -1613,7 +1658,9 @@ __global__ __launch_bounds__(NTH2) void ipa_core32_kernel(const float* __restric
 #pragma unroll
             for (int rt = 0; rt < 2; ++rt) {
                 const int il = rt * 16 + fm, i = i0 + il;
-                const bool mi = (i < L) && mk[min(i, L - 1)] != 0;
+                bool mi;
+                if constexpr (QC) { const int qi = rt == 0 ? qg_.at(fm) : -1; mi = qi >= 0 && mk[max(qi, 0)] != 0; }
+                else mi = (i < L) && mk[min(i, L - 1)] != 0;
                 const float inv = mi ? 1.f / lsum[il * SCLD + h] : 0.f;
                 if constexpr (FUSE) {
                     const f32x4 a0 = accV[hh][rt][0], a1 = accV[hh][rt][1];
@@ -1642,11 +1689,16 @@ __global__ __launch_bounds__(NTH2) void ipa_core32_kernel(const float* __restric
     } else {
         // ---------------------------------------------------------------- all waves: LayerNorm1, mlp_transition, LayerNorm2 of the 32 rows (tail_common.h)
         const int64_t row0 = row0f, row_end = row_endf;
-        pre = tail_p2_prefetch<NTH2 / 64>(ta.x, ta.ubias, mask, ta.g1, ta.be1, ta.wmf, row0, row_end, wave, lane);
+        if constexpr (QC) pre = tail_p2_prefetch<NTH2 / 64>(ta.x, ta.ubias, mask, ta.g1, ta.be1, ta.wmf, row0, row_end, wave, lane, qg_);
+        else pre = tail_p2_prefetch<NTH2 / 64>(ta.x, ta.ubias, mask, ta.g1, ta.be1, ta.wmf, row0, row_end, wave, lane);
         float (*bias)[F] = reinterpret_cast<float (*)[F]>(smem_raw + C32F_BIAS_OFF);
         __syncthreads();                                                    // U: u and the biases are in LDS
         const float (*us)[XLD] = reinterpret_cast<const float (*)[XLD]>(smem_raw + C32F_U_OFF);
         auto get_u = [&](int rl) { return *reinterpret_cast<const float2*>(&us[rl][2 * lane]); };
+        if constexpr (QC)
+        tail_p2_run<NTH2 / 64, false>(pre, get_u, reinterpret_cast<float (*)[XLD]>(smem_raw + C32F_YS_OFF), bias, smem_raw + C32F_APA_OFF,
+                                      smem_raw + C32F_PTS_OFF, ta.wmf, ta.g2, ta.be2, ta.out, nullptr, 0, row0, row_end, wave, lane, ta.xt, nullptr, 0, qg_);
+        else
         tail_p2_run<NTH2 / 64, false>(pre, get_u, reinterpret_cast<float (*)[XLD]>(smem_raw + C32F_YS_OFF), bias, smem_raw + C32F_APA_OFF,
                                       smem_raw + C32F_PTS_OFF, ta.wmf, ta.g2, ta.be2, ta.out, nullptr, 0, row0, row_end, wave, lane, ta.xt,
                                       NF ? reinterpret_cast<unsigned*>(smem_raw + C32F_U_OFF) : nullptr, NF_XLDS_STRIDE);
@@ -1863,17 +1915,19 @@ static int launch_core_variant(const CorePlan& plan, const float* qfrag, const f
 }
 
 // ipa_core32_kernel<FUSE, ZT> from a Core32 plan: the core alone into `feat`, or (FUSE) core + tail with `ta`.  ZT: `pair_terms` is given.
-template <bool FUSE, bool ZT, bool NF = false, bool QROWS = false>
+// QC: `tiles` workgroups per sample, each on 16 rows of the list in ta.qlist (the kernel decodes its block number with the tile count in the place of nib2)
+template <bool FUSE, bool ZT, bool NF = false, bool QROWS = false, bool QC = false>
 static int launch_core32(const CorePlan& plan, const float* qfrag, const float* kvfrag, const float* z, const uint8_t* mask, const float* R, const float* t, float* feat,
-                         const float* pbc, int N, int L, hipStream_t st, int z_shared, const TailArgsT<NF, QROWS>& ta, const float* pair_terms) {
-    const int nib2 = (L + BI2 - 1) / BI2, nchunk = (L + JC - 1) / JC;
+                         const float* pbc, int N, int L, hipStream_t st, int z_shared, const TailArgsT<NF, QROWS, QC>& ta, const float* pair_terms, int tiles = 0) {
+    const int nib2 = QC ? tiles : (L + BI2 - 1) / BI2, nchunk = (L + JC - 1) / JC;
+    ABOPT_CHECK_ARG(!QC || (tiles >= 1 && tiles <= (L + BI - 1) / BI), "ipa_core: %d tiles of gathered rows per sample at L=%d", tiles, L);
     const size_t lds = FUSE ? (size_t)C32F_LDS_BYTES : core32_lds_bytes(nchunk);
     ABOPT_CHECK_ARG(lds <= 160 * 1024, "ipa_core: L=%d needs %zu bytes of LDS for the key mask (max 163840)", L, lds);
     static LdsConfig lds_cfg;                                               // per instantiation
-    if (int rc = ensure_dynamic_lds(reinterpret_cast<const void*>(ipa_core32_kernel<FUSE, ZT, NF, QROWS>), lds, lds_cfg)) return rc;
+    if (int rc = ensure_dynamic_lds(reinterpret_cast<const void*>(ipa_core32_kernel<FUSE, ZT, NF, QROWS, QC>), lds, lds_cfg)) return rc;
     const float* zsc = ZT ? pair_terms + pair_terms_floats(z_shared ? N / z_shared : N, L) : nullptr;
     prof::begin(st);
-    hipLaunchKernelGGL((ipa_core32_kernel<FUSE, ZT, NF, QROWS>), dim3(plan.grid), dim3(NTH2), lds, st, qfrag, kvfrag, z, mask, R, t, feat, pbc, L, nib2, plan.remap, z_shared, ta,
+    hipLaunchKernelGGL((ipa_core32_kernel<FUSE, ZT, NF, QROWS, QC>), dim3(QC ? (unsigned)N * (unsigned)tiles : plan.grid), dim3(NTH2), lds, st, qfrag, kvfrag, z, mask, R, t, feat, pbc, L, nib2, plan.remap, z_shared, ta,
                        prof::next_span_slot(), ZT ? pair_terms : nullptr, zsc);
     prof::end(st);
     ABOPT_LAUNCH_CHECK();
@@ -1885,9 +1939,11 @@ static int launch_core32(const CorePlan& plan, const float* qfrag, const float* 
 int launch_ipa_block_fused(const CorePlan& plan, const float* qfrag, const float* kvfrag, const float* z, const uint8_t* mask, const float* R, const float* t,
                            const float* pair_bias_cache, int N, int L, hipStream_t st, int z_shared, const float* wot, const float* wmf, const float* x,
                            const float* ubias, const float* g1, const float* be1, const float* b0, const float* b1, const float* b2, const float* g2,
-                           const float* be2, float* out, const float* pair_terms, float* xt_out, const NodeCarryArgs* carry, const uint8_t* query_rows) {
+                           const float* be2, float* out, const float* pair_terms, float* xt_out, const NodeCarryArgs* carry, const uint8_t* query_rows,
+                           const int32_t* query_row_list, int query_row_tiles) {
     ABOPT_CHECK_ARG(plan.form == CoreForm::Core32 && pair_bias_cache && wot && wmf, "ipa_block_fused: not a 32-row plan with a cache and packed tail weights");
     ABOPT_CHECK_ARG(!query_rows || !carry, "ipa_block_fused: a block with masked query rows carries nothing");
+    ABOPT_CHECK_ARG(!query_row_tiles || (query_rows && query_row_list), "ipa_block_fused: gathered query rows come as a list, on top of the masked form's bytes");
     const TailArgs ta0{wot, wmf, x, ubias, g1, be1, b0, b1, b2, g2, be2, out, reinterpret_cast<unsigned*>(xt_out)};
     if (carry) {
         ABOPT_CHECK_ARG(carry->w_node_frag && carry->spatial_coef && carry->qfrag && carry->kvfrag && carry->qfrag != qfrag && carry->kvfrag != kvfrag,
@@ -1897,6 +1953,13 @@ int launch_ipa_block_fused(const CorePlan& plan, const float* qfrag, const float
         tn.nc = *carry;
         return pair_terms ? launch_core32<true, true, true>(plan, qfrag, kvfrag, z, mask, R, t, nullptr, pair_bias_cache, N, L, st, z_shared, tn, pair_terms)
                           : launch_core32<true, false, true>(plan, qfrag, kvfrag, z, mask, R, t, nullptr, pair_bias_cache, N, L, st, z_shared, tn, nullptr);
+    }
+    if (query_row_tiles) {
+        TailArgsT<false, true, true> tc;
+        static_cast<TailArgs&>(tc) = ta0;
+        tc.qlist = query_row_list;
+        return pair_terms ? launch_core32<true, true, false, true, true>(plan, qfrag, kvfrag, z, mask, R, t, nullptr, pair_bias_cache, N, L, st, z_shared, tc, pair_terms, query_row_tiles)
+                          : launch_core32<true, false, false, true, true>(plan, qfrag, kvfrag, z, mask, R, t, nullptr, pair_bias_cache, N, L, st, z_shared, tc, nullptr, query_row_tiles);
     }
     if (query_rows) {
         TailArgsT<false, true> tq;

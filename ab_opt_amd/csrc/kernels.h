@@ -44,7 +44,10 @@ int launch_ipa_block_fused(const CorePlan& plan, const float* qfrag, const float
                            const float* be2, float* out, const float* pair_terms = nullptr, float* xt_out = nullptr,
                            const NodeCarryArgs* carry = nullptr /* the next block's fragments are written too (ipa_core32_kernel<true, *, true>) */,
                            const uint8_t* query_rows = nullptr /* [N L], forward_plan.h: query_rows_masked -- `out` is read on the rows marked here only: the others stream
-                                                                  neither pair data nor bias and leave finite, unspecified rows (ipa_core32_kernel<true, *, false, true>) */);
+                                                                  neither pair data nor bias and leave finite, unspecified rows (ipa_core32_kernel<true, *, false, true>) */,
+                           const int32_t* query_row_list = nullptr, int query_row_tiles = 0 /* forward_plan.h: query_rows_compact -- the rows of query_rows as the list of
+                                                                  abopt_query_row_list, query_row_tiles 16-row tiles of it per sample: one workgroup per tile, and `out` is
+                                                                  WRITTEN on listed rows only (ipa_core32_kernel<true, *, false, true, true>) */);
 
 // node_frags.hip: x [N*L,128] -> qfrag / kvfrag directly (projection GEMM + frame transform + fragment layout in one kernel)
 size_t node_wfrag_floats();
@@ -121,6 +124,7 @@ int launch_heads_epilogue_backward(const float* R, const float* eps_rot, int ld3
                                    float* deps_crd, float* deps_rot, int64_t rows, hipStream_t st);
 // out[n, b] = mean_l in[n, l, b]
 int launch_mean_over_L(const float* in, float* out, int N, int L, int B, hipStream_t st);
+int launch_query_row_list(const uint8_t* mask_generate, int N, int L, int32_t* rows /* [N][ceil(L / 16) x 16] */, int32_t* count /* [N] */, hipStream_t st);
 
 // ipa_train.hip: training side of the IPA core -----------------------------------------------------
 size_t ipa_train_ws_floats(int N, int L);

@@ -476,4 +476,30 @@ int launch_mean_over_L(const float* in, float* out, int N, int L, int B, hipStre
     return ABOPT_OK;
 }
 
+// The generated rows of every sample as a list (include/abopt.h: abopt_query_row_list): rows [n][0 .. count[n]) ascending, -1 behind them up to the sample's
+// stride of ceil(L / 16) x 16 entries.  One wave per sample walks the mask 64 rows at a time: a row's place is the count so far plus the rows marked below it in the
+// wave's ballot.  Masks are constant over the steps of a loop: once per sample() / optimize() call, beside the pair-bias cache.
+__global__ __launch_bounds__(64) void query_row_list_kernel(const uint8_t* __restrict__ gen, int L, int stride, int32_t* __restrict__ rows, int32_t* __restrict__ count) {
+    const int n = blockIdx.x, lane = threadIdx.x;
+    const uint8_t* g = gen + (int64_t)n * L;
+    int32_t* out = rows + (int64_t)n * stride;
+    int base = 0;
+    for (int l0 = 0; l0 < L; l0 += 64) {
+        const int l = l0 + lane;
+        const bool on = l < L && g[l] != 0;
+        const unsigned long long b = __builtin_amdgcn_ballot_w64(on);
+        if (on) out[base + __popcll(b & ((1ull << lane) - 1ull))] = l;       // base + rank < count <= L <= stride
+        base += __popcll(b);
+    }
+    for (int e = base + lane; e < stride; e += 64) out[e] = -1;
+    if (lane == 0) count[n] = base;
+}
+
+int launch_query_row_list(const uint8_t* mask_generate, int N, int L, int32_t* rows, int32_t* count, hipStream_t st) {
+    if (N == 0) return ABOPT_OK;
+    hipLaunchKernelGGL(query_row_list_kernel, dim3(N), dim3(64), 0, st, mask_generate, L, ((L + 15) / 16) * 16, rows, count);
+    ABOPT_LAUNCH_CHECK();
+    return ABOPT_OK;
+}
+
 }  // namespace abopt

@@ -7,6 +7,7 @@
 // pre-split and scaled by a power of two per matrix (pack_tail_weights_kernel), the inverse scales ride in w_mlp_frag behind the layer weights.  The
 // backward chain (tail_backward_kernel) keeps the three-term bf16 products and its own helpers below (store_terms2, MlpW, mlp_partial).
 #pragma once
+#include <type_traits>
 #include "ipa_common.h"
 
 namespace abopt {
@@ -168,15 +169,21 @@ struct TailP2Pre {
     f32x4 inv;                                // 1 / S of W_out, W_mlp0..2
     MlpRaw mw;
 };
-template <int NW>
+// Which global row a workgroup's local row rl is.  TailRowsDense: row0 + rl, rows from row_end on are clamped for reads and not stored (every kernel but one).
+// A map of the caller's (ipa_core32_kernel<true, *, false, true, true>: rows gathered from a list) answers load(rl) -> a valid row to read, and
+// store(rl) -> the row to write, or a negative number for a local row that is nobody's.
+struct TailRowsDense {};
+template <int NW, class RM = TailRowsDense>
 __device__ __forceinline__ TailP2Pre<NW> tail_p2_prefetch(const float* __restrict__ x, const float* __restrict__ ubias, const uint8_t* __restrict__ mask,
                                                          const float* __restrict__ g1, const float* __restrict__ be1, const float* __restrict__ wmf,
-                                                         int64_t row0, int64_t row_end, int wave, int lane) {
+                                                         int64_t row0, int64_t row_end, int wave, int lane, RM rm = RM{}) {
     constexpr int RW = MR / NW;
     TailP2Pre<NW> p;
 #pragma unroll
     for (int rr = 0; rr < RW; ++rr) {
-        const int64_t row = min(row0 + wave * RW + rr, row_end - 1);
+        int64_t row;
+        if constexpr (std::is_same<RM, TailRowsDense>::value) row = min(row0 + wave * RW + rr, row_end - 1);
+        else row = rm.load(wave * RW + rr);
         p.keep[rr] = mask ? (mask[row] != 0) : true;
         p.xv[rr] = reinterpret_cast<const float2*>(x + row * F)[lane];
     }
@@ -197,11 +204,13 @@ __device__ __forceinline__ void tail_p2_stage_bias(float (*bias)[F], const float
 // GetU(rl) -> this lane's two columns (2 lane, 2 lane + 1) of S_out u, u = feat . W_out^T for local row rl, WITHOUT the bias.  The caller has
 // passed the barrier that publishes u and the staged biases.  ys [MR][XLD] fp32, apA / apB two sets of OT_NT fp16 planes (AP_PLANE each);
 // none of them may alias what GetU reads.  DUMP (training): five [rows, 128] slabs, see out_ln_mlp_kernel.
-template <int NW, bool DUMP, class GetU>
+template <int NW, bool DUMP, class GetU, class RM = TailRowsDense>
 __device__ __forceinline__ void tail_p2_run(TailP2Pre<NW>& pre, GetU&& get_u, float (*ys)[XLD], float (*bias)[F], char* apA, char* apB,
                                             const float* __restrict__ wmf, const float* __restrict__ g2, const float* __restrict__ be2,
                                             float* __restrict__ out, float* __restrict__ dump, int64_t slab, int64_t row0, int64_t row_end,
-                                            int wave, int lane, unsigned* __restrict__ xt_out = nullptr, unsigned* xt_lds = nullptr, int xt_lds_stride = 0) {
+                                            int wave, int lane, unsigned* __restrict__ xt_out = nullptr, unsigned* xt_lds = nullptr, int xt_lds_stride = 0,
+                                            RM rm = RM{}) {
+    static_assert(std::is_same<RM, TailRowsDense>::value || !DUMP, "the training slabs are dense");
     constexpr int RW = MR / NW;
     const int fm = lane & 15, kq = lane >> 4;
     const bool mlpw = wave < 8;                                                                          // waves 0..7 own the eight 16-column tiles
@@ -285,9 +294,12 @@ __device__ __forceinline__ void tail_p2_run(TailP2Pre<NW>& pre, GetU&& get_u, fl
         for (int rr = 0; rr < RW; ++rr) { v[rr].x -= mean[rr]; v[rr].y -= mean[rr]; var[rr] = wave_sum(v[rr].x * v[rr].x + v[rr].y * v[rr].y) * (1.f / F); }
 #pragma unroll
         for (int rr = 0; rr < RW; ++rr) {
-            const int64_t row = row0 + wave * RW + rr;
+            int64_t row;
+            bool mine;
+            if constexpr (std::is_same<RM, TailRowsDense>::value) { row = row0 + wave * RW + rr; mine = row < row_end; }
+            else { row = rm.store(wave * RW + rr); mine = row >= 0; }
             const float sd = sqrtf(var[rr] + 1e-10f);
-            if (row < row_end) {
+            if (mine) {
                 const float o0 = v[rr].x / sd * g.x + bt.x, o1 = v[rr].y / sd * g.y + bt.y;
                 reinterpret_cast<float2*>(out + row * F)[lane] = make_float2(o0, o1);
                 // round 6: the same row as two fp16 terms ([64 words of high terms | 64 words of low terms], split_pair2) for the NEXT block's node_frags, whose 24

@@ -39,6 +39,8 @@ class _LoopSpec:
     constrained: bool = False                   # the loop's inputs end with aa_allowed, the allowed residue types per residue (the contents are data, not key)
     timesteps: tuple | int = 0                  # the steps the loop visits: 0 every step t_start .. 1; K > 0 the K evenly respaced ones, respaced_steps(t_start, K);
                                                 # a tuple: these (t_start first, strictly decreasing, >= 1)
+    query_row_tiles: int = 0                    # 16-row tiles the generated rows of the loop's longest sample fill (FullDPM._denoise settles it from the masks, once
+                                                # per call); 0: the loop holds no row list (include/abopt.h: abopt_eps_net_step_rows_compact)
 
 
 def respaced_steps(t_start, steps=None, timesteps=None):
@@ -264,7 +266,7 @@ class FullDPM(_Derived, nn.Module):
             # is 0.1 ms of host time per call); a loop that is or will be captured is judged with the graph's own copy of pair_feat on top
             cache = (Nc != N or (capturable and _graph_key(dataclasses.replace(spec, use_bias_cache=True), inputs, token) in self._graphs)
                      or self._bias_cache_fits(Nc, L, res_feat.device, graph=capturable))
-        spec = dataclasses.replace(spec, use_bias_cache=bool(cache))
+        spec = dataclasses.replace(spec, use_bias_cache=bool(cache), query_row_tiles=self._query_row_tiles(spec, inputs[2], bool(cache)))
         key = _graph_key(spec, inputs, token)
         if capturable and key not in self._graphs and graph == 'auto' and key not in self._graph_seen:       # a one-off call should not pay for a capture
             if len(self._graph_seen) >= 64:
@@ -294,6 +296,15 @@ class FullDPM(_Derived, nn.Module):
         if graph:
             need += n_pair * L * L * 64 * 4
         return need <= _free_bytes(dev) // 2
+
+    def _query_row_tiles(self, spec, mask_generate, cache):
+        """_LoopSpec.query_row_tiles of a loop on these masks: ceil(most generated rows of a sample / 16), read from the device once per call and outside any
+        capture -- a captured loop's key holds it, so masks that fill more tiles (or fewer) find another graph.  0 where no step of the loop could use a row list:
+        the AbDock flavour (its prmsd and perplexity reduce over every row), no pair-bias cache, ABOPT_STEP_COMPACT=0."""
+        if spec.query_row_tiles or self.abdock or not cache or not mask_generate.is_cuda or os.environ.get('ABOPT_STEP_COMPACT', '')[:1] == '0':
+            return spec.query_row_tiles
+        most = int(mask_generate.sum(dim=1).max()) if mask_generate.numel() else 0
+        return (most + 15) // 16
 
     def _pair_terms_wanted(self, N, L, n_pair, dev):
         """The fp16 pair terms pay where the library's launch geometry takes the 32-row block kernels (abopt_pair_terms_used) and their
@@ -338,6 +349,9 @@ class FullDPM(_Derived, nn.Module):
         pbc = hip.pair_bias_cache(self.eps_net.encoder.packed_array(), len(self.eps_net.encoder.blocks), pair_feat) if use_bias_cache else None
         # ... and, where the 32-row block kernels will run, re-lay pair_feat once as the fp16 operands of their pair aggregation (hip.pair_terms; ~0.25 ms)
         pterms = hip.pair_terms(pair_feat) if (use_bias_cache and self._pair_terms_wanted(N, L, Nc, dev)) else None
+        # ... and, for a loop whose spec says how many 16-row tiles its generated rows fill, list them once: the masks are constant over the steps too (hip.query_row_list;
+        # inside a captured loop the list is rebuilt by every replay, from the masks the replay copied into the static buffers)
+        qrows = (*hip.query_row_list(mask_generate), spec.query_row_tiles) if (spec.query_row_tiles > 0 and use_bias_cache) else None
         X, cdf = self._loop_tables(pairs)
         beta_rows = self.trans_pos.var_sched.betas[:T0 + 1, None].expand(T0 + 1, N).contiguous()    # beta_t per sample, one row per step
         net = dict(v_next=torch.empty(N, L, 3, **f32), R_next=torch.empty(N, L, 3, 3, **f32), eps_pos=torch.empty(N, L, 3, **f32),
@@ -367,9 +381,10 @@ class FullDPM(_Derived, nn.Module):
                              self._step_params(t, spec.sample_structure, spec.sample_sequence, spec.ppl_masked, spec.optimize_mode, t_prev),
                              noise[t] if noise is not None else None, seed, rng_offset, tp[i], X[j], cdf[j] if noise is None else None, out,
                              pair_bias_cache=pbc, pair_feat_shared=(group if shared else 0), pair_terms=pterms, seed_dev=seed_dev, aa_allowed=aa_allowed,
-                             carry_in=j > 0, carry_out=more, context_outputs_unused=True)
+                             carry_in=j > 0, carry_out=more, context_outputs_unused=True, query_rows=qrows)
             evals += 1
-        self.last_run_info = dict(bias_cache=use_bias_cache, pair_terms=pterms is not None, shared_context=shared, graph=seed_dev is not None, steps=evals)
+        self.last_run_info = dict(bias_cache=use_bias_cache, pair_terms=pterms is not None, shared_context=shared, graph=seed_dev is not None, steps=evals,
+                                  query_row_tiles=qrows[2] if qrows else 0)
         return tv, tp, ts, tpr, tpp
 
     def _to_traj(self, T0, tv, tp, ts, tpr, tpp, timesteps=0):

@@ -13,7 +13,7 @@ import torch
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # ABOPT_LIB_PATH: developer override to load a variant build of the same ABI (csrc/Makefile VARIANT=...: A/B of two source trees)
 LIB_PATH = os.environ.get('ABOPT_LIB_PATH') or os.path.join(_HERE, 'libabopt_hip.so')
-ABI_VERSION = 51
+ABI_VERSION = 52
 
 c_f = C.c_void_p        # device float*
 c_i64 = C.c_void_p      # device int64*
@@ -122,6 +122,10 @@ _SIGNATURES = {
     'abopt_eps_net_step_rows': (c_int, [POINTER(EpsWeights), c_f, c_f, c_i64, c_f, c_f, c_f, c_u8, c_u8] + [c_f] * 5 + [c_int] * 4 + [c_f, c_int, c_f, c_void_p, c_size_t] +
                                 [POINTER(StepParams), POINTER(StepNoise), c_uint64, c_uint64, c_f, c_f, c_f, c_int, c_int] + [c_f, c_f, c_i64] + [c_f] * 4 +
                                 [c_void_p, c_i32, c_int, c_int, c_int, c_stream]),
+    'abopt_query_row_list': (c_int, [c_u8, c_int, c_int, c_void_p, c_void_p, c_stream]),
+    'abopt_eps_net_step_rows_compact': (c_int, [POINTER(EpsWeights), c_f, c_f, c_i64, c_f, c_f, c_f, c_u8, c_u8] + [c_f] * 5 + [c_int] * 4 + [c_f, c_int, c_f, c_void_p, c_size_t] +
+                                        [POINTER(StepParams), POINTER(StepNoise), c_uint64, c_uint64, c_f, c_f, c_f, c_int, c_int] + [c_f, c_f, c_i64] + [c_f] * 4 +
+                                        [c_void_p, c_i32, c_int, c_int, c_i32, c_i32, c_int, c_stream]),
     'abopt_igso3_tables': (c_int, [c_f, c_int, c_int, c_int, c_f, c_f, c_f, c_stream]),
     'abopt_sample_init': (c_int, [c_f, c_f, c_i64, c_u8, c_f, c_f, c_i64, c_uint64, c_uint64, c_float, c_void_p, c_int, c_int, c_f, c_f, c_i64, c_i32, c_int, c_int, c_stream]),
     'abopt_add_noise': (c_int, [c_i64, c_f, c_f, c_u8, c_f, c_f, c_int, c_int, POINTER(AddNoiseNoise), c_uint64, c_uint64, c_f, c_f, c_i64, c_u8, c_float, c_void_p, c_int, c_int, c_int,
@@ -519,6 +523,18 @@ def pair_bias_cache(blocks_array, num_layers, pair_feat):
     return cache
 
 
+def query_row_list(mask_generate):
+    """mask_generate (N, L) -> (rows, count): per sample the ascending indices of its generated residues, -1 behind them (int32, (N, ceil(L / 16) * 16)), and their
+    number (int32, (N,)) -- one launch, nothing read on the host (include/abopt.h: abopt_query_row_list).  With tiles = ceil(count.max() / 16) the triple
+    (rows, count, tiles) is what eps_net_step(query_rows=...) takes."""
+    N, L = mask_generate.shape
+    mask_generate, = _contig(mask_generate)
+    rows = torch.empty(N, (L + 15) // 16 * 16, dtype=torch.int32, device=mask_generate.device)
+    count = torch.empty(N, dtype=torch.int32, device=mask_generate.device)
+    _check(lib().abopt_query_row_list(ptr(mask_generate, torch.bool), N, L, ptr(rows), ptr(count), stream()))
+    return rows, count
+
+
 def _allowed_ptr(aa_allowed, mask_generate):
     """aa_allowed (optional): contiguous int32 (N, L) device tensor, bit k of a word = residue type k may be drawn there (include/abopt.h)."""
     if aa_allowed is not None and aa_allowed.shape != mask_generate.shape:
@@ -549,11 +565,13 @@ def denoise_step(sp, noise, seed, offset, v_t, p_t, s_t, v_net, p_net, c_net, pr
 
 def eps_net_step(ew, v_t, p_t, s_t, res_feat, pair_feat, beta, mask_generate, mask_res, num_bins, net, sp, noise, seed, offset, p_angstrom, ig_X_row, ig_cdf_row, out,
                  pair_bias_cache=None, pair_feat_shared=False, pair_terms=None, want_post=False, seed_dev=None, aa_allowed=None, carry_in=False, carry_out=False,
-                 context_outputs_unused=False):
+                 context_outputs_unused=False, query_rows=None):
     """One loop iteration in one C call (include/abopt.h: abopt_eps_net_step): eps_net_forward(..., out=net) then denoise_step(..., out) on its outputs, bit-identical
     to the two calls; where the library fuses the step's tail, carry_out leaves the next evaluation's mixer output in the workspace and carry_in says the previous
     call did so for exactly this v_t / s_t.  net: the dict eps_net_forward fills (prmsd_logits None without the head); out: as for denoise_step.
-    context_outputs_unused (abopt_eps_net_step_rows): the caller reads `net` on generated residues only; `out` and the posterior are what they are without it."""
+    context_outputs_unused (abopt_eps_net_step_rows): the caller reads `net` on generated residues only; `out` and the posterior are what they are without it.
+    query_rows (abopt_eps_net_step_rows_compact; implies context_outputs_unused): (rows, count, tiles) -- query_row_list(mask_generate) of THIS mask and the number of
+    16-row tiles of the list its longest sample fills; the same results, with the last block on listed rows only where the library's plan takes that form."""
     N, L = mask_res.shape
     F, Cd = res_feat.shape[-1], pair_feat.shape[-1]
     nz = None
@@ -563,7 +581,13 @@ def eps_net_step(ew, v_t, p_t, s_t, res_feat, pair_feat, beta, mask_generate, ma
     post = torch.empty(N, L, 20, device=v_t.device) if want_post else None
     buf = Workspace.get(lib().abopt_eps_workspace_bytes(N, L, F, Cd), res_feat.device)
     v_t, p_t, s_t, res_feat, pair_feat, beta, mask_generate, mask_res = _contig(v_t, p_t, s_t, res_feat, pair_feat, beta, mask_generate, mask_res)
-    fn, tail = (lib().abopt_eps_net_step_rows, (1,)) if context_outputs_unused else (lib().abopt_eps_net_step, ())
+    if query_rows is not None:
+        rows, count, tiles = query_rows
+        if rows.shape != (N, (L + 15) // 16 * 16) or count.shape != (N,):
+            raise ValueError(f'query_rows: a list of shape {tuple(rows.shape)} / {tuple(count.shape)} does not belong to a mask of shape {(N, L)}')
+        fn, tail = lib().abopt_eps_net_step_rows_compact, (ptr(rows, torch.int32), ptr(count, torch.int32), int(tiles))
+    else:
+        fn, tail = (lib().abopt_eps_net_step_rows, (1,)) if context_outputs_unused else (lib().abopt_eps_net_step, ())
     _check(fn(C.byref(ew), ptr(v_t, torch.float32), ptr(p_t, torch.float32), ptr(s_t, torch.int64), ptr(res_feat, torch.float32),
               ptr(pair_feat, torch.float32), ptr(beta, torch.float32), ptr(mask_generate, torch.bool), ptr(mask_res, torch.bool),
               ptr(net['v_next']), ptr(net['R_next']), ptr(net['eps_pos']), ptr(net['c']), ptr(net['prmsd_logits'], optional=True),

@@ -23,7 +23,7 @@
 extern "C" {
 #endif
 
-#define ABOPT_ABI_VERSION 51
+#define ABOPT_ABI_VERSION 52
 
 enum { ABOPT_OK = 0, ABOPT_EINVAL = 1, ABOPT_EHIP = 2, ABOPT_EUNSUPPORTED = 3, ABOPT_EWORKSPACE = 4 };
 
@@ -332,6 +332,30 @@ int abopt_eps_net_step_rows(const abopt_eps_weights* w, const float* v_t, const 
                             float* v_next, float* p_next, int64_t* s_next, float* prmsd, float* perplexity, float* post_out, float* p_next_norm,
                             const uint64_t* seed_offset_dev, const int32_t* aa_allowed, int carry_in, int carry_out, int context_outputs_unused,
                             abopt_stream stream);
+
+/* The generated rows of every sample as a list (ABI 52): rows [N][ceil(L / 16) * 16] int32 takes, per sample, the ascending indices of the residues with
+ * mask_generate != 0 and -1 in every entry behind them; count [N] int32 takes their number.  One launch; the host learns nothing. */
+int abopt_query_row_list(const uint8_t* mask_generate, int N, int L, void* rows, void* count, abopt_stream stream);
+
+/* abopt_eps_net_step_rows with context_outputs_unused != 0, from a loop that also holds the row list of its mask_generate (ABI 52): query_rows and query_row_count
+ * are what abopt_query_row_list wrote for THIS mask_generate, N and L, and query_row_tiles >= ceil(max_n count[n] / 16) is the number of 16-row tiles of the list the
+ * longest sample fills (the caller reads the counts once per loop; masks do not change over its steps).  The contract is that call's: v_next, p_next, s_next, post_out
+ * and p_next_norm bit-identical everywhere, v_net, R_net, eps_pos and c_denoised bit-identical on generated residues, finite but unspecified on the others.  What the
+ * library does with the list: where abopt_eps_net_step_rows would mask the last block's query rows, the net has three blocks or more, N * query_row_tiles workgroups
+ * fit the device's CUs in one round and query_row_tiles <= ceil(L / 32), that block runs one workgroup per 16 LISTED rows instead of one per 32 rows of the sample.
+ * Every other call -- query_row_tiles = 0 among them -- makes the launches of abopt_eps_net_step_rows; ABOPT_STEP_COMPACT=0 makes all do.  A list that does not
+ * belong to mask_generate, or fewer tiles than the longest sample fills, leaves generated rows of the network's outputs unspecified. */
+int abopt_eps_net_step_rows_compact(const abopt_eps_weights* w, const float* v_t, const float* p_t, const int64_t* s_t,
+                                    const float* res_feat, const float* pair_feat, const float* beta,
+                                    const uint8_t* mask_generate, const uint8_t* mask_res,
+                                    float* v_net, float* R_net, float* eps_pos, float* c_denoised, float* prmsd_logits,
+                                    int N, int L, int F, int C,
+                                    const float* pair_bias_cache, int pair_feat_shared, const float* pair_terms, void* ws, size_t ws_bytes,
+                                    const abopt_step_params* sp, const abopt_step_noise* noise, uint64_t seed, uint64_t offset, const float* p_angstrom,
+                                    const float* igso3_X, const float* igso3_cdf, int igso3_bins, int num_bins,
+                                    float* v_next, float* p_next, int64_t* s_next, float* prmsd, float* perplexity, float* post_out, float* p_next_norm,
+                                    const uint64_t* seed_offset_dev, const int32_t* aa_allowed, int carry_in, int carry_out,
+                                    const int32_t* query_rows, const int32_t* query_row_count, int query_row_tiles, abopt_stream stream);
 
 /* ---- IGSO(3) angle histograms for arbitrary standard deviations (ABI 45): the tables ApproxAngularDistribution builds on the host at construction
  * (D/modules/common/so3.py:82-109), for the strides of a respaced loop, whose sigmas are chosen per call.  Row r, bin b at x_b = linspace(0, pi, bins)[b]:

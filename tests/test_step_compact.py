@@ -1,0 +1,256 @@
+"""The last IPA block of a sampling step on GATHERED generated rows (csrc/forward_plan.h: query_rows_compact; csrc/ipa_core.hip: ipa_core32_kernel<true, *, false, true, true>;
+include/abopt.h: abopt_query_row_list, abopt_eps_net_step_rows_compact).  With the list of its generated rows, the last block runs one
+workgroup per 16 listed rows of a sample.  Against abopt_eps_net_step_rows with context_outputs_unused (the masked form): what the step hands on -- v_next, p_next,
+s_next, the posterior, p_next_norm -- is torch.equal on every row and the network's four outputs are torch.equal on generated rows; where the plan refuses (more than
+half the rows generated, ABOPT_STEP_COMPACT=0) every output is equal on every row.  ABOPT_CORE32=1 so that the small shapes take the 32-row kernels; that these shapes
+do gather on a 256-CU device is pinned without a device in tests/test_forward_plan_compact.py::test_shapes_of_the_gpu_test_gather, and checked here on context rows,
+which the gathered form leaves as an earlier block wrote them."""
+import pytest
+import torch
+
+from ab_opt_amd import hip
+from ab_opt_amd.dpm import FullDPM, _LoopSpec
+from ab_opt_amd.utils import synth
+
+pytestmark = pytest.mark.gpu
+
+DEV = torch.device('cuda:0')
+T = 3
+NET = ('v_next', 'R_next', 'eps_pos', 'c')
+OUT = ('v', 'p', 's', 'p_norm')
+
+
+def _model():
+    m = FullDPM(128, 64, num_steps=T, eps_net_opt=dict(num_layers=3), _abdesign=True).eval()
+    return synth.fill_module_(m, seed=5).to(DEV)
+
+
+@pytest.fixture(scope='module')
+def design():
+    return _model()
+
+
+@pytest.fixture(autouse=True)
+def core32(monkeypatch):
+    monkeypatch.setenv('ABOPT_CORE32', '1')
+    monkeypatch.setenv('ABOPT_CORE_NO_SPLIT', '1')
+    for name in ('ABOPT_STEP_ROWS', 'ABOPT_STEP_COMPACT', 'ABOPT_PAIR_TERMS'):
+        monkeypatch.delenv(name, raising=False)
+
+
+# N, L, lengths (mask_res), samples per shared pair_feat entry (0: distinct)
+SHAPES = {
+    'five_tiles_three_blocks_ragged': (2, 80, [80, 73], 0),               # five 16-row tiles, three 32-row blocks, a ragged last block; sample 1 ends at row 72
+    'shared_pair_features': (3, 48, [48, 41, 48], 3),
+}
+
+
+def _rows(N, L, per_sample):
+    g = torch.zeros(N, L, dtype=torch.bool)
+    for n, rows in enumerate(per_sample[:N]):
+        g[n, list(rows)] = True
+    return g
+
+
+# the plan gathers up to ceil(L / 32) tiles per sample: 48 rows at L = 80, 32 at L = 48
+MASKS = {
+    # runs across the 16- and the 32-row boundaries, a run that ends at L - 1; sample 1's run crosses the end of its mask_res (rows past it are dropped below)
+    'straddling_runs': lambda N, L: _rows(N, L, [list(range(10, 22)) + list(range(28, 37)) + list(range(L - 4, L)), range(L - 14, L), range(30, 34)]),
+    # exactly 16 rows (every third row: one full tile, scattered), exactly 17 (one full tile and one row), none
+    'sixteen_and_seventeen': lambda N, L: _rows(N, L, [range(0, 48, 3), range(5, 22), []]),
+    'none_beside_many': lambda N, L: _rows(N, L, [[], range(2, 32), range(1, 33)]),
+    'scattered_singles': lambda N, L: _rows(N, L, [[0, 17, 33, L - 1], [7], [15, 16, 31, 32]]),
+}
+REFUSED = {
+    'all_ones': lambda N, L: torch.ones(N, L, dtype=torch.bool),
+    'more_than_half': lambda N, L: _rows(N, L, [range(0, L // 2 + 9), [3], range(4, 9)]),             # 49 of 80 / 33 of 48 rows: one tile too many
+}
+
+
+def _inputs(shape, mask, salt=1300):
+    N, L, lengths, group = SHAPES[shape]
+    v, p, s, res_feat, pair_feat, _, _, mres = [a.to(DEV) for a in synth.eps_inputs(N, L, lengths, [], salt=salt, num_steps=T, t=2)]
+    gen = {**MASKS, **REFUSED}[mask](N, L).to(DEV) & mres
+    if mask == 'straddling_runs':
+        assert gen[0, L - 1] and not mres[1, L - 1] and gen[1].any() and not gen[1, lengths[1]:].any()     # a row at L - 1; a mask_res shorter than L cuts a run
+    if mask == 'sixteen_and_seventeen':
+        assert [int(c) for c in gen.sum(1)[:2]] == [16, 17]
+    if group:
+        pair_feat = pair_feat[:N // group].contiguous()
+    tiles = (int(gen.sum(1).max()) + 15) // 16
+    assert (tiles <= (L + 31) // 32) == (mask in MASKS)
+    return dict(N=N, L=L, group=group, v=v, p=p * 10.0, s=s, res_feat=res_feat, pair_feat=pair_feat, gen=gen, mres=mres, tiles=tiles)
+
+
+def _steps(d, inp, compact, nsteps, terms, pbc, pterms):
+    """nsteps calls of the step entry from t = T down, the mixer carried from call to call; compact: with the row list (built here, once), else the masked form"""
+    N, L = inp['N'], inp['L']
+    f32 = dict(dtype=torch.float32, device=DEV)
+    ew = d.eps_net.packed()
+    X, cdf = d._loop_tables(d._loop_steps(_LoopSpec(T)))
+    v, p, s = inp['v'], inp['p'], inp['s']
+    p_norm = ((p - d.position_mean) / d.position_scale).contiguous()
+    qrows = (*hip.query_row_list(inp['gen']), inp['tiles']) if compact else None
+    res = []
+    for j in range(nsteps):
+        t = T - j
+        net = dict(v_next=torch.empty(N, L, 3, **f32), R_next=torch.empty(N, L, 3, 3, **f32), eps_pos=torch.empty(N, L, 3, **f32), c=torch.empty(N, L, 20, **f32),
+                   prmsd_logits=None)
+        out = dict(v=torch.empty(N, L, 3, **f32), p=torch.empty(N, L, 3, **f32), s=torch.empty(N, L, dtype=torch.int64, device=DEV), p_norm=torch.empty(N, L, 3, **f32))
+        beta = d.trans_pos.var_sched.betas[t].expand(N).contiguous()
+        post = hip.eps_net_step(ew, v, p_norm, s, inp['res_feat'], inp['pair_feat'], beta, inp['gen'], inp['mres'], d.num_bins, net,
+                                d._step_params(t, True, True, True, False, t - 1), None, 11, 4096, p, X[j], cdf[j], out, pair_bias_cache=pbc,
+                                pair_feat_shared=inp['group'], pair_terms=pterms if terms else None, want_post=True, carry_in=j > 0, carry_out=j + 1 < nsteps,
+                                context_outputs_unused=True, query_rows=qrows)
+        res.append(dict(net=net, out=out, post=post))
+        v, p, s, p_norm = out['v'], out['p'], out['s'], out['p_norm']
+    return res
+
+
+def _run(d, inp, compact, nsteps, terms, replays=0):
+    """eagerly (replays = 0), or captured once and replayed `replays` times: the results of the last replay"""
+    pf = inp['pair_feat']
+    pbc = hip.pair_bias_cache(d.eps_net.encoder.packed_array(), len(d.eps_net.encoder.blocks), pf)
+    pterms = hip.pair_terms(pf)
+    hip.nonfinite_flag(reset=True)
+    if not replays:
+        res = _steps(d, inp, compact, nsteps, terms, pbc, pterms)
+    else:
+        hip.prof_enable(False)
+        _steps(d, inp, compact, 1, terms, pbc, pterms)                      # warm: kernel attributes, host-side caches
+        torch.cuda.synchronize()
+        before = set(hip.Workspace._bufs)
+        g = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(g):
+            res = _steps(d, inp, compact, nsteps, terms, pbc, pterms)
+        keep = [hip.Workspace._bufs.pop(k) for k in set(hip.Workspace._bufs) - before]       # the slab the capture allocated lives in the graph's pool
+        for _ in range(replays):
+            for r in res:
+                for a in list(r['net'].values()) + list(r['out'].values()) + [r['post']]:
+                    if a is not None:
+                        a.fill_(7)                                            # a replay that wrote nothing would be seen
+            g.replay()
+        torch.cuda.synchronize()
+        clone = lambda d_: {k: (a.clone() if a is not None else None) for k, a in d_.items()}
+        res = [dict(net=clone(r['net']), out=clone(r['out']), post=r['post'].clone()) for r in res]      # own storage: the buffers are the graph's static ones
+        del keep, g
+    torch.cuda.synchronize()
+    flag = hip.nonfinite_flag(reset=True)
+    return res, flag
+
+
+def _check(got, flag_got, ref, flag_ref, inp, gathered):
+    """gathered: the plan takes the form -- generated rows equal, context rows finite and (first step) not the masked form's; else every row equal"""
+    assert not flag_ref and not flag_got                                    # abopt_nonfinite_flag reads 0
+    assert len(got) == len(ref)
+    gen = inp['gen']
+    for a, b in zip(got, ref):
+        for k in OUT:
+            assert torch.equal(a['out'][k], b['out'][k]), (k, int((a['out'][k] != b['out'][k]).sum()))
+        assert torch.equal(a['post'], b['post'])
+        for k in NET:
+            assert torch.isfinite(a['net'][k]).all() and torch.isfinite(b['net'][k]).all(), k
+            assert torch.equal(a['net'][k][gen], b['net'][k][gen]), (k, int((a['net'][k][gen] != b['net'][k][gen]).sum()))
+            if not gathered:
+                assert torch.equal(a['net'][k], b['net'][k]), k
+    if gathered:
+        ctx = inp['mres'] & ~gen
+        assert not torch.equal(got[0]['net']['c'][ctx], ref[0]['net']['c'][ctx])      # the comparisons above prove nothing if the plan refused
+
+
+@pytest.fixture(scope='module')
+def reference():
+    """the masked form, computed once per (shape, mask, terms, steps) and shared"""
+    return {}
+
+
+def _ref(reference, d, shape, mask, terms, nsteps):
+    key = (shape, mask, terms, nsteps)
+    if key not in reference:
+        inp = _inputs(shape, mask)
+        reference[key] = (inp,) + _run(d, inp, False, nsteps, terms)
+    return reference[key]
+
+
+@pytest.mark.parametrize('terms', [True, False], ids=['pair_terms', 'fp32_stream'])
+@pytest.mark.parametrize('mask', list(MASKS) + list(REFUSED))
+@pytest.mark.parametrize('shape', list(SHAPES))
+def test_one_step(design, reference, monkeypatch, shape, mask, terms):
+    if not terms:
+        monkeypatch.setenv('ABOPT_PAIR_TERMS', '0')
+    inp, ref, fr = _ref(reference, design, shape, mask, terms, 1)
+    got, fg = _run(design, inp, True, 1, terms)
+    _check(got, fg, ref, fr, inp, gathered=mask in MASKS)
+    assert not torch.equal(got[0]['out']['s'], inp['s'])                    # the step moved the generated residues
+
+
+@pytest.mark.parametrize('terms', [True, False], ids=['pair_terms', 'fp32_stream'])
+@pytest.mark.parametrize('mask', list(MASKS))
+@pytest.mark.parametrize('shape', list(SHAPES))
+def test_three_steps_carried_eager_and_replayed_twice(design, reference, monkeypatch, shape, mask, terms):
+    if not terms:
+        monkeypatch.setenv('ABOPT_PAIR_TERMS', '0')
+    inp, ref, fr = _ref(reference, design, shape, mask, terms, 3)
+    got, fg = _run(design, inp, True, 3, terms)
+    _check(got, fg, ref, fr, inp, gathered=True)
+    rep, fp = _run(design, inp, True, 3, terms, replays=2)
+    _check(rep, fp, ref, fr, inp, gathered=True)
+
+
+def test_switch_restores_the_masked_form(design, reference, monkeypatch):
+    """ABOPT_STEP_COMPACT=0: the call with the list runs what the call without it runs -- every output equal, context rows of the network's included"""
+    inp, ref, fr = _ref(reference, design, 'five_tiles_three_blocks_ragged', 'straddling_runs', True, 1)
+    monkeypatch.setenv('ABOPT_STEP_COMPACT', '0')
+    got, fg = _run(design, inp, True, 1, True)
+    _check(got, fg, ref, fr, inp, gathered=False)
+
+
+def test_flag_stays_down_on_a_fresh_model_and_a_poisoned_workspace(monkeypatch):
+    """The gathered form writes generated rows of the encoder's output only and the heads read every row: with three blocks the others hold block 0's output of the
+    same forward, whatever the buffer held before -- here NaN bit patterns in every byte of the workspace, under a first step without a carried mixer"""
+    d = _model()
+    inp = _inputs('five_tiles_three_blocks_ragged', 'scattered_singles')
+    ws = hip.Workspace.get(hip.lib().abopt_eps_workspace_bytes(inp['N'], inp['L'], 128, 64), DEV)
+    for compact in (False, True):
+        ws.fill_(0xff)
+        res, flag = _run(d, inp, compact, 1, True)
+        assert not flag, compact
+        assert all(torch.isfinite(res[0]['net'][k]).all() for k in NET), compact
+
+
+@pytest.mark.parametrize('graph', [False, True], ids=['eager', 'graph'])
+def test_loop_trajectories(design, monkeypatch, graph):
+    """FullDPM._run for three steps at N = 2, L = 80: the trajectories with ABOPT_STEP_COMPACT=0 and without it; the loop settles the tile count from its masks"""
+    inp = _inputs('five_tiles_three_blocks_ragged', 'straddling_runs')
+
+    def loop(compact):
+        if compact:
+            monkeypatch.delenv('ABOPT_STEP_COMPACT', raising=False)
+        else:
+            monkeypatch.setenv('ABOPT_STEP_COMPACT', '0')
+        design.clear_graphs()
+        out = design._run((inp['v'], inp['p'], inp['s']), T, inp['res_feat'], inp['pair_feat'], inp['gen'], inp['mres'], True, True, True, None, 11, 4096, False, graph=graph)
+        torch.cuda.synchronize()
+        info = design.last_run_info
+        assert info['steps'] == T and info['pair_terms'] and bool(info['graph']) == graph and info['query_row_tiles'] == (inp['tiles'] if compact else 0)
+        if graph:
+            assert [k[-2].query_row_tiles for k in design._graphs] == [inp['tiles'] if compact else 0]     # the captured loop's key holds the tile count
+        res = [a.clone() for a in out if a is not None]
+        design.clear_graphs()
+        return res
+    ref, got = loop(False), loop(True)
+    assert len(got) == len(ref) == 3 and all(torch.equal(a, b) for a, b in zip(got, ref)), [int((a != b).sum()) for a, b in zip(got, ref)]
+    assert not torch.equal(ref[0][0], ref[0][-1])                           # the loop moved the state
+
+
+@pytest.mark.parametrize('shape', list(SHAPES))
+def test_row_list_against_nonzero(shape):
+    N, L = SHAPES[shape][:2]
+    for mask in list(MASKS) + list(REFUSED) + ['zeros']:
+        gen = (torch.zeros(N, L, dtype=torch.bool) if mask == 'zeros' else {**MASKS, **REFUSED}[mask](N, L)).to(DEV)
+        rows, count = hip.query_row_list(gen)
+        assert rows.dtype == count.dtype == torch.int32 and rows.shape == (N, (L + 15) // 16 * 16) and count.shape == (N,)
+        assert torch.equal(count.long(), gen.sum(1))
+        for n in range(N):
+            want = torch.nonzero(gen[n]).flatten().int()
+            assert torch.equal(rows[n, :len(want)], want) and (rows[n, len(want):] == -1).all(), (mask, n)
