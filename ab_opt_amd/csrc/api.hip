@@ -556,8 +556,8 @@ EpsScratch carve_eps(Carver& cv, int64_t M, int N, int L, int num_bins) {
 // what abopt_eps_net_step adds to a forward: the arguments of abopt_denoise_step that the forward does not have already, and the carry
 struct StepCall {
     const abopt_step_params* sp; const abopt_step_noise* noise; uint64_t seed, offset; const float* p_angstrom; const float *igX, *igCdf; int bins, num_bins;
-    float *v_next, *p_next; int64_t* s_next; float *prmsd, *ppl, *post_out, *p_next_norm; const uint64_t* seed_dev; const int32_t* aa_allowed; int carry_in, carry_out, context_unused;
-    const int32_t* query_row_list = nullptr; int query_row_tiles = 0;      // abopt_eps_net_step_rows_compact
+    float *v_next, *p_next; int64_t* s_next; float *prmsd, *ppl, *post_out, *p_next_norm; const uint64_t* seed_dev; const int32_t* aa_allowed; int carry_in, carry_out;
+    int context_unused; const int32_t* query_row_list; int query_row_tiles;      // the loop's two optional facts; a row list implies context_unused
 };
 }  // namespace
 
@@ -683,6 +683,13 @@ extern "C" int abopt_eps_net_forward(const abopt_eps_weights* w, const float* v_
                        pair_bias_cache, pair_feat_shared, pair_terms, ws, ws_bytes, stream, nullptr);
 }
 
+extern "C" int abopt_query_row_list(const uint8_t* mask_generate, int N, int L, void* rows, void* count, abopt_stream stream) {
+    ABOPT_CHECK_ARG(N >= 0 && L >= 0 && (int64_t)N * (L + 15) < (1ll << 31), "query_row_list: bad dims N=%d L=%d", N, L);
+    if (N == 0) return ABOPT_OK;
+    ABOPT_CHECK_ARG(mask_generate && rows && count, "query_row_list: NULL argument");
+    return launch_query_row_list(mask_generate, N, L, (int32_t*)rows, (int32_t*)count, (hipStream_t)stream);
+}
+
 extern "C" int abopt_eps_net_step(const abopt_eps_weights* w, const float* v_t, const float* p_t, const int64_t* s_t,
                                   const float* res_feat, const float* pair_feat, const float* beta,
                                   const uint8_t* mask_generate, const uint8_t* mask_res,
@@ -692,52 +699,12 @@ extern "C" int abopt_eps_net_step(const abopt_eps_weights* w, const float* v_t, 
                                   const abopt_step_params* sp, const abopt_step_noise* noise, uint64_t seed, uint64_t offset, const float* p_angstrom,
                                   const float* igso3_X, const float* igso3_cdf, int igso3_bins, int num_bins,
                                   float* v_next, float* p_next, int64_t* s_next, float* prmsd, float* perplexity, float* post_out, float* p_next_norm,
-                                  const uint64_t* seed_offset_dev, const int32_t* aa_allowed, int carry_in, int carry_out, abopt_stream stream) {
+                                  const uint64_t* seed_offset_dev, const int32_t* aa_allowed, int carry_in, int carry_out,
+                                  int context_outputs_unused, const int32_t* query_rows, const int32_t* query_row_count, int query_row_tiles,
+                                  abopt_stream stream) {
+    ABOPT_CHECK_ARG(query_row_tiles >= 0 && (query_row_tiles == 0 || (query_rows && query_row_count)), "eps_net_step: %d tiles of a row list that is not given", query_row_tiles);
     const StepCall sc{sp, noise, seed, offset, p_angstrom, igso3_X, igso3_cdf, igso3_bins, num_bins, v_next, p_next, s_next, prmsd, perplexity, post_out, p_next_norm,
-                      seed_offset_dev, aa_allowed, carry_in, carry_out, 0};
-    return eps_forward(w, v_t, p_t, s_t, res_feat, pair_feat, beta, mask_generate, mask_res, v_net, R_net, eps_pos, c_denoised, prmsd_logits, N, L, Fd, Cd, 0,
-                       pair_bias_cache, pair_feat_shared, pair_terms, ws, ws_bytes, stream, &sc);
-}
-
-extern "C" int abopt_eps_net_step_rows(const abopt_eps_weights* w, const float* v_t, const float* p_t, const int64_t* s_t,
-                                       const float* res_feat, const float* pair_feat, const float* beta,
-                                       const uint8_t* mask_generate, const uint8_t* mask_res,
-                                       float* v_net, float* R_net, float* eps_pos, float* c_denoised, float* prmsd_logits,
-                                       int N, int L, int Fd, int Cd, const float* pair_bias_cache, int pair_feat_shared,
-                                       const float* pair_terms, void* ws, size_t ws_bytes,
-                                       const abopt_step_params* sp, const abopt_step_noise* noise, uint64_t seed, uint64_t offset, const float* p_angstrom,
-                                       const float* igso3_X, const float* igso3_cdf, int igso3_bins, int num_bins,
-                                       float* v_next, float* p_next, int64_t* s_next, float* prmsd, float* perplexity, float* post_out, float* p_next_norm,
-                                       const uint64_t* seed_offset_dev, const int32_t* aa_allowed, int carry_in, int carry_out, int context_outputs_unused,
-                                       abopt_stream stream) {
-    const StepCall sc{sp, noise, seed, offset, p_angstrom, igso3_X, igso3_cdf, igso3_bins, num_bins, v_next, p_next, s_next, prmsd, perplexity, post_out, p_next_norm,
-                      seed_offset_dev, aa_allowed, carry_in, carry_out, context_outputs_unused};
-    return eps_forward(w, v_t, p_t, s_t, res_feat, pair_feat, beta, mask_generate, mask_res, v_net, R_net, eps_pos, c_denoised, prmsd_logits, N, L, Fd, Cd, 0,
-                       pair_bias_cache, pair_feat_shared, pair_terms, ws, ws_bytes, stream, &sc);
-}
-
-extern "C" int abopt_query_row_list(const uint8_t* mask_generate, int N, int L, void* rows, void* count, abopt_stream stream) {
-    ABOPT_CHECK_ARG(N >= 0 && L >= 0 && (int64_t)N * (L + 15) < (1ll << 31), "query_row_list: bad dims N=%d L=%d", N, L);
-    if (N == 0) return ABOPT_OK;
-    ABOPT_CHECK_ARG(mask_generate && rows && count, "query_row_list: NULL argument");
-    return launch_query_row_list(mask_generate, N, L, (int32_t*)rows, (int32_t*)count, (hipStream_t)stream);
-}
-
-extern "C" int abopt_eps_net_step_rows_compact(const abopt_eps_weights* w, const float* v_t, const float* p_t, const int64_t* s_t,
-                                               const float* res_feat, const float* pair_feat, const float* beta,
-                                               const uint8_t* mask_generate, const uint8_t* mask_res,
-                                               float* v_net, float* R_net, float* eps_pos, float* c_denoised, float* prmsd_logits,
-                                               int N, int L, int Fd, int Cd, const float* pair_bias_cache, int pair_feat_shared,
-                                               const float* pair_terms, void* ws, size_t ws_bytes,
-                                               const abopt_step_params* sp, const abopt_step_noise* noise, uint64_t seed, uint64_t offset, const float* p_angstrom,
-                                               const float* igso3_X, const float* igso3_cdf, int igso3_bins, int num_bins,
-                                               float* v_next, float* p_next, int64_t* s_next, float* prmsd, float* perplexity, float* post_out, float* p_next_norm,
-                                               const uint64_t* seed_offset_dev, const int32_t* aa_allowed, int carry_in, int carry_out,
-                                               const int32_t* query_rows, const int32_t* query_row_count, int query_row_tiles, abopt_stream stream) {
-    ABOPT_CHECK_ARG(query_row_tiles >= 0 && (query_row_tiles == 0 || (query_rows && query_row_count)), "eps_net_step_rows_compact: %d tiles of a row list that is not given", query_row_tiles);
-    StepCall sc{sp, noise, seed, offset, p_angstrom, igso3_X, igso3_cdf, igso3_bins, num_bins, v_next, p_next, s_next, prmsd, perplexity, post_out, p_next_norm,
-                seed_offset_dev, aa_allowed, carry_in, carry_out, 1};
-    sc.query_row_list = query_rows; sc.query_row_tiles = query_row_tiles;
+                      seed_offset_dev, aa_allowed, carry_in, carry_out, context_outputs_unused || query_row_tiles > 0, query_rows, query_row_tiles};
     return eps_forward(w, v_t, p_t, s_t, res_feat, pair_feat, beta, mask_generate, mask_res, v_net, R_net, eps_pos, c_denoised, prmsd_logits, N, L, Fd, Cd, 0,
                        pair_bias_cache, pair_feat_shared, pair_terms, ws, ws_bytes, stream, &sc);
 }

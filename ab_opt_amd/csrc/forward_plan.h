@@ -40,8 +40,8 @@ struct ForwardQuery {
     // (carry_in: the previous call of the entry wrote it); the next evaluation's is wanted (carry_out)
     bool step = false, ppl = false, carry_in = false, carry_out = false;
     bool frag2 = false;             // the workspace holds a second fragment pair (api.hip: carve_ga aliases it onto proj | feat where it fits)
-    bool context_unused = false;    // abopt_eps_net_step_rows: the caller reads nothing of the network's outputs on rows that are not generated
-    int query_row_tiles = 0;        // abopt_eps_net_step_rows_compact: the caller's list of generated rows fills at most this many 16-row tiles per sample; 0: no list
+    bool context_unused = false;    // abopt_eps_net_step with context_outputs_unused or a row list: the caller reads nothing of the network's outputs on rows that are not generated
+    int query_row_tiles = 0;        // abopt_eps_net_step with a row list: the caller's list of generated rows fills at most this many 16-row tiles per sample; 0: no list
 };
 
 enum class NodeForm { Kernel, Gemm };               // node_frags | projection GEMM + ipa_frags

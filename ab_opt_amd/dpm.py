@@ -40,7 +40,7 @@ class _LoopSpec:
     timesteps: tuple | int = 0                  # the steps the loop visits: 0 every step t_start .. 1; K > 0 the K evenly respaced ones, respaced_steps(t_start, K);
                                                 # a tuple: these (t_start first, strictly decreasing, >= 1)
     query_row_tiles: int = 0                    # 16-row tiles the generated rows of the loop's longest sample fill (FullDPM._denoise settles it from the masks, once
-                                                # per call); 0: the loop holds no row list (include/abopt.h: abopt_eps_net_step_rows_compact)
+                                                # per call); 0: the loop holds no row list (include/abopt.h: abopt_eps_net_step, query_row_tiles)
 
 
 def respaced_steps(t_start, steps=None, timesteps=None):

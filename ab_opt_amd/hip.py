@@ -13,7 +13,7 @@ import torch
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # ABOPT_LIB_PATH: developer override to load a variant build of the same ABI (csrc/Makefile VARIANT=...: A/B of two source trees)
 LIB_PATH = os.environ.get('ABOPT_LIB_PATH') or os.path.join(_HERE, 'libabopt_hip.so')
-ABI_VERSION = 52
+ABI_VERSION = 53
 
 c_f = C.c_void_p        # device float*
 c_i64 = C.c_void_p      # device int64*
@@ -116,16 +116,10 @@ _SIGNATURES = {
                               [c_f, c_int, c_f, c_void_p, c_size_t, c_stream]),
     'abopt_denoise_step': (c_int, [POINTER(StepParams), POINTER(StepNoise), c_uint64, c_uint64, c_f, c_f, c_i64] + [c_f] * 4 + [c_u8, c_f, c_f, c_int, c_int] +
                            [c_f, c_f, c_i64] + [c_f] * 4 + [c_void_p, c_i32, c_int, c_int, c_stream]),
+    'abopt_query_row_list': (c_int, [c_u8, c_int, c_int, c_void_p, c_void_p, c_stream]),
     'abopt_eps_net_step': (c_int, [POINTER(EpsWeights), c_f, c_f, c_i64, c_f, c_f, c_f, c_u8, c_u8] + [c_f] * 5 + [c_int] * 4 + [c_f, c_int, c_f, c_void_p, c_size_t] +
                            [POINTER(StepParams), POINTER(StepNoise), c_uint64, c_uint64, c_f, c_f, c_f, c_int, c_int] + [c_f, c_f, c_i64] + [c_f] * 4 +
-                           [c_void_p, c_i32, c_int, c_int, c_stream]),
-    'abopt_eps_net_step_rows': (c_int, [POINTER(EpsWeights), c_f, c_f, c_i64, c_f, c_f, c_f, c_u8, c_u8] + [c_f] * 5 + [c_int] * 4 + [c_f, c_int, c_f, c_void_p, c_size_t] +
-                                [POINTER(StepParams), POINTER(StepNoise), c_uint64, c_uint64, c_f, c_f, c_f, c_int, c_int] + [c_f, c_f, c_i64] + [c_f] * 4 +
-                                [c_void_p, c_i32, c_int, c_int, c_int, c_stream]),
-    'abopt_query_row_list': (c_int, [c_u8, c_int, c_int, c_void_p, c_void_p, c_stream]),
-    'abopt_eps_net_step_rows_compact': (c_int, [POINTER(EpsWeights), c_f, c_f, c_i64, c_f, c_f, c_f, c_u8, c_u8] + [c_f] * 5 + [c_int] * 4 + [c_f, c_int, c_f, c_void_p, c_size_t] +
-                                        [POINTER(StepParams), POINTER(StepNoise), c_uint64, c_uint64, c_f, c_f, c_f, c_int, c_int] + [c_f, c_f, c_i64] + [c_f] * 4 +
-                                        [c_void_p, c_i32, c_int, c_int, c_i32, c_i32, c_int, c_stream]),
+                           [c_void_p, c_i32, c_int, c_int, c_int, c_i32, c_i32, c_int, c_stream]),
     'abopt_igso3_tables': (c_int, [c_f, c_int, c_int, c_int, c_f, c_f, c_f, c_stream]),
     'abopt_sample_init': (c_int, [c_f, c_f, c_i64, c_u8, c_f, c_f, c_i64, c_uint64, c_uint64, c_float, c_void_p, c_int, c_int, c_f, c_f, c_i64, c_i32, c_int, c_int, c_stream]),
     'abopt_add_noise': (c_int, [c_i64, c_f, c_f, c_u8, c_f, c_f, c_int, c_int, POINTER(AddNoiseNoise), c_uint64, c_uint64, c_f, c_f, c_i64, c_u8, c_float, c_void_p, c_int, c_int, c_int,
@@ -569,9 +563,9 @@ def eps_net_step(ew, v_t, p_t, s_t, res_feat, pair_feat, beta, mask_generate, ma
     """One loop iteration in one C call (include/abopt.h: abopt_eps_net_step): eps_net_forward(..., out=net) then denoise_step(..., out) on its outputs, bit-identical
     to the two calls; where the library fuses the step's tail, carry_out leaves the next evaluation's mixer output in the workspace and carry_in says the previous
     call did so for exactly this v_t / s_t.  net: the dict eps_net_forward fills (prmsd_logits None without the head); out: as for denoise_step.
-    context_outputs_unused (abopt_eps_net_step_rows): the caller reads `net` on generated residues only; `out` and the posterior are what they are without it.
-    query_rows (abopt_eps_net_step_rows_compact; implies context_outputs_unused): (rows, count, tiles) -- query_row_list(mask_generate) of THIS mask and the number of
-    16-row tiles of the list its longest sample fills; the same results, with the last block on listed rows only where the library's plan takes that form."""
+    context_outputs_unused: the caller reads `net` on generated residues only; `out` and the posterior are what they are without it.
+    query_rows (implies context_outputs_unused): (rows, count, tiles) -- query_row_list(mask_generate) of THIS mask and the number of 16-row tiles of the list its
+    longest sample fills; the same results, with the last block on listed rows only where the library's plan takes that form."""
     N, L = mask_res.shape
     F, Cd = res_feat.shape[-1], pair_feat.shape[-1]
     nz = None
@@ -581,23 +575,21 @@ def eps_net_step(ew, v_t, p_t, s_t, res_feat, pair_feat, beta, mask_generate, ma
     post = torch.empty(N, L, 20, device=v_t.device) if want_post else None
     buf = Workspace.get(lib().abopt_eps_workspace_bytes(N, L, F, Cd), res_feat.device)
     v_t, p_t, s_t, res_feat, pair_feat, beta, mask_generate, mask_res = _contig(v_t, p_t, s_t, res_feat, pair_feat, beta, mask_generate, mask_res)
-    if query_rows is not None:
-        rows, count, tiles = query_rows
-        if rows.shape != (N, (L + 15) // 16 * 16) or count.shape != (N,):
-            raise ValueError(f'query_rows: a list of shape {tuple(rows.shape)} / {tuple(count.shape)} does not belong to a mask of shape {(N, L)}')
-        fn, tail = lib().abopt_eps_net_step_rows_compact, (ptr(rows, torch.int32), ptr(count, torch.int32), int(tiles))
-    else:
-        fn, tail = (lib().abopt_eps_net_step_rows, (1,)) if context_outputs_unused else (lib().abopt_eps_net_step, ())
-    _check(fn(C.byref(ew), ptr(v_t, torch.float32), ptr(p_t, torch.float32), ptr(s_t, torch.int64), ptr(res_feat, torch.float32),
-              ptr(pair_feat, torch.float32), ptr(beta, torch.float32), ptr(mask_generate, torch.bool), ptr(mask_res, torch.bool),
-              ptr(net['v_next']), ptr(net['R_next']), ptr(net['eps_pos']), ptr(net['c']), ptr(net['prmsd_logits'], optional=True),
-              N, L, F, Cd, ptr(pair_bias_cache, torch.float32, optional=True), int(pair_feat_shared),
-              ptr(pair_terms, torch.float32, optional=True), ptr(buf), buf.numel(),
-              C.byref(sp), C.byref(nz) if nz is not None else None, seed, offset, ptr(p_angstrom, torch.float32),
-              ptr(ig_X_row, torch.float32), ptr(ig_cdf_row, optional=True), ig_X_row.numel(), num_bins,
-              ptr(out['v']), ptr(out['p']), ptr(out['s']), ptr(out.get('prmsd'), optional=True), ptr(out.get('ppl'), optional=True),
-              ptr(post, optional=True), ptr(out.get('p_norm'), optional=True), ptr(seed_dev, torch.int64, optional=True),
-              _allowed_ptr(aa_allowed, mask_generate), int(carry_in), int(carry_out), *tail, stream()))
+    rows, count, tiles = query_rows if query_rows is not None else (None, None, 0)
+    if query_rows is not None and (rows.shape != (N, (L + 15) // 16 * 16) or count.shape != (N,)):
+        raise ValueError(f'query_rows: a list of shape {tuple(rows.shape)} / {tuple(count.shape)} does not belong to a mask of shape {(N, L)}')
+    _check(lib().abopt_eps_net_step(
+        C.byref(ew), ptr(v_t, torch.float32), ptr(p_t, torch.float32), ptr(s_t, torch.int64), ptr(res_feat, torch.float32),
+        ptr(pair_feat, torch.float32), ptr(beta, torch.float32), ptr(mask_generate, torch.bool), ptr(mask_res, torch.bool),
+        ptr(net['v_next']), ptr(net['R_next']), ptr(net['eps_pos']), ptr(net['c']), ptr(net['prmsd_logits'], optional=True),
+        N, L, F, Cd, ptr(pair_bias_cache, torch.float32, optional=True), int(pair_feat_shared),
+        ptr(pair_terms, torch.float32, optional=True), ptr(buf), buf.numel(),
+        C.byref(sp), C.byref(nz) if nz is not None else None, seed, offset, ptr(p_angstrom, torch.float32),
+        ptr(ig_X_row, torch.float32), ptr(ig_cdf_row, optional=True), ig_X_row.numel(), num_bins,
+        ptr(out['v']), ptr(out['p']), ptr(out['s']), ptr(out.get('prmsd'), optional=True), ptr(out.get('ppl'), optional=True),
+        ptr(post, optional=True), ptr(out.get('p_norm'), optional=True), ptr(seed_dev, torch.int64, optional=True),
+        _allowed_ptr(aa_allowed, mask_generate), int(carry_in), int(carry_out),
+        int(bool(context_outputs_unused) or query_rows is not None), ptr(rows, torch.int32, optional=True), ptr(count, torch.int32, optional=True), int(tiles), stream()))
     return post
 
 

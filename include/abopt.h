@@ -23,7 +23,7 @@
 extern "C" {
 #endif
 
-#define ABOPT_ABI_VERSION 52
+#define ABOPT_ABI_VERSION 53
 
 enum { ABOPT_OK = 0, ABOPT_EINVAL = 1, ABOPT_EHIP = 2, ABOPT_EUNSUPPORTED = 3, ABOPT_EWORKSPACE = 4 };
 
@@ -294,16 +294,37 @@ int abopt_denoise_step(const abopt_step_params* sp, const abopt_step_noise* nois
                        const int32_t* aa_allowed /* optional [N,L]: allowed residue types, see above */,
                        int N, int L, abopt_stream stream);
 
-/* One whole loop iteration (ABI 46): abopt_eps_net_forward (grad_mode 0) followed by abopt_denoise_step on its outputs, as one call.  The arguments are those of the
- * two functions, once each: v_t / s_t / mask_generate / N / L / stream are shared, p_t is the normalised position the network takes and p_angstrom the state the
- * step moves, v_net / R_net / eps_pos / c_denoised / prmsd_logits are the network's outputs (written as by abopt_eps_net_forward, read as the step's v_net / p_net /
- * c_net / prmsd_logits).  p_next_norm may be p_t itself.  Every output is bit-identical to the two calls in a row.
+/* The generated rows of every sample as a list (ABI 52): rows [N][ceil(L / 16) * 16] int32 takes, per sample, the ascending indices of the residues with
+ * mask_generate != 0 and -1 in every entry behind them; count [N] int32 takes their number.  One launch; the host learns nothing. */
+int abopt_query_row_list(const uint8_t* mask_generate, int N, int L, void* rows, void* count, abopt_stream stream);
+
+/* One whole loop iteration (ABI 46; one entry for all its forms since ABI 53): abopt_eps_net_forward (grad_mode 0) followed by abopt_denoise_step on its outputs, as
+ * one call.  The arguments are those of the two functions, once each: v_t / s_t / mask_generate / N / L / stream are shared, p_t is the normalised position the
+ * network takes and p_angstrom the state the step moves, v_net / R_net / eps_pos / c_denoised / prmsd_logits are the network's outputs (written as by
+ * abopt_eps_net_forward, read as the step's v_net / p_net / c_net / prmsd_logits).  p_next_norm may be p_t itself.
+ * The plain call -- context_outputs_unused = 0, query_row_tiles = 0; query_rows and query_row_count may be NULL: every output is bit-identical to the two calls in a row.
  * Where the packed mixer and heads operands are given, neither prmsd nor perplexity is asked for (no prmsd head in w, perplexity NULL) and ABOPT_FUSE_STEP is not 0,
  * the heads, the step's transitions and -- carry_out -- the mixer step of the NEXT evaluation on the state just sampled run as ONE launch behind the encoder;
  * otherwise the call makes the launches of the two functions, in their order, and ignores the carry.
  *   carry_out != 0: also leave the next evaluation's mixer output (for v_next / s_next and the same res_feat) in ws.
  *   carry_in  != 0: ws already holds this evaluation's mixer output -- the previous call of this function, with carry_out set, on the same ws, N, L, w and res_feat,
- *                   produced exactly this v_t / s_t, and nothing wrote ws in between.  The mixer launch is skipped. */
+ *                   produced exactly this v_t / s_t, and nothing wrote ws in between.  The mixer launch is skipped.
+ * Two optional facts a loop may add; neither changes what the step hands on:
+ *   context_outputs_unused != 0 (ABI 50): the caller reads the network's outputs on generated residues only.  v_next, p_next, s_next, post_out and p_next_norm are
+ *     still bit-identical to the plain call's -- the transitions keep the old state wherever mask_generate is 0, whatever the network says there -- and so are v_net,
+ *     R_net, eps_pos and c_denoised on residues with mask_generate set; on the other residues those four are finite but unspecified, and abopt_nonfinite_flag does not
+ *     rise because of them.  What the library does with the freedom: where the step's tail is fused (see above: packed operands, no prmsd head, perplexity NULL) and
+ *     the last block of the encoder is the fused 32-row kernel on a pair-bias cache, that block streams pair features and pair bias for generated query rows only.
+ *     Every other call runs exactly as the plain call does; ABOPT_STEP_ROWS=0 makes all do.
+ *   query_row_tiles > 0 (ABI 52): the caller also holds the row list of its mask_generate.  query_rows and query_row_count, both required then, are what
+ *     abopt_query_row_list wrote for THIS mask_generate, N and L, and query_row_tiles >= ceil(max_n count[n] / 16) is the number of 16-row tiles of the list the longest
+ *     sample fills (the caller reads the counts once per loop; masks do not change over its steps).  A row list implies the caller's word: context outputs are unused
+ *     whatever context_outputs_unused says, and the contract is that of the flag -- v_next, p_next, s_next, post_out and p_next_norm bit-identical everywhere, v_net,
+ *     R_net, eps_pos and c_denoised bit-identical on generated residues, finite but unspecified on the others.  What the library does with the list: where the flag
+ *     alone would mask the last block's query rows, the net has three blocks or more, N * query_row_tiles workgroups fit the device's CUs in one round and
+ *     query_row_tiles <= ceil(L / 32), that block runs one workgroup per 16 LISTED rows instead of one per 32 rows of the sample.  Every other call makes the launches
+ *     of the flag alone; ABOPT_STEP_COMPACT=0 makes all do.  A list that does not belong to mask_generate, or fewer tiles than the longest sample fills, leaves
+ *     generated rows of the network's outputs unspecified.  query_row_tiles = 0: no list, the pointers are not read. */
 int abopt_eps_net_step(const abopt_eps_weights* w, const float* v_t, const float* p_t, const int64_t* s_t,
                        const float* res_feat, const float* pair_feat, const float* beta,
                        const uint8_t* mask_generate, const uint8_t* mask_res,
@@ -313,49 +334,9 @@ int abopt_eps_net_step(const abopt_eps_weights* w, const float* v_t, const float
                        const abopt_step_params* sp, const abopt_step_noise* noise, uint64_t seed, uint64_t offset, const float* p_angstrom,
                        const float* igso3_X, const float* igso3_cdf, int igso3_bins, int num_bins,
                        float* v_next, float* p_next, int64_t* s_next, float* prmsd, float* perplexity, float* post_out, float* p_next_norm,
-                       const uint64_t* seed_offset_dev, const int32_t* aa_allowed, int carry_in, int carry_out, abopt_stream stream);
-
-/* The same call from a loop that reads the network's outputs on generated residues only (ABI 50).  context_outputs_unused = 0: abopt_eps_net_step, bit for bit.
- * context_outputs_unused != 0: v_next, p_next, s_next, post_out and p_next_norm are still bit-identical to abopt_eps_net_step's -- the transitions keep the old state
- * wherever mask_generate is 0, whatever the network says there -- and so are v_net, R_net, eps_pos and c_denoised on residues with mask_generate set; on the other
- * residues those four are finite but unspecified, and abopt_nonfinite_flag does not rise because of them.  What the library does with the freedom: where the step's
- * tail is fused (see above: packed operands, no prmsd head, perplexity NULL) and the last block of the encoder is the fused 32-row kernel on a pair-bias cache, that
- * block streams pair features and pair bias for generated query rows only.  Every other call runs exactly as abopt_eps_net_step does; ABOPT_STEP_ROWS=0 makes all do. */
-int abopt_eps_net_step_rows(const abopt_eps_weights* w, const float* v_t, const float* p_t, const int64_t* s_t,
-                            const float* res_feat, const float* pair_feat, const float* beta,
-                            const uint8_t* mask_generate, const uint8_t* mask_res,
-                            float* v_net, float* R_net, float* eps_pos, float* c_denoised, float* prmsd_logits,
-                            int N, int L, int F, int C,
-                            const float* pair_bias_cache, int pair_feat_shared, const float* pair_terms, void* ws, size_t ws_bytes,
-                            const abopt_step_params* sp, const abopt_step_noise* noise, uint64_t seed, uint64_t offset, const float* p_angstrom,
-                            const float* igso3_X, const float* igso3_cdf, int igso3_bins, int num_bins,
-                            float* v_next, float* p_next, int64_t* s_next, float* prmsd, float* perplexity, float* post_out, float* p_next_norm,
-                            const uint64_t* seed_offset_dev, const int32_t* aa_allowed, int carry_in, int carry_out, int context_outputs_unused,
-                            abopt_stream stream);
-
-/* The generated rows of every sample as a list (ABI 52): rows [N][ceil(L / 16) * 16] int32 takes, per sample, the ascending indices of the residues with
- * mask_generate != 0 and -1 in every entry behind them; count [N] int32 takes their number.  One launch; the host learns nothing. */
-int abopt_query_row_list(const uint8_t* mask_generate, int N, int L, void* rows, void* count, abopt_stream stream);
-
-/* abopt_eps_net_step_rows with context_outputs_unused != 0, from a loop that also holds the row list of its mask_generate (ABI 52): query_rows and query_row_count
- * are what abopt_query_row_list wrote for THIS mask_generate, N and L, and query_row_tiles >= ceil(max_n count[n] / 16) is the number of 16-row tiles of the list the
- * longest sample fills (the caller reads the counts once per loop; masks do not change over its steps).  The contract is that call's: v_next, p_next, s_next, post_out
- * and p_next_norm bit-identical everywhere, v_net, R_net, eps_pos and c_denoised bit-identical on generated residues, finite but unspecified on the others.  What the
- * library does with the list: where abopt_eps_net_step_rows would mask the last block's query rows, the net has three blocks or more, N * query_row_tiles workgroups
- * fit the device's CUs in one round and query_row_tiles <= ceil(L / 32), that block runs one workgroup per 16 LISTED rows instead of one per 32 rows of the sample.
- * Every other call -- query_row_tiles = 0 among them -- makes the launches of abopt_eps_net_step_rows; ABOPT_STEP_COMPACT=0 makes all do.  A list that does not
- * belong to mask_generate, or fewer tiles than the longest sample fills, leaves generated rows of the network's outputs unspecified. */
-int abopt_eps_net_step_rows_compact(const abopt_eps_weights* w, const float* v_t, const float* p_t, const int64_t* s_t,
-                                    const float* res_feat, const float* pair_feat, const float* beta,
-                                    const uint8_t* mask_generate, const uint8_t* mask_res,
-                                    float* v_net, float* R_net, float* eps_pos, float* c_denoised, float* prmsd_logits,
-                                    int N, int L, int F, int C,
-                                    const float* pair_bias_cache, int pair_feat_shared, const float* pair_terms, void* ws, size_t ws_bytes,
-                                    const abopt_step_params* sp, const abopt_step_noise* noise, uint64_t seed, uint64_t offset, const float* p_angstrom,
-                                    const float* igso3_X, const float* igso3_cdf, int igso3_bins, int num_bins,
-                                    float* v_next, float* p_next, int64_t* s_next, float* prmsd, float* perplexity, float* post_out, float* p_next_norm,
-                                    const uint64_t* seed_offset_dev, const int32_t* aa_allowed, int carry_in, int carry_out,
-                                    const int32_t* query_rows, const int32_t* query_row_count, int query_row_tiles, abopt_stream stream);
+                       const uint64_t* seed_offset_dev, const int32_t* aa_allowed, int carry_in, int carry_out,
+                       int context_outputs_unused, const int32_t* query_rows, const int32_t* query_row_count, int query_row_tiles,
+                       abopt_stream stream);
 
 /* ---- IGSO(3) angle histograms for arbitrary standard deviations (ABI 45): the tables ApproxAngularDistribution builds on the host at construction
  * (D/modules/common/so3.py:82-109), for the strides of a respaced loop, whose sigmas are chosen per call.  Row r, bin b at x_b = linspace(0, pi, bins)[b]:

@@ -1,14 +1,11 @@
 """The launches of a denoiser forward (ab_opt_amd/csrc/forward_plan.h: plan_block / plan_encoder / plan_network) without a device: tests/forward_plan_table.cpp, a
 host-only program, tabulates the plans of a three-block net over geometries, CU counts, operands given, switches and weight lists; what the kernels rely on -- who
 writes term-form fragments and x terms, and who reads them -- is checked on every line, and three forwards are pinned."""
-import os
-import shutil
-import subprocess
 from collections import namedtuple
 
 import pytest
 
-from conftest import ROOT
+from plan_tables import table_lines
 
 GEOMETRIES = {(2, 33), (3, 70), (8, 256), (16, 256), (32, 256), (48, 256), (1000, 48), (1366, 256)}
 Query = namedtuple('Query', 'N L cus z cache terms ask ws ovr no_split fuse_tail x_terms fuse_heads wl mix heads prmsd')
@@ -24,13 +21,9 @@ def _block(text):
 
 
 @pytest.fixture(scope='module')
-def table(tmp_path_factory):
-    cxx = next((c for c in ('/opt/rocm/lib/llvm/bin/clang++', shutil.which('g++'), shutil.which('clang++')) if c and os.path.exists(c)), None)
-    assert cxx, 'no host C++ compiler (clang++ of the ROCm LLVM directory, g++)'
-    exe = str(tmp_path_factory.mktemp('forward_plan') / 'forward_plan_table')
-    subprocess.run([cxx, '-std=c++17', '-O1', '-Wall', '-Werror', os.path.join(ROOT, 'tests', 'forward_plan_table.cpp'), '-o', exe], check=True)
+def table():
     rows = []
-    for line in subprocess.run([exe], check=True, capture_output=True, text=True).stdout.splitlines():
+    for line in table_lines('forward_plan_table'):
         q, net, *blocks, enc, single = line.split(' | ')
         e = list(map(int, enc.split()))
         s = single.split()

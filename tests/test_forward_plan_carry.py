@@ -3,33 +3,21 @@ a host-only program, tabulates the decision over the grid of tests/forward_plan_
 second fragment pair in the workspace; a forward whose 32-row workgroups need more than one round of the CUs is not carried (measured: forward_plan.h); what the
 kernels rely on -- who writes which fragment slot while who reads which -- is checked on every line, the columns of the older table are compared with that
 program's own output, and two forwards are pinned."""
-import os
-import shutil
-import subprocess
 from collections import namedtuple
 
 import pytest
 
-from conftest import ROOT
+from plan_tables import table_lines
 
 Variant = namedtuple('Variant', 'fuse_node frag2 same blocks')        # blocks: [(carry_next, carried, frag_slot)]
 Row = namedtuple('Row', 'legacy q ok tails node_kernel variants')
 
 
-def _build(tmp, name):
-    cxx = next((c for c in ('/opt/rocm/lib/llvm/bin/clang++', shutil.which('g++'), shutil.which('clang++')) if c and os.path.exists(c)), None)
-    assert cxx, 'no host C++ compiler (clang++ of the ROCm LLVM directory, g++)'
-    exe = str(tmp / name)
-    subprocess.run([cxx, '-std=c++17', '-O1', '-Wall', '-Werror', os.path.join(ROOT, 'tests', name + '.cpp'), '-o', exe], check=True)
-    return subprocess.run([exe], check=True, capture_output=True, text=True).stdout.splitlines()
-
-
 @pytest.fixture(scope='module')
-def tables(tmp_path_factory):
-    tmp = tmp_path_factory.mktemp('forward_plan_carry')
-    old = _build(tmp, 'forward_plan_table')
+def tables():
+    old = table_lines('forward_plan_table')
     rows, pins = [], {}
-    for line in _build(tmp, 'forward_plan_carry_table'):
+    for line in table_lines('forward_plan_carry_table'):
         if line.startswith('pin '):
             head, _, body = line[4:].partition('|')
             h, b = list(map(int, head.split())), list(map(int, body.split()))

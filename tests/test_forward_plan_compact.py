@@ -2,28 +2,18 @@
 host-only program, tabulates plan_network for abopt_eps_net_step over geometries, CU counts, block counts, tile counts of the caller's row list and the switches; here
 the rule is restated from the columns of every line: the last block gathers only where it masks its query rows already, the caller gave a list, ABOPT_STEP_COMPACT is
 not 0, N x tiles workgroups fit the CUs in one round, tiles <= ceil(L / 32) and the net has three blocks or more -- and it moves nothing else in the plan."""
-import os
-import shutil
-import subprocess
 from collections import namedtuple
 
 import pytest
 
-from conftest import ROOT
+from plan_tables import build_table
 
 Row = namedtuple('Row', 'N L cus z terms ovr nb tiles context_unused step_rows step_compact ppl prmsd ok masked compact compact_grid core_grid elsewhere same')
 
 
 @pytest.fixture(scope='module')
-def table(tmp_path_factory):
-    cxx = next((c for c in ('/opt/rocm/lib/llvm/bin/clang++', shutil.which('g++'), shutil.which('clang++')) if c and os.path.exists(c)), None)
-    assert cxx, 'no host C++ compiler (clang++ of the ROCm LLVM directory, g++)'
-    exe = str(tmp_path_factory.mktemp('forward_plan_compact') / 'forward_plan_compact_table')
-    subprocess.run([cxx, '-std=c++17', '-O1', '-Wall', '-Werror', os.path.join(ROOT, 'tests', 'forward_plan_compact_table.cpp'), '-o', exe], check=True)
-    rows = []
-    for line in subprocess.run([exe], check=True, capture_output=True, text=True).stdout.splitlines():
-        rows.append(Row(*map(int, line.replace('|', ' ').split())))
-    return rows
+def table():
+    return build_table('forward_plan_compact_table', Row)
 
 
 def test_grid_is_complete(table):
@@ -68,7 +58,7 @@ def test_pinned_bench_shape(table):
 
 
 def test_shapes_of_the_gpu_test_gather(table):
-    """tests/test_step_compact.py compares the compact entry with the masked form bit for bit, which proves nothing where the plan refuses: its shapes under
+    """tests/test_step_compact.py compares the entry with the row list against the masked form bit for bit, which proves nothing where the plan refuses: its shapes under
     ABOPT_CORE32=1 on 256 CUs with a three-block net gather for one to three (L = 80) and one or two (L = 48) tiles, and refuse beyond"""
     for N, L, most in ((2, 80, 3), (3, 48, 2)):
         for terms in (0, 1):

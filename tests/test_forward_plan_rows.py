@@ -2,14 +2,11 @@
 program, tabulates plan_network for both entries (abopt_eps_net_forward, abopt_eps_net_step), with and without the caller's context_unused, over geometries, CU counts,
 operands, weight lists and the switches; here the rule is restated from the columns of every line: the flag is set on the LAST block and nowhere else, only for a step
 whose tail is fused, whose last block is the fused 32-row kernel on a pair-bias cache, with ABOPT_STEP_ROWS not 0 -- and it moves nothing else in the plan."""
-import os
-import shutil
-import subprocess
 from collections import namedtuple
 
 import pytest
 
-from conftest import ROOT
+from plan_tables import table_lines
 
 Query = namedtuple('Query', 'N L cus z cache terms ovr wl mix heads prmsd')
 Call = namedtuple('Call', 'entry ppl context_unused fuse_step fuse_heads fuse_tail step_rows fuse_node dbg')
@@ -18,13 +15,9 @@ Row = namedtuple('Row', 'q c step_fused ok blocks same')
 
 
 @pytest.fixture(scope='module')
-def table(tmp_path_factory):
-    cxx = next((c for c in ('/opt/rocm/lib/llvm/bin/clang++', shutil.which('g++'), shutil.which('clang++')) if c and os.path.exists(c)), None)
-    assert cxx, 'no host C++ compiler (clang++ of the ROCm LLVM directory, g++)'
-    exe = str(tmp_path_factory.mktemp('forward_plan_rows') / 'forward_plan_rows_table')
-    subprocess.run([cxx, '-std=c++17', '-O1', '-Wall', '-Werror', os.path.join(ROOT, 'tests', 'forward_plan_rows_table.cpp'), '-o', exe], check=True)
+def table():
     rows = []
-    for line in subprocess.run([exe], check=True, capture_output=True, text=True).stdout.splitlines():
+    for line in table_lines('forward_plan_rows_table'):
         body, same = line.split(' || ')
         q, c, net, blocks = body.split(' | ')
         net, f = list(map(int, net.split())), blocks.lstrip('| ').split()

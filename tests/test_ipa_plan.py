@@ -1,13 +1,10 @@
 """The dispatch of the IPA core (ab_opt_amd/csrc/ipa_plan.h: plan_ipa_core) without a device: tests/ipa_plan_table.cpp, a host-only program, tabulates the
 plan over a grid of launch geometries; the invariants the kernels rely on are checked on every line and ten rows are pinned."""
-import os
-import shutil
-import subprocess
 from collections import namedtuple
 
 import pytest
 
-from conftest import ROOT
+from plan_tables import build_table
 
 NS = (1, 2, 8, 16, 23, 32, 48, 62, 64, 1000, 1365, 1366, 2732, 3000)
 LS = (1, 16, 17, 48, 64, 128, 192, 200, 256, 400, 2048, 2049)
@@ -20,17 +17,8 @@ Row = namedtuple('Row', 'N L cus z cache dump ws wsf ovr no_split form nsplit re
 
 
 @pytest.fixture(scope='module')
-def table(tmp_path_factory):
-    cxx = next((c for c in ('/opt/rocm/lib/llvm/bin/clang++', shutil.which('g++'), shutil.which('clang++')) if c and os.path.exists(c)), None)
-    assert cxx, 'no host C++ compiler (clang++ of the ROCm LLVM directory, g++)'
-    exe = str(tmp_path_factory.mktemp('ipa_plan') / 'ipa_plan_table')
-    subprocess.run([cxx, '-std=c++17', '-O1', '-Wall', '-Werror', os.path.join(ROOT, 'tests', 'ipa_plan_table.cpp'), '-o', exe], check=True)
-    rows = []
-    for line in subprocess.run([exe], check=True, capture_output=True, text=True).stdout.splitlines():
-        q, p = line.split(' | ')
-        form, *rest = p.split()
-        rows.append(Row(*map(int, q.split()), form, *map(int, rest)))
-    return rows
+def table():
+    return build_table('ipa_plan_table', Row)
 
 
 def slab_fits_u32(r):

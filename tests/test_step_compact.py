@@ -1,6 +1,6 @@
 """The last IPA block of a sampling step on GATHERED generated rows (csrc/forward_plan.h: query_rows_compact; csrc/ipa_core.hip: ipa_core32_kernel<true, *, false, true, true>;
-include/abopt.h: abopt_query_row_list, abopt_eps_net_step_rows_compact).  With the list of its generated rows, the last block runs one
-workgroup per 16 listed rows of a sample.  Against abopt_eps_net_step_rows with context_outputs_unused (the masked form): what the step hands on -- v_next, p_next,
+include/abopt.h: abopt_query_row_list, abopt_eps_net_step with query_rows).  With the list of its generated rows, the last block runs one
+workgroup per 16 listed rows of a sample.  Against the same entry with context_outputs_unused alone (the masked form): what the step hands on -- v_next, p_next,
 s_next, the posterior, p_next_norm -- is torch.equal on every row and the network's four outputs are torch.equal on generated rows; where the plan refuses (more than
 half the rows generated, ABOPT_STEP_COMPACT=0) every output is equal on every row.  ABOPT_CORE32=1 so that the small shapes take the 32-row kernels; that these shapes
 do gather on a 256-CU device is pinned without a device in tests/test_forward_plan_compact.py::test_shapes_of_the_gpu_test_gather, and checked here on context rows,
@@ -9,20 +9,10 @@ import pytest
 import torch
 
 from ab_opt_amd import hip
-from ab_opt_amd.dpm import FullDPM, _LoopSpec
 from ab_opt_amd.utils import synth
+from step_harness import DEV, NET, T, cached_reference, check, core32_env, model as _model, run
 
 pytestmark = pytest.mark.gpu
-
-DEV = torch.device('cuda:0')
-T = 3
-NET = ('v_next', 'R_next', 'eps_pos', 'c')
-OUT = ('v', 'p', 's', 'p_norm')
-
-
-def _model():
-    m = FullDPM(128, 64, num_steps=T, eps_net_opt=dict(num_layers=3), _abdesign=True).eval()
-    return synth.fill_module_(m, seed=5).to(DEV)
 
 
 @pytest.fixture(scope='module')
@@ -32,10 +22,7 @@ def design():
 
 @pytest.fixture(autouse=True)
 def core32(monkeypatch):
-    monkeypatch.setenv('ABOPT_CORE32', '1')
-    monkeypatch.setenv('ABOPT_CORE_NO_SPLIT', '1')
-    for name in ('ABOPT_STEP_ROWS', 'ABOPT_STEP_COMPACT', 'ABOPT_PAIR_TERMS'):
-        monkeypatch.delenv(name, raising=False)
+    core32_env(monkeypatch)
 
 
 # N, L, lengths (mask_res), samples per shared pair_feat entry (0: distinct)
@@ -82,79 +69,11 @@ def _inputs(shape, mask, salt=1300):
     return dict(N=N, L=L, group=group, v=v, p=p * 10.0, s=s, res_feat=res_feat, pair_feat=pair_feat, gen=gen, mres=mres, tiles=tiles)
 
 
-def _steps(d, inp, compact, nsteps, terms, pbc, pterms):
-    """nsteps calls of the step entry from t = T down, the mixer carried from call to call; compact: with the row list (built here, once), else the masked form"""
-    N, L = inp['N'], inp['L']
-    f32 = dict(dtype=torch.float32, device=DEV)
-    ew = d.eps_net.packed()
-    X, cdf = d._loop_tables(d._loop_steps(_LoopSpec(T)))
-    v, p, s = inp['v'], inp['p'], inp['s']
-    p_norm = ((p - d.position_mean) / d.position_scale).contiguous()
-    qrows = (*hip.query_row_list(inp['gen']), inp['tiles']) if compact else None
-    res = []
-    for j in range(nsteps):
-        t = T - j
-        net = dict(v_next=torch.empty(N, L, 3, **f32), R_next=torch.empty(N, L, 3, 3, **f32), eps_pos=torch.empty(N, L, 3, **f32), c=torch.empty(N, L, 20, **f32),
-                   prmsd_logits=None)
-        out = dict(v=torch.empty(N, L, 3, **f32), p=torch.empty(N, L, 3, **f32), s=torch.empty(N, L, dtype=torch.int64, device=DEV), p_norm=torch.empty(N, L, 3, **f32))
-        beta = d.trans_pos.var_sched.betas[t].expand(N).contiguous()
-        post = hip.eps_net_step(ew, v, p_norm, s, inp['res_feat'], inp['pair_feat'], beta, inp['gen'], inp['mres'], d.num_bins, net,
-                                d._step_params(t, True, True, True, False, t - 1), None, 11, 4096, p, X[j], cdf[j], out, pair_bias_cache=pbc,
-                                pair_feat_shared=inp['group'], pair_terms=pterms if terms else None, want_post=True, carry_in=j > 0, carry_out=j + 1 < nsteps,
-                                context_outputs_unused=True, query_rows=qrows)
-        res.append(dict(net=net, out=out, post=post))
-        v, p, s, p_norm = out['v'], out['p'], out['s'], out['p_norm']
-    return res
-
-
-def _run(d, inp, compact, nsteps, terms, replays=0):
-    """eagerly (replays = 0), or captured once and replayed `replays` times: the results of the last replay"""
-    pf = inp['pair_feat']
-    pbc = hip.pair_bias_cache(d.eps_net.encoder.packed_array(), len(d.eps_net.encoder.blocks), pf)
-    pterms = hip.pair_terms(pf)
-    hip.nonfinite_flag(reset=True)
-    if not replays:
-        res = _steps(d, inp, compact, nsteps, terms, pbc, pterms)
-    else:
-        hip.prof_enable(False)
-        _steps(d, inp, compact, 1, terms, pbc, pterms)                      # warm: kernel attributes, host-side caches
-        torch.cuda.synchronize()
-        before = set(hip.Workspace._bufs)
-        g = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(g):
-            res = _steps(d, inp, compact, nsteps, terms, pbc, pterms)
-        keep = [hip.Workspace._bufs.pop(k) for k in set(hip.Workspace._bufs) - before]       # the slab the capture allocated lives in the graph's pool
-        for _ in range(replays):
-            for r in res:
-                for a in list(r['net'].values()) + list(r['out'].values()) + [r['post']]:
-                    if a is not None:
-                        a.fill_(7)                                            # a replay that wrote nothing would be seen
-            g.replay()
-        torch.cuda.synchronize()
-        clone = lambda d_: {k: (a.clone() if a is not None else None) for k, a in d_.items()}
-        res = [dict(net=clone(r['net']), out=clone(r['out']), post=r['post'].clone()) for r in res]      # own storage: the buffers are the graph's static ones
-        del keep, g
-    torch.cuda.synchronize()
-    flag = hip.nonfinite_flag(reset=True)
-    return res, flag
-
-
 def _check(got, flag_got, ref, flag_ref, inp, gathered):
     """gathered: the plan takes the form -- generated rows equal, context rows finite and (first step) not the masked form's; else every row equal"""
-    assert not flag_ref and not flag_got                                    # abopt_nonfinite_flag reads 0
-    assert len(got) == len(ref)
-    gen = inp['gen']
-    for a, b in zip(got, ref):
-        for k in OUT:
-            assert torch.equal(a['out'][k], b['out'][k]), (k, int((a['out'][k] != b['out'][k]).sum()))
-        assert torch.equal(a['post'], b['post'])
-        for k in NET:
-            assert torch.isfinite(a['net'][k]).all() and torch.isfinite(b['net'][k]).all(), k
-            assert torch.equal(a['net'][k][gen], b['net'][k][gen]), (k, int((a['net'][k][gen] != b['net'][k][gen]).sum()))
-            if not gathered:
-                assert torch.equal(a['net'][k], b['net'][k]), k
+    check(got, flag_got, ref, flag_ref, inp['gen'], everything=not gathered)
     if gathered:
-        ctx = inp['mres'] & ~gen
+        ctx = inp['mres'] & ~inp['gen']
         assert not torch.equal(got[0]['net']['c'][ctx], ref[0]['net']['c'][ctx])      # the comparisons above prove nothing if the plan refused
 
 
@@ -164,12 +83,13 @@ def reference():
     return {}
 
 
+def _run(d, inp, compact, nsteps, terms, replays=0):
+    """compact: with the row list, else the masked form"""
+    return run(d, inp, nsteps, terms, replays, context_outputs_unused=True, query_rows=True if compact else None)
+
+
 def _ref(reference, d, shape, mask, terms, nsteps):
-    key = (shape, mask, terms, nsteps)
-    if key not in reference:
-        inp = _inputs(shape, mask)
-        reference[key] = (inp,) + _run(d, inp, False, nsteps, terms)
-    return reference[key]
+    return cached_reference(reference, _inputs, d, shape, mask, terms, nsteps, context_outputs_unused=True)
 
 
 @pytest.mark.parametrize('terms', [True, False], ids=['pair_terms', 'fp32_stream'])

@@ -1,30 +1,19 @@
 """When a denoising step's tail runs as one launch (ab_opt_amd/csrc/forward_plan.h: NetPlan::step_fused / mixer_launch / step_carry behind abopt_eps_net_step), without a
 device: tests/step_plan_table.cpp, a host-only program, tabulates the fields over the switch, the packed mixer / heads operands, the prmsd head, a perplexity request
 and the carry flags; the rule is checked on every line, and the bench shape (fused) and an AbDock call (not fused) are pinned."""
-import os
-import shutil
-import subprocess
 from collections import namedtuple
 
 import pytest
 
-from conftest import ROOT
+from plan_tables import build_table
 
 Query = namedtuple('Query', 'fuse_step fuse_heads x_terms mix heads prmsd ppl step carry_in carry_out')
 Plan = namedtuple('Plan', 'step_fused mixer_launch step_carry mixer_kernel mixer_xt heads_kernel heads_epilogue')
 
 
 @pytest.fixture(scope='module')
-def table(tmp_path_factory):
-    cxx = next((c for c in ('/opt/rocm/lib/llvm/bin/clang++', shutil.which('g++'), shutil.which('clang++')) if c and os.path.exists(c)), None)
-    assert cxx, 'no host C++ compiler (clang++ of the ROCm LLVM directory, g++)'
-    exe = str(tmp_path_factory.mktemp('step_plan') / 'step_plan_table')
-    subprocess.run([cxx, '-std=c++17', '-O1', '-Wall', '-Werror', os.path.join(ROOT, 'tests', 'step_plan_table.cpp'), '-o', exe], check=True)
-    rows = {}
-    for line in subprocess.run([exe], check=True, capture_output=True, text=True).stdout.splitlines():
-        q, p = line.split(' | ')
-        rows[Query(*map(int, q.split()))] = Plan(*map(int, p.split()))
-    return rows
+def table():
+    return dict(build_table('step_plan_table', lambda *f: (Query(*f[:len(Query._fields)]), Plan(*f[len(Query._fields):]))))
 
 
 def test_grid_is_complete(table):

@@ -1,5 +1,5 @@
 """The last IPA block of a sampling step on generated query rows only (csrc/forward_plan.h: query_rows_masked; csrc/ipa_core.hip: ipa_core32_kernel<true, *, false, true>;
-include/abopt.h: abopt_eps_net_step_rows).  With the caller's word that it reads the network's outputs on generated residues only, the last
+include/abopt.h: abopt_eps_net_step, context_outputs_unused).  With the caller's word that it reads the network's outputs on generated residues only, the last
 block's pair waves send the z / term and bias requests of every other query row through a descriptor of zero records: zeros come back, nothing is fetched.  What the
 step hands on -- v_next, p_next, s_next, the posterior, p_next_norm -- and the network's outputs on generated rows are torch.equal to the same call without the word;
 the network's outputs on the other rows are finite and the range guard stays down.  ABOPT_CORE32=1 so that the small shapes take the 32-row kernels; that these shapes
@@ -7,30 +7,20 @@ do mask on a 256-CU device is pinned without a device in tests/test_forward_plan
 import pytest
 import torch
 
-from ab_opt_amd import hip
-from ab_opt_amd.dpm import FullDPM, _LoopSpec
 from ab_opt_amd.utils import synth
+from step_harness import DEV, T, cached_reference, check as _check, core32_env, model, run
 
 pytestmark = pytest.mark.gpu
-
-DEV = torch.device('cuda:0')
-T = 3
-NET = ('v_next', 'R_next', 'eps_pos', 'c')
-OUT = ('v', 'p', 's', 'p_norm')
 
 
 @pytest.fixture(scope='module')
 def design():
-    m = FullDPM(128, 64, num_steps=T, eps_net_opt=dict(num_layers=3), _abdesign=True).eval()
-    return synth.fill_module_(m, seed=5).to(DEV)
+    return model()
 
 
 @pytest.fixture(autouse=True)
 def core32(monkeypatch):
-    monkeypatch.setenv('ABOPT_CORE32', '1')
-    monkeypatch.setenv('ABOPT_CORE_NO_SPLIT', '1')
-    monkeypatch.delenv('ABOPT_STEP_ROWS', raising=False)
-    monkeypatch.delenv('ABOPT_PAIR_TERMS', raising=False)
+    core32_env(monkeypatch)
 
 
 # N, L, lengths, samples per shared pair_feat entry (0: distinct)
@@ -73,88 +63,18 @@ def _inputs(shape, mask, salt=1200):
     return dict(N=N, L=L, group=group, v=v, p=p * 10.0, s=s, res_feat=res_feat, pair_feat=pair_feat, gen=gen, mres=mres)
 
 
-def _steps(d, inp, unused, nsteps, terms, pbc, pterms):
-    """nsteps calls of the step entry from t = T down, the mixer carried from call to call; every call has network and output buffers of its own"""
-    N, L = inp['N'], inp['L']
-    f32 = dict(dtype=torch.float32, device=DEV)
-    ew = d.eps_net.packed()
-    X, cdf = d._loop_tables(d._loop_steps(_LoopSpec(T)))
-    v, p, s = inp['v'], inp['p'], inp['s']
-    p_norm = ((p - d.position_mean) / d.position_scale).contiguous()
-    res = []
-    for j in range(nsteps):
-        t = T - j
-        net = dict(v_next=torch.empty(N, L, 3, **f32), R_next=torch.empty(N, L, 3, 3, **f32), eps_pos=torch.empty(N, L, 3, **f32), c=torch.empty(N, L, 20, **f32),
-                   prmsd_logits=None)
-        out = dict(v=torch.empty(N, L, 3, **f32), p=torch.empty(N, L, 3, **f32), s=torch.empty(N, L, dtype=torch.int64, device=DEV), p_norm=torch.empty(N, L, 3, **f32))
-        beta = d.trans_pos.var_sched.betas[t].expand(N).contiguous()
-        post = hip.eps_net_step(ew, v, p_norm, s, inp['res_feat'], inp['pair_feat'], beta, inp['gen'], inp['mres'], d.num_bins, net,
-                                d._step_params(t, True, True, True, False, t - 1), None, 11, 4096, p, X[j], cdf[j], out, pair_bias_cache=pbc,
-                                pair_feat_shared=inp['group'], pair_terms=pterms if terms else None, want_post=True, carry_in=j > 0, carry_out=j + 1 < nsteps,
-                                context_outputs_unused=unused)
-        res.append(dict(net=net, out=out, post=post))
-        v, p, s, p_norm = out['v'], out['p'], out['s'], out['p_norm']
-    return res
-
-
-def _run(d, inp, unused, nsteps, terms, replays=0):
-    """eagerly (replays = 0), or captured once and replayed `replays` times: the results of the last replay"""
-    pf = inp['pair_feat']
-    pbc = hip.pair_bias_cache(d.eps_net.encoder.packed_array(), len(d.eps_net.encoder.blocks), pf)
-    pterms = hip.pair_terms(pf)
-    hip.nonfinite_flag(reset=True)
-    if not replays:
-        res = _steps(d, inp, unused, nsteps, terms, pbc, pterms)
-    else:
-        hip.prof_enable(False)
-        _steps(d, inp, unused, 1, terms, pbc, pterms)                       # warm: kernel attributes, host-side caches
-        torch.cuda.synchronize()
-        before = set(hip.Workspace._bufs)
-        g = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(g):
-            res = _steps(d, inp, unused, nsteps, terms, pbc, pterms)
-        keep = [hip.Workspace._bufs.pop(k) for k in set(hip.Workspace._bufs) - before]       # the slab the capture allocated lives in the graph's pool
-        for _ in range(replays):
-            for r in res:
-                for a in list(r['net'].values()) + list(r['out'].values()) + [r['post']]:
-                    if a is not None:
-                        a.fill_(7)                                            # a replay that wrote nothing would be seen
-            g.replay()
-        torch.cuda.synchronize()
-        clone = lambda d_: {k: (a.clone() if a is not None else None) for k, a in d_.items()}
-        res = [dict(net=clone(r['net']), out=clone(r['out']), post=r['post'].clone()) for r in res]      # own storage: the buffers are the graph's static ones
-        del keep, g
-    torch.cuda.synchronize()
-    flag = hip.nonfinite_flag(reset=True)
-    return res, flag
-
-
-def _check(got, flag_got, ref, flag_ref, gen, everything):
-    assert not flag_ref and not flag_got                                    # abopt_nonfinite_flag reads 0
-    assert len(got) == len(ref)
-    for a, b in zip(got, ref):
-        for k in OUT:
-            assert torch.equal(a['out'][k], b['out'][k]), (k, int((a['out'][k] != b['out'][k]).sum()))
-        assert torch.equal(a['post'], b['post'])
-        for k in NET:
-            assert torch.isfinite(a['net'][k]).all() and torch.isfinite(b['net'][k]).all(), k
-            assert torch.equal(a['net'][k][gen], b['net'][k][gen]), (k, int((a['net'][k][gen] != b['net'][k][gen]).sum()))
-            if everything:
-                assert torch.equal(a['net'][k], b['net'][k]), k
-
-
 @pytest.fixture(scope='module')
 def reference():
     """flag off, computed once per (shape, mask, terms, steps) and shared"""
     return {}
 
 
+def _run(d, inp, unused, nsteps, terms, replays=0):
+    return run(d, inp, nsteps, terms, replays, context_outputs_unused=unused)
+
+
 def _ref(reference, d, shape, mask, terms, nsteps):
-    key = (shape, mask, terms, nsteps)
-    if key not in reference:
-        inp = _inputs(shape, mask)
-        reference[key] = (inp,) + _run(d, inp, False, nsteps, terms)
-    return reference[key]
+    return cached_reference(reference, _inputs, d, shape, mask, terms, nsteps, context_outputs_unused=False)
 
 
 @pytest.mark.parametrize('terms', [True, False], ids=['pair_terms', 'fp32_stream'])
