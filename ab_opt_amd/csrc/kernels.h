@@ -168,4 +168,9 @@ size_t lddt_ws_bytes(int G, int S, int L);
 int launch_lddt(const float* pos, const uint8_t* mask, int mask_shared, const float* ref_pos, const uint8_t* ref_mask, const uint8_t* rows,
                 const int32_t* group, int G, int S, int L, int A, float cutoff, int32_t* num, int32_t* den, void* ws, hipStream_t st);
 
+// sasa.hip ------------------------------------------------------------------------------------
+// Shrake-Rupley surface counts and areas (include/abopt.h: abopt_sasa_grouped, defined in sasa.hip with its checks).  The workspace: one bounding sphere
+// (float4) per residue of every candidate, 16-byte aligned.
+size_t sasa_ws_bytes(int G, int S, int L, int A);
+
 }  // namespace abopt

@@ -13,7 +13,7 @@ import torch
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # ABOPT_LIB_PATH: developer override to load a variant build of the same ABI (csrc/Makefile VARIANT=...: A/B of two source trees)
 LIB_PATH = os.environ.get('ABOPT_LIB_PATH') or os.path.join(_HERE, 'libabopt_hip.so')
-ABI_VERSION = 53
+ABI_VERSION = 54
 
 c_f = C.c_void_p        # device float*
 c_i64 = C.c_void_p      # device int64*
@@ -168,6 +168,8 @@ _SIGNATURES = {
     'abopt_lddt_ws_bytes': (c_size_t, [c_int, c_int, c_int]),
     'abopt_lddt_ca_grouped': (c_int, [c_f, c_u8, c_int, c_f, c_u8, c_u8, c_i32] + [c_int] * 4 + [c_float, c_void_p, c_void_p, c_void_p, c_size_t, c_stream]),
     'abopt_lddt_ca_ensemble': (c_int, [c_f, c_u8, c_int, c_u8, c_i32] + [c_int] * 4 + [c_float, c_void_p, c_void_p, c_void_p, c_size_t, c_stream]),
+    'abopt_sasa_ws_bytes': (c_size_t, [c_int] * 4),
+    'abopt_sasa_grouped': (c_int, [c_f, c_u8, c_int, c_i32, c_f, c_f] + [c_int] * 5 + [c_float] * 2 + [c_void_p] * 3 + [c_size_t, c_stream]),
     'abopt_prof_enable': (c_int, [c_int]),
     'abopt_prof_spans_reset': (c_int, [c_stream]),
     'abopt_prof_spans': (c_int, [POINTER(c_int), POINTER(c_double)]),
@@ -800,6 +802,78 @@ def interface_geometry_grouped(pos, mask, group, clash_cutoff=3.0, contact_cutof
     if want_freq:
         res['freq'] = freq
     return res
+
+
+def check_probe_radius(name, v):
+    """float(v), or ValueError for a negative or non-finite one (the check abopt_sasa_grouped makes on its probe radius, ahead of any device work)."""
+    import math
+    c = float(v)
+    if not math.isfinite(c) or c < 0.0:
+        raise ValueError(f'{name} must be finite and >= 0 (got {v!r})')
+    return c
+
+
+_SPHERE_POINTS = {}
+
+
+def sphere_points(n, device='cpu'):
+    """n unit vectors spread over the sphere by the golden-section spiral: z_k = 1 - (2 k + 1) / n, rho = sqrt(1 - z^2), phi = k pi (3 - sqrt 5),
+    (rho cos phi, rho sin phi, z) -- computed in float64 on the host and rounded to fp32 once.  -> (n, 3) fp32 on `device`, cached per (n, device): treat it as
+    read-only."""
+    import math
+    n = int(n)
+    if not 1 <= n <= 1024:
+        raise ValueError(f'sphere_points: n={n} test points, expected 1 .. 1024')
+    key = (n, str(torch.device(device)))
+    if key not in _SPHERE_POINTS:
+        k = torch.arange(n, dtype=torch.float64)
+        z = 1.0 - (2.0 * k + 1.0) / n
+        rho = torch.sqrt(1.0 - z * z)
+        phi = k * (math.pi * (3.0 - math.sqrt(5.0)))
+        _SPHERE_POINTS[key] = torch.stack([rho * torch.cos(phi), rho * torch.sin(phi), z], 1).float().to(device)
+    return _SPHERE_POINTS[key]
+
+
+def sasa_grouped(pos, mask, group, radius, probe=1.4, points=128):
+    """Shrake-Rupley surface of G*S candidates in G groups, free and in the complex (include/abopt.h: abopt_sasa_grouped).
+    pos (G*S,L,A,3); mask (G*S,L,A), or (G,L,A) shared by the S candidates of a group; group (G,L) int: 1 and 2 name the two sides, anything else takes no part
+    (neither scored nor an occluder); radius (G,L,A), or (L,A) or (A,) broadcast to it: the van der Waals radius per atom slot in Angstrom, 0 (or NaN, or > 16) =
+    the slot takes no part; probe in Angstrom; points: test points per atom (`sphere_points`), 1 .. 1024.
+    -> dict of device tensors: pts (G*S,4) int32 (free-exposed points of side 1, of side 2, complex-exposed points of side 1, of side 2) and area (G*S,L,2) fp32
+    (free and complex exposed area per residue; their difference is the buried area).  Stream-ordered, no host synchronisation, capturable in a torch.cuda.graph."""
+    import math
+    if group.dim() != 2 or pos.dim() != 4 or mask.dim() != 3:
+        raise ValueError(f'sasa_grouped: expected pos (G*S, L, A, 3), mask (G*S or G, L, A) and group (G, L), got {tuple(pos.shape)}, '
+                         f'{tuple(mask.shape)} and {tuple(group.shape)}')
+    G, L = group.shape
+    N, A = pos.shape[0], pos.shape[2]
+    if L < 1 or tuple(pos.shape[1:]) != (L, A, 3) or (N % G if G else N):
+        raise ValueError(f'sasa_grouped: {tuple(pos.shape)} candidates are not whole groups of the {G} rows of group {tuple(group.shape)}')
+    if not 1 <= A <= 15:
+        raise ValueError(f'sasa_grouped: A={A} atoms per residue, expected 1 .. 15')
+    S = N // G if G else 0
+    shared = mask.shape[0] != N or S == 1
+    if tuple(mask.shape) != ((G if shared else N), L, A):
+        raise ValueError(f'sasa_grouped: mask {tuple(mask.shape)} is neither per candidate nor per group')
+    if tuple(radius.shape) not in ((G, L, A), (L, A), (A,)):
+        raise ValueError(f'sasa_grouped: radius {tuple(radius.shape)} must be (G, L, A) = {(G, L, A)}, (L, A) or (A,)')
+    n = int(points)
+    if not 1 <= n <= 1024:
+        raise ValueError(f'sasa_grouped: points={points!r} test points per atom, expected 1 .. 1024')
+    probe = check_probe_radius('sasa_grouped: probe', probe)
+    ptr(pos, strided=True)                                          # a CPU tensor is refused here, before anything is allocated
+    pos, mask = _contig(pos.float(), mask if mask.dtype in (torch.bool, torch.uint8) else mask.bool())
+    dev = pos.device
+    group = group.to(torch.int32).contiguous()
+    radius = radius.to(device=dev, dtype=torch.float32).expand(G, L, A).contiguous()
+    dirs = sphere_points(n, dev)
+    k = float(torch.tensor(4.0 * math.pi / n, dtype=torch.float64).float())       # float32(4 pi / n) from float64
+    pts = (torch.empty if N else torch.zeros)(N, 4, dtype=torch.int32, device=dev)         # an empty call launches nothing
+    area = (torch.empty if N else torch.zeros)(N, L, 2, dtype=torch.float32, device=dev)
+    buf = Workspace.get(max(16, lib().abopt_sasa_ws_bytes(G, S, L, A)), dev)
+    _check(lib().abopt_sasa_grouped(ptr(pos, torch.float32), ptr(mask), int(shared), ptr(group, torch.int32), ptr(radius, torch.float32), ptr(dirs, torch.float32),
+                                    n, G, S, L, A, probe, k, ptr(pts), ptr(area), ptr(buf), buf.numel(), stream()))
+    return dict(pts=pts, area=area)
 
 
 def check_lddt_cutoff(name, v):

@@ -154,6 +154,52 @@ def interface_geometry(batch, pos, mask, groups='chains', **cutoffs):
     return hip.interface_geometry_grouped(pos, mask, grp, link=link, **cutoffs)
 
 
+BONDI_RADII = (1.55, 1.70, 1.70, 1.52, 1.70)                    # N, CA, C, O, CB (Bondi 1964: N 1.55, C 1.70, O 1.52 Angstrom)
+
+
+def slot_radii(A, atoms=5):
+    """The default van der Waals radius of each of the A atom slots of a residue, in Angstrom -> (A,) fp32 on the CPU: slots 0-4 are N, CA, C, O, CB with Bondi
+    radii 1.55, 1.70, 1.70, 1.52, 1.70; slots >= `atoms` (at most 5) get 0 and so take no part in `buried_surface`.  A rebuilt residue has backbone + CB only
+    (geometry.reconstruct_backbone_partially) and the package holds no per-type side-chain atom table, so by default EVERY residue is scored on those five slots:
+    a coarse-grained area, comparable between candidates of one complex, not an all-atom SASA.  A caller with a full-atom radius table passes radius= instead."""
+    A, atoms = int(A), int(atoms)
+    if A < 1 or not 0 <= atoms <= len(BONDI_RADII):
+        raise ValueError(f'slot_radii: need A >= 1 and 0 <= atoms <= {len(BONDI_RADII)} (got A={A}, atoms={atoms})')
+    r = torch.zeros(A, dtype=torch.float32)
+    n = min(A, atoms)
+    r[:n] = torch.tensor(BONDI_RADII[:n], dtype=torch.float32)
+    return r
+
+
+def buried_surface(batch, pos, mask, groups='chains', probe=1.4, points=128, radius=None):
+    """Buried solvent-accessible surface area (Shrake-Rupley) of candidate structures of the complexes of `batch` (hip.sasa_grouped).
+    batch, pos, mask and groups ('chains': antibody against antigen; 'generated': the generated residues against every other real residue) as for
+    `interface_geometry`; probe in Angstrom, points = test points per atom; radius (optional; (A,), (L, A) or (G, L, A)): the van der Waals radius per atom slot,
+    default `slot_radii(A)` -- five backbone + CB slots for every residue, see there.
+    -> dict of device tensors, N = G*S: sasa_res (N, L) fp32, the exposed area of each residue in the complex; bsa_res (N, L) fp32 = its exposed area with the other
+    side taken away minus that, >= 0: the paratope and the epitope in A^2; bsa (N,) and sasa (N,) fp32, their sums over the residues (taken in float64, rounded
+    once) -- bsa is the buried area of BOTH sides together (some tools report half of it, the "interface area"); pts (N, 4) int32, the point counts of
+    hip.sasa_grouped.  No host synchronisation."""
+    from . import hip, screen
+    ft = batch['fragment_type']
+    if groups == 'chains':
+        grp = screen.chain_groups(ft)
+    elif groups == 'generated':
+        grp = torch.where(batch['generate_flag'].bool(), 1, torch.where(ft > 0, 2, 0))
+    else:
+        raise ValueError(f"buried_surface: groups must be 'chains' or 'generated', not {groups!r}")
+    if radius is None:
+        radius = slot_radii(pos.shape[2] if pos.dim() == 4 else 1)
+    return surface_summary(hip.sasa_grouped(pos, mask, grp, radius, probe=probe, points=points))
+
+
+def surface_summary(sa):
+    """pts / area of hip.sasa_grouped -> the dict `buried_surface` returns.  Pure torch, no host read."""
+    free, cplx = sa['area'][..., 0], sa['area'][..., 1]
+    bsa_res = free - cplx                                                              # free >= complex per atom, so per residue, in the same order of summation
+    return dict(sasa_res=cplx, bsa_res=bsa_res, bsa=bsa_res.sum(-1, dtype=torch.float64).float(), sasa=cplx.sum(-1, dtype=torch.float64).float(), pts=sa['pts'])
+
+
 def _lddt_group(name, fragment_type, interface, G):
     """group (G, L) of the interface form from fragment_type (G, L) or (L,) (screen.chain_groups), or None."""
     from . import screen

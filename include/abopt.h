@@ -23,7 +23,7 @@
 extern "C" {
 #endif
 
-#define ABOPT_ABI_VERSION 53
+#define ABOPT_ABI_VERSION 54
 
 enum { ABOPT_OK = 0, ABOPT_EINVAL = 1, ABOPT_EHIP = 2, ABOPT_EUNSUPPORTED = 3, ABOPT_EWORKSPACE = 4 };
 
@@ -733,6 +733,35 @@ int abopt_lddt_ca_grouped(const float* pos, const uint8_t* mask, int mask_shared
                           abopt_stream stream);
 int abopt_lddt_ca_ensemble(const float* pos, const uint8_t* mask, int mask_shared, const uint8_t* rows, const int32_t* group, int G, int S, int L, int A,
                            float cutoff, void* num, void* den, void* ws, size_t ws_bytes, abopt_stream stream);
+
+/* ---- Buried surface area (ABI 54): the solvent-accessible surface of each side of a docked candidate, alone and in the complex (Shrake-Rupley), per residue:
+ * how much surface a pose buries, and on which residues -- the paratope and the epitope in A^2, where the contacts above count touches.  Nothing in the
+ * reference is matched (its interface energy and dSASA came from its relax stage); the definition is this library's own.  G groups of S
+ * candidates, conventions of abopt_interface_geometry_grouped:
+ *   pos [G*S,L,A,3] fp32; mask [G*S,L,A], or [G,L,A] shared by the S candidates of a group (mask_shared != 0); group [G,L] int32: 1 and 2 name the two sides,
+ *   any other value takes no part -- it is neither scored nor an occluder; radius [G,L,A] fp32, the van der Waals radius per atom slot in Angstrom;
+ *   dirs [n_points,3] fp32 unit vectors, supplied by the caller, 1 <= n_points <= 1024; probe fp32, finite and >= 0; k fp32, the caller's rounding of 4 pi / n_points.
+ *   taking part an atom takes part iff its mask byte is set, its residue's group is 1 or 2, its three coordinates are finite, and 0 < r <= 16 (a NaN radius takes no
+ *               part).  An atom that takes no part has count 0 and occludes nothing.
+ *   arithmetic  every step is rounded once, in fp32: __fadd_rn / __fsub_rn / __fmul_rn only, no fmaf, so that numpy float32 reproduces it bit for bit.
+ *               For atom i with centre c and radius r:  R_i = r_i + probe;  T_i = R_i R_i;  test point p of atom i: q = c_i + R_i u_p per coordinate (one multiply,
+ *               one add);  for an occluder j != i of the same candidate, in the same residue or any other: dx = q_x - c_jx (dy, dz likewise),
+ *               d2 = (dx dx + dy dy) + dz dz in exactly this association;  point p is HIDDEN BY j iff d2 < T_j (strict).
+ *   verdicts    own: the point is hidden by some participating atom of i's own side; other: by some participating atom of the other side.  The point is
+ *               free-exposed iff not own, complex-exposed iff neither own nor other.  Every comparison is a pure function of the inputs: no pruning, tile order or
+ *               early exit changes a verdict.
+ *   pts [G*S,4] int32 (DEVICE, spelled void*): free-exposed points of side 1, of side 2, complex-exposed points of side 1, of side 2.
+ *   area [G*S,L,2] fp32 (DEVICE, spelled void*): the free and the complex exposed area of each residue.  acc starts at 0.0f; for the participating atoms
+ *               a = 0 .. A - 1 in ascending order acc = acc + float(count_a) (k T_a): the inner product is rounded first, then the product with the count, then the
+ *               sum (an atom that takes no part is passed over: it would add 0).  A residue that takes no part gets 0, 0.  Free >= complex per atom by construction.
+ *   ws: abopt_sasa_ws_bytes(G, S, L, A) bytes, 16-byte aligned (one bounding sphere per residue of every candidate; 0 for an empty call).
+ * Stream-ordered (two launches in one chain, outputs cleared by a kernel, no memset node: capturable into a hipGraph), nothing allocated, no host synchronisation.
+ * L >= 1, 1 <= A <= 15, G S <= 2^31 - 1, G <= 65535, G = 0 or S = 0 is a no-op; every check precedes the first launch (ABOPT_EINVAL; a workspace that is too
+ * small: ABOPT_EWORKSPACE).  Occluder residues are pruned by bounding spheres; the prune is conservative in fp32 (it measures the caller's directions itself)
+ * and never changes a verdict.  Only the four integer counters of pts are accumulated with atomics; a group's result is that of a call on the group alone. */
+size_t abopt_sasa_ws_bytes(int G, int S, int L, int A);
+int abopt_sasa_grouped(const float* pos, const uint8_t* mask, int mask_shared, const int32_t* group, const float* radius, const float* dirs, int n_points,
+                       int G, int S, int L, int A, float probe, float k, void* pts, void* area, void* ws, size_t ws_bytes, abopt_stream stream);
 
 /* ---- Measurement hook (bench.py's roofline leg).  When enabled, every launch of the IPA-core kernel is bracketed
  * by hipEvents on the stream it is launched on; abopt_prof_collect synchronises those events and returns the number
