@@ -330,6 +330,11 @@ int abopt::check_step_args(const abopt_step_params* sp, const abopt_step_noise* 
     ABOPT_CHECK_ARG(sp, "denoise_step: NULL argument");
     ABOPT_CHECK_ARG(igso3_X && igso3_bins >= 2, "denoise_step: IGSO(3) histogram row missing");
     ABOPT_CHECK_ARG(sp->t_prev >= 0 && sp->t_prev < sp->t, "denoise_step: the step must land below where it starts (t=%d t_prev=%d)", sp->t, sp->t_prev);
+    if (sp->tempered) {         // (the comparisons refuse a NaN too)
+        ABOPT_CHECK_ARG(sp->seq_temperature >= 0.f && sp->seq_temperature < INFINITY && (sp->seq_temperature == 0.f || sp->seq_temperature >= 1e-3f),
+                        "denoise_step: seq_temperature must be 0 or a finite value >= 1e-3 (got %g)", (double)sp->seq_temperature);
+        ABOPT_CHECK_ARG(sp->noise_scale >= 0.f && sp->noise_scale < INFINITY, "denoise_step: noise_scale must be finite and >= 0 (got %g)", (double)sp->noise_scale);
+    }
     *nz = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
     if (noise && noise->axis) {
         ABOPT_CHECK_ARG(noise->bin && noise->ubin && noise->gauss && noise->z && noise->s_next, "denoise_step: injected noise must provide all six draws");

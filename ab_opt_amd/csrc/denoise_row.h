@@ -7,6 +7,10 @@
 // Allowed residue types (include/abopt.h: aa_allowed): one int32 word per residue, bit k = type k may be drawn, read on generated residues only.  A disallowed
 // class leaves the categorical BEFORE it is normalised (its unnormalised product becomes 0), so post_out, the draw and the perplexity term all see the distribution
 // that is sampled; with every bit set each operation below is the unconstrained one on the same values in the same order.
+//
+// Sampling at a temperature (include/abopt.h: abopt_step_params.tempered): behind the wave-uniform sp.tempered the rotation noise angle and the
+// position noise's sigma are multiplied by sp.noise_scale and the row's prediction is tempered before the posterior is formed; with the flag clear every function below
+// is the code of the earlier ABIs.
 #pragma once
 #include "abopt_common.h"
 #include "kernels.h"
@@ -75,7 +79,8 @@ __device__ __forceinline__ void denoise_rot_noise(const RowDraws& d, const abopt
     const float nrm = fmaxf(sqrtf(ax * ax + ay * ay + az * az), 1e-12f);
     const float hist = igX[d.bin] + d.ubin * (igX[d.bin + 1] - igX[d.bin]);
     const float gau = fmodf(fabsf(fmaf(d.gss, sp.igso3_std, sp.igso3_std * 2.f)), PI_F);      // std 2 + gss std: the doubling is exact, the one rounding is the fma's
-    const float th = sp.igso3_gaussian ? gau : hist;
+    float th = sp.igso3_gaussian ? gau : hist;
+    if (sp.tempered) th = rounded_mul(th, sp.noise_scale);       // the angle at the noise scale lambda (include/abopt.h: noise_scale); x 1 is exact
     ex = ax / nrm * th; ey = ay / nrm * th; ez = az / nrm * th;
     if (!(sp.t_prev > 0)) { ex = 0.f; ey = 0.f; ez = 0.f; }       // no noise on the step that lands on 0 (the reference's t > 1: t_prev = t - 1 there)
 }
@@ -93,6 +98,7 @@ __device__ __forceinline__ void denoise_rotation(float ex, float ey, float ez, c
 __device__ __forceinline__ void denoise_position(const abopt_step_params& sp, const float* pa, const float* pnet_row, const float* zn, bool gen, float* pn, float* pt) {
     const float c0 = 1.0f / sqrtf(sp.alpha_clamped + 1e-8f);
     const float c1 = (1.f - sp.alpha_clamped) / sqrtf(1.f - sp.alpha_bar + 1e-8f);
+    const float sigma = sp.tempered ? rounded_mul(sp.sigma, sp.noise_scale) : sp.sigma;       // sigma_eff = sigma lambda, rounded once (include/abopt.h: noise_scale)
 #pragma unroll
     for (int k = 0; k < 3; ++k) {
         pt[k] = (pa[k] - sp.position_mean[k]) / sp.position_scale;
@@ -102,7 +108,7 @@ __device__ __forceinline__ void denoise_position(const abopt_step_params& sp, co
         const float zk = (sp.t_prev > 0) ? zn[k] : 0.f;
         // c0 (pt - c1 eps) + sigma z with the product that is rounded and the one that is fused spelled out: left to the compiler, the choice between the two
         // contractions follows the operand order its passes leave, which differs between the kernels this function is inlined into
-        const float nx = fmaf(sp.sigma, zk, rounded_mul(c0, pt[k] - c1 * eps));
+        const float nx = fmaf(sigma, zk, rounded_mul(c0, pt[k] - c1 * eps));
         pn[k] = gen ? nx : pt[k];
     }
 }
@@ -117,22 +123,58 @@ __device__ __forceinline__ void denoise_store_position(int64_t i, const abopt_st
     }
 }
 
+// ---- the row's prediction at the temperature tau = sp.seq_temperature (include/abopt.h: seq_temperature) into cp[0..19]: cn itself where the row does not draw, tau is 1
+// or there is nothing to sharpen.  Every product is rounded where it stands and every c'_k is the result of a division: nothing contracts into what follows.
+__device__ __forceinline__ void denoise_temper(const abopt_step_params& sp, const float* cn, uint32_t allow, bool draws, float* cp) {
+    const float tau = sp.seq_temperature;
+    float m = 0.f;                                  // max over the allowed classes of max(c_k, 0): fmaxf drops a NaN
+#pragma unroll
+    for (int k = 0; k < KAA; ++k) m = ((allow >> k) & 1u) ? fmaxf(m, cn[k]) : m;
+    const bool temper = draws && tau != 1.f && m > 0.f && m < INFINITY;
+    const bool greedy = tau == 0.f;
+    const float lm = log2f(m), rtau = 1.f / tau;
+    float esum = 0.f;
+    bool found = false;
+#pragma unroll
+    for (int k = 0; k < KAA; ++k) {
+        const bool ok = ((allow >> k) & 1u) != 0u;
+        const float ck = fmaxf(cn[k], 0.f);
+        const bool first = ok && !found && ck == m;                                             // tau = 0: all mass on the lowest-index maximum
+        found = found || first;
+        const float e = greedy ? (first ? 1.f : 0.f) : (ok ? exp2f(rounded_mul(log2f(ck) - lm, rtau)) : 0.f);
+        cp[k] = e;
+        esum += e;
+    }
+#pragma unroll
+    for (int k = 0; k < KAA; ++k) cp[k] = temper ? cp[k] / esum : cn[k];
+}
+
+// the unnormalised posterior of a row from its prediction c (cn, or the tempered one: c may be post itself), disallowed classes zeroed; returns the sum
+__device__ __forceinline__ float denoise_posterior_raw(float ab, float unif, bool st_ok, int64_t st, const float* c, uint32_t allow, float* post) {
+    float tot = 0.f;
+#pragma unroll
+    for (int k = 0; k < KAA; ++k) {
+        const float ct = (st_ok && st == k) ? 1.f : 0.f;
+        const float raw = ((ab * ct) + unif) * ((ab * c[k]) + unif);
+        const bool ok = ((allow >> k) & 1u) != 0u;
+        tot = ok ? tot + raw : tot;                 // `tot + raw` as the unconstrained code spells it: the compiler contracts it to the same fma
+        post[k] = ok ? raw : 0.f;
+    }
+    return tot;
+}
+
 // ---- sequence (transition.py:202-245): NOTE alpha_bar_t multiplies both factors (reference quirk).  cn: the row's 20 values of c_net.  Leaves the posterior in post
 // (and post_out) and its maximum in pmax; returns what s_next takes
 __device__ __forceinline__ int64_t denoise_sequence(int64_t i, const abopt_step_params& sp, const abopt_step_noise& nz, bool injected, float useq, int64_t st, const float* cn,
                                                     uint32_t allow, bool gen, float* post_out, float* post, float& pmax) {
     const bool st_ok = st >= 0 && st < KAA;
     const bool draws = gen && allow != 0u;          // an empty set: the type is frozen, its posterior is onehot(s_t) like a context residue's (the structure above still moved)
-    float tot = 0.f;
+    float tot;
     const float ab = sp.alpha_bar, unif = (1.f - ab) / (float)KAA;
-#pragma unroll
-    for (int k = 0; k < KAA; ++k) {
-        const float ct = (st_ok && st == k) ? 1.f : 0.f;
-        const float raw = ((ab * ct) + unif) * ((ab * cn[k]) + unif);
-        const bool ok = ((allow >> k) & 1u) != 0u;
-        tot = ok ? tot + raw : tot;                 // `tot + raw` as the unconstrained code spells it: the compiler contracts it to the same fma
-        post[k] = ok ? raw : 0.f;
-    }
+    if (sp.tempered) {                              // wave-uniform: the untempered step runs the code below the else, as every earlier ABI
+        denoise_temper(sp, cn, allow, draws, post);
+        tot = denoise_posterior_raw(ab, unif, st_ok, st, post, allow, post);
+    } else tot = denoise_posterior_raw(ab, unif, st_ok, st, cn, allow, post);
     pmax = -INFINITY;
 #pragma unroll
     for (int k = 0; k < KAA; ++k) {

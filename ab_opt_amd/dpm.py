@@ -41,6 +41,8 @@ class _LoopSpec:
                                                 # a tuple: these (t_start first, strictly decreasing, >= 1)
     query_row_tiles: int = 0                    # 16-row tiles the generated rows of the loop's longest sample fill (FullDPM._denoise settles it from the masks, once
                                                 # per call); 0: the loop holds no row list (include/abopt.h: abopt_eps_net_step, query_row_tiles)
+    seq_temperature: float = 1.0                # tau: the temperature of the predicted residue-type distribution of every step (include/abopt.h: seq_temperature)
+    noise_scale: float = 1.0                    # lambda: the scale of the structure noise of every step; both 1: the steps carry tempered = 0
 
 
 def respaced_steps(t_start, steps=None, timesteps=None):
@@ -184,9 +186,10 @@ class FullDPM(_Derived, nn.Module):
         a = ab[t] / ab[t_prev]
         return a, math.sqrt((1.0 - ab[t_prev]) / (1.0 - ab[t]) * (1.0 - a))
 
-    def _step_params(self, t, sample_structure, sample_sequence, ppl_masked, optimize_mode=False, t_prev=None):
+    def _step_params(self, t, sample_structure, sample_sequence, ppl_masked, optimize_mode=False, t_prev=None, seq_temperature=1.0, noise_scale=1.0):
         """The scalars of the step t -> t_prev (None: t - 1).  A unit stride reads every one of them from the buffers, as the reference does; a longer one
-        computes alpha', sigma and the IGSO(3) width of the stride (_stride) and rounds them once to fp32 -- alpha_bar and the two pred_x0 factors stay those of t."""
+        computes alpha', sigma and the IGSO(3) width of the stride (_stride) and rounds them once to fp32 -- alpha_bar and the two pred_x0 factors stay those of t.
+        seq_temperature / noise_scale: the step is tempered only when one of them differs from 1, so the default step hands the kernels the bytes of every earlier ABI."""
         h = self._sched_host()
         u = t - 1 if t_prev is None else int(t_prev)
         sp = hip.StepParams()
@@ -209,6 +212,10 @@ class FullDPM(_Derived, nn.Module):
         sp.sample_structure, sp.sample_sequence = int(sample_structure), int(sample_sequence)
         sp.dist_min, sp.dist_max = float(self.dist_min), float(self.dist_max)
         sp.ppl_masked = int(ppl_masked)
+        if float(seq_temperature) != 1.0 or float(noise_scale) != 1.0:
+            sp.tempered = 1
+            sp.seq_temperature = hip.check_temperature('seq_temperature', seq_temperature)
+            sp.noise_scale = hip.check_noise_scale('noise_scale', noise_scale)
         return sp
 
     @staticmethod
@@ -378,7 +385,8 @@ class FullDPM(_Derived, nn.Module):
             # `net` never leaves this function and the transitions keep the old state on context residues: the library may leave it unspecified there
             # (context_outputs_unused; it does where the step's tail is fused, so never with the prmsd head and the perplexity of abdock)
             hip.eps_net_step(ew, tv[i], p_norm, ts[i], res_feat, pair_feat, beta_rows[t], mask_generate, mask_res, self.num_bins, net,
-                             self._step_params(t, spec.sample_structure, spec.sample_sequence, spec.ppl_masked, spec.optimize_mode, t_prev),
+                             self._step_params(t, spec.sample_structure, spec.sample_sequence, spec.ppl_masked, spec.optimize_mode, t_prev,
+                                               spec.seq_temperature, spec.noise_scale),
                              noise[t] if noise is not None else None, seed, rng_offset, tp[i], X[j], cdf[j] if noise is None else None, out,
                              pair_bias_cache=pbc, pair_feat_shared=(group if shared else 0), pair_terms=pterms, seed_dev=seed_dev, aa_allowed=aa_allowed,
                              carry_in=j > 0, carry_out=more, context_outputs_unused=True, query_rows=qrows)
@@ -408,28 +416,37 @@ class FullDPM(_Derived, nn.Module):
 
     @torch.no_grad()
     def sample(self, v, p, s, res_feat, pair_feat, mask_generate, mask_res, sample_structure=True, sample_sequence=True,
-               pbar=False, noise=None, seed=None, rng_offset=0, use_bias_cache=None, graph=None, aa_allowed=None, steps=None, timesteps=None, **kwargs):
+               pbar=False, noise=None, seed=None, rng_offset=0, use_bias_cache=None, graph=None, aa_allowed=None, steps=None, timesteps=None,
+               seq_temperature=1.0, noise_scale=1.0, **kwargs):
         """dpm_full.py:236-302.  `noise` (optional) = {'init': {q4,p,s}, t: {axis,bin,ubin,gauss,z,s_next}} replays
         recorded draws; otherwise a Philox stream seeded from torch's CPU generator is used.
         aa_allowed (optional; no reference counterpart): the residue types that may appear at each generated residue, (N, L) / (1, L) / (L,) int32 or int64 words with
         bit k = type k (model.aa_allowed_mask builds them).  The initial state and every step draw from the allowed types only, so a forbidden type never enters s_t.
         steps = K / timesteps = [...] (optional; no reference counterpart): denoise over a sub-sequence of the trained steps (respaced_steps) --
-        K network evaluations instead of num_steps; the trajectory holds the visited steps (and 0) only, and `noise` needs entries for those alone."""
+        K network evaluations instead of num_steps; the trajectory holds the visited steps (and 0) only, and `noise` needs entries for those alone.
+        seq_temperature = tau / noise_scale = lambda (optional; no reference counterpart): every step draws its residue types from the
+        posterior of the network's prediction at temperature tau (0: greedy; below 1 sharper, above 1 flatter) and adds lambda times the structure noise (0: a
+        deterministic structure update).  The initial state is not touched.  With both at 1 the loop is today's, bit for bit; the perplexity of a tau != 1 run
+        describes the tempered distribution and is not comparable with one at tau = 1."""
+        tau, lam = hip.check_temperature('seq_temperature', seq_temperature), hip.check_noise_scale('noise_scale', noise_scale)
         allowed = _checked_allowed(aa_allowed, mask_generate)
         visited = _spec_timesteps(self.num_steps, steps, timesteps)
         seed, h = self._begin(seed)
         state = hip.sample_init(v.float(), p.float(), s, mask_generate, noise['init'] if noise is not None else None, seed, rng_offset,
                                 h['scale'], h['mean'], sample_structure, sample_sequence, aa_allowed=allowed)
         spec = _LoopSpec(self.num_steps, None, bool(sample_structure), bool(sample_sequence), ppl_masked=True, use_bias_cache=use_bias_cache,
-                         constrained=allowed is not None, timesteps=visited)
+                         constrained=allowed is not None, timesteps=visited, seq_temperature=tau, noise_scale=lam)
         inputs = self._inputs(res_feat, pair_feat, mask_generate, mask_res, allowed)
         return self._to_traj(spec.t_start, *_range_guarded(lambda safe: self._denoise(spec, state, inputs, noise, seed, rng_offset, pbar, graph, safe)), timesteps=visited)
 
     @torch.no_grad()
     def optimize(self, v, p, s, opt_step, res_feat, pair_feat, mask_generate, mask_res, sample_structure=True,
-                 sample_sequence=True, pbar=False, noise=None, seed=None, rng_offset=0, use_bias_cache=None, graph=None, aa_allowed=None, steps=None, timesteps=None):
+                 sample_sequence=True, pbar=False, noise=None, seed=None, rng_offset=0, use_bias_cache=None, graph=None, aa_allowed=None, steps=None, timesteps=None,
+                 seq_temperature=1.0, noise_scale=1.0):
         """dpm_full.py:304-367: noise the input to step `opt_step`, then denoise.  aa_allowed: as in sample(); the forward noising draws from the allowed types too.
-        steps = K / timesteps: as in sample(), over [0, opt_step] (K <= opt_step)."""
+        steps = K / timesteps: as in sample(), over [0, opt_step] (K <= opt_step).  seq_temperature / noise_scale: as in sample(), on the denoising steps; the
+        forward noising to opt_step is not touched."""
+        tau, lam = hip.check_temperature('seq_temperature', seq_temperature), hip.check_noise_scale('noise_scale', noise_scale)
         allowed = _checked_allowed(aa_allowed, mask_generate)
         visited = _spec_timesteps(opt_step, steps, timesteps)
         seed, h = self._begin(seed)
@@ -444,7 +461,7 @@ class FullDPM(_Derived, nn.Module):
         # dpm_full.py:351-358: the loop feeds the net's third output to the position update as noise whatever `obj` is,
         # and averages the perplexity over all residues (calc_perplexity(logits) without a mask)
         spec = _LoopSpec(opt_step, None, bool(sample_structure), bool(sample_sequence), ppl_masked=False, optimize_mode=True, use_bias_cache=use_bias_cache,
-                         constrained=allowed is not None, timesteps=visited)
+                         constrained=allowed is not None, timesteps=visited, seq_temperature=tau, noise_scale=lam)
         inputs = self._inputs(res_feat, pair_feat, mask_generate, mask_res, allowed)
         # same counters as add_noise, other sub-sequence tags (csrc/denoise.hip): a sample's stream position does not depend on the batch it sits in
         traj = self._to_traj(opt_step, *_range_guarded(lambda safe: self._denoise(spec, state, inputs, noise, seed, rng_offset, pbar, graph, safe)), timesteps=visited)

@@ -13,7 +13,7 @@ import torch
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # ABOPT_LIB_PATH: developer override to load a variant build of the same ABI (csrc/Makefile VARIANT=...: A/B of two source trees)
 LIB_PATH = os.environ.get('ABOPT_LIB_PATH') or os.path.join(_HERE, 'libabopt_hip.so')
-ABI_VERSION = 54
+ABI_VERSION = 55
 
 c_f = C.c_void_p        # device float*
 c_i64 = C.c_void_p      # device int64*
@@ -65,7 +65,8 @@ class StepParams(C.Structure):
                 ('sqrt_recip_abar', C.c_float), ('sqrt_recipm1_abar', C.c_float), ('igso3_std', C.c_float),
                 ('igso3_gaussian', C.c_int), ('position_scale', C.c_float), ('position_mean', C.c_float * 3),
                 ('pred_x0', C.c_int), ('sample_structure', C.c_int), ('sample_sequence', C.c_int),
-                ('dist_min', C.c_float), ('dist_max', C.c_float), ('ppl_masked', C.c_int), ('t_prev', C.c_int)]
+                ('dist_min', C.c_float), ('dist_max', C.c_float), ('ppl_masked', C.c_int), ('t_prev', C.c_int),
+                ('tempered', C.c_int), ('seq_temperature', C.c_float), ('noise_scale', C.c_float)]
 
 
 class AddNoiseNoise(C.Structure):
@@ -529,6 +530,27 @@ def query_row_list(mask_generate):
     count = torch.empty(N, dtype=torch.int32, device=mask_generate.device)
     _check(lib().abopt_query_row_list(ptr(mask_generate, torch.bool), N, L, ptr(rows), ptr(count), stream()))
     return rows, count
+
+
+def check_temperature(name, tau):
+    """float(tau) of a sampling temperature (include/abopt.h: seq_temperature), or ValueError: it must be finite and >= 0, and a non-zero one below 1e-3 is refused
+    -- the kernel multiplies by 1 / tau in fp32; 0 is the greedy limit and has a path of its own.  No device is needed."""
+    import math
+    t = float(tau)
+    if not math.isfinite(t) or t < 0.0:
+        raise ValueError(f'{name} must be finite and >= 0 (got {tau!r})')
+    if 0.0 < t < 1e-3:
+        raise ValueError(f'{name} must be 0 (greedy) or at least 1e-3 (got {tau!r})')
+    return t
+
+
+def check_noise_scale(name, lam):
+    """float(lam) of a structure-noise scale (include/abopt.h: noise_scale), or ValueError for a negative or non-finite one.  No device is needed."""
+    import math
+    s = float(lam)
+    if not math.isfinite(s) or s < 0.0:
+        raise ValueError(f'{name} must be finite and >= 0 (got {lam!r})')
+    return s
 
 
 def _allowed_ptr(aa_allowed, mask_generate):

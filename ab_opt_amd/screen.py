@@ -140,7 +140,7 @@ def _scored_mean_std(t, dim):
 def optimize_antibody(dock_model, design_model, complex_, num_poses, designs_per_pose, redocks_per_design, design_flag=None, redock_flag=None,
                       contig='', screened_per_pose=1, seed=0, poses_per_launch=8, group=None, screen_by='first', timings=None, allowed_aa=None,
                       dock_steps=None, design_steps=None, cluster_cutoff=None, max_clusters=None, redock_cutoff=None, clash_cutoff=None, contact_cutoff=None,
-                      bond_max=None, seq_mismatch=None, share_redocks=False, lddt_cutoff=None):
+                      bond_max=None, seq_mismatch=None, share_redocks=False, lddt_cutoff=None, design_temperature=None, dock_noise_scale=None):
     """Dock -> redesign -> re-dock screen of one antibody-antigen complex (module docstring).
 
     complex_: batch dict with batch dim 1 (cropped, as sample_replicated takes it); its generate_flag marks the residues to dock.
@@ -154,6 +154,13 @@ def optimize_antibody(dock_model, design_model, complex_, num_poses, designs_per
     dock_steps / design_steps (optional; default: every trained step): the network evaluations of every dock and re-dock trajectory / of every design trajectory,
     over the evenly respaced sub-sequence of the model's steps (FullDPM.sample(steps=K)) -- the screen spends P + P S + P k D trajectories per
     antibody, and this trades their depth for breadth.  Sample quality against K is unmeasured.
+    design_temperature (optional, 0 or >= 1e-3; default None: nothing changes, bit for bit): the temperature of the design stage's residue
+    types (FullDPM.sample(seq_temperature=tau)) -- below 1 every design trajectory draws from a sharper distribution of the network's prediction, 0 takes its most
+    probable allowed type at every step: "confident, conservative designs" from the sampler instead of oversampling and keeping the designs of lowest PPL.  ppl is
+    then the perplexity of the tempered distribution: comparable between designs of one call, not with a call at another temperature.  allowed_aa holds as ever.
+    dock_noise_scale (optional, >= 0; default None: nothing changes, bit for bit): the scale of the structure noise of every dock and re-dock step
+    (FullDPM.sample(noise_scale=lambda)); below 1 the ensembles tighten, 0 leaves the initial draw as a trajectory's only randomness.  What either does to hit
+    rates is unmeasured.
     cluster_cutoff (optional, Angstrom; default None: every pose goes on, nothing below changes): cluster the P poses after stage 1 and run stages 2 and 3 on the
     C cluster centres only (module docstring); max_clusters (optional, >= 1; needs cluster_cutoff) caps C -- poses left over at the cap keep label -1 and
     are not screened.  The result gains cluster_label (P,), cluster_centre (C,) (pose indices) and cluster_size (C,), all int64; pose_ca / pose_score
@@ -243,8 +250,11 @@ def optimize_antibody(dock_model, design_model, complex_, num_poses, designs_per
     a, b = sampler.shard_range(P, world, rank)
     mine = b - a
     depth = dict(dock=dock_steps, design=design_steps, redock=dock_steps)
+    noise = {} if dock_noise_scale is None else dict(noise_scale=hip.check_noise_scale('optimize_antibody: dock_noise_scale', dock_noise_scale))
+    knobs = dict(dock=noise, redock=noise,          # None adds no key: the stage's options, and so its loop, are those of a call without the argument
+                 design={} if design_temperature is None else dict(seq_temperature=hip.check_temperature('optimize_antibody: design_temperature', design_temperature)))
     rngs = lambda stage, lo, kk=k: dict(seed=stage_seed(seed, stage), rng_offset=stage_rng_offset(stage, lo, L, S, kk, D),
-                                        **({} if depth[stage] is None else dict(steps=int(depth[stage]))))
+                                        **({} if depth[stage] is None else dict(steps=int(depth[stage]))), **knobs[stage])
     aa = one['aa'][0]
     f32 = dict(dtype=torch.float32, device=dev)
     clock = {}

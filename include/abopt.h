@@ -23,7 +23,7 @@
 extern "C" {
 #endif
 
-#define ABOPT_ABI_VERSION 54
+#define ABOPT_ABI_VERSION 55
 
 enum { ABOPT_OK = 0, ABOPT_EINVAL = 1, ABOPT_EHIP = 2, ABOPT_EUNSUPPORTED = 3, ABOPT_EWORKSPACE = 4 };
 
@@ -245,7 +245,25 @@ typedef struct {
     float dist_min, dist_max;/* prmsd bounds (prmsd.py:41) */
     int   ppl_masked;        /* 1: perplexity averaged over generated residues (sample, dpm_full.py:293); 0: over all L (optimize, :358) */
     int   t_prev;            /* the step this one lands on, t - 1 in the full loop: no noise is added when it is 0 (the reference's t > 1, transition.py:94-98,155) */
+    int   tempered;          /* 0: the two fields below are not read; the step is that of every earlier ABI (so a zero-initialised tail keeps it).  ABI 55, see below */
+    float seq_temperature;   /* tau >= 0: the temperature of the predicted residue-type distribution; 1 takes the untempered path, 0 is greedy */
+    float noise_scale;       /* lambda >= 0: scales the structure noise of the step; 1 multiplies by 1 (exact), 0 makes the structure update deterministic */
 } abopt_step_params;
+
+/* Sampling at a temperature (ABI 55; no reference counterpart).  With tempered != 0:
+ *   Residue types.  Where a row draws its type (mask_generate set, a non-empty allowed set A -- all 20 classes without aa_allowed) and tau != 1, the network's
+ *     prediction c_net[0..19] of the row is replaced, BEFORE the posterior is formed, by its tempered form over A.  With m = max_{k in A} max(c_k, 0):
+ *       e_k = exp2((log2(max(c_k, 0)) - log2(m)) / tau) for k in A, e_k = 0 outside A, c'_k = e_k / sum_j e_j;
+ *       tau = 0: c' is one-hot at the lowest-index class of A with max(c_k, 0) == m;   m == 0 or not finite: c' = c (nothing to sharpen).
+ *     Everything downstream is the untempered code on c': the products ((ab ct) + unif) ((ab c'_k) + unif), the aa_allowed zeroing, the normalisation, post_out,
+ *     the perplexity term and the inverse-CDF walk -- so post_out and the perplexity describe the distribution that is sampled (a perplexity at tau != 1 is not
+ *     comparable with one at tau = 1).  The temperature acts on the predicted x0 distribution, not on the posterior: the forward-noise term the network is
+ *     conditioned on stays.  Context rows and frozen rows (an empty set) never read c_net for their posterior and still do not; an injected s_next is taken as
+ *     it is, post_out is still the tempered posterior.  tau = 1 takes the untempered path verbatim.
+ *   Structure.  The position update adds sigma_eff z with sigma_eff = the rounded fp32 product sigma * lambda; the rotation noise angle (either IGSO(3) branch,
+ *     after the select) is multiplied by lambda before it scales the axis.  Injected structure noise is scaled likewise; the step that lands on 0 still adds
+ *     nothing.  No random number is added or dropped: the Philox counter layout is that of every earlier ABI.
+ * tau and lambda must be finite and >= 0, and a non-zero tau below 1e-3 is refused (1 / tau has to stay a sane fp32; 0 is the greedy limit): ABOPT_EINVAL. */
 
 /* Explicit draws for teacher-forced replay, reference draw order; all NULL => the
  * device Philox stream (seed, offset) is used instead. */

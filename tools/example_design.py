@@ -3,9 +3,11 @@
 
     encode once -> N samples of one complex (shared context) -> all-atom backbone of every sample -> rank by commonness
 
-    python tools/example_design.py [num_samples] [L] [--steps K]
+    python tools/example_design.py [num_samples] [L] [--steps K] [--temperature TAU] [--noise-scale LAMBDA]
 
 --steps K: K network evaluations per sample over the evenly respaced sub-sequence of the 100 trained steps (default: all 100).
+--temperature TAU / --noise-scale LAMBDA: draw the residue types at temperature TAU (0: greedy) / add LAMBDA times the structure noise at every step
+(default 1 and 1: the plain sampler).
 """
 import os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -16,14 +18,24 @@ from ab_opt_amd import sampler, geometry
 from ab_opt_amd.utils.synth import make_batch, LAYOUT_256, LAYOUT_128
 
 argv = sys.argv[1:]
-K = int(argv.pop(argv.index('--steps') + 1)) if '--steps' in argv else 100
-argv = [a for a in argv if a != '--steps']
+def flag(name, kind, default):
+    """the value behind `name` in argv (removed from it with the flag), or default"""
+    if name not in argv:
+        return default
+    i = argv.index(name)
+    value = kind(argv.pop(i + 1))
+    argv.pop(i)
+    return value
+
+
+K = flag('--steps', int, 100)
+TAU, LAMBDA = flag('--temperature', float, 1.0), flag('--noise-scale', float, 1.0)
 n = int(argv[0]) if len(argv) > 0 else 16
 L = int(argv[1]) if len(argv) > 1 else 256
 dev = torch.device('cuda:0')
 model = build_model(100, 7, flavour='abdock', device=dev).eval()
 complex_ = {k: v.to(dev) for k, v in make_batch(1, LAYOUT_256 if L == 256 else LAYOUT_128, seed=2022).items()}
-opt = {'sample_structure': True, 'sample_sequence': True, 'steps': K}
+opt = {'sample_structure': True, 'sample_sequence': True, 'steps': K, 'seq_temperature': TAU, 'noise_scale': LAMBDA}
 rep = lambda a: a.expand(n, *a.shape[1:]).contiguous()
 
 
@@ -42,6 +54,6 @@ design()                                                    # warm-up (library l
 torch.cuda.synchronize(); t0 = time.perf_counter()
 pos, mask, gen, prmsd, ppl, top = design()
 torch.cuda.synchronize(); dt = time.perf_counter() - t0
-print(f'{n} designs of one {L}-residue complex: {dt * 1e3:.1f} ms end to end at {K} steps ({n * K / dt:.0f} sample-steps/s incl. encode, backbone rebuild and ranking)')
+print(f'{n} designs of one {L}-residue complex: {dt * 1e3:.1f} ms end to end at {K} steps, temperature {TAU:g}, noise scale {LAMBDA:g} ({n * K / dt:.0f} sample-steps/s incl. encode, backbone rebuild and ranking)')
 print('most common designs:', top.tolist(), '| predicted CA-RMSD of the best:', round(float(prmsd[top[0]]), 3), '| perplexity:', round(float(ppl[top[0]]), 3))
 assert torch.isfinite(pos).all() and mask[gen][:, :4].all()

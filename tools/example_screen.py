@@ -4,7 +4,8 @@ stage and the designs the notebook's median filter keeps.
     python tools/example_screen.py [--poses 16 --designs 8 --redocks 8 --screened 1 --steps 100 --per-launch 8 --contig 97-103 --exclude CM
                                     --dock-steps 20 --design-steps 20 --cluster-cutoff 2.0 --max-clusters 4 --redock-cutoff 2.0
                                     --clash-cutoff 3.0 --contact-cutoff 5.0 --bond-max 2.0
-                                    --seq-mismatch 2 --screen-by diverse --share-redocks --allow A,G,S,T,AV,LK,DE --lddt-cutoff 15.0]
+                                    --seq-mismatch 2 --screen-by diverse --share-redocks --allow A,G,S,T,AV,LK,DE --lddt-cutoff 15.0
+                                    --design-temperature 0.2 --dock-noise-scale 0.5]
 
 --cluster-cutoff clusters the docked poses on the device and screens one centre per cluster: the run prints the number of clusters C,
 their sizes and the stage times.  How many clusters a trained model's poses fall into is unmeasured.
@@ -23,6 +24,10 @@ How many duplicates trained weights produce, and so what sharing saves in practi
 --lddt-cutoff A scores every re-dock by lDDT-CA of the re-docked residues, against its design and among the re-docks of the design: the
 run prints, per design, lddt_mean, the mean consistency of its re-docks and the re-docked residues whose mean per-residue lDDT is below 0.5 -- where the
 re-docks disagree with the design.  What lDDT values trained weights produce, and whether 0.5 is a useful threshold, is unmeasured.
+
+--design-temperature TAU draws the design stage's residue types at temperature TAU (0: greedy) and --dock-noise-scale LAMBDA scales the structure noise of every
+dock and re-dock step: with --seq-mismatch the run shows how the families per pose shrink, and the last line before the table how
+dockq_std moves.  That is what hash-filled weights do; what either knob does to the hit rate of a trained model is unmeasured.
 
 The weights are not a trained checkpoint, so the numbers say nothing about antibodies; the stage times are what a screen of this size costs.
 """
@@ -65,6 +70,8 @@ def main():
     ap.add_argument('--screen-by', choices=('first', 'ppl', 'diverse'), default='first', help="the designs that are re-docked ('diverse': one per sequence cluster; needs --seq-mismatch)")
     ap.add_argument('--share-redocks', action='store_true', help='re-dock every distinct chosen sequence once (the re-dock must cover the docked residues: it does here)')
     ap.add_argument('--lddt-cutoff', type=float, default=None, metavar='A', help='score every re-dock by lDDT-CA at this inclusion radius (15.0 is the usual one)')
+    ap.add_argument('--design-temperature', type=float, default=None, metavar='TAU', help='temperature of the designed residue types (0: greedy; default: 1, the plain sampler)')
+    ap.add_argument('--dock-noise-scale', type=float, default=None, metavar='LAMBDA', help='scale of the structure noise of every dock / re-dock step (default: 1)')
     ap.add_argument('--allow', default='', metavar='SETS', help='allowed types per contig position, comma-separated in contig order, e.g. A,G,S,T,AV,LK,DE')
     args = ap.parse_args()
     dev = torch.device('cuda:0')
@@ -85,7 +92,8 @@ def main():
               dock_steps=args.dock_steps, design_steps=args.design_steps,
               cluster_cutoff=args.cluster_cutoff, max_clusters=args.max_clusters, redock_cutoff=args.redock_cutoff,
               clash_cutoff=args.clash_cutoff, contact_cutoff=args.contact_cutoff, bond_max=args.bond_max,
-              allowed_aa=allowed, seq_mismatch=args.seq_mismatch, screen_by=args.screen_by, share_redocks=args.share_redocks, lddt_cutoff=args.lddt_cutoff)
+              allowed_aa=allowed, seq_mismatch=args.seq_mismatch, screen_by=args.screen_by, share_redocks=args.share_redocks, lddt_cutoff=args.lddt_cutoff,
+              design_temperature=args.design_temperature, dock_noise_scale=args.dock_noise_scale)
     print(f'L={one["aa"].shape[1]} P={args.poses} S={args.designs} k={args.screened} D={args.redocks} T={args.steps} dock_steps={args.dock_steps or args.steps} design_steps={args.design_steps or args.steps} per_launch={args.per_launch} '
           f'contig={args.contig!r} device={torch.cuda.get_device_name(dev)}')
     t0 = time.perf_counter()
@@ -133,6 +141,8 @@ def main():
                 low = redocked[(m >= 0) & (m < 0.5)].tolist()
                 print(f'{p:>4} {int(res["chosen"][p, j]):>6} {res["lddt_mean"][p, j].item():9.4f} {res["lddt_std"][p, j].item():8.4f} '
                       f'{res["redock_consistency"][p, j].mean().item():7.4f}  {low}')
+    print(f'design_temperature={args.design_temperature} dock_noise_scale={args.dock_noise_scale}: dockq_std mean {res["dockq_std"].mean().item():.4f} '
+          f'prmsd_std mean {res["prmsd_std"].mean().item():.4f} over {res["dockq_std"].numel()} screened designs')
     keep = screen.screen_filter(res)
     print(f'{int(keep.sum())} of {keep.numel()} screened designs pass the median filter')
     print(f'{"pose":>4} {"design":>6} {"seq":>9} {"AAR":>6} {"PPL":>7} {"DockQ_avg":>9} {"DockQ_std":>9} {"prmsd_avg":>9} {"prmsd_std":>9}')
