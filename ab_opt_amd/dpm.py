@@ -43,6 +43,14 @@ class _LoopSpec:
                                                 # per call); 0: the loop holds no row list (include/abopt.h: abopt_eps_net_step, query_row_tiles)
     seq_temperature: float = 1.0                # tau: the temperature of the predicted residue-type distribution of every step (include/abopt.h: seq_temperature)
     noise_scale: float = 1.0                    # lambda: the scale of the structure noise of every step; both 1: the steps carry tempered = 0
+    guided: bool = False                        # every step is followed by hip.guide_positions and the loop's inputs end with `role` (behind aa_allowed; the contents
+                                                # are data, not key); False: the launches of a loop without the six fields below, which then keep their defaults
+    guide_attract: float = 0.0                  # w_att, r_att, w_rep, r_rep, max_shift of include/abopt.h: abopt_guide_positions
+    guide_attract_radius: float = 0.0
+    guide_repel: float = 0.0
+    guide_repel_radius: float = 0.0
+    guide_max_shift: float = 0.0
+    guide_decay: int = 0                        # k of the step weight g(u) = (u / num_steps)^k on w_att and w_rep, for the step that lands on u
 
 
 def respaced_steps(t_start, steps=None, timesteps=None):
@@ -86,8 +94,9 @@ def _free_bytes(dev):
 
 
 def _loop_inputs(inputs):
-    """(res_feat, pair_feat, mask_generate, mask_res[, aa_allowed]) checked and as the kernels read them (contiguous, features fp32): the caller's own tensors where
-    they already are.  aa_allowed, the fifth input of a constrained loop (_LoopSpec.constrained), is the int32 (N, L) tensor of _checked_allowed.
+    """(res_feat, pair_feat, mask_generate, mask_res[, aa_allowed][, role]) checked and as the kernels read them (contiguous, features fp32): the caller's own tensors
+    where they already are.  aa_allowed, the fifth input of a constrained loop (_LoopSpec.constrained), is the int32 (N, L) tensor of _checked_allowed; role, the last
+    input of a guided loop (_LoopSpec.guided), the int32 (N, L) tensor of _checked_role.
     Replicated-complex batches (one crop, N samples: design_for_pdb.py:141-147) may pass the context ONCE: res_feat (1,L,F) / pair_feat (1,L,L,C) are then shared by all
     N samples -- the kernels index pair_feat and its bias cache with batch stride 0, so the 100 x 6 passes over it are served from L2/MALL instead of HBM.  And a test set
     of complexes x S samples may pass G complexes once each: pair_feat (G,L,L,C), samples S c .. S c + S - 1 share entry c (design_for_testset.py:556-589; BASELINE config 4)."""
@@ -124,6 +133,34 @@ def _checked_allowed(aa_allowed, mask_generate):
         raise ValueError(f'aa_allowed: generated residue {first % L + 1} of sample {first // L} has an empty set of allowed types '
                          '(at least one of bits 0..19 must be set wherever generate_flag is)')
     return a
+
+
+def _checked_role(guide_role, mask_generate):
+    """guide_role of sample() / optimize() -> None, or the int32 (N, L) tensor the guidance kernel reads: bit 0 of a word marks a hotspot, bit 1 a repeller
+    (model.guide_roles builds them).  Accepts (N, L), (1, L) or (L,) of any integer dtype.  No device read."""
+    if guide_role is None:
+        return None
+    N, L = mask_generate.shape
+    a = torch.as_tensor(guide_role, device=mask_generate.device)
+    if a.dtype.is_floating_point or a.dtype.is_complex or a.dtype == torch.bool:
+        raise TypeError(f'guide_role must hold integers (bit 0: hotspot, bit 1: repeller), got {a.dtype}')
+    if a.dim() == 1:
+        a = a[None]
+    if a.dim() != 2 or a.shape[1] != L or a.shape[0] not in (1, N):
+        raise ValueError(f'guide_role must be ({N}, {L}), (1, {L}) or ({L},), got {tuple(a.shape)}')
+    return a.to(torch.int32).expand(N, L).contiguous()
+
+
+def _guidance(guide_role, mask_generate, sample_structure, knobs):
+    """(role, the guide fields of the _LoopSpec) of sample(guide_role=, guide_attract=, ...) / optimize(...).  The loop is guided iff a role is given and one of the two
+    weights is non-zero; otherwise (None, {}): the spec, and so the launches and the graph key, of a call without the keywords.  The knobs are checked either way
+    (hip.check_guidance), and guidance of a loop that does not sample the structure is refused: its positions are not the loop's to move.  No device call."""
+    kn = hip.check_guidance(**knobs)
+    if guide_role is None or (kn['guide_attract'] == 0.0 and kn['guide_repel'] == 0.0):
+        return None, {}
+    if not sample_structure:
+        raise ValueError('guidance moves the generated positions: it needs sample_structure=True (guide_role with a non-zero guide_attract or guide_repel was given)')
+    return _checked_role(guide_role, mask_generate), dict(guided=True, **kn)
 
 
 class FullDPM(_Derived, nn.Module):
@@ -255,12 +292,12 @@ class FullDPM(_Derived, nn.Module):
         return self._denoise(spec, state, self._inputs(res_feat, pair_feat, mask_generate, mask_res, allowed), noise, seed, rng_offset, pbar, graph)
 
     @staticmethod
-    def _inputs(res_feat, pair_feat, mask_generate, mask_res, allowed):
-        """The loop inputs: the four tensors every loop takes and, for a constrained one, the checked aa_allowed behind them."""
-        return (res_feat, pair_feat, mask_generate, mask_res) + (() if allowed is None else (allowed,))
+    def _inputs(res_feat, pair_feat, mask_generate, mask_res, allowed, role=None):
+        """The loop inputs: the four tensors every loop takes, for a constrained one the checked aa_allowed behind them and, for a guided one, the checked role last."""
+        return (res_feat, pair_feat, mask_generate, mask_res) + (() if allowed is None else (allowed,)) + (() if role is None else (role,))
 
     def _denoise(self, spec, state, inputs, noise, seed, rng_offset, pbar, graph=None, range_safe=False):
-        """The loop `spec` on inputs = (res_feat, pair_feat, mask_generate, mask_res[, aa_allowed]), eagerly or from its captured graph.  Settles spec.use_bias_cache,
+        """The loop `spec` on inputs = (res_feat, pair_feat, mask_generate, mask_res[, aa_allowed][, role]), eagerly or from its captured graph.  Settles spec.use_bias_cache,
         here and nowhere else.  range_safe: eagerly, the dense layers as fp32 GEMMs (the answer to a raised range guard)."""
         graph = self.graph_mode if graph is None else graph
         res_feat, pair_feat, _, mask_res = inputs[:4]
@@ -328,10 +365,13 @@ class FullDPM(_Derived, nn.Module):
     def _run_eager(self, spec, state, inputs, noise, seed, rng_offset, pbar, seed_dev=None, range_safe=False):
         """The loop itself, one C call per step (network evaluation + transitions: hip.eps_net_step); spec.use_bias_cache is settled (_denoise).
         seed_dev: device {seed, offset} (graph capture)."""
-        res_feat, pair_feat, mask_generate, mask_res, *allowed = _loop_inputs(inputs)
-        if spec.constrained != bool(allowed):
-            raise ValueError('a constrained loop takes aa_allowed as its fifth input, an unconstrained one takes four')
-        aa_allowed = allowed[0] if allowed else None
+        res_feat, pair_feat, mask_generate, mask_res, *extra = _loop_inputs(inputs)
+        if len(extra) != int(spec.constrained) + int(spec.guided):
+            raise ValueError('a constrained loop takes aa_allowed as its fifth input and a guided one role as its last; a loop that is neither takes four inputs')
+        aa_allowed = extra[0] if spec.constrained else None
+        role = extra[-1] if spec.guided else None
+        if spec.guided and not spec.sample_structure:
+            raise ValueError('a loop that does not sample the structure is never guided: its positions are not the loop\'s to move')
         dev = res_feat.device
         N, L = mask_res.shape
         T0, Nc, use_bias_cache = spec.t_start, pair_feat.shape[0], spec.use_bias_cache
@@ -364,6 +404,7 @@ class FullDPM(_Derived, nn.Module):
         net = dict(v_next=torch.empty(N, L, 3, **f32), R_next=torch.empty(N, L, 3, 3, **f32), eps_pos=torch.empty(N, L, 3, **f32),
                    c=torch.empty(N, L, 20, **f32), prmsd_logits=torch.empty(N, self.num_bins, **f32) if self.abdock else None)
         p_norm = torch.empty(N, L, 3, **f32)
+        h_scale, h_mean = self._sched_host()['scale'], self._sched_host()['mean']
         it = enumerate(pairs)
         if pbar:
             from tqdm.auto import tqdm
@@ -390,9 +431,16 @@ class FullDPM(_Derived, nn.Module):
                              noise[t] if noise is not None else None, seed, rng_offset, tp[i], X[j], cdf[j] if noise is None else None, out,
                              pair_bias_cache=pbc, pair_feat_shared=(group if shared else 0), pair_terms=pterms, seed_dev=seed_dev, aa_allowed=aa_allowed,
                              carry_in=j > 0, carry_out=more, context_outputs_unused=True, query_rows=qrows)
+            if spec.guided:
+                # The nudge of the state the step just stored (p in Angstrom and its normalised copy, the next evaluation's input), the last step included.  The mixer
+                # the fused tail carried to the next call reads s_next and v_next only, never the positions: the carry stays valid.  The weights of the step that lands
+                # on t_prev: float64 here, rounded once to fp32 at the call, baked into the captured node like every other per-step scalar.
+                g = hip.guide_weight(t_prev, self.num_steps, spec.guide_decay)
+                hip.guide_positions(tp[i - 1], p_norm, mask_generate, mask_res, role, spec.guide_attract * g, spec.guide_attract_radius, spec.guide_repel * g,
+                                    spec.guide_repel_radius, spec.guide_max_shift, h_scale, h_mean)
             evals += 1
         self.last_run_info = dict(bias_cache=use_bias_cache, pair_terms=pterms is not None, shared_context=shared, graph=seed_dev is not None, steps=evals,
-                                  query_row_tiles=qrows[2] if qrows else 0)
+                                  query_row_tiles=qrows[2] if qrows else 0, **(dict(guided=True) if spec.guided else {}))
         return tv, tp, ts, tpr, tpp
 
     def _to_traj(self, T0, tv, tp, ts, tpr, tpp, timesteps=0):
@@ -417,7 +465,8 @@ class FullDPM(_Derived, nn.Module):
     @torch.no_grad()
     def sample(self, v, p, s, res_feat, pair_feat, mask_generate, mask_res, sample_structure=True, sample_sequence=True,
                pbar=False, noise=None, seed=None, rng_offset=0, use_bias_cache=None, graph=None, aa_allowed=None, steps=None, timesteps=None,
-               seq_temperature=1.0, noise_scale=1.0, **kwargs):
+               seq_temperature=1.0, noise_scale=1.0, guide_role=None, guide_attract=0.0, guide_attract_radius=8.0, guide_repel=0.0, guide_repel_radius=3.0,
+               guide_max_shift=2.0, guide_decay='constant', **kwargs):
         """dpm_full.py:236-302.  `noise` (optional) = {'init': {q4,p,s}, t: {axis,bin,ubin,gauss,z,s_next}} replays
         recorded draws; otherwise a Philox stream seeded from torch's CPU generator is used.
         aa_allowed (optional; no reference counterpart): the residue types that may appear at each generated residue, (N, L) / (1, L) / (L,) int32 or int64 words with
@@ -427,26 +476,41 @@ class FullDPM(_Derived, nn.Module):
         seq_temperature = tau / noise_scale = lambda (optional; no reference counterpart): every step draws its residue types from the
         posterior of the network's prediction at temperature tau (0: greedy; below 1 sharper, above 1 flatter) and adds lambda times the structure noise (0: a
         deterministic structure update).  The initial state is not touched.  With both at 1 the loop is today's, bit for bit; the perplexity of a tau != 1 run
-        describes the tempered distribution and is not comparable with one at tau = 1."""
+        describes the tempered distribution and is not comparable with one at tau = 1.
+        guide_role (optional; no reference counterpart): (N, L) / (1, L) / (L,) integer words, bit 0 = hotspot, bit 1 = repeller
+        (model.guide_roles builds them).  After every step the generated residues are pulled, as one rigid set, towards the centroid of the hotspot residues by
+        guide_attract (<= 1) times what their centroid's distance exceeds guide_attract_radius, and each is pushed away from the repeller residues closer than
+        guide_repel_radius with weight guide_repel; no residue moves more than guide_max_shift per step (all in Angstrom; 8, 3 and 2 are conventional values, not tuned
+        ones).  guide_decay 'constant' / 'linear' / 'quadratic': both weights times (u / num_steps)^k for the step that lands on u.  Hotspots and repellers are
+        context residues; bits on generated or masked-out residues mean nothing.  Without a role, or with both weights 0, the loop is today's, bit for bit.
+        Needs sample_structure=True."""
         tau, lam = hip.check_temperature('seq_temperature', seq_temperature), hip.check_noise_scale('noise_scale', noise_scale)
+        role, guide = _guidance(guide_role, mask_generate, sample_structure, dict(
+            guide_attract=guide_attract, guide_attract_radius=guide_attract_radius, guide_repel=guide_repel, guide_repel_radius=guide_repel_radius,
+            guide_max_shift=guide_max_shift, guide_decay=guide_decay))
         allowed = _checked_allowed(aa_allowed, mask_generate)
         visited = _spec_timesteps(self.num_steps, steps, timesteps)
         seed, h = self._begin(seed)
         state = hip.sample_init(v.float(), p.float(), s, mask_generate, noise['init'] if noise is not None else None, seed, rng_offset,
                                 h['scale'], h['mean'], sample_structure, sample_sequence, aa_allowed=allowed)
         spec = _LoopSpec(self.num_steps, None, bool(sample_structure), bool(sample_sequence), ppl_masked=True, use_bias_cache=use_bias_cache,
-                         constrained=allowed is not None, timesteps=visited, seq_temperature=tau, noise_scale=lam)
-        inputs = self._inputs(res_feat, pair_feat, mask_generate, mask_res, allowed)
+                         constrained=allowed is not None, timesteps=visited, seq_temperature=tau, noise_scale=lam, **guide)
+        inputs = self._inputs(res_feat, pair_feat, mask_generate, mask_res, allowed, role)
         return self._to_traj(spec.t_start, *_range_guarded(lambda safe: self._denoise(spec, state, inputs, noise, seed, rng_offset, pbar, graph, safe)), timesteps=visited)
 
     @torch.no_grad()
     def optimize(self, v, p, s, opt_step, res_feat, pair_feat, mask_generate, mask_res, sample_structure=True,
                  sample_sequence=True, pbar=False, noise=None, seed=None, rng_offset=0, use_bias_cache=None, graph=None, aa_allowed=None, steps=None, timesteps=None,
-                 seq_temperature=1.0, noise_scale=1.0):
+                 seq_temperature=1.0, noise_scale=1.0, guide_role=None, guide_attract=0.0, guide_attract_radius=8.0, guide_repel=0.0, guide_repel_radius=3.0,
+                 guide_max_shift=2.0, guide_decay='constant'):
         """dpm_full.py:304-367: noise the input to step `opt_step`, then denoise.  aa_allowed: as in sample(); the forward noising draws from the allowed types too.
         steps = K / timesteps: as in sample(), over [0, opt_step] (K <= opt_step).  seq_temperature / noise_scale: as in sample(), on the denoising steps; the
-        forward noising to opt_step is not touched."""
+        forward noising to opt_step is not touched.  guide_role and the guide_* knobs: as in sample(), behind every denoising step; the step weight of
+        guide_decay counts in the model's num_steps, not in opt_step."""
         tau, lam = hip.check_temperature('seq_temperature', seq_temperature), hip.check_noise_scale('noise_scale', noise_scale)
+        role, guide = _guidance(guide_role, mask_generate, sample_structure, dict(
+            guide_attract=guide_attract, guide_attract_radius=guide_attract_radius, guide_repel=guide_repel, guide_repel_radius=guide_repel_radius,
+            guide_max_shift=guide_max_shift, guide_decay=guide_decay))
         allowed = _checked_allowed(aa_allowed, mask_generate)
         visited = _spec_timesteps(opt_step, steps, timesteps)
         seed, h = self._begin(seed)
@@ -461,8 +525,8 @@ class FullDPM(_Derived, nn.Module):
         # dpm_full.py:351-358: the loop feeds the net's third output to the position update as noise whatever `obj` is,
         # and averages the perplexity over all residues (calc_perplexity(logits) without a mask)
         spec = _LoopSpec(opt_step, None, bool(sample_structure), bool(sample_sequence), ppl_masked=False, optimize_mode=True, use_bias_cache=use_bias_cache,
-                         constrained=allowed is not None, timesteps=visited, seq_temperature=tau, noise_scale=lam)
-        inputs = self._inputs(res_feat, pair_feat, mask_generate, mask_res, allowed)
+                         constrained=allowed is not None, timesteps=visited, seq_temperature=tau, noise_scale=lam, **guide)
+        inputs = self._inputs(res_feat, pair_feat, mask_generate, mask_res, allowed, role)
         # same counters as add_noise, other sub-sequence tags (csrc/denoise.hip): a sample's stream position does not depend on the batch it sits in
         traj = self._to_traj(opt_step, *_range_guarded(lambda safe: self._denoise(spec, state, inputs, noise, seed, rng_offset, pbar, graph, safe)), timesteps=visited)
         return {k: tuple(e) for k, e in traj.items()}
@@ -481,6 +545,7 @@ class _LoopGraph:
         static = tuple(a.clone() for a in _loop_inputs(inputs))
         self.res_feat, self.pair_feat, self.mask_generate, self.mask_res = static[:4]
         self.aa_allowed = static[4] if spec.constrained else None      # a constrained loop's mask is an input like mask_generate: refreshed before each replay
+        self.role = static[-1] if spec.guided else None                # and so are a guided loop's roles
         self.seed_dev = torch.zeros(2, dtype=torch.int64, device=self.res_feat.device)
         self.tables = dpm._loop_tables(dpm._loop_steps(spec))          # the IGSO(3) rows the captured steps read: the cache that built them may drop them, this graph may not
         run = lambda stop_after: dpm._run_eager(dataclasses.replace(spec, stop_after=stop_after), self.state, static, None, 0, 0, False, seed_dev=self.seed_dev)
@@ -506,7 +571,7 @@ class _LoopGraph:
         self._pf_src = None                                             # (weakref to the caller's pair_feat, its _version) of the last copy
 
     def replay(self, state, inputs, seed, rng_offset):
-        res_feat, pair_feat, mask_generate, mask_res, *allowed = inputs
+        res_feat, pair_feat, mask_generate, mask_res, *extra = inputs
         for dst, src in zip(self.state, state):
             dst.copy_(src)
         self.res_feat.copy_(res_feat if res_feat.shape == self.res_feat.shape else res_feat.expand_as(self.res_feat))
@@ -528,7 +593,9 @@ class _LoopGraph:
         self.mask_generate.copy_(mask_generate)
         self.mask_res.copy_(mask_res)
         if self.aa_allowed is not None:
-            self.aa_allowed.copy_(allowed[0])
+            self.aa_allowed.copy_(extra[0])
+        if self.role is not None:
+            self.role.copy_(extra[-1])
         self.seed_dev.copy_(torch.tensor([int(seed), int(rng_offset)], dtype=torch.int64))
         self.graph.replay()
         return self.out

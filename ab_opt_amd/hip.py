@@ -13,7 +13,7 @@ import torch
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # ABOPT_LIB_PATH: developer override to load a variant build of the same ABI (csrc/Makefile VARIANT=...: A/B of two source trees)
 LIB_PATH = os.environ.get('ABOPT_LIB_PATH') or os.path.join(_HERE, 'libabopt_hip.so')
-ABI_VERSION = 55
+ABI_VERSION = 56
 
 c_f = C.c_void_p        # device float*
 c_i64 = C.c_void_p      # device int64*
@@ -171,6 +171,7 @@ _SIGNATURES = {
     'abopt_lddt_ca_ensemble': (c_int, [c_f, c_u8, c_int, c_u8, c_i32] + [c_int] * 4 + [c_float, c_void_p, c_void_p, c_void_p, c_size_t, c_stream]),
     'abopt_sasa_ws_bytes': (c_size_t, [c_int] * 4),
     'abopt_sasa_grouped': (c_int, [c_f, c_u8, c_int, c_i32, c_f, c_f] + [c_int] * 5 + [c_float] * 2 + [c_void_p] * 3 + [c_size_t, c_stream]),
+    'abopt_guide_positions': (c_int, [c_f, c_f, c_u8, c_u8, c_i32, c_int, c_int, c_int] + [c_float] * 6 + [c_void_p, c_stream]),
     'abopt_prof_enable': (c_int, [c_int]),
     'abopt_prof_spans_reset': (c_int, [c_stream]),
     'abopt_prof_spans': (c_int, [POINTER(c_int), POINTER(c_double)]),
@@ -551,6 +552,63 @@ def check_noise_scale(name, lam):
     if not math.isfinite(s) or s < 0.0:
         raise ValueError(f'{name} must be finite and >= 0 (got {lam!r})')
     return s
+
+
+GUIDE_DECAY = {'constant': 0, 'linear': 1, 'quadratic': 2}      # guide_decay -> k of the step weight g(u) = (u / num_steps)^k
+
+
+def check_guidance(guide_attract=0.0, guide_attract_radius=8.0, guide_repel=0.0, guide_repel_radius=3.0, guide_max_shift=2.0, guide_decay='constant'):
+    """The knobs of guided sampling (include/abopt.h: abopt_guide_positions) as a dict of floats under their own names plus guide_decay as
+    its exponent k (0, 1, 2; the names of GUIDE_DECAY, or k itself), or ValueError: every scalar finite and >= 0, guide_attract <= 1 (the pull may not overshoot),
+    guide_max_shift > 0.  No device is needed.  8, 3 and 2 Angstrom are conventional values, not tuned ones."""
+    import math
+    out = {}
+    for name, v in (('guide_attract', guide_attract), ('guide_attract_radius', guide_attract_radius), ('guide_repel', guide_repel),
+                    ('guide_repel_radius', guide_repel_radius), ('guide_max_shift', guide_max_shift)):
+        f = float(v)
+        if not math.isfinite(f) or f < 0.0:
+            raise ValueError(f'{name} must be finite and >= 0 (got {v!r})')
+        out[name] = f
+    if out['guide_attract'] > 1.0:
+        raise ValueError(f'guide_attract must be <= 1: a larger weight would pull the generated residues past the hotspots (got {guide_attract!r})')
+    if out['guide_max_shift'] == 0.0:
+        raise ValueError('guide_max_shift must be > 0')
+    if isinstance(guide_decay, str):
+        if guide_decay not in GUIDE_DECAY:
+            raise ValueError(f'guide_decay must be one of {sorted(GUIDE_DECAY)} (got {guide_decay!r})')
+        out['guide_decay'] = GUIDE_DECAY[guide_decay]
+    else:
+        if isinstance(guide_decay, bool) or guide_decay not in (0, 1, 2):
+            raise ValueError(f'guide_decay must be one of {sorted(GUIDE_DECAY)} or their exponents 0, 1, 2 (got {guide_decay!r})')
+        out['guide_decay'] = int(guide_decay)
+    return out
+
+
+def guide_weight(u, num_steps, decay):
+    """g(u) = (u / num_steps)^k of the step that lands on u, in float64 (the caller multiplies a weight by it and rounds the product once to fp32)."""
+    return (float(u) / float(num_steps)) ** int(decay) if int(decay) else 1.0
+
+
+def guide_positions(p, p_norm, mask_generate, mask_res, role, w_att=0.0, r_att=8.0, w_rep=0.0, r_rep=3.0, max_shift=2.0, position_scale=10.0,
+                    position_mean=(0.0, 0.0, 0.0), role_shared=0):
+    """One guidance nudge, in place (include/abopt.h: abopt_guide_positions): p (N, L, 3) fp32 in Angstrom and -- optional -- p_norm, its
+    normalised copy; mask_generate, mask_res (N, L) bool; role (N, L) int32, or (N / role_shared, L) shared by role_shared consecutive samples: bit 0 hotspot,
+    bit 1 repeller.  Only the rows gen & res change.  Stream-ordered, no host synchronisation, capturable.  -> p."""
+    ptr(p, strided=True)                                            # a CPU tensor is refused here, before anything else
+    kn = check_guidance(w_att, r_att, w_rep, r_rep, max_shift)
+    if p.dim() != 3 or p.shape[2] != 3 or mask_generate.shape != p.shape[:2] or mask_res.shape != p.shape[:2]:
+        raise ValueError(f'guide_positions: expected p (N, L, 3) and masks (N, L), got {tuple(p.shape)}, {tuple(mask_generate.shape)} and {tuple(mask_res.shape)}')
+    N, L = mask_res.shape
+    S = int(role_shared)
+    if S < 0 or (N % S if S else 0) or role.dim() != 2 or tuple(role.shape) != ((N // S if S else N), L):
+        raise ValueError(f'guide_positions: role {tuple(role.shape)} does not fit {N} samples of {L} residues with role_shared={role_shared}')
+    if p_norm is not None and p_norm.shape != p.shape:
+        raise ValueError('guide_positions: p_norm must have the shape of p')
+    mean = (C.c_float * 3)(*[float(m) for m in position_mean])
+    _check(lib().abopt_guide_positions(ptr(p, torch.float32), ptr(p_norm, torch.float32, optional=True), ptr(mask_generate), ptr(mask_res), ptr(role, torch.int32),
+                                       S, N, L, kn['guide_attract'], kn['guide_attract_radius'], kn['guide_repel'], kn['guide_repel_radius'],
+                                       kn['guide_max_shift'], float(position_scale), mean, stream()))
+    return p
 
 
 def _allowed_ptr(aa_allowed, mask_generate):

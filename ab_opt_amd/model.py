@@ -70,6 +70,51 @@ def aa_allowed_mask(length, exclude='', at=None, device=None):
     return mask.to(device) if device is not None else mask
 
 
+ROLE_HOTSPOT, ROLE_REPEL = 1, 2          # the bits of a guide_role word (include/abopt.h: abopt_guide_positions)
+
+
+def guide_roles(batch_or_length, hotspots=None, repel=None, device=None):
+    """The per-residue roles that batch['guide_role'] takes (guided sampling): int32 words, bit 0 = hotspot (the generated residues are
+    pulled towards the centroid of these), bit 1 = repeller (every generated residue is pushed out of these residues' radius).
+    batch_or_length: a batch dict -> (N, L) like batch['aa'], on its device; or a length -> (length,) for one complex.
+    hotspots: 1-based positions like `contig` (an iterable of ints), or a bool mask of the result's shape (or (L,)).
+    repel: None; a bool mask; or, with a batch, 'context' (every real residue that is not generated) / 'antigen' (fragment_type 3).
+    The kernel ignores the bits of generated and of masked-out residues, so a mask need not be exact there."""
+    if isinstance(batch_or_length, dict):
+        batch = batch_or_length
+        shape, device = tuple(batch['aa'].shape), batch['aa'].device
+    else:
+        batch, shape = None, (int(batch_or_length),)
+    L = shape[-1]
+    role = torch.zeros(shape, dtype=torch.int32, device=device)
+
+    def as_mask(name, m):
+        m = torch.as_tensor(m, device=role.device)
+        if m.dtype != torch.bool or m.shape[-1] != L or m.dim() > len(shape) or (m.dim() == len(shape) and tuple(m.shape) != shape):
+            raise ValueError(f'{name}: expected a bool mask of shape {shape} or ({L},), got {m.dtype} {tuple(m.shape)}')
+        return m.expand(shape)
+    if hotspots is not None:
+        if torch.is_tensor(hotspots) and hotspots.dtype == torch.bool:
+            hot = as_mask('hotspots', hotspots)
+        else:
+            hot = torch.zeros(L, dtype=torch.bool)
+            for pos in (hotspots.tolist() if torch.is_tensor(hotspots) else hotspots):
+                if int(pos) != pos or not 1 <= int(pos) <= L:
+                    raise ValueError(f'hotspot position {pos!r} is outside 1..{L}')
+                hot[int(pos) - 1] = True
+            hot = hot.to(role.device).expand(shape)
+        role = role | torch.where(hot, ROLE_HOTSPOT, 0).to(torch.int32)
+    if repel is not None:
+        if isinstance(repel, str):
+            if batch is None or repel not in ('context', 'antigen'):
+                raise ValueError(f"repel={repel!r}: 'context' and 'antigen' need a batch dict; otherwise pass a bool mask")
+            rm = torch.logical_and(batch['mask'].bool(), ~batch['generate_flag'].bool()) if repel == 'context' else batch['fragment_type'] == 3
+        else:
+            rm = as_mask('repel', repel)
+        role = role | torch.where(rm, ROLE_REPEL, 0).to(torch.int32)
+    return role
+
+
 def generate_random_mask_from(tensor, mask_ratio_min, mask_ratio_max):
     """diffab.py:166-180."""
     ratio = float(torch.empty(1).uniform_(mask_ratio_min, mask_ratio_max))
@@ -141,7 +186,9 @@ class _DiffabBase(nn.Module):
         v_0 = hip.so3_log(R_0, grad_mode=False)
         opt = {k: v for k, v in sample_opt.items() if k != 'contig'}
         # batch['aa_allowed'] (optional, (N, L); no reference counterpart): the types each generated residue may take -- with a contig, at those that remain generated
-        return self.diffusion.sample(v_0, p_0, batch['aa'], res_feat, pair_feat, mask_generate, mask_res, aa_allowed=batch.get('aa_allowed'), **opt)
+        # batch['guide_role'] (optional, (N, L); no reference counterpart): hotspot and repeller residues of guided sampling (guide_roles); the knobs ride in sample_opt
+        return self.diffusion.sample(v_0, p_0, batch['aa'], res_feat, pair_feat, mask_generate, mask_res, aa_allowed=batch.get('aa_allowed'),
+                                     guide_role=batch.get('guide_role'), **opt)
 
     @torch.no_grad()
     def optimize(self, batch, opt_step, optimize_opt={'sample_structure': True, 'sample_sequence': True}):
@@ -151,7 +198,7 @@ class _DiffabBase(nn.Module):
                                                     remove_sequence=optimize_opt.get('sample_sequence', True))
         v_0 = hip.so3_log(R_0, grad_mode=False)
         return self.diffusion.optimize(v_0, p_0, batch['aa'], opt_step, res_feat, pair_feat, mask_generate, mask_res, aa_allowed=batch.get('aa_allowed'),
-                                       **optimize_opt)
+                                       guide_role=batch.get('guide_role'), **optimize_opt)
 
 
 @register_model('diffab_abdock')

@@ -297,6 +297,8 @@ def sample_replicated(model, complex_batch, num_samples, sample_opt=None, optimi
     masks = (rep(one['generate_flag']), rep(one['mask']))
     if one.get('aa_allowed') is not None:                       # the complex's allowed residue types: replicated like generate_flag
         sample_opt['aa_allowed'] = rep(one['aa_allowed'])
+    if one.get('guide_role') is not None:                       # the complex's hotspots and repellers (model.guide_roles): the knobs ride in sample_opt
+        sample_opt['guide_role'] = rep(one['guide_role'])
     if optimize_step is None:
         return model.diffusion.sample(*args, res_feat, pair_feat, *masks, **sample_opt)
     return model.diffusion.optimize(*args, optimize_step, res_feat, pair_feat, *masks, **sample_opt)
@@ -345,6 +347,8 @@ def sample_grouped(model, complexes, num_samples, sample_opt=None, optimize_step
     L = max(max(int(c['aa'].shape[1]) for c in complexes), int(pad_to or 0))
     if any(c.get('aa_allowed') is not None for c in complexes):      # allowed residue types of some complexes: the others allow every type
         complexes = [c if c.get('aa_allowed') is not None else dict(c, aa_allowed=torch.full_like(c['aa'], -1, dtype=torch.int32)) for c in complexes]
+    if any(c.get('guide_role') is not None for c in complexes):      # roles of some complexes: the others have neither hotspots nor repellers, nothing moves there
+        complexes = [c if c.get('guide_role') is not None else dict(c, guide_role=torch.zeros_like(c['aa'], dtype=torch.int32)) for c in complexes]
     padded = [pad_complex(c, L) for c in complexes]
     batch = {k: (torch.cat([c[k][:1] for c in padded], 0) if torch.is_tensor(v) else v) for k, v in padded[0].items()}
     res_feat, pair_feat, R_0, p_0 = model.encode(batch, remove_structure=sample_opt.get('sample_structure', True),
@@ -355,6 +359,8 @@ def sample_grouped(model, complexes, num_samples, sample_opt=None, optimize_step
     masks = (rep(batch['generate_flag']), rep(batch['mask']))
     if batch.get('aa_allowed') is not None:
         sample_opt['aa_allowed'] = rep(batch['aa_allowed'])
+    if batch.get('guide_role') is not None:
+        sample_opt['guide_role'] = rep(batch['guide_role'])
     if optimize_step is None:
         return model.diffusion.sample(*args, res_feat, pair_feat, *masks, **sample_opt)
     return model.diffusion.optimize(*args, optimize_step, res_feat, pair_feat, *masks, **sample_opt)

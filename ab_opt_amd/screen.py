@@ -140,7 +140,8 @@ def _scored_mean_std(t, dim):
 def optimize_antibody(dock_model, design_model, complex_, num_poses, designs_per_pose, redocks_per_design, design_flag=None, redock_flag=None,
                       contig='', screened_per_pose=1, seed=0, poses_per_launch=8, group=None, screen_by='first', timings=None, allowed_aa=None,
                       dock_steps=None, design_steps=None, cluster_cutoff=None, max_clusters=None, redock_cutoff=None, clash_cutoff=None, contact_cutoff=None,
-                      bond_max=None, seq_mismatch=None, share_redocks=False, lddt_cutoff=None, design_temperature=None, dock_noise_scale=None):
+                      bond_max=None, seq_mismatch=None, share_redocks=False, lddt_cutoff=None, design_temperature=None, dock_noise_scale=None,
+                      hotspots=None, dock_guide=None):
     """Dock -> redesign -> re-dock screen of one antibody-antigen complex (module docstring).
 
     complex_: batch dict with batch dim 1 (cropped, as sample_replicated takes it); its generate_flag marks the residues to dock.
@@ -161,6 +162,11 @@ def optimize_antibody(dock_model, design_model, complex_, num_poses, designs_per
     dock_noise_scale (optional, >= 0; default None: nothing changes, bit for bit): the scale of the structure noise of every dock and re-dock step
     (FullDPM.sample(noise_scale=lambda)); below 1 the ensembles tighten, 0 leaves the initial draw as a trajectory's only randomness.  What either does to hit
     rates is unmeasured.
+    hotspots / dock_guide (optional; default None: nothing changes, bit for bit): guided docking.  dock_guide is a dict of the guide_* knobs
+    of FullDPM.sample (guide_attract, guide_attract_radius, guide_repel, guide_repel_radius, guide_max_shift, guide_decay) and, optionally, repel = 'context' /
+    'antigen' / a bool mask (model.guide_roles); hotspots are 1-based positions like `contig`, or a bool mask (L,): the epitope the docked residues are pulled to.
+    Every dock and re-dock step is followed by the nudge; the design stage, which keeps the structure, is not guided.  hotspots without dock_guide is an error.  No
+    result key is added.  What guidance does to DockQ or to hit rates is unmeasured.
     cluster_cutoff (optional, Angstrom; default None: every pose goes on, nothing below changes): cluster the P poses after stage 1 and run stages 2 and 3 on the
     C cluster centres only (module docstring); max_clusters (optional, >= 1; needs cluster_cutoff) caps C -- poses left over at the cap keep label -1 and
     are not screened.  The result gains cluster_label (P,), cluster_centre (C,) (pose indices) and cluster_size (C,), all int64; pose_ca / pose_score
@@ -251,6 +257,16 @@ def optimize_antibody(dock_model, design_model, complex_, num_poses, designs_per
     mine = b - a
     depth = dict(dock=dock_steps, design=design_steps, redock=dock_steps)
     noise = {} if dock_noise_scale is None else dict(noise_scale=hip.check_noise_scale('optimize_antibody: dock_noise_scale', dock_noise_scale))
+    guide_extra = {}
+    if dock_guide is not None:
+        from . import model as model_
+        dg = dict(dock_guide)
+        repel = dg.pop('repel', None)
+        if hotspots is not None or repel is not None or one.get('guide_role') is None:
+            guide_extra = dict(guide_role=model_.guide_roles(one, hotspots=hotspots, repel=one['mask'].bool() if isinstance(repel, str) and repel == 'context' else repel))
+        noise = dict(noise, **hip.check_guidance(**dg))                 # the dock and re-dock stages' options: the knobs ride beside noise_scale
+    elif hotspots is not None:
+        raise ValueError('optimize_antibody: hotspots need dock_guide (e.g. dict(guide_attract=0.5)): without a weight nothing is pulled')
     knobs = dict(dock=noise, redock=noise,          # None adds no key: the stage's options, and so its loop, are those of a call without the argument
                  design={} if design_temperature is None else dict(seq_temperature=hip.check_temperature('optimize_antibody: design_temperature', design_temperature)))
     rngs = lambda stage, lo, kk=k: dict(seed=stage_seed(seed, stage), rng_offset=stage_rng_offset(stage, lo, L, S, kk, D),
@@ -276,7 +292,7 @@ def optimize_antibody(dock_model, design_model, complex_, num_poses, designs_per
     geom_cols = ('clash', 'contacts', 'iface1', 'iface2', 'breaks')
     for lo, hi in plan:
         n = hi - lo
-        traj = sampler.sample_replicated(dock_model, one, n, dict(sample_structure=True, sample_sequence=False, **rngs('dock', lo)))
+        traj = sampler.sample_replicated(dock_model, _with(one, **guide_extra), n, dict(sample_structure=True, sample_sequence=False, **rngs('dock', lo)))
         rep = lambda t: t.expand(n, *t.shape[1:]).contiguous()
         pos, mask = _rebuild(rep(one['pos_heavyatom']), rep(one['mask_heavyatom']), traj[0], 0, n, rep(one['aa']), gen, one)
         pose_pos[lo - a:hi - a], pose_mask[lo - a:hi - a] = pos, mask
@@ -355,7 +371,7 @@ def optimize_antibody(dock_model, design_model, complex_, num_poses, designs_per
     def redock(npos, nmask, naa, rng):
         """D re-docks of each of the n given design complexes -> their rebuilt coordinates and everything that depends on the trajectories alone."""
         n = npos.shape[0]
-        cx = [_with(one, pos_heavyatom=npos[i:i + 1], mask_heavyatom=nmask[i:i + 1], aa=naa[i:i + 1], generate_flag=rflag[None]) for i in range(n)]
+        cx = [_with(one, pos_heavyatom=npos[i:i + 1], mask_heavyatom=nmask[i:i + 1], aa=naa[i:i + 1], generate_flag=rflag[None], **guide_extra) for i in range(n)]
         traj = sampler.sample_grouped(dock_model, cx, D, dict(sample_structure=True, sample_sequence=False, **rng), pad_to=L)
         rep = lambda t: t.repeat_interleave(D, dim=0)
         pos, mask = _rebuild(rep(npos), rep(nmask), traj[0], 0, n * D, rep(naa), rflag, one)

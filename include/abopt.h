@@ -23,7 +23,7 @@
 extern "C" {
 #endif
 
-#define ABOPT_ABI_VERSION 55
+#define ABOPT_ABI_VERSION 56
 
 enum { ABOPT_OK = 0, ABOPT_EINVAL = 1, ABOPT_EHIP = 2, ABOPT_EUNSUPPORTED = 3, ABOPT_EWORKSPACE = 4 };
 
@@ -780,6 +780,33 @@ int abopt_lddt_ca_ensemble(const float* pos, const uint8_t* mask, int mask_share
 size_t abopt_sasa_ws_bytes(int G, int S, int L, int A);
 int abopt_sasa_grouped(const float* pos, const uint8_t* mask, int mask_shared, const int32_t* group, const float* radius, const float* dirs, int n_points,
                        int G, int S, int L, int A, float probe, float k, void* pts, void* area, void* ws, size_t ws_bytes, abopt_stream stream);
+
+/* ---- Guided sampling (ABI 56; no reference counterpart): after a reverse step t -> u, a geometric potential nudges the generated
+ * residues of every sample -- towards an epitope, away from clashes.  In place on the step's stored state:
+ *   p [N,L,3] fp32, Angstrom (the step's p_next); p_norm (optional, may be NULL) [N,L,3], its normalised copy (p_next_norm); mask_generate, mask_res [N,L];
+ *   role [N,L] int32: bit 0 marks a hotspot, bit 1 a repeller, other bits are ignored.  role_shared = S > 0: role is [N/S,L] and sample n reads row n / S
+ *   (the convention of pair_feat_shared); 0: one row per sample.
+ *   row sets    per sample: the moved rows M = gen & res; the context rows ctx = res & ~gen; H = ctx & bit 0; R = ctx & bit 1.  Role bits on generated or
+ *               masked-out rows mean nothing.
+ *   scalars     fp32, finite and >= 0: w_att <= 1, r_att, w_rep, r_rep, max_shift > 0; position_scale > 0 and position_mean[3] (HOST) as abopt_step_params
+ *               carries them.
+ *   attraction  a rigid pull of the generated set towards the hotspots: with M and H both non-empty, d = mean_H p - mean_M p, D = |d|,
+ *               a = w_att max(D - r_att, 0) / D d; a = 0 if D = 0 or either set is empty.  The same a applies to every moved row; with w_att <= 1 the pull
+ *               never overshoots.
+ *   repulsion   per moved row i: f_i = w_rep sum_{j in R} max(r_rep - d_ij, 0) / d_ij (p_i - p_j); a pair with d_ij^2 < 1e-12 contributes 0.  Moved rows do
+ *               not repel one another: the network owns the loop's internal geometry.
+ *   shift       D_i = a + f_i; if |D_i| > max_shift then D_i <- D_i max_shift / |D_i|.
+ *   write-back  for the moved rows whose D_i has a non-zero component: p_i <- p_i + D_i and p_norm_i <- (p_i - position_mean) / position_scale per component,
+ *               the formula of the step itself.  Every other element of p and p_norm keeps its bits.
+ * All forces are formed from the positions BEFORE the update: only M changes, and the forces read context rows and the old centroid of M.  The potential is
+ * continuous everywhere (its branch points are the two max(., 0) and the cap, and the shift is continuous at each), so the device is held to a float64 statement
+ * of the above by a tolerance, not bit for bit; the sums are taken in fp32 in a fixed order (coordinates relative to position_mean), so repeated calls agree bit
+ * for bit.  One launch, one workgroup per sample; no float atomic, no workspace, no memset, no host synchronisation: capturable into a hipGraph.
+ * N = 0 or L = 0 is a no-op, and so is w_att = w_rep = 0.  A NULL pointer (p_norm apart), N % S != 0, a negative or non-finite scalar, w_att > 1, max_shift = 0 or
+ * position_scale = 0: ABOPT_EINVAL with a message, before any launch.  The caller scales w_att and w_rep per step (Python: guide_decay). */
+int abopt_guide_positions(float* p, float* p_norm, const uint8_t* mask_generate, const uint8_t* mask_res, const int32_t* role, int role_shared, int N, int L,
+                          float w_att, float r_att, float w_rep, float r_rep, float max_shift, float position_scale, const float* position_mean,
+                          abopt_stream stream);
 
 /* ---- Measurement hook (bench.py's roofline leg).  When enabled, every launch of the IPA-core kernel is bracketed
  * by hipEvents on the stream it is launched on; abopt_prof_collect synchronises those events and returns the number

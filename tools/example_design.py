@@ -3,11 +3,13 @@
 
     encode once -> N samples of one complex (shared context) -> all-atom backbone of every sample -> rank by commonness
 
-    python tools/example_design.py [num_samples] [L] [--steps K] [--temperature TAU] [--noise-scale LAMBDA]
+    python tools/example_design.py [num_samples] [L] [--steps K] [--temperature TAU] [--noise-scale LAMBDA] [--hotspots P,Q,...] [--guide-attract W]
 
 --steps K: K network evaluations per sample over the evenly respaced sub-sequence of the 100 trained steps (default: all 100).
 --temperature TAU / --noise-scale LAMBDA: draw the residue types at temperature TAU (0: greedy) / add LAMBDA times the structure noise at every step
 (default 1 and 1: the plain sampler).
+--hotspots P,Q,... / --guide-attract W: after every step pull the generated residues, as one rigid set, towards the centroid of the residues at these 1-based
+positions with weight W <= 1 (guided sampling; the 8 A radius and the 2 A cap per step are conventional values).
 """
 import os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -30,12 +32,16 @@ def flag(name, kind, default):
 
 K = flag('--steps', int, 100)
 TAU, LAMBDA = flag('--temperature', float, 1.0), flag('--noise-scale', float, 1.0)
+HOTSPOTS, ATTRACT = flag('--hotspots', lambda t: [int(x) for x in t.split(',') if x], None), flag('--guide-attract', float, 0.0)
 n = int(argv[0]) if len(argv) > 0 else 16
 L = int(argv[1]) if len(argv) > 1 else 256
 dev = torch.device('cuda:0')
 model = build_model(100, 7, flavour='abdock', device=dev).eval()
 complex_ = {k: v.to(dev) for k, v in make_batch(1, LAYOUT_256 if L == 256 else LAYOUT_128, seed=2022).items()}
-opt = {'sample_structure': True, 'sample_sequence': True, 'steps': K, 'seq_temperature': TAU, 'noise_scale': LAMBDA}
+opt = {'sample_structure': True, 'sample_sequence': True, 'steps': K, 'seq_temperature': TAU, 'noise_scale': LAMBDA, 'guide_attract': ATTRACT}
+if HOTSPOTS:
+    from ab_opt_amd.model import guide_roles
+    complex_['guide_role'] = guide_roles(complex_, hotspots=HOTSPOTS)
 rep = lambda a: a.expand(n, *a.shape[1:]).contiguous()
 
 

@@ -5,7 +5,8 @@ stage and the designs the notebook's median filter keeps.
                                     --dock-steps 20 --design-steps 20 --cluster-cutoff 2.0 --max-clusters 4 --redock-cutoff 2.0
                                     --clash-cutoff 3.0 --contact-cutoff 5.0 --bond-max 2.0
                                     --seq-mismatch 2 --screen-by diverse --share-redocks --allow A,G,S,T,AV,LK,DE --lddt-cutoff 15.0
-                                    --design-temperature 0.2 --dock-noise-scale 0.5]
+                                    --design-temperature 0.2 --dock-noise-scale 0.5
+                                    --hotspots 150,151,152 --guide-attract 0.5 --guide-repel 0.5]
 
 --cluster-cutoff clusters the docked poses on the device and screens one centre per cluster: the run prints the number of clusters C,
 their sizes and the stage times.  How many clusters a trained model's poses fall into is unmeasured.
@@ -28,6 +29,11 @@ re-docks disagree with the design.  What lDDT values trained weights produce, an
 --design-temperature TAU draws the design stage's residue types at temperature TAU (0: greedy) and --dock-noise-scale LAMBDA scales the structure noise of every
 dock and re-dock step: with --seq-mismatch the run shows how the families per pose shrink, and the last line before the table how
 dockq_std moves.  That is what hash-filled weights do; what either knob does to the hit rate of a trained model is unmeasured.
+
+--hotspots P,Q,... (1-based positions of antigen residues) with --guide-attract W pulls the docked residues of every dock and re-dock step towards the centroid
+of those residues, and --guide-repel W pushes each of them out of 3 A of every other residue of the complex (guided sampling; 8 A, 3 A and
+the 2 A cap per step are conventional values, not tuned ones).  The run prints the distance of the docked residues' centroid from the hotspots' over the poses.
+What guidance does to DockQ or to hit rates of a trained model is unmeasured.
 
 The weights are not a trained checkpoint, so the numbers say nothing about antibodies; the stage times are what a screen of this size costs.
 """
@@ -72,6 +78,9 @@ def main():
     ap.add_argument('--lddt-cutoff', type=float, default=None, metavar='A', help='score every re-dock by lDDT-CA at this inclusion radius (15.0 is the usual one)')
     ap.add_argument('--design-temperature', type=float, default=None, metavar='TAU', help='temperature of the designed residue types (0: greedy; default: 1, the plain sampler)')
     ap.add_argument('--dock-noise-scale', type=float, default=None, metavar='LAMBDA', help='scale of the structure noise of every dock / re-dock step (default: 1)')
+    ap.add_argument('--hotspots', default='', metavar='P,Q,...', help='1-based positions of the residues the docked residues are pulled to (needs --guide-attract)')
+    ap.add_argument('--guide-attract', type=float, default=0.0, metavar='W', help='weight (<= 1) of the pull towards the hotspots after every dock / re-dock step')
+    ap.add_argument('--guide-repel', type=float, default=0.0, metavar='W', help='weight of the push of every docked residue out of 3 A of the other residues')
     ap.add_argument('--allow', default='', metavar='SETS', help='allowed types per contig position, comma-separated in contig order, e.g. A,G,S,T,AV,LK,DE')
     args = ap.parse_args()
     dev = torch.device('cuda:0')
@@ -87,13 +96,17 @@ def main():
         first = int(args.contig.split('-')[0])
         at = {first + i: letters for i, letters in enumerate(args.allow.split(','))} if args.allow else None
         allowed = model.aa_allowed_mask(one['aa'].shape[1], exclude=args.exclude, at=at, device=dev)
+    hotspots = [int(x) for x in args.hotspots.split(',') if x] or None
+    guide = None
+    if args.guide_attract or args.guide_repel:
+        guide = dict(guide_attract=args.guide_attract, guide_repel=args.guide_repel, repel='context' if args.guide_repel else None)
     kw = dict(num_poses=args.poses, designs_per_pose=args.designs, redocks_per_design=args.redocks, screened_per_pose=args.screened,
               contig=args.contig, seed=args.seed, poses_per_launch=args.per_launch, redock_flag=heavy,
               dock_steps=args.dock_steps, design_steps=args.design_steps,
               cluster_cutoff=args.cluster_cutoff, max_clusters=args.max_clusters, redock_cutoff=args.redock_cutoff,
               clash_cutoff=args.clash_cutoff, contact_cutoff=args.contact_cutoff, bond_max=args.bond_max,
               allowed_aa=allowed, seq_mismatch=args.seq_mismatch, screen_by=args.screen_by, share_redocks=args.share_redocks, lddt_cutoff=args.lddt_cutoff,
-              design_temperature=args.design_temperature, dock_noise_scale=args.dock_noise_scale)
+              design_temperature=args.design_temperature, dock_noise_scale=args.dock_noise_scale, hotspots=hotspots, dock_guide=guide)
     print(f'L={one["aa"].shape[1]} P={args.poses} S={args.designs} k={args.screened} D={args.redocks} T={args.steps} dock_steps={args.dock_steps or args.steps} design_steps={args.design_steps or args.steps} per_launch={args.per_launch} '
           f'contig={args.contig!r} device={torch.cuda.get_device_name(dev)}')
     t0 = time.perf_counter()
@@ -143,6 +156,11 @@ def main():
                       f'{res["redock_consistency"][p, j].mean().item():7.4f}  {low}')
     print(f'design_temperature={args.design_temperature} dock_noise_scale={args.dock_noise_scale}: dockq_std mean {res["dockq_std"].mean().item():.4f} '
           f'prmsd_std mean {res["prmsd_std"].mean().item():.4f} over {res["dockq_std"].numel()} screened designs')
+    if hotspots:
+        hot = one['pos_heavyatom'][0, [h - 1 for h in hotspots], 1].mean(0)           # CA of the hotspot residues
+        dist = (res['pose_ca'].mean(1) - hot).norm(dim=-1)
+        print(f'hotspots {hotspots} guide_attract={args.guide_attract} guide_repel={args.guide_repel}: centroid of the docked residues to the hotspots\' centroid, '
+              f'mean {dist.mean().item():.2f} A, min {dist.min().item():.2f} A, max {dist.max().item():.2f} A over {dist.numel()} poses')
     keep = screen.screen_filter(res)
     print(f'{int(keep.sum())} of {keep.numel()} screened designs pass the median filter')
     print(f'{"pose":>4} {"design":>6} {"seq":>9} {"AAR":>6} {"PPL":>7} {"DockQ_avg":>9} {"DockQ_std":>9} {"prmsd_avg":>9} {"prmsd_std":>9}')
