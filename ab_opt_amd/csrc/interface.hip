@@ -7,50 +7,17 @@
 #include <math.h>
 #include <algorithm>
 #include "abopt_common.h"
+#include "candidate_common.h"
 #include "kernels.h"
 
 namespace abopt {
 
-constexpr int IG_MAX_A = 15;               // atoms per residue: the project's maximum (pos_heavyatom)
 constexpr int IG_T1 = 16;                  // side-1 residues staged at a time: 4 per wave
 constexpr int IG_T2 = 64;                  // side-2 residues staged at a time: one per lane
-constexpr int IG_MAX_SLICES = 64;          // workgroups a candidate is split over at most
-constexpr int IG_GRID_X = 1 << 22;         // workgroups along x: candidates beyond fold into y (x times the 256 threads of a workgroup has to stay under 2^32)
 constexpr int IG_WS_COUNTERS = 4;          // int32 per candidate behind its bit row: clash, contacts, breaks, (pad)
 
-// The ONE distance of this file: fmaf(dz, dz, fmaf(dy, dy, dx dx)) with every step rounded once, spelled so that the compiler contracts nothing
-// differently in different places.  (x - y)^2 == (y - x)^2, so d2(p, q) == d2(q, p) bit for bit.
-__device__ __forceinline__ float ig_d2(float ax, float ay, float az, float bx, float by, float bz) {
-    const float dx = __fsub_rn(ax, bx), dy = __fsub_rn(ay, by), dz = __fsub_rn(az, bz);
-    return fmaf(dz, dz, fmaf(dy, dy, __fmul_rn(dx, dx)));
-}
-
-// Wave-uniform: append the residues r >= cur with grp[r] == side to idx[0 .. cap), in index order, until `cap` are found or the row ends; cur moves past
-// the last residue taken.  Every wave of the workgroup runs this with the same arguments and gets the same answer (no exchange needed); `write` picks the
-// one that stores.  idx == nullptr with write == false just skips `cap` residues of the side.
-__device__ __forceinline__ int ig_take(const int32_t* __restrict__ grp, int L, int side, int& cur, int cap, int* idx, bool write) {
-    const int lane = threadIdx.x & 63;
-    int n = 0;
-    while (n < cap && cur < L) {
-        const int r = cur + lane;
-        const bool f = r < L && grp[r] == side;
-        const unsigned long long b = __ballot(f);
-        const int pos = n + __popcll(b & ((1ull << lane) - 1ull));
-        if (write && f && pos < cap) idx[pos] = r;
-        const int tot = __popcll(b);
-        if (n + tot >= cap) {
-            cur += __ffsll((long long)__ballot(f && pos == cap - 1));            // the lane that filled the last place: 1-based, so this is "one past it"
-            n = cap;
-        } else {
-            n += tot;
-            cur += 64;
-        }
-    }
-    return n;
-}
-
 // Bounding sphere of one residue from its staged atoms (masked-out atoms are NaN there and are told apart by the mask word `m`): centre = mean of the masked
-// atoms, radius = the largest ig_d2 distance from that centre.  No atoms: radius -inf, which the prune below always skips.  A NaN coordinate makes centre
+// atoms, radius = the largest d2_fma distance from that centre.  No atoms: radius -inf, which the prune below always skips.  A NaN coordinate makes centre
 // and radius NaN, which the prune never skips (every comparison with NaN is false).
 __device__ __forceinline__ float4 ig_sphere(const float* __restrict__ atoms, int stride, int A, unsigned m) {
     float sx = 0.f, sy = 0.f, sz = 0.f;
@@ -62,7 +29,7 @@ __device__ __forceinline__ float4 ig_sphere(const float* __restrict__ atoms, int
     float r2 = 0.f;
     for (int p = 0; p < A; ++p)
         if ((m >> p) & 1u) {
-            const float d2 = ig_d2(cx, cy, cz, atoms[p * stride], atoms[p * stride + 1], atoms[p * stride + 2]);
+            const float d2 = d2_fma(cx, cy, cz, atoms[p * stride], atoms[p * stride + 1], atoms[p * stride + 2]);
             r2 = d2 > r2 ? d2 : (d2 == d2 ? r2 : d2);                          // a NaN distance sticks
         }
     return make_float4(cx, cy, cz, sqrtf(r2));
@@ -70,7 +37,7 @@ __device__ __forceinline__ float4 ig_sphere(const float* __restrict__ atoms, int
 
 // Grid (candidate folded over x and y, slice in z), 4 waves.  The side-1 residues of the candidate are numbered in index order and slice s takes the ranks
 // [n1 s / slices, n1 (s + 1) / slices): the re-dock shape has fewer candidates than the chip has CUs.  Per workgroup:
-//   side-1 tile   up to 16 residues of the slice: indices compacted by ballots (ig_take), atoms staged in LDS as float4 (masked-out atoms as NaN: they
+//   side-1 tile   up to 16 residues of the slice: indices compacted by ballots (take, candidate_common.h), atoms staged in LDS as float4 (masked-out atoms as NaN: they
 //                 drop out of every comparison below, like a NaN coordinate does by definition), mask words and bounding spheres next to them
 //   side-2 tile   up to 64 residues, compacted likewise, atoms staged with an odd stride, spheres; then every lane holds ITS residue's atoms in registers
 //   pairs         a wave owns one side-1 residue at a time (4 per tile) against the 64 lanes.  Prune: the pair is entered unless the spheres prove that no atom
@@ -80,7 +47,7 @@ __device__ __forceinline__ float4 ig_sphere(const float* __restrict__ atoms, int
 //   marks         one atomicOr per marked residue into the candidate's bit row in the workspace; counters by one atomicAdd per wave.
 // LDS: 3.8 KB + 11.5 KB of atoms + 1.7 KB of indices, masks and spheres, whatever L is.
 //
-// The prune is conservative in fp32.  Every distance here is ig_d2 between two fp32 POINTS followed (for the spheres) by sqrtf: the subtraction of two fp32
+// The prune is conservative in fp32.  Every distance here is d2_fma (candidate_common.h) between two fp32 POINTS followed (for the spheres) by sqrtf: the subtraction of two fp32
 // numbers is rounded once, relative to the difference (u = 2^-24) whatever the magnitude of the coordinates, the square and the two fmas add three more
 // roundings of non-negative terms, so a computed d2 is the true one x (1 +- 5 u) and a computed distance the true one x (1 +- 4 u).  The centre is whatever
 // fp32 point the mean rounds to -- the radius is measured from THAT point, so the mean's own rounding costs tightness, not correctness.  For atoms p of a, q of b
@@ -100,7 +67,7 @@ __global__ __launch_bounds__(256) void interface_pairs_kernel(const float* __res
     __shared__ __attribute__((aligned(16))) float4 sph2[IG_T2];
     __shared__ int idx1[IG_T1], idx2[IG_T2];
     __shared__ unsigned msk1[IG_T1];
-    const int64_t c64 = (int64_t)blockIdx.y * gridDim.x + blockIdx.x;
+    const int64_t c64 = folded_block();
     if (c64 >= N) return;                                                       // the last row of a folded grid; block-uniform
     const int c = (int)c64, slice = blockIdx.z, slices = gridDim.z, g = c / S;
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
@@ -121,7 +88,7 @@ __global__ __launch_bounds__(256) void interface_pairs_kernel(const float* __res
             if (r < L - 1 && link[r] && mask[(int64_t)r * A + 2] && mask[(int64_t)(r + 1) * A]) {
                 const float* cp = pos + ((int64_t)r * A + 2) * 3;
                 const float* np_ = pos + (int64_t)(r + 1) * A * 3;
-                brk = !(ig_d2(cp[0], cp[1], cp[2], np_[0], np_[1], np_[2]) <= thr_bond);      // a NaN coordinate is a break
+                brk = !(d2_fma(cp[0], cp[1], cp[2], np_[0], np_[1], np_[2]) <= thr_bond);      // a NaN coordinate is a break
             }
             nb += __popcll(__ballot(brk));
         }
@@ -129,19 +96,17 @@ __global__ __launch_bounds__(256) void interface_pairs_kernel(const float* __res
     }
 
     // ---- this slice's ranks of side-1 residues (every wave counts the row itself: wave-uniform, no exchange)
-    int n1 = 0;
-    for (int r0 = 0; r0 < L; r0 += 64) n1 += __popcll(__ballot(r0 + lane < L && grp[r0 + lane] == 1));
-    const int lo = (int)((int64_t)n1 * slice / slices), hi = (int)((int64_t)n1 * (slice + 1) / slices);
-    if (lo == hi) return;                                                       // block-uniform
-    int cur1 = 0;
-    ig_take(grp, L, 1, cur1, lo, nullptr, false);
+    const OnSide side1{grp, 1}, side2{grp, 2};
+    int cur1;
+    int left = slice_ranks(L, side1, slice, slices, cur1);
+    if (left == 0) return;                                                      // block-uniform
 
     int clash = 0, contacts = 0;                                                // clash: per lane; contacts: wave-uniform
-    for (int left = hi - lo; left > 0;) {
+    while (left > 0) {
         __syncthreads();                                                        // the previous tile's reads are done
-        const int n1t = ig_take(grp, L, 1, cur1, min(IG_T1, left), idx1, wave == 0);
+        const int n1t = take(L, side1, cur1, min(IG_T1, left), idx1, wave == 0);
         left -= n1t;
-        if (n1t == 0) break;                                                    // cannot happen (n1 was counted on the same row); block-uniform
+        if (n1t == 0) break;                                                    // cannot happen (the ranks were counted on the same row); block-uniform
         __syncthreads();
         for (int t = tid; t < n1t * AQ; t += 256) {
             const int i = t / AQ, p = t % AQ, r = idx1[i];
@@ -160,7 +125,7 @@ __global__ __launch_bounds__(256) void interface_pairs_kernel(const float* __res
         int cur2 = 0;
         while (true) {
             __syncthreads();                                                    // the previous side-2 tile's reads are done (and sph1 is written)
-            const int n2t = ig_take(grp, L, 2, cur2, IG_T2, idx2, wave == 0);
+            const int n2t = take(L, side2, cur2, IG_T2, idx2, wave == 0);
             if (n2t == 0) break;                                                // block-uniform
             __syncthreads();
             for (int t = tid; t < n2t * (AQ * 3); t += 256) {
@@ -192,7 +157,7 @@ __global__ __launch_bounds__(256) void interface_pairs_kernel(const float* __res
                 const int a = idx1[i];
                 const float4 sa = sph1[i];
                 const float reach = fmaf(__fadd_rn(__fadd_rn(sa.w, sb.w), cut_max), 1.f + 1.52587890625e-5f, 0.01f);
-                bool skip = !live || sqrtf(ig_d2(sa.x, sa.y, sa.z, sb.x, sb.y, sb.z)) > reach;
+                bool skip = !live || sqrtf(d2_fma(sa.x, sa.y, sa.z, sb.x, sb.y, sb.z)) > reach;
                 if (link && live) skip = skip || (b == a + 1 && link[a]) || (a == b + 1 && link[b]);
                 if (__ballot(!skip) == 0ull) continue;
                 float best = INFINITY;
@@ -202,7 +167,7 @@ __global__ __launch_bounds__(256) void interface_pairs_kernel(const float* __res
                         const float4 pa = at1[i][p];                            // one broadcast read
 #pragma unroll
                         for (int q = 0; q < AQ; ++q) {
-                            const float d2 = ig_d2(pa.x, pa.y, pa.z, bx[q], by[q], bz[q]);
+                            const float d2 = d2_fma(pa.x, pa.y, pa.z, bx[q], by[q], bz[q]);
                             best = fminf(best, d2);                             // a NaN (masked-out or not a number) never lowers it
                             clash += d2 < thr_clash ? 1 : 0;
                         }
@@ -230,7 +195,7 @@ __global__ __launch_bounds__(256) void interface_pairs_kernel(const float* __res
 // group's freq row, and the five outputs stored.
 __global__ __launch_bounds__(256) void interface_count_kernel(const unsigned* __restrict__ ws_all, const int32_t* __restrict__ group_all, int32_t* __restrict__ out,
                                                               int32_t* __restrict__ freq, int N, int S, int L, int ws_stride) {
-    const int64_t c64 = ((int64_t)blockIdx.y * gridDim.x + blockIdx.x) * 4 + (threadIdx.x >> 6);
+    const int64_t c64 = folded_block() * 4 + (threadIdx.x >> 6);
     const int c = (int)c64, lane = threadIdx.x & 63;
     if (c64 >= N) return;                                                         // wave-uniform
     const int g = c / S;
@@ -272,27 +237,23 @@ extern "C" size_t abopt_interface_geometry_ws_bytes(int G, int S, int L) {
 extern "C" int abopt_interface_geometry_grouped(const float* pos, const uint8_t* mask, int mask_shared, const int32_t* group, const uint8_t* link,
                                                 int G, int S, int L, int A, float clash_d, float contact_d, float bond_max, void* out, void* freq,
                                                 void* ws, size_t ws_bytes, abopt_stream stream) {
-    ABOPT_CHECK_ARG(G >= 0 && S >= 0 && L >= 1 && A >= 1 && (int64_t)G * S <= 0x7fffffff && (int64_t)L * A * 3 <= 0x7fffffff,
-                    "interface_geometry_grouped: bad dims G=%d S=%d L=%d A=%d", G, S, L, A);
-    ABOPT_CHECK_ARG(A <= IG_MAX_A, "interface_geometry_grouped: A=%d atoms per residue exceed the maximum of %d", A, IG_MAX_A);
+    int rc = check_candidate_dims("interface_geometry_grouped", G, S, L, A);
+    if (rc != ABOPT_OK) return rc;
     ABOPT_CHECK_ARG(isfinite(clash_d) && clash_d >= 0.f && isfinite(contact_d) && contact_d >= 0.f,
                     "interface_geometry_grouped: the cutoffs must be finite and >= 0 (got clash %g, contact %g)", (double)clash_d, (double)contact_d);
     ABOPT_CHECK_ARG(isfinite(bond_max), "interface_geometry_grouped: bond_max must be finite (negative: breaks are not counted), got %g", (double)bond_max);
     ABOPT_CHECK_ARG(!link || A >= 3, "interface_geometry_grouped: link needs the backbone atoms N, CA, C (A >= 3, got %d)", A);
     if (G == 0 || S == 0) return ABOPT_OK;
-    ABOPT_CHECK_ARG(G <= 65535, "interface_geometry_grouped: G=%d groups exceed one launch (max 65535)", G);
+    if ((rc = check_group_count("interface_geometry_grouped", G)) != ABOPT_OK) return rc;
     ABOPT_CHECK_ARG(pos && mask && group && out && ws, "interface_geometry_grouped: NULL argument");
-    ABOPT_CHECK_ARG(((uintptr_t)ws & 3) == 0, "interface_geometry_grouped: the workspace must be 4-byte aligned");
     const size_t need = abopt_interface_geometry_ws_bytes(G, S, L);
-    if (ws_bytes < need) { set_error("interface_geometry_grouped: workspace too small (%zu bytes given, %zu needed)", ws_bytes, need); return ABOPT_EWORKSPACE; }
+    if ((rc = check_workspace("interface_geometry_grouped", ws, 4, ws_bytes, need)) != ABOPT_OK) return rc;
     hipStream_t st = (hipStream_t)stream;
     const int N = G * S, ws_stride = (L + 31) / 32 + IG_WS_COUNTERS;
     int cus = 0;
-    int rc = device_cu_count(&cus);
-    if (rc != ABOPT_OK) return rc;
+    if ((rc = device_cu_count(&cus)) != ABOPT_OK) return rc;
     // enough workgroups for four per CU, no slice thinner than four residues of the row
-    const int slices = (int)std::max<int64_t>(1, std::min<int64_t>(std::min<int64_t>(IG_MAX_SLICES, ((int64_t)L + 3) / 4), ((int64_t)cus * 4 + N - 1) / N));
-    auto fold = [](int64_t blocks, unsigned z) { const int64_t x = std::min<int64_t>(blocks, IG_GRID_X); return dim3((unsigned)x, (unsigned)((blocks + x - 1) / x), z); };
+    const int slices = slice_count(cus, 4, N, ((int64_t)L + 3) / 4);
     const float thr_clash = clash_d * clash_d, thr_contact = contact_d * contact_d, thr_bond = bond_max * bond_max;   // each rounded once
     const float cut_max = clash_d > contact_d ? clash_d : contact_d;
     const int count_breaks = bond_max >= 0.f ? 1 : 0;
@@ -301,11 +262,11 @@ extern "C" int abopt_interface_geometry_grouped(const float* pos, const uint8_t*
     const size_t clear_blocks = std::min<size_t>((std::max(nws, nfreq) + 255) / 256, 4096);
     hipLaunchKernelGGL(interface_clear_kernel, dim3((unsigned)clear_blocks), dim3(256), 0, st, (unsigned*)ws, nws, (unsigned*)freq, nfreq);
     ABOPT_LAUNCH_CHECK();
-    auto kernel = A <= 4 ? interface_pairs_kernel<4> : A <= 8 ? interface_pairs_kernel<8> : interface_pairs_kernel<IG_MAX_A>;
-    hipLaunchKernelGGL(kernel, fold((int64_t)N, (unsigned)slices), dim3(256), 0, st, pos, mask, mask_shared ? 1 : 0, group, link, (unsigned*)ws, N, S, L, A,
+    auto kernel = A <= 4 ? interface_pairs_kernel<4> : A <= 8 ? interface_pairs_kernel<8> : interface_pairs_kernel<kMaxAtoms>;
+    hipLaunchKernelGGL(kernel, fold_grid(N, (unsigned)slices), dim3(256), 0, st, pos, mask, mask_shared ? 1 : 0, group, link, (unsigned*)ws, N, S, L, A,
                        ws_stride, thr_clash, thr_contact, cut_max, thr_bond, count_breaks);
     ABOPT_LAUNCH_CHECK();
-    hipLaunchKernelGGL(interface_count_kernel, fold(((int64_t)N + 3) / 4, 1u), dim3(256), 0, st, (const unsigned*)ws, group, (int32_t*)out, (int32_t*)freq,
+    hipLaunchKernelGGL(interface_count_kernel, fold_grid(((int64_t)N + 3) / 4, 1u), dim3(256), 0, st, (const unsigned*)ws, group, (int32_t*)out, (int32_t*)freq,
                        N, S, L, ws_stride);
     ABOPT_LAUNCH_CHECK();
     return ABOPT_OK;

@@ -7,9 +7,10 @@
 #include <math.h>
 #include <algorithm>
 #include "abopt_common.h"
+#include "candidate_common.h"
 #include "kernels.h"
 
-// Every fp32 step of this file is rounded once; nothing may be contracted into an fma.  hipcc contracts a * b + c across statements and across inlined
+// Every fp32 step of this file is rounded once; nothing may be contracted into an fma.  (So d2_fma of candidate_common.h is not for this file.)  hipcc contracts a * b + c across statements and across inlined
 // functions by default, and __fadd_rn / __fsub_rn / __fmul_rn are plain operators to it that carry the permission with them from their header: written with
 // them, q = c + R u and d2 were compiled to v_fma_f32 / v_fmac_f32.  So the round-to-nearest steps are spelled sa_add / sa_sub / sa_mul below -- the same
 // operators, compiled under contract(off), which no later pass may fuse.  The two fmaf of the prune are explicit.
@@ -17,11 +18,8 @@
 
 namespace abopt {
 
-constexpr int SA_MAX_A = 15;               // atoms per residue: the project's maximum (pos_heavyatom)
 constexpr int SA_MAX_POINTS = 1024;        // test points per atom
 constexpr int SA_TO = 64;                  // occluder residues staged at a time: one per lane for the prune
-constexpr int SA_MAX_SLICES = 64;          // workgroups a candidate is split over at most
-constexpr int SA_GRID_X = 1 << 22;         // workgroups along x: the rest folds into y
 constexpr float SA_MAX_RADIUS = 16.f;      // a larger van der Waals radius takes no part
 
 __device__ __forceinline__ float sa_add(float a, float b) { return a + b; }
@@ -40,30 +38,6 @@ __device__ __forceinline__ float sa_d2(float ax, float ay, float az, float bx, f
     return sa_add(sa_add(sa_mul(dx, dx), sa_mul(dy, dy)), sa_mul(dz, dz));
 }
 
-// Wave-uniform: append the residues r >= cur with grp[r] in {1, 2} to idx[0 .. cap), in index order, until `cap` are found or the row ends; cur moves past the
-// last residue taken.  Every wave of the workgroup runs this with the same arguments and gets the same answer; `write` picks the one that stores.
-__device__ __forceinline__ int sa_take(const int32_t* __restrict__ grp, int L, int& cur, int cap, int* idx, bool write) {
-    const int lane = threadIdx.x & 63;
-    int n = 0;
-    while (n < cap && cur < L) {
-        const int r = cur + lane;
-        const int s = r < L ? grp[r] : 0;
-        const bool f = s == 1 || s == 2;
-        const unsigned long long b = __ballot(f);
-        const int pos = n + __popcll(b & ((1ull << lane) - 1ull));
-        if (write && f && pos < cap) idx[pos] = r;
-        const int tot = __popcll(b);
-        if (n + tot >= cap) {
-            cur += __ffsll((long long)__ballot(f && pos == cap - 1));                // the lane that filled the last place: 1-based, so "one past it"
-            n = cap;
-        } else {
-            n += tot;
-            cur += 64;
-        }
-    }
-    return n;
-}
-
 // One thread per (candidate, residue): the residue's bounding sphere into the workspace -- centre = the mean of its participating atoms, radius = the largest
 // (distance from the centre + R) over them, so that every point an atom of the residue can hide lies inside; (0, 0, 0, -inf) for a residue that takes no part or
 // has no participating atom (the prune always skips it; it hides nothing anyway) -- and zeroes for the residue's two areas and, from residue 0, the candidate's
@@ -71,7 +45,7 @@ __device__ __forceinline__ int sa_take(const int32_t* __restrict__ grp, int L, i
 __global__ __launch_bounds__(256) void sasa_prepare_kernel(const float* __restrict__ pos_all, const uint8_t* __restrict__ mask_all, int mask_shared,
                                                            const int32_t* __restrict__ group_all, const float* __restrict__ radius_all, float4* __restrict__ sph_all,
                                                            int32_t* __restrict__ pts, float* __restrict__ area, int64_t rows, int S, int L, int A, float probe) {
-    const int64_t row = ((int64_t)blockIdx.y * gridDim.x + blockIdx.x) * 256 + threadIdx.x;
+    const int64_t row = folded_block() * 256 + threadIdx.x;
     if (row >= rows) return;
     const int64_t c = row / L;
     const int r = (int)(row - c * L);
@@ -106,7 +80,7 @@ __global__ __launch_bounds__(256) void sasa_prepare_kernel(const float* __restri
 
 // Grid (candidate folded over x and y, slice in z), 4 waves.  The participating residues of the candidate (group 1 or 2) are numbered in index order and slice s
 // takes the ranks [np s / slices, np (s + 1) / slices): the re-dock shape has fewer candidates than the chip has CUs.  Per workgroup:
-//   target tile   up to TT residues of the slice (TT / 4 per wave): indices compacted by ballots (sa_take), atoms staged in LDS as float4 (x, y, z, R); an atom
+//   target tile   up to TT residues of the slice (TT / 4 per wave): indices compacted by ballots (take, candidate_common.h), atoms staged in LDS as float4 (x, y, z, R); an atom
 //                 that takes no part is staged as NaN and skipped.  Two verdict words per (residue, atom, pass of 64 points) in LDS, bit = lane = point: hidden by
 //                 the own side / by the other side.  They persist while the occluder tiles go by.
 //   occluder tile up to 64 participating residues of the candidate, atoms staged as float4 (x, y, z, T) -- an atom that takes no part as NaN, which drops out of
@@ -145,7 +119,7 @@ __global__ __launch_bounds__(256) void sasa_points_kernel(const float* __restric
     __shared__ __attribute__((aligned(16))) float4 sph_o[SA_TO];
     __shared__ __attribute__((aligned(16))) ulonglong2 vb[TT][AQ][PQ];
     __shared__ int idx_o[SA_TO], side_o[SA_TO], idx_t[TT], side_t[TT];
-    const int64_t c64 = (int64_t)blockIdx.y * gridDim.x + blockIdx.x;
+    const int64_t c64 = folded_block();
     if (c64 >= N) return;                                                       // the last row of a folded grid; block-uniform
     const int slice = blockIdx.z, slices = gridDim.z;
     const int64_t g = c64 / S;
@@ -160,15 +134,10 @@ __global__ __launch_bounds__(256) void sasa_points_kernel(const float* __restric
     const int passes = (n + 63) >> 6;                                           // <= PQ, checked by the host
 
     // ---- this slice's ranks of participating residues (every wave counts the row itself: wave-uniform, no exchange)
-    int np = 0;
-    for (int r0 = 0; r0 < L; r0 += 64) {
-        const int s = r0 + lane < L ? grp[r0 + lane] : 0;
-        np += __popcll(__ballot(s == 1 || s == 2));
-    }
-    const int lo = (int)((int64_t)np * slice / slices), hi = (int)((int64_t)np * (slice + 1) / slices);
-    if (lo == hi) return;                                                       // block-uniform
-    int cur_t = 0;
-    sa_take(grp, L, cur_t, lo, nullptr, false);
+    const OnEitherSide part{grp};
+    int cur_t;
+    int left = slice_ranks(L, part, slice, slices, cur_t);
+    if (left == 0) return;                                                      // block-uniform
 
     // ---- the largest length of a direction, widened: wave-uniform
     float umax = 0.f;
@@ -180,11 +149,11 @@ __global__ __launch_bounds__(256) void sasa_points_kernel(const float* __restric
     umax = sqrtf(umax) * (1.f + 9.5367431640625e-7f);
 
     int free1 = 0, free2 = 0, cplx1 = 0, cplx2 = 0;                             // wave-uniform: exposed points by side, free and in the complex
-    for (int left = hi - lo; left > 0;) {
+    while (left > 0) {
         __syncthreads();                                                        // the previous tile's reads are done
-        const int ntt = sa_take(grp, L, cur_t, min(TT, left), idx_t, wave == 0);
+        const int ntt = take(L, part, cur_t, min(TT, left), idx_t, wave == 0);
         left -= ntt;
-        if (ntt == 0) break;                                                    // cannot happen (np was counted on the same row); block-uniform
+        if (ntt == 0) break;                                                    // cannot happen (the ranks were counted on the same row); block-uniform
         __syncthreads();
         for (int t = tid; t < ntt * AQ; t += 256) {
             const int i = t / AQ, p = t % AQ, r = idx_t[i];
@@ -202,7 +171,7 @@ __global__ __launch_bounds__(256) void sasa_points_kernel(const float* __restric
         int cur_o = 0;
         while (true) {
             __syncthreads();                                                    // the previous occluder tile's reads are done (and the target tile is written)
-            const int nto = sa_take(grp, L, cur_o, SA_TO, idx_o, wave == 0);
+            const int nto = take(L, part, cur_o, SA_TO, idx_o, wave == 0);
             if (nto == 0) break;                                                // block-uniform
             __syncthreads();
             for (int t = tid; t < nto * AQ; t += 256) {
@@ -313,33 +282,28 @@ extern "C" size_t abopt_sasa_ws_bytes(int G, int S, int L, int A) { return sasa_
 extern "C" int abopt_sasa_grouped(const float* pos, const uint8_t* mask, int mask_shared, const int32_t* group, const float* radius, const float* dirs,
                                   int n_points, int G, int S, int L, int A, float probe, float k, void* pts, void* area, void* ws, size_t ws_bytes,
                                   abopt_stream stream) {
-    ABOPT_CHECK_ARG(G >= 0 && S >= 0 && L >= 1 && A >= 1 && (int64_t)G * S <= 0x7fffffff && (int64_t)L * A * 3 <= 0x7fffffff,
-                    "sasa_grouped: bad dims G=%d S=%d L=%d A=%d", G, S, L, A);
-    ABOPT_CHECK_ARG(A <= SA_MAX_A, "sasa_grouped: A=%d atoms per residue exceed the maximum of %d", A, SA_MAX_A);
+    int rc = check_candidate_dims("sasa_grouped", G, S, L, A);
+    if (rc != ABOPT_OK) return rc;
     ABOPT_CHECK_ARG(n_points >= 1 && n_points <= SA_MAX_POINTS, "sasa_grouped: n_points=%d test points per atom, expected 1 .. %d", n_points, SA_MAX_POINTS);
     ABOPT_CHECK_ARG(isfinite(probe) && probe >= 0.f, "sasa_grouped: the probe radius must be finite and >= 0 (got %g)", (double)probe);
     ABOPT_CHECK_ARG(isfinite(k), "sasa_grouped: k (the area of one test point on the unit sphere, 4 pi / n) must be finite (got %g)", (double)k);
     if (G == 0 || S == 0) return ABOPT_OK;
-    ABOPT_CHECK_ARG(G <= 65535, "sasa_grouped: G=%d groups exceed one launch (max 65535)", G);
+    if ((rc = check_group_count("sasa_grouped", G)) != ABOPT_OK) return rc;
     ABOPT_CHECK_ARG(pos && mask && group && radius && dirs && pts && area && ws, "sasa_grouped: NULL argument");
-    ABOPT_CHECK_ARG(((uintptr_t)ws & 15) == 0, "sasa_grouped: the workspace must be 16-byte aligned");
     const int64_t N = (int64_t)G * S, rows = N * L, prep_blocks = (rows + 255) / 256;
-    ABOPT_CHECK_ARG(prep_blocks <= (int64_t)SA_GRID_X * 65535, "sasa_grouped: G S L = %lld residues exceed one launch", (long long)rows);
-    const size_t need = sasa_ws_bytes(G, S, L, A);
-    if (ws_bytes < need) { set_error("sasa_grouped: workspace too small (%zu bytes given, %zu needed)", ws_bytes, need); return ABOPT_EWORKSPACE; }
+    ABOPT_CHECK_ARG(prep_blocks <= (int64_t)kGridX * 65535, "sasa_grouped: G S L = %lld residues exceed one launch", (long long)rows);
+    if ((rc = check_workspace("sasa_grouped", ws, 16, ws_bytes, sasa_ws_bytes(G, S, L, A))) != ABOPT_OK) return rc;
     hipStream_t st = (hipStream_t)stream;
     int cus = 0;
-    int rc = device_cu_count(&cus);
-    if (rc != ABOPT_OK) return rc;
+    if ((rc = device_cu_count(&cus)) != ABOPT_OK) return rc;
     // enough workgroups for four per CU, no slice thinner than four residues of the row
-    const int slices = (int)std::max<int64_t>(1, std::min<int64_t>(std::min<int64_t>(SA_MAX_SLICES, ((int64_t)L + 3) / 4), ((int64_t)cus * 4 + N - 1) / N));
-    auto fold = [](int64_t blocks, unsigned z) { const int64_t x = std::min<int64_t>(blocks, SA_GRID_X); return dim3((unsigned)x, (unsigned)((blocks + x - 1) / x), z); };
-    hipLaunchKernelGGL(sasa_prepare_kernel, fold(prep_blocks, 1u), dim3(256), 0, st, pos, mask, mask_shared ? 1 : 0, group, radius, (float4*)ws, (int32_t*)pts,
+    const int slices = slice_count(cus, 4, N, ((int64_t)L + 3) / 4);
+    hipLaunchKernelGGL(sasa_prepare_kernel, fold_grid(prep_blocks, 1u), dim3(256), 0, st, pos, mask, mask_shared ? 1 : 0, group, radius, (float4*)ws, (int32_t*)pts,
                        (float*)area, rows, S, L, A, probe);
     ABOPT_LAUNCH_CHECK();
     const bool few = n_points <= 128;
-    auto kernel = A <= 5 ? (few ? sasa_points_kernel<5, 2> : sasa_points_kernel<5, 16>) : (few ? sasa_points_kernel<SA_MAX_A, 2> : sasa_points_kernel<SA_MAX_A, 16>);
-    hipLaunchKernelGGL(kernel, fold(N, (unsigned)slices), dim3(256), 0, st, pos, mask, mask_shared ? 1 : 0, group, radius, dirs, n_points, (const float4*)ws,
+    auto kernel = A <= 5 ? (few ? sasa_points_kernel<5, 2> : sasa_points_kernel<5, 16>) : (few ? sasa_points_kernel<kMaxAtoms, 2> : sasa_points_kernel<kMaxAtoms, 16>);
+    hipLaunchKernelGGL(kernel, fold_grid(N, (unsigned)slices), dim3(256), 0, st, pos, mask, mask_shared ? 1 : 0, group, radius, dirs, n_points, (const float4*)ws,
                        (int32_t*)pts, (float*)area, (int)N, S, L, A, probe, k);
     ABOPT_LAUNCH_CHECK();
     return ABOPT_OK;

@@ -842,6 +842,33 @@ def check_distance_cutoff(name, v):
     return c
 
 
+def _candidate_args(name, pos, mask, group):
+    """The shape contract of the scorers that compare the two sides of `group`, checked without a device: group (G, L), pos (G*S, L, A, 3) in whole groups of S,
+    mask (G*S, L, A) or (G, L, A) shared by the candidates of a group, 1 <= A <= 15.  -> (G, S, L, A, shared: the mask is per group), or ValueError."""
+    if group.dim() != 2 or pos.dim() != 4 or mask.dim() != 3:
+        raise ValueError(f'{name}: expected pos (G*S, L, A, 3), mask (G*S or G, L, A) and group (G, L), got {tuple(pos.shape)}, '
+                         f'{tuple(mask.shape)} and {tuple(group.shape)}')
+    G, L = group.shape
+    N, A = pos.shape[0], pos.shape[2]
+    if L < 1 or tuple(pos.shape[1:]) != (L, A, 3) or (N % G if G else N):
+        raise ValueError(f'{name}: {tuple(pos.shape)} candidates are not whole groups of the {G} rows of group {tuple(group.shape)}')
+    if not 1 <= A <= 15:
+        raise ValueError(f'{name}: A={A} atoms per residue, expected 1 .. 15')
+    S = N // G if G else 0
+    shared = mask.shape[0] != N or S == 1
+    if tuple(mask.shape) != ((G if shared else N), L, A):
+        raise ValueError(f'{name}: mask {tuple(mask.shape)} is neither per candidate nor per group')
+    return G, S, L, A, shared
+
+
+def _candidate_tensors(pos, mask, group, link=None):
+    """What the entry points of those scorers read: pos as contiguous fp32, mask and link (None stays None) as contiguous bool or uint8, group as contiguous int32.
+    A CPU tensor is refused first, before anything is allocated.  -> (pos, mask, group, link)"""
+    ptr(pos, strided=True)
+    as_flags = lambda t: None if t is None else (t if t.dtype in (torch.bool, torch.uint8) else t != 0).contiguous()
+    return pos.float().contiguous(), as_flags(mask), group.to(torch.int32).contiguous(), as_flags(link)
+
+
 def interface_geometry_grouped(pos, mask, group, clash_cutoff=3.0, contact_cutoff=5.0, link=None, bond_max=None, want_freq=False):
     """Clashes, contacts, interface residues and chain breaks of G*S candidates in G groups (include/abopt.h: abopt_interface_geometry_grouped; DESIGN.md
     section 6.3).  pos (G*S,L,A,3); mask (G*S,L,A), or (G,L,A) shared by the S candidates of a group; group (G,L) int: 1 and 2 name the two sides, anything else
@@ -850,29 +877,15 @@ def interface_geometry_grouped(pos, mask, group, clash_cutoff=3.0, contact_cutof
     min d <= contact_cutoff per residue pair.
     -> dict of device tensors: clash, contacts, iface1, iface2, breaks (G*S,) int32 [, freq (G,L) int32 with want_freq: in how many of the group's candidates
     each residue is in a contact].  Stream-ordered, no host synchronisation."""
-    if group.dim() != 2 or pos.dim() != 4 or mask.dim() != 3:
-        raise ValueError(f'interface_geometry_grouped: expected pos (G*S, L, A, 3), mask (G*S or G, L, A) and group (G, L), got {tuple(pos.shape)}, '
-                         f'{tuple(mask.shape)} and {tuple(group.shape)}')
-    G, L = group.shape
-    N, A = pos.shape[0], pos.shape[2]
-    if L < 1 or tuple(pos.shape[1:]) != (L, A, 3) or (N % G if G else N):
-        raise ValueError(f'interface_geometry_grouped: {tuple(pos.shape)} candidates are not whole groups of the {G} rows of group {tuple(group.shape)}')
-    if not 1 <= A <= 15:
-        raise ValueError(f'interface_geometry_grouped: A={A} atoms per residue, expected 1 .. 15')
-    S = N // G if G else 0
-    shared = mask.shape[0] != N or S == 1
-    if tuple(mask.shape) != ((G if shared else N), L, A):
-        raise ValueError(f'interface_geometry_grouped: mask {tuple(mask.shape)} is neither per candidate nor per group')
+    name = 'interface_geometry_grouped'
+    G, S, L, A, shared = _candidate_args(name, pos, mask, group)
     if link is not None and (tuple(link.shape) != (G, L) or A < 3):
-        raise ValueError(f'interface_geometry_grouped: link {tuple(link.shape)} must be (G, L) = {(G, L)} and needs the backbone atoms (A >= 3, got {A})')
-    clash = check_distance_cutoff('interface_geometry_grouped: clash_cutoff', clash_cutoff)
-    contact = check_distance_cutoff('interface_geometry_grouped: contact_cutoff', contact_cutoff)
-    bond = -1.0 if bond_max is None else check_distance_cutoff('interface_geometry_grouped: bond_max', bond_max)
-    ptr(pos, strided=True)                                          # a CPU tensor is refused here, before anything is allocated
-    pos, mask = _contig(pos.float(), mask if mask.dtype in (torch.bool, torch.uint8) else mask.bool())
-    group = group.to(torch.int32).contiguous()
-    link = None if link is None else link.bool().contiguous()
-    dev = pos.device
+        raise ValueError(f'{name}: link {tuple(link.shape)} must be (G, L) = {(G, L)} and needs the backbone atoms (A >= 3, got {A})')
+    clash = check_distance_cutoff(f'{name}: clash_cutoff', clash_cutoff)
+    contact = check_distance_cutoff(f'{name}: contact_cutoff', contact_cutoff)
+    bond = -1.0 if bond_max is None else check_distance_cutoff(f'{name}: bond_max', bond_max)
+    pos, mask, group, link = _candidate_tensors(pos, mask, group, link)
+    N, dev = G * S, pos.device
     out = torch.empty(N, 5, dtype=torch.int32, device=dev)
     freq = (torch.empty if N else torch.zeros)(G, L, dtype=torch.int32, device=dev) if want_freq else None      # an empty call launches nothing
     buf = Workspace.get(max(8, lib().abopt_interface_geometry_ws_bytes(G, S, L)), dev)
@@ -922,29 +935,15 @@ def sasa_grouped(pos, mask, group, radius, probe=1.4, points=128):
     -> dict of device tensors: pts (G*S,4) int32 (free-exposed points of side 1, of side 2, complex-exposed points of side 1, of side 2) and area (G*S,L,2) fp32
     (free and complex exposed area per residue; their difference is the buried area).  Stream-ordered, no host synchronisation, capturable in a torch.cuda.graph."""
     import math
-    if group.dim() != 2 or pos.dim() != 4 or mask.dim() != 3:
-        raise ValueError(f'sasa_grouped: expected pos (G*S, L, A, 3), mask (G*S or G, L, A) and group (G, L), got {tuple(pos.shape)}, '
-                         f'{tuple(mask.shape)} and {tuple(group.shape)}')
-    G, L = group.shape
-    N, A = pos.shape[0], pos.shape[2]
-    if L < 1 or tuple(pos.shape[1:]) != (L, A, 3) or (N % G if G else N):
-        raise ValueError(f'sasa_grouped: {tuple(pos.shape)} candidates are not whole groups of the {G} rows of group {tuple(group.shape)}')
-    if not 1 <= A <= 15:
-        raise ValueError(f'sasa_grouped: A={A} atoms per residue, expected 1 .. 15')
-    S = N // G if G else 0
-    shared = mask.shape[0] != N or S == 1
-    if tuple(mask.shape) != ((G if shared else N), L, A):
-        raise ValueError(f'sasa_grouped: mask {tuple(mask.shape)} is neither per candidate nor per group')
+    G, S, L, A, shared = _candidate_args('sasa_grouped', pos, mask, group)
     if tuple(radius.shape) not in ((G, L, A), (L, A), (A,)):
         raise ValueError(f'sasa_grouped: radius {tuple(radius.shape)} must be (G, L, A) = {(G, L, A)}, (L, A) or (A,)')
     n = int(points)
     if not 1 <= n <= 1024:
         raise ValueError(f'sasa_grouped: points={points!r} test points per atom, expected 1 .. 1024')
     probe = check_probe_radius('sasa_grouped: probe', probe)
-    ptr(pos, strided=True)                                          # a CPU tensor is refused here, before anything is allocated
-    pos, mask = _contig(pos.float(), mask if mask.dtype in (torch.bool, torch.uint8) else mask.bool())
-    dev = pos.device
-    group = group.to(torch.int32).contiguous()
+    pos, mask, group, _ = _candidate_tensors(pos, mask, group)
+    N, dev = G * S, pos.device
     radius = radius.to(device=dev, dtype=torch.float32).expand(G, L, A).contiguous()
     dirs = sphere_points(n, dev)
     k = float(torch.tensor(4.0 * math.pi / n, dtype=torch.float64).float())       # float32(4 pi / n) from float64

@@ -133,6 +133,18 @@ def backbone_links(chain_nb, res_nb):
     return link
 
 
+def _sides(name, batch, groups):
+    """group (G, L) of the two sides a scorer compares: groups='chains': antibody (1) against antigen (2), as DockQ sees them (screen.chain_groups); 'generated':
+    the generated residues (1) against every other real residue (2)."""
+    from . import screen
+    ft = batch['fragment_type']
+    if groups == 'chains':
+        return screen.chain_groups(ft)
+    if groups == 'generated':
+        return torch.where(batch['generate_flag'].bool(), 1, torch.where(ft > 0, 2, 0))
+    raise ValueError(f"{name}: groups must be 'chains' or 'generated', not {groups!r}")
+
+
 def interface_geometry(batch, pos, mask, groups='chains', **cutoffs):
     """Clashes, contacts, interface residues and chain breaks of candidate structures of the complexes of `batch` (hip.interface_geometry_grouped; DESIGN.md
     section 6.3).  batch: G complexes (fragment_type, chain_nb, res_nb, generate_flag (G, L)); pos (G*S, L, A, 3), mask (G*S, L, A) or (G, L, A): S candidates of
@@ -140,14 +152,8 @@ def interface_geometry(batch, pos, mask, groups='chains', **cutoffs):
     groups='chains': antibody (side 1) against antigen (side 2), as DockQ sees them (screen.chain_groups); 'generated': the generated residues (side 1) against
     every other real residue (side 2), bonded neighbours excluded.  cutoffs: clash_cutoff, contact_cutoff, bond_max, want_freq of hip.interface_geometry_grouped;
     the links are those of `backbone_links` (passed with 'generated', and whenever bond_max asks for the breaks)."""
-    from . import hip, screen
-    ft = batch['fragment_type']
-    if groups == 'chains':
-        grp = screen.chain_groups(ft)
-    elif groups == 'generated':
-        grp = torch.where(batch['generate_flag'].bool(), 1, torch.where(ft > 0, 2, 0))
-    else:
-        raise ValueError(f"interface_geometry: groups must be 'chains' or 'generated', not {groups!r}")
+    from . import hip
+    grp = _sides('interface_geometry', batch, groups)
     link = None
     if groups == 'generated' or cutoffs.get('bond_max') is not None:
         link = backbone_links(batch['chain_nb'], batch['res_nb'])
@@ -180,14 +186,8 @@ def buried_surface(batch, pos, mask, groups='chains', probe=1.4, points=128, rad
     side taken away minus that, >= 0: the paratope and the epitope in A^2; bsa (N,) and sasa (N,) fp32, their sums over the residues (taken in float64, rounded
     once) -- bsa is the buried area of BOTH sides together (some tools report half of it, the "interface area"); pts (N, 4) int32, the point counts of
     hip.sasa_grouped.  No host synchronisation."""
-    from . import hip, screen
-    ft = batch['fragment_type']
-    if groups == 'chains':
-        grp = screen.chain_groups(ft)
-    elif groups == 'generated':
-        grp = torch.where(batch['generate_flag'].bool(), 1, torch.where(ft > 0, 2, 0))
-    else:
-        raise ValueError(f"buried_surface: groups must be 'chains' or 'generated', not {groups!r}")
+    from . import hip
+    grp = _sides('buried_surface', batch, groups)
     if radius is None:
         radius = slot_radii(pos.shape[2] if pos.dim() == 4 else 1)
     return surface_summary(hip.sasa_grouped(pos, mask, grp, radius, probe=probe, points=points))

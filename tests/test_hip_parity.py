@@ -18,6 +18,7 @@ from conftest import load_golden, build_model, max_abs
 from ab_opt_amd.utils import synth
 from ab_opt_amd.dpm import _LoopSpec
 from test_oracle_golden import standalone_block_sd, standalone_abdesign_dpm, noise_dict
+from scorer_harness import spawn2
 
 pytestmark = pytest.mark.gpu
 
@@ -1124,20 +1125,6 @@ def test_dockq_lite_vs_reference():
 
 
 # ------------------------------------------------------------------------------------------ two ranks on one GPU
-def _spawn2(fn, tmp_path):
-    import socket
-    import torch.multiprocessing as mp
-    for attempt in range(2):
-        sk = socket.socket(); sk.bind(('127.0.0.1', 0)); port = sk.getsockname()[1]; sk.close()
-        try:
-            mp.spawn(fn, args=(2, port, str(tmp_path)), nprocs=2, join=True)
-            return
-        except Exception as e:             # a rendezvous that failed (the free port was taken between close() and the workers' bind, a slow first import
-            msg = str(e)                   # on a fresh box) is retried once on a new port; anything the workers compute is not
-            if attempt == 1 or not any(w in msg for w in ('init_process_group', 'ddress already in use', 'onnection', 'timed out', 'Timeout')):
-                raise
-
-
 def test_two_rank_sharded_sampling_is_bit_identical_to_one_rank(tmp_path):
     """sampler.sample_sharded on 2 ranks (both on cuda:0, gloo group, gather through host memory) against the same call in one
     process: gathered candidates and top-k are bit-equal -- Philox counters depend on the GLOBAL sample index, never on the rank.
@@ -1151,7 +1138,7 @@ def test_two_rank_sharded_sampling_is_bit_identical_to_one_rank(tmp_path):
     cx = [{k: dev(v) for k, v in synth.make_batch(1, synth.LAYOUT_128, seed=100 + c).items()} for c in range(3)]
     ref = sampler.design_testset_sharded(m, cx, 4, k=2, seed=7, complexes_per_launch=1)
     assert [r['complex'] for r in ref] == [0, 1, 2] and ref[0]['ca'].shape[0] == 4
-    _spawn2(mp_workers.sharded_worker, tmp_path)
+    spawn2(mp_workers.sharded_worker, tmp_path)
     parts = [torch.load(tmp_path / f'sharded_{r}.pt') for r in range(2)]
     assert (parts[0]['a'], parts[0]['e'], parts[1]['a'], parts[1]['e']) == (0, 3, 3, 5)
     for p_ in parts:
@@ -1263,7 +1250,7 @@ def test_two_rank_ddp_gradients_equal_the_mean(tmp_path):
         sum(m({k: dev(v[r:r + 1]) for k, v in full.items()}).values()).backward()
         grads.append({n: p.grad.detach().cpu().clone() for n, p in m.named_parameters() if p.grad is not None})
     m.zero_grad(); m.eval()
-    _spawn2(mp_workers.ddp_worker, tmp_path)
+    spawn2(mp_workers.ddp_worker, tmp_path)
     got = [torch.load(tmp_path / f'ddp_{r}.pt') for r in range(2)]
     assert len(got[0]['grads']) > 150
     for n, g0 in got[0]['grads'].items():
@@ -2282,7 +2269,7 @@ def test_two_devices_rccl_bench_sampling_and_graphed_ddp(tmp_path):
     traj, _, top, cand = sampler.sample_sharded(m, b, dict(sample_structure=True, sample_sequence=True, contig=''), k=2, seed=42)
     cx = [{k: dev(v) for k, v in synth.make_batch(1, synth.LAYOUT_128, seed=100 + c).items()} for c in range(3)]
     ref = sampler.design_testset_sharded(m, cx, 4, k=2, seed=7, complexes_per_launch=1)
-    _spawn2(mp_workers.two_device_worker, tmp_path)
+    spawn2(mp_workers.two_device_worker, tmp_path)
     got = [torch.load(tmp_path / f'twodev_{r}.pt', weights_only=False) for r in range(2)]
     assert [g_['device'] for g_ in got] == [0, 1] and all(g_['backend'] == 'nccl' for g_ in got)
     for g_ in got:
@@ -2429,7 +2416,7 @@ def test_two_rank_ddp_with_fused_adam_and_graph_guard(tmp_path):
     refuses the DDP model there (a gloo all-reduce inside backward cannot be captured; with find_unused_parameters=True neither could an
     RCCL one) instead of capturing a step that would silently skip the gradient exchange."""
     import mp_workers
-    _spawn2(mp_workers.ddp_fused_adam_worker, tmp_path)
+    spawn2(mp_workers.ddp_fused_adam_worker, tmp_path)
     a, b = [torch.load(tmp_path / f'ddpadam_{r}.pt') for r in range(2)]
     assert a['refused'] and 'nccl' in a['refused'] and b['refused']
     assert all(math.isfinite(x) for x in a['losses'] + b['losses'])

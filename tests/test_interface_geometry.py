@@ -14,11 +14,11 @@ import pytest
 import torch
 
 import interface_geometry_workers
+import scorer_harness as harness
 import screen_workers
 from ab_opt_amd import screen
-from ab_opt_amd.model import generate_mask_from_str
+from scorer_harness import DEV, dev, screen_models                 # noqa: F401 (screen_models: the fixture)
 
-DEV = torch.device('cuda:0')
 CLASH, CONTACT, BOND = 3.0, 5.0, 2.0                      # the conventional values the screen defaults to
 COLS = ('clash', 'contacts', 'iface1', 'iface2', 'breaks')
 GS = [(1, 1), (3, 2), (2, 5)]
@@ -195,10 +195,6 @@ def case(G, S, L, A):
     return res
 
 
-def _dev(c, *names):
-    return [torch.from_numpy(c[n]).to(DEV) for n in names]
-
-
 def _stack(res):
     return torch.stack([res[k] for k in COLS], 1).cpu().numpy().astype(np.int64)
 
@@ -337,7 +333,7 @@ def test_counts_equal_the_float64_statement(G, S, L, A):
     distances of 1.33 A and 3.5 A set by hand (one break each at least).  bond_max=None with link: the same counts, breaks 0."""
     from ab_opt_amd import hip
     c = case(G, S, L, A)
-    pos, mask, group, link = _dev(c, 'pos', 'mask', 'group', 'link')
+    pos, mask, group, link = dev(c, 'pos', 'mask', 'group', 'link')
     got = hip.interface_geometry_grouped(pos, mask, group, c['clash'], c['contact'], want_freq=True)
     print(f'(G, S, L, A) = {(G, S, L, A)}: clash {c["out"][:, 0].tolist()} contacts {c["out"][:, 1].tolist()}')
     _assert_equals_statement(got, c['out'], c['freq'], (G, S, L, A, 'no link'))
@@ -361,7 +357,7 @@ def test_torch_statement_equals_the_float64_statement():
     """geometry_torch (the cdist statement the kernel's time is compared with in DESIGN.md section 6.3) gives the same four counts on a case with a margin."""
     G, S, L, A = 1, 1, 65, 15
     c = case(G, S, L, A)
-    pos, mask, group = _dev(c, 'pos', 'mask', 'group')
+    pos, mask, group = dev(c, 'pos', 'mask', 'group')
     got = geometry_torch(pos, mask, group[0], c['clash'], c['contact'])
     assert np.array_equal(got.cpu().numpy(), c['out'][:, :4])
 
@@ -389,7 +385,7 @@ def far_case(G, S, L, A, shift):
 def _far_check(G, S, L, A, shift):
     from ab_opt_amd import hip
     c = far_case(G, S, L, A, shift)
-    pos, mask, group, link = _dev(c, 'pos', 'mask', 'group', 'link')
+    pos, mask, group, link = dev(c, 'pos', 'mask', 'group', 'link')
     lk = dict(link=link, bond_max=c['bond']) if A >= 3 else {}
     lk64 = dict(link=c['link'], bond_max=c['bond']) if A >= 3 else {}
     want, wfreq = statement(c['pos'], c['mask'], c['group'], S, c['clash'], c['contact'], **lk64)
@@ -466,7 +462,7 @@ def test_degenerate_inputs():
     from ab_opt_amd import hip
     G, S, L, A = 2, 5, 65, 15
     c = case(G, S, L, A)
-    pos, mask, group, link = _dev(c, 'pos', 'mask', 'group', 'link')
+    pos, mask, group, link = dev(c, 'pos', 'mask', 'group', 'link')
     kw = dict(clash_cutoff=c['clash'], contact_cutoff=c['contact'], link=link, bond_max=c['bond'], want_freq=True)
     for side in (1, 2):
         empty = torch.where(group == side, 0, group)
@@ -500,15 +496,9 @@ def test_grouped_call_equals_per_group_calls():
     for G, S in ((3, 2), (2, 5)):
         for L, A in ((7, 4), (65, 15), (130, 15)):
             c = case(G, S, L, A)
-            pos, mask, group, link = _dev(c, 'pos', 'mask', 'group', 'link')
             kw = dict(clash_cutoff=c['clash'], contact_cutoff=c['contact'], bond_max=c['bond'], want_freq=True)
-            got = hip.interface_geometry_grouped(pos, mask, group, link=link, **kw)
-            for g in range(G):
-                sl = slice(g * S, (g + 1) * S)
-                one = hip.interface_geometry_grouped(pos[sl], mask[sl], group[g:g + 1], link=link[g:g + 1], **kw)
-                for k in COLS:
-                    assert torch.equal(got[k][sl], one[k]), (G, S, L, A, g, k)
-                assert torch.equal(got['freq'][g:g + 1], one['freq']), (G, S, L, A, g)
+            inputs = dict(zip(('pos', 'mask', 'group', 'link'), dev(c, 'pos', 'mask', 'group', 'link')))
+            harness.grouped_equals_per_group(lambda **t: hip.interface_geometry_grouped(**t, **kw), [((G, S, L, A), G, S, inputs)], {'group', 'link', 'freq'})
 
 
 @pytest.mark.gpu
@@ -517,7 +507,7 @@ def test_shared_mask_equals_expanded_mask():
     from ab_opt_amd import hip
     for G, S, L, A in ((3, 2, 65, 15), (2, 5, 63, 4)):
         c = case(G, S, L, A)
-        pos, mask, group, link = _dev(c, 'pos', 'mask', 'group', 'link')
+        pos, mask, group, link = dev(c, 'pos', 'mask', 'group', 'link')
         shared = mask[::S].contiguous()                                                         # the first candidate's mask of every group
         # another mask compares other atom pairs: the cutoffs are placed anew in the gaps of what this call compares, and the margin asserted on it
         exp = np.repeat(c['mask'][::S], S, 0)
@@ -543,7 +533,7 @@ def test_bad_arguments_are_refused_before_any_launch():
     L_ = hip.lib()
     G, S, L, A = 2, 5, 65, 15
     c = case(G, S, L, A)
-    pos, mask, group, link = _dev(c, 'pos', 'mask', 'group', 'link')
+    pos, mask, group, link = dev(c, 'pos', 'mask', 'group', 'link')
     out = torch.full((G * S, 5), 77, dtype=torch.int32, device=DEV)
     freq = torch.full((G, L), 77, dtype=torch.int32, device=DEV)
     need = L_.abopt_interface_geometry_ws_bytes(G, S, L)
@@ -595,41 +585,17 @@ def test_call_is_capturable():
     G, S, L, A = 2, 5, 65, 15
     a = case(G, S, L, A)
     other = _raw(G, S, L, A, 4242)                                                # other inputs of the same shape; eager against captured, no float64 here
-    pos, mask, group, link = _dev(a, 'pos', 'mask', 'group', 'link')
+    names = ('pos', 'mask', 'group', 'link')
     kw = dict(clash_cutoff=a['clash'], contact_cutoff=a['contact'], bond_max=a['bond'], want_freq=True)
-    hip.interface_geometry_grouped(pos, mask, group, link=link, **kw)              # library load, device queries
-    torch.cuda.synchronize()
-    graph = torch.cuda.CUDAGraph()
-    with torch.cuda.graph(graph):
-        held = hip.interface_geometry_grouped(pos, mask, group, link=link, **kw)
-    graph.replay()
-    torch.cuda.synchronize()
-    _assert_equals_statement(held, a['out_link'], a['freq_link'], 'replay on the captured inputs')
-    for dst, src in zip((pos, mask, group, link), other):
-        dst.copy_(torch.from_numpy(src).to(DEV))
-    graph.replay()
-    torch.cuda.synchronize()
-    eager = hip.interface_geometry_grouped(pos, mask, group, link=link, **kw)
-    for k in COLS + ('freq',):
-        assert torch.equal(held[k], eager[k]), k
+    first, held = harness.capture_replays_on_other_inputs(lambda **t: hip.interface_geometry_grouped(**t, **kw), dict(zip(names, dev(a, *names))),
+                                                          {n: torch.from_numpy(src).to(DEV) for n, src in zip(names, other)})
+    _assert_equals_statement(first, a['out_link'], a['freq_link'], 'replay on the captured inputs')
     assert not torch.equal(held['contacts'], torch.from_numpy(a['out_link'][:, 1]).to(DEV).int()), 'the other inputs give other counts'
 
 
 # ------------------------------------------------------------------------------------------ GPU: the screen
 GEOM = dict(interface_geometry_workers.GEOM)
 assert GEOM == dict(clash_cutoff=CLASH, contact_cutoff=CONTACT, bond_max=BOND)
-
-
-@pytest.fixture
-def screen_models():
-    """(dock, design) of screen_workers with no captured denoising loop before or after the test (tests/test_pose_clusters.py: the graph key does not hold the
-    ABOPT_PAIR_TERMS / ABOPT_CORE_NO_SPLIT switches, so a graph captured under one test's switches must not be replayed under another's)."""
-    pair = screen_workers.models(DEV)
-    for m in pair:
-        m.diffusion.clear_graphs()
-    yield pair
-    for m in pair:
-        m.diffusion.clear_graphs()
 
 
 @pytest.mark.gpu
@@ -656,34 +622,6 @@ def test_screen_fields_do_not_change_with_geometry_on(screen_models):
     assert screen.screen_filter(geom, max_clashes=10 ** 9, min_contacts=0).equal(screen.screen_filter(plain))
 
 
-def _stages(dock, design, one, P, S, k, D, contig, seed):
-    """The three stages written out with the public calls (tests/test_screen.py: _composition) -> the poses and the re-docks as (pos, mask)."""
-    from ab_opt_amd import geometry, hip, sampler
-    rep = lambda t, n: t.expand(n, *t.shape[1:]).contiguous()
-    aa, cn, rn = one['aa'], one['chain_nb'], one['res_nb']
-    gen = one['generate_flag'][0]
-    t1 = sampler.sample_replicated(dock, one, P, dict(sample_structure=True, sample_sequence=False, seed=screen.stage_seed(seed, 'dock'), rng_offset=0))[0]
-    g1 = rep(gen[None], P)
-    pose_pos, pose_mask = geometry.reconstruct_backbone_partially(rep(one['pos_heavyatom'], P), hip.so3_exp(t1[0]), t1[1], torch.where(g1, t1[2], rep(aa, P)),
-                                                                  rep(cn, P), rep(rn, P), rep(one['mask_heavyatom'], P), g1)
-    dflag = gen & generate_mask_from_str(contig, gen)
-    cx = [dict(one, pos_heavyatom=pose_pos[i:i + 1], mask_heavyatom=pose_mask[i:i + 1], generate_flag=dflag[None]) for i in range(P)]
-    t2 = sampler.sample_grouped(design, cx, S, dict(sample_structure=False, sample_sequence=True, seed=screen.stage_seed(seed, 'design'), rng_offset=0))[0]
-    g2 = rep(dflag[None], P * S)
-    aa2 = torch.where(g2, t2[2], rep(aa, P * S))
-    des_pos, des_mask = geometry.reconstruct_backbone_partially(pose_pos.repeat_interleave(S, 0), hip.so3_exp(t2[0]), t2[1], aa2, rep(cn, P * S), rep(rn, P * S),
-                                                                pose_mask.repeat_interleave(S, 0), g2)
-    chosen = torch.sort(t2[4].to(DEV).view(P, S), dim=1, stable=True)[1][:, :k]
-    rows = (torch.arange(P, device=DEV)[:, None] * S + chosen).reshape(-1)
-    npos, nmask, naa = des_pos[rows], des_mask[rows], aa2[rows]
-    cx = [dict(one, pos_heavyatom=npos[i:i + 1], mask_heavyatom=nmask[i:i + 1], aa=naa[i:i + 1], generate_flag=gen[None]) for i in range(P * k)]
-    t3 = sampler.sample_grouped(dock, cx, D, dict(sample_structure=True, sample_sequence=False, seed=screen.stage_seed(seed, 'redock'), rng_offset=0))[0]
-    g3 = rep(gen[None], P * k * D)
-    rpos, rmask = geometry.reconstruct_backbone_partially(npos.repeat_interleave(D, 0), hip.so3_exp(t3[0]), t3[1], torch.where(g3, t3[2], naa.repeat_interleave(D, 0)),
-                                                          rep(cn, P * k * D), rep(rn, P * k * D), nmask.repeat_interleave(D, 0), g3)
-    return pose_pos, pose_mask, rpos, rmask
-
-
 @pytest.mark.gpu
 def test_screen_geometry_equals_the_public_calls(screen_models):
     """pose_geom, and redock_geom / epitope_freq of the one chunk of a screen with all poses in one launch, against the same stages written out with the public
@@ -694,7 +632,7 @@ def test_screen_geometry_equals_the_public_calls(screen_models):
     dock, design = screen_models
     one = screen_workers.complex_(DEV)
     L = one['aa'].shape[1]
-    pose_pos, pose_mask, rpos, rmask = _stages(dock, design, one, P, S, k, D, contig, seed)
+    pose_pos, pose_mask, rpos, rmask = harness.stages(dock, design, one, P, S, k, D, contig, seed)
     res = screen.optimize_antibody(dock, design, one, P, S, D, contig=contig, screened_per_pose=k, seed=seed, poses_per_launch=P, screen_by='ppl', **GEOM)
     stack = lambda g: torch.stack([g[c] for c in COLS], 1).long()
     poses = sampler.interface_geometry(one, pose_pos, pose_mask, groups='chains', **GEOM)
@@ -725,17 +663,8 @@ def test_screen_geometry_equals_the_public_calls(screen_models):
 def test_screen_geometry_does_not_depend_on_poses_per_launch(monkeypatch, screen_models):
     """The screen with geometry on, with all, 1 and 2 poses per launch: every field, the three new ones included, bit for bit -- ABOPT_PAIR_TERMS=0 /
     ABOPT_CORE_NO_SPLIT=1 pin one arithmetic form of the denoiser, as DESIGN.md section 6.1 prescribes and tests/test_screen.py does."""
-    monkeypatch.setenv('ABOPT_PAIR_TERMS', '0')
-    monkeypatch.setenv('ABOPT_CORE_NO_SPLIT', '1')
-    dock, design = screen_models
-    one = screen_workers.complex_(DEV)
-    kw = dict(screen_workers.SCREEN)
-    runs = [screen.optimize_antibody(dock, design, one, poses_per_launch=n, **kw, **GEOM) for n in (kw['num_poses'], 1, 2)]
-    assert {'pose_geom', 'redock_geom', 'epitope_freq'} <= set(runs[0])
-    for r in runs[1:]:
-        assert set(r) == set(runs[0])
-        for name, v in runs[0].items():
-            assert torch.equal(r[name], v), name
+    harness.pin_denoiser_form(monkeypatch)
+    harness.screen_is_launch_size_invariant(screen_models, GEOM, {'pose_geom', 'redock_geom', 'epitope_freq'})
 
 
 @pytest.mark.gpu
@@ -743,19 +672,12 @@ def test_two_rank_screen_gathers_the_geometry_fields(tmp_path, monkeypatch, scre
     """Two gloo ranks sharing cuda:0 (5 poses split 3 + 2, two per launch) return what one process returns, the three new fields included, bit for bit -- without
     clustering, where pose_geom travels in the final gather, and with cluster_cutoff = 0.0, where it is gathered with the poses before stage 2 and stays (P, 5).
     ABOPT_PAIR_TERMS=0 / ABOPT_CORE_NO_SPLIT=1 as in tests/test_screen.py."""
-    from test_hip_parity import _spawn2
-    monkeypatch.setenv('ABOPT_PAIR_TERMS', '0')
-    monkeypatch.setenv('ABOPT_CORE_NO_SPLIT', '1')
+    harness.pin_denoiser_form(monkeypatch)
     dock, design = screen_models
     one = screen_workers.complex_(DEV)
     kw = dict(screen_workers.SCREEN)
-    ref = dict(plain=screen.optimize_antibody(dock, design, one, poses_per_launch=kw['num_poses'], **kw, **GEOM),
-               zero=screen.optimize_antibody(dock, design, one, poses_per_launch=kw['num_poses'], cluster_cutoff=0.0, **kw, **GEOM))
-    assert torch.equal(ref['plain']['pose_geom'], ref['zero']['pose_geom']) and torch.equal(ref['plain']['redock_geom'], ref['zero']['redock_geom'])
-    _spawn2(interface_geometry_workers.geometry_screen_worker, tmp_path)
-    for tag, want in ref.items():
-        for r in range(2):
-            got = torch.load(tmp_path / f'geometry_{tag}_{r}.pt')
-            assert set(got) == set(want), (tag, r)
-            for name, v in want.items():
-                assert torch.equal(got[name], v.cpu()), (tag, r, name)
+    ref = {f'geometry_{tag}': screen.optimize_antibody(dock, design, one, poses_per_launch=kw['num_poses'], **kw, **GEOM, **extra)
+           for tag, extra in interface_geometry_workers.RUNS.items()}
+    plain, zero = ref['geometry_plain'], ref['geometry_zero']
+    assert torch.equal(plain['pose_geom'], zero['pose_geom']) and torch.equal(plain['redock_geom'], zero['redock_geom'])
+    harness.two_ranks_return(interface_geometry_workers.geometry_screen_worker, tmp_path, ref)

@@ -787,10 +787,10 @@ def test_screen_fields_do_not_change_with_lddt_on(screen_models):
 
 @pytest.mark.gpu
 def test_screen_lddt_equals_the_public_calls(screen_models):
-    """The new fields of a screen with all poses in one launch against the same stages written out with the public calls (tests/test_interface_geometry.py:
-    _stages) and scored by sampler.lddt_scores / sampler.lddt_consistency with rows = the re-docked residues, and design by design by single-group hip calls."""
+    """The new fields of a screen with all poses in one launch against the same stages written out with the public calls (tests/scorer_harness.py:
+    stages) and scored by sampler.lddt_scores / sampler.lddt_consistency with rows = the re-docked residues, and design by design by single-group hip calls."""
     from ab_opt_amd import geometry, hip, sampler
-    from test_interface_geometry import _stages
+    from scorer_harness import stages as _stages
     P, S, k, D, contig, seed = 4, 3, 2, 3, '33-39', 5
     dock, design = screen_models
     one = screen_workers.complex_(DEV)
@@ -890,7 +890,7 @@ def test_screen_lddt_with_share_redocks_and_with_cluster_cutoff(monkeypatch, scr
 def test_two_rank_screen_gathers_the_lddt_fields(tmp_path, monkeypatch, screen_models):
     """Two gloo ranks sharing cuda:0 (5 poses split 3 + 2, two per launch) return what one process returns, the six new fields included, bit for bit -- plainly and
     with share_redocks, where the versus-design fields travel per owner and redock_consistency per unit."""
-    from test_hip_parity import _spawn2
+    from scorer_harness import spawn2 as _spawn2
     monkeypatch.setenv('ABOPT_PAIR_TERMS', '0')
     monkeypatch.setenv('ABOPT_CORE_NO_SPLIT', '1')
     dock, design = screen_models

@@ -12,9 +12,11 @@ import pytest
 import torch
 
 import pose_cluster_workers
+import scorer_harness as harness
 import screen_workers
 from ab_opt_amd import screen
 from ab_opt_amd.model import generate_mask_from_str
+from scorer_harness import screen_models                           # noqa: F401 (the fixture)
 
 DEV = torch.device('cuda:0')
 SHAPES = [(G, S, n) for G in (1, 3) for S in (1, 2, 63, 64, 65, 130) for n in (1, 7, 50)]          # S: word boundaries of the bit rows
@@ -301,19 +303,6 @@ def test_bad_arguments_are_refused_before_any_launch():
 
 
 # ------------------------------------------------------------------------------------------ GPU: the clustered screen
-@pytest.fixture
-def screen_models():
-    """(dock, design) of screen_workers with no captured denoising loop before or after the test.  The models are the session's cached ones and a loop is captured
-    into a hipGraph from its second call with the same shapes, with the kernel forms of the environment at that moment (the graph key does not hold
-    ABOPT_PAIR_TERMS / ABOPT_CORE_NO_SPLIT): a graph captured by one of these tests must not be replayed under another test's switches, here or in tests/test_screen.py."""
-    pair = screen_workers.models(DEV)
-    for m in pair:
-        m.diffusion.clear_graphs()
-    yield pair
-    for m in pair:
-        m.diffusion.clear_graphs()
-
-
 def _pair_gap_cutoff(ca):
     """A cutoff that merges exactly the closest pair of poses: halfway between the two smallest float64 pairwise RMSDs; the margin (relative to the
     cutoff) is asserted > 1e-3, as for every input of this file."""
@@ -431,26 +420,12 @@ def test_clustered_screen_does_not_depend_on_poses_per_launch_or_ranks(tmp_path,
     """The clustered screen (cutoff placed as in test_clustered_screen_equals_the_composition_of_public_calls: C = P - 1 = 4 clusters; re-docks clustered
     too) with all, 1 and 2 centres per launch, and on two gloo ranks sharing cuda:0 (4 centres split 2 + 2, the poses split 3 + 2 before the
     clustering), bit for bit -- ABOPT_PAIR_TERMS=0 / ABOPT_CORE_NO_SPLIT=1 pin one arithmetic form, as in tests/test_screen.py."""
-    from test_hip_parity import _spawn2
-    monkeypatch.setenv('ABOPT_PAIR_TERMS', '0')
-    monkeypatch.setenv('ABOPT_CORE_NO_SPLIT', '1')
+    harness.pin_denoiser_form(monkeypatch)
     dock, design = screen_models
     one = screen_workers.complex_(DEV)
-    kw = dict(screen_workers.SCREEN)
-    P = kw['num_poses']
-    cutoff = _pair_gap_cutoff(_stage1(dock, one, P, kw['seed'])[0])
-    extra = dict(cluster_cutoff=cutoff, redock_cutoff=pose_cluster_workers.REDOCK_CUTOFF)
-    runs = [screen.optimize_antibody(dock, design, one, poses_per_launch=n, **kw, **extra) for n in (P, 1, 2)]
-    ref = runs[0]
+    P = screen_workers.SCREEN['num_poses']
+    cutoff = _pair_gap_cutoff(_stage1(dock, one, P, screen_workers.SCREEN['seed'])[0])
+    ref = harness.screen_is_launch_size_invariant(screen_models, dict(cluster_cutoff=cutoff, redock_cutoff=pose_cluster_workers.REDOCK_CUTOFF))
     assert ref['cluster_centre'].shape == (P - 1,) and ref['seqs'].shape[0] == P - 1 and ref['pose_ca'].shape[0] == P
-    for r in runs[1:]:
-        assert set(r) == set(ref)
-        for name, v in ref.items():
-            assert torch.equal(r[name], v), name
     (tmp_path / 'cutoff.txt').write_text(repr(cutoff))
-    _spawn2(pose_cluster_workers.clustered_screen_worker, tmp_path)
-    for r in range(2):
-        got = torch.load(tmp_path / f'clustered_{r}.pt')
-        assert set(got) == set(ref)
-        for name, v in ref.items():
-            assert torch.equal(got[name], v.cpu()), (r, name)
+    harness.two_ranks_return(pose_cluster_workers.clustered_screen_worker, tmp_path, dict(clustered=ref))

@@ -10,10 +10,11 @@ import numpy as np
 import pytest
 import torch
 
+import scorer_harness as harness
 import screen_workers
 from ab_opt_amd import hip, sampler, screen
+from scorer_harness import DEV, dev
 
-DEV = torch.device('cuda:0')
 PROBE = 1.4
 RADII = (1.55, 1.70, 1.70, 1.52, 1.70)                    # N, CA, C, O, CB; every further slot 1.70
 SHIFT = (900.0, -700.0, 500.0)
@@ -171,8 +172,9 @@ def case(G, S, L, A, n, far=False):
     return dict(pos=pos, mask=mask, group=group, radius=radii_of(A), pts=pts, area=area, free_share=free / max(1, total), buried_share=buried)
 
 
-def _dev(c, *names):
-    return [torch.from_numpy(np.ascontiguousarray(c[n])).to(DEV) for n in names]
+def _bits(res):
+    """pts and area of a result, the areas as their int32 bit patterns: torch.equal on them is bit for bit"""
+    return dict(pts=res['pts'], area=res['area'].view(torch.int32))
 
 
 def _assert_equals_statement(got, pts, area, tag):
@@ -185,7 +187,7 @@ def _assert_equals_statement(got, pts, area, tag):
 
 
 def _run(c, n, probe=PROBE, **over):
-    t = dict(zip(('pos', 'mask', 'group', 'radius'), _dev(c, 'pos', 'mask', 'group', 'radius')))
+    t = dict(zip(('pos', 'mask', 'group', 'radius'), dev(c, 'pos', 'mask', 'group', 'radius')))
     t.update(over)
     return hip.sasa_grouped(t['pos'], t['mask'], t['group'], t['radius'], probe=probe, points=n)
 
@@ -413,7 +415,7 @@ def test_degenerate_inputs():
     lone = dict(pos=np.array([[[[3.0, -2.0, 1.0]]]], dtype=np.float32), mask=np.ones((1, 1, 1), bool), group=np.array([[2]], dtype=np.int32), radius=radii_of(1))
     pts, area = check(lone, 'one lone atom')
     assert pts.tolist() == [[0, n, 0, n]] and area[0, 0, 0] == area[0, 0, 1] > 0
-    pos, mask, group, rad = _dev(base, 'pos', 'mask', 'group', 'radius')
+    pos, mask, group, rad = dev(base, 'pos', 'mask', 'group', 'radius')
     for g_, p_, m_ in ((group[:0], pos[:0], mask[:0]),):
         got = hip.sasa_grouped(p_, m_, g_, rad)
         assert got['pts'].shape == (0, 4) and got['area'].shape == (0, L, 2)
@@ -432,19 +434,15 @@ def test_degenerate_inputs():
 def test_grouped_call_equals_per_group_calls():
     G, S, L, A, n = 3, 2, 63, 5, 63
     c = case(G, S, L, A, n)
-    pos, mask, group, rad = _dev(c, 'pos', 'mask', 'group', 'radius')
-    whole = hip.sasa_grouped(pos, mask, group, rad, points=n)
-    for g in range(G):
-        sl = slice(g * S, (g + 1) * S)
-        alone = hip.sasa_grouped(pos[sl], mask[sl], group[g:g + 1], rad, points=n)
-        assert torch.equal(whole['pts'][sl], alone['pts']) and torch.equal(whole['area'][sl].view(torch.int32), alone['area'].view(torch.int32)), g
+    pos, mask, group, rad = dev(c, 'pos', 'mask', 'group', 'radius')
+    harness.grouped_equals_per_group(lambda **t: _bits(hip.sasa_grouped(radius=rad, points=n, **t)), [('sasa', G, S, dict(pos=pos, mask=mask, group=group))], {'group'})
 
 
 @pytest.mark.gpu
 def test_shared_mask_equals_expanded_mask():
     G, S, L, A, n = 2, 5, 65, 5, 64
     c = case(G, S, L, A, n)
-    pos, mask, group, rad = _dev(c, 'pos', 'mask', 'group', 'radius')
+    pos, mask, group, rad = dev(c, 'pos', 'mask', 'group', 'radius')
     shared = mask[::S].contiguous()                                                     # (G, L, A): the first candidate's mask for the whole group
     a = hip.sasa_grouped(pos, shared, group, rad, points=n)
     b = hip.sasa_grouped(pos, shared.repeat_interleave(S, 0), group, rad, points=n)
@@ -460,7 +458,7 @@ def test_bad_arguments_are_refused_before_any_launch():
     L_ = hip.lib()
     G, S, L, A, n = 2, 5, 65, 5, 64
     c = case(G, S, L, A, n)
-    pos, mask, group = _dev(c, 'pos', 'mask', 'group')
+    pos, mask, group = dev(c, 'pos', 'mask', 'group')
     rad = torch.from_numpy(np.ascontiguousarray(np.broadcast_to(c['radius'], (G, L, A)))).to(DEV)
     dirs = hip.sphere_points(n, DEV)
     pts = torch.full((G * S, 4), 77, dtype=torch.int32, device=DEV)
@@ -507,22 +505,11 @@ def test_call_is_capturable():
     G, S, L, A, n = 2, 5, 65, 5, 64
     a = case(G, S, L, A, n)
     other = _raw(G, S, L, A, 4242)
-    pos, mask, group = _dev(a, 'pos', 'mask', 'group')
+    pos, mask, group = dev(a, 'pos', 'mask', 'group')
     rad = torch.from_numpy(np.ascontiguousarray(np.broadcast_to(a['radius'], (G, L, A)))).to(DEV)
-    hip.sasa_grouped(pos, mask, group, rad, points=n)                                   # library load, device queries, the cached directions
-    torch.cuda.synchronize()
-    graph = torch.cuda.CUDAGraph()
-    with torch.cuda.graph(graph):
-        held = hip.sasa_grouped(pos, mask, group, rad, points=n)
-    graph.replay()
-    torch.cuda.synchronize()
-    _assert_equals_statement(held, a['pts'], a['area'], 'replay on the captured inputs')
-    for dst, src in zip((pos, mask, group), other):
-        dst.copy_(torch.from_numpy(src).to(DEV))
-    graph.replay()
-    torch.cuda.synchronize()
-    eager = hip.sasa_grouped(pos, mask, group, rad, points=n)
-    assert torch.equal(held['pts'], eager['pts']) and torch.equal(held['area'].view(torch.int32), eager['area'].view(torch.int32))
+    first, held = harness.capture_replays_on_other_inputs(lambda **t: _bits(hip.sasa_grouped(radius=rad, points=n, **t)), dict(pos=pos, mask=mask, group=group),
+                                                          {k: torch.from_numpy(src).to(DEV) for k, src in zip(('pos', 'mask', 'group'), other)})
+    _assert_equals_statement(dict(pts=first['pts'], area=first['area'].view(torch.float32)), a['pts'], a['area'], 'replay on the captured inputs')
     assert not np.array_equal(held['pts'].cpu().numpy(), a['pts']), 'the other inputs give other counts'
 
 

@@ -213,12 +213,12 @@ def test_optimize_antibody_does_not_depend_on_poses_per_launch(monkeypatch):
 def test_two_rank_screen_equals_one_rank(tmp_path, monkeypatch):
     """Two ranks sharing cuda:0 (gloo; 5 poses split 3 + 2, two poses per launch) gather the same result as one process, bit for bit
     (ABOPT_PAIR_TERMS=0 / ABOPT_CORE_NO_SPLIT=1, as in test_optimize_antibody_does_not_depend_on_poses_per_launch)."""
-    from test_hip_parity import _spawn2
+    from scorer_harness import spawn2
     monkeypatch.setenv('ABOPT_PAIR_TERMS', '0')
     monkeypatch.setenv('ABOPT_CORE_NO_SPLIT', '1')
     dock, design = screen_workers.models(DEV)
     ref = screen.optimize_antibody(dock, design, screen_workers.complex_(DEV), poses_per_launch=5, **screen_workers.SCREEN)
-    _spawn2(screen_workers.screen_worker, tmp_path)
+    spawn2(screen_workers.screen_worker, tmp_path)
     for r in range(2):
         got = torch.load(tmp_path / f'screen_{r}.pt')
         assert set(got) == set(ref)

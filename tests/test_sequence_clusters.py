@@ -10,10 +10,12 @@ import numpy as np
 import pytest
 import torch
 
+import scorer_harness as harness
 import screen_workers
 import sequence_cluster_workers as workers
 from ab_opt_amd import screen
 from ab_opt_amd.model import generate_mask_from_str
+from scorer_harness import screen_models                           # noqa: F401 (the fixture)
 
 DEV = torch.device('cuda:0')
 S_LIST = (1, 2, 63, 64, 65, 130)
@@ -316,17 +318,6 @@ def test_bad_arguments_are_refused_before_any_launch():
 
 
 # ------------------------------------------------------------------------------------------ GPU: the screen
-@pytest.fixture
-def screen_models():
-    """(dock, design) of screen_workers with no captured denoising loop before or after the test (tests/test_pose_clusters.py: screen_models)."""
-    pair = screen_workers.models(DEV)
-    for m in pair:
-        m.diffusion.clear_graphs()
-    yield pair
-    for m in pair:
-        m.diffusion.clear_graphs()
-
-
 def _rep(t, n):
     return t.expand(n, *t.shape[1:]).contiguous()
 
@@ -568,25 +559,8 @@ def test_shared_redocks_equal_the_composition(screen_models):
 def test_sequence_screens_do_not_depend_on_poses_per_launch_or_ranks(tmp_path, monkeypatch, screen_models):
     """The diverse screen and the shared screen with all, 1 and 2 poses (units) per launch, and on two gloo ranks sharing cuda:0, bit for bit --
     ABOPT_PAIR_TERMS=0 / ABOPT_CORE_NO_SPLIT=1 pin one arithmetic form, as in tests/test_screen.py."""
-    from test_hip_parity import _spawn2
-    monkeypatch.setenv('ABOPT_PAIR_TERMS', '0')
-    monkeypatch.setenv('ABOPT_CORE_NO_SPLIT', '1')
-    dock, design = screen_models
-    one = screen_workers.complex_(DEV)
+    harness.pin_denoiser_form(monkeypatch)
     P = screen_workers.SCREEN['num_poses']
-    refs = {}
-    for name, extra in workers.options(DEV).items():
-        runs = [screen.optimize_antibody(dock, design, one, poses_per_launch=n, **_screen_kw(**extra)) for n in (P, 1, 2)]
-        refs[name] = runs[0]
-        for r in runs[1:]:
-            assert set(r) == set(runs[0])
-            for field, v in runs[0].items():
-                assert torch.equal(r[field], v), (name, field)
+    refs = {name: harness.screen_is_launch_size_invariant(screen_models, extra) for name, extra in workers.options(DEV).items()}
     assert 'unit_owner' in refs['shared'] and refs['shared']['unit_owner'].shape[0] < P * screen_workers.SCREEN['screened_per_pose']
-    _spawn2(workers.sequence_screen_worker, tmp_path)
-    for name, ref in refs.items():
-        for r in range(2):
-            got = torch.load(tmp_path / f'{name}_{r}.pt')
-            assert set(got) == set(ref)
-            for field, v in ref.items():
-                assert torch.equal(got[field], v.cpu()), (name, r, field)
+    harness.two_ranks_return(workers.sequence_screen_worker, tmp_path, refs)
