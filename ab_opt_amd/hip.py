@@ -13,7 +13,7 @@ import torch
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # ABOPT_LIB_PATH: developer override to load a variant build of the same ABI (csrc/Makefile VARIANT=...: A/B of two source trees)
 LIB_PATH = os.environ.get('ABOPT_LIB_PATH') or os.path.join(_HERE, 'libabopt_hip.so')
-ABI_VERSION = 56
+ABI_VERSION = 57
 
 c_f = C.c_void_p        # device float*
 c_i64 = C.c_void_p      # device int64*
@@ -172,6 +172,8 @@ _SIGNATURES = {
     'abopt_sasa_ws_bytes': (c_size_t, [c_int] * 4),
     'abopt_sasa_grouped': (c_int, [c_f, c_u8, c_int, c_i32, c_f, c_f] + [c_int] * 5 + [c_float] * 2 + [c_void_p] * 3 + [c_size_t, c_stream]),
     'abopt_guide_positions': (c_int, [c_f, c_f, c_u8, c_u8, c_i32, c_int, c_int, c_int] + [c_float] * 6 + [c_void_p, c_stream]),
+    'abopt_relax_max_moved': (c_int, []),
+    'abopt_relax_grouped': (c_int, [c_f, c_f, c_u8, c_int, c_u8, c_u8] + [c_int] * 5 + [c_float] * 8 + [c_int, c_f, c_stream]),
     'abopt_prof_enable': (c_int, [c_int]),
     'abopt_prof_spans_reset': (c_int, [c_stream]),
     'abopt_prof_spans': (c_int, [POINTER(c_int), POINTER(c_double)]),
@@ -861,12 +863,16 @@ def _candidate_args(name, pos, mask, group):
     return G, S, L, A, shared
 
 
+def _as_flags(t):
+    """a per-residue or per-atom flag tensor as contiguous bool or uint8 (None stays None)"""
+    return None if t is None else (t if t.dtype in (torch.bool, torch.uint8) else t != 0).contiguous()
+
+
 def _candidate_tensors(pos, mask, group, link=None):
-    """What the entry points of those scorers read: pos as contiguous fp32, mask and link (None stays None) as contiguous bool or uint8, group as contiguous int32.
-    A CPU tensor is refused first, before anything is allocated.  -> (pos, mask, group, link)"""
+    """What the entry points of those scorers read: pos as contiguous fp32, mask and link (None stays None) as contiguous bool or uint8, group as contiguous int32
+    (None -- a caller whose rows are flags, not sides -- stays None).  A CPU tensor is refused first, before anything is allocated.  -> (pos, mask, group, link)"""
     ptr(pos, strided=True)
-    as_flags = lambda t: None if t is None else (t if t.dtype in (torch.bool, torch.uint8) else t != 0).contiguous()
-    return pos.float().contiguous(), as_flags(mask), group.to(torch.int32).contiguous(), as_flags(link)
+    return pos.float().contiguous(), _as_flags(mask), None if group is None else group.to(torch.int32).contiguous(), _as_flags(link)
 
 
 def interface_geometry_grouped(pos, mask, group, clash_cutoff=3.0, contact_cutoff=5.0, link=None, bond_max=None, want_freq=False):
@@ -895,6 +901,69 @@ def interface_geometry_grouped(pos, mask, group, clash_cutoff=3.0, contact_cutof
     if want_freq:
         res['freq'] = freq
     return res
+
+
+RELAX_MAX_ITERS = 1024      # iterations of one call at most
+RELAX_MAX_MOVED = 256       # moved residues of one candidate at most (abopt_relax_max_moved(): what fits the LDS of a workgroup with 15 atom slots)
+
+
+def check_relax(w_bond=1.0, w_ca=1.0, w_clash=1.0, w_tether=0.05, clash_cutoff=3.0, step=0.2, max_shift=0.5, max_angle=0.2, iters=50, max_moved=None):
+    """The knobs of the relax (include/abopt.h: abopt_relax_grouped) as a dict under their own names -- floats, iters and max_moved (None
+    stays None) as ints --, or ValueError naming the argument: every scalar finite and >= 0, max_shift and max_angle > 0, iters 0 .. 1024, max_moved 1 ..
+    RELAX_MAX_MOVED.  No device is needed."""
+    import math
+    out = {}
+    for name, v in (('w_bond', w_bond), ('w_ca', w_ca), ('w_clash', w_clash), ('w_tether', w_tether), ('clash_cutoff', clash_cutoff), ('step', step),
+                    ('max_shift', max_shift), ('max_angle', max_angle)):
+        f = float(v)
+        if not math.isfinite(f) or f < 0.0:
+            raise ValueError(f'{name} must be finite and >= 0 (got {v!r})')
+        out[name] = f
+    for name in ('max_shift', 'max_angle'):
+        if out[name] == 0.0:
+            raise ValueError(f'{name} must be > 0')
+    if isinstance(iters, bool) or int(iters) != iters or not 0 <= int(iters) <= RELAX_MAX_ITERS:
+        raise ValueError(f'iters must be an integer in 0 .. {RELAX_MAX_ITERS} (got {iters!r})')
+    out['iters'] = int(iters)
+    if max_moved is not None and (isinstance(max_moved, bool) or int(max_moved) != max_moved or not 1 <= int(max_moved) <= RELAX_MAX_MOVED):
+        raise ValueError(f'max_moved must be an integer in 1 .. {RELAX_MAX_MOVED} (got {max_moved!r})')
+    out['max_moved'] = None if max_moved is None else int(max_moved)
+    return out
+
+
+def relax_grouped(pos, mask, move, link=None, w_bond=1.0, w_ca=1.0, w_clash=1.0, w_tether=0.05, clash_cutoff=3.0, step=0.2, max_shift=0.5, max_angle=0.2,
+                  iters=50, out=None, max_moved=None):
+    """Relax G*S candidates in G groups: `iters` Jacobi steps of a rigid-residue descent on atom-level clashes, peptide-bond and CA-CA violations, tethered to
+    the input (include/abopt.h: abopt_relax_grouped).  pos (G*S,L,A,3) with atom slots 0, 1, 2 = N, CA, C (3 <= A <= 15); mask (G*S,L,A), or
+    (G,L,A) shared by the S candidates of a group; move (G,L) bool: the residues that may move; link (optional, (G,L) bool): residue r is peptide-bonded to
+    r + 1 -- without it there is no bond term, no CA term and no neighbour exclusion.  Weights are per squared Angstrom, clash_cutoff / max_shift in Angstrom,
+    max_angle in rad.  The defaults are conventional values (3 A between heavy atoms, half an Angstrom and a fifth of a radian per step), NOT tuned ones: no
+    trained checkpoint exists to tune them on.  out (optional): the tensor the result is written to, contiguous fp32 of pos's shape -- pos itself relaxes in place.
+    max_moved (optional): the caller's bound on the moved residues of any one candidate, at most RELAX_MAX_MOVED; it sizes the workgroup's LDS (default
+    min(L, RELAX_MAX_MOVED)).  A candidate with more moved residues than the bound comes back unchanged with NaN energies -- the count lives on the device and no
+    host read is made for it.
+    -> dict of device tensors: pos (G*S,L,A,3) fp32 and energy (G*S,2,4) fp32: bond, ca, clash, tether before and after.  Stream-ordered, no host
+    synchronisation, capturable in a torch.cuda.graph."""
+    name = 'relax_grouped'
+    ptr(pos, strided=True)                                          # a CPU tensor is refused here, before anything else
+    kn = check_relax(w_bond, w_ca, w_clash, w_tether, clash_cutoff, step, max_shift, max_angle, iters, max_moved)
+    G, S, L, A, shared = _candidate_args(name, pos, mask, move)
+    if A < 3:
+        raise ValueError(f'{name}: A={A} atoms per residue, the slots 0, 1, 2 are N, CA, C (expected 3 .. 15)')
+    if link is not None and tuple(link.shape) != (G, L):
+        raise ValueError(f'{name}: link {tuple(link.shape)} must be (G, L) = {(G, L)}')
+    src, mask, _, link = _candidate_tensors(pos, mask, None, link)
+    move = _as_flags(move)
+    if out is None:
+        out = torch.empty_like(src)
+    elif out.shape != src.shape or out.dtype != torch.float32 or not out.is_contiguous() or out.device != src.device:
+        raise ValueError(f'{name}: out must be a contiguous fp32 tensor of shape {tuple(src.shape)} on {src.device}')
+    N, dev = G * S, src.device
+    energy = (torch.empty if N else torch.zeros)(N, 2, 4, dtype=torch.float32, device=dev)       # an empty call launches nothing
+    _check(lib().abopt_relax_grouped(ptr(src, torch.float32), ptr(out, torch.float32), ptr(mask), int(shared), ptr(move), ptr(link, optional=True), G, S, L, A,
+                                     kn['max_moved'] or min(L, RELAX_MAX_MOVED), kn['w_bond'], kn['w_ca'], kn['w_clash'], kn['w_tether'], kn['clash_cutoff'],
+                                     kn['step'], kn['max_shift'], kn['max_angle'], kn['iters'], ptr(energy, torch.float32), stream()))
+    return dict(pos=out, energy=energy)
 
 
 def check_probe_radius(name, v):

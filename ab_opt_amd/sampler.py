@@ -160,6 +160,34 @@ def interface_geometry(batch, pos, mask, groups='chains', **cutoffs):
     return hip.interface_geometry_grouped(pos, mask, grp, link=link, **cutoffs)
 
 
+def relax_candidates(batch, pos, mask, move='generated', bond_max=2.0, **knobs):
+    """Relax candidate structures of the complexes of `batch` and say what it did in the units the screen reports (hip.relax_grouped).
+    batch, pos, mask as for `interface_geometry`.  move: 'generated' -- the residues of generate_flag move; 'antibody' -- every antibody residue moves
+    (screen.chain_groups == 1); or a (G, L) bool tensor.  The links are those of `backbone_links`.  knobs: w_bond, w_ca, w_clash, w_tether, clash_cutoff, step,
+    max_shift, max_angle, iters, out, max_moved of hip.relax_grouped -- conventional defaults, not tuned ones.
+    -> dict of device tensors, N = G*S: pos (N, L, A, 3) and energy (N, 2, 4) of hip.relax_grouped; clashes_before / clashes_after / breaks_before / breaks_after
+    (N,) int32 from two `interface_geometry` calls with groups='generated', the same clash_cutoff and bond_max (Angstrom): the generated residues against every
+    other real residue, whichever set moved.  A candidate with more moved residues than the bound (max_moved, by default min(L, 256): an antibody of more than 256
+    residues with move='antibody') is NOT relaxed and raises nothing -- the count lives on the device; it comes back unchanged with NaN in all of its `energy`:
+    check `energy` for NaN.  The screen does not call this: apply it to what optimize_antibody / sample_grouped return.
+    No host synchronisation."""
+    from . import hip, screen
+    if isinstance(move, str):
+        if move == 'generated':
+            mv = batch['generate_flag'].bool()
+        elif move == 'antibody':
+            mv = screen.chain_groups(batch['fragment_type']) == 1
+        else:
+            raise ValueError(f"relax_candidates: move must be 'generated', 'antibody' or a (G, L) tensor, not {move!r}")
+    else:
+        mv = move
+    geom = dict(clash_cutoff=knobs.get('clash_cutoff', 3.0), bond_max=bond_max)
+    before = interface_geometry(batch, pos, mask, groups='generated', **geom)              # before the relax: `out` may be pos itself
+    res = hip.relax_grouped(pos, mask, mv, link=backbone_links(batch['chain_nb'], batch['res_nb']), **knobs)
+    after = interface_geometry(batch, res['pos'], mask, groups='generated', **geom)
+    return dict(res, clashes_before=before['clash'], clashes_after=after['clash'], breaks_before=before['breaks'], breaks_after=after['breaks'])
+
+
 BONDI_RADII = (1.55, 1.70, 1.70, 1.52, 1.70)                    # N, CA, C, O, CB (Bondi 1964: N 1.55, C 1.70, O 1.52 Angstrom)
 
 

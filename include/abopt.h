@@ -23,7 +23,7 @@
 extern "C" {
 #endif
 
-#define ABOPT_ABI_VERSION 56
+#define ABOPT_ABI_VERSION 57
 
 enum { ABOPT_OK = 0, ABOPT_EINVAL = 1, ABOPT_EHIP = 2, ABOPT_EUNSUPPORTED = 3, ABOPT_EWORKSPACE = 4 };
 
@@ -807,6 +807,45 @@ int abopt_sasa_grouped(const float* pos, const uint8_t* mask, int mask_shared, c
 int abopt_guide_positions(float* p, float* p_norm, const uint8_t* mask_generate, const uint8_t* mask_res, const int32_t* role, int role_shared, int N, int L,
                           float w_att, float r_att, float w_rep, float r_rep, float max_shift, float position_scale, const float* position_mean,
                           abopt_stream stream);
+
+/* ---- Relax of docked candidates (ABI 57; no reference counterpart: the reference relaxes with OpenMM / Rosetta): a deterministic,
+ * training-free descent with a fixed number of iterations that moves every movable residue as a rigid body, down atom-level clashes and peptide-bond / CA-CA
+ * violations, tethered to where the residue started.  The smallest honest relax, no force field.  G groups of S candidates, conventions of
+ * abopt_interface_geometry_grouped:
+ *   pos_in [G*S,L,A,3] fp32, read only; pos_out [G*S,L,A,3] fp32, may be the same pointer as pos_in; mask [G*S,L,A], or [G,L,A] shared by the S candidates of a
+ *   group (mask_shared != 0); move [G,L]: the residues that may move; link (optional) [G,L] as for abopt_interface_geometry_grouped: without it there is no bond
+ *   term, no CA term and no neighbour exclusion.  Atom slots 0, 1, 2 are N, CA, C, so 3 <= A <= 15.
+ *   scalars     fp32, each finite and >= 0: w_bond, w_ca, w_clash, w_tether, clash_d (Angstrom), step; max_shift > 0 (Angstrom), max_angle > 0 (rad);
+ *               iters 0 .. 1024.  max_moved: the caller's bound on the moved residues of any one candidate, 1 .. 256 after min(max_moved, L) -- it sizes the
+ *               workgroup's LDS; a larger one: ABOPT_EUNSUPPORTED, before the launch.  (abopt_relax_max_moved() returns the 256.)
+ *   taking part an atom takes part iff its mask byte is set and its three input coordinates are finite.  A residue is MOVED iff its byte of move is set and it has
+ *               at least one participating atom.  An atom that takes no part is copied to pos_out bit for bit; it exerts nothing and feels nothing.
+ *   energy      of a candidate at the positions x (x0: the input), d the Euclidean distance, b0 = 1.329 A and a0 = 3.80 A the conventional trans-peptide values:
+ *     bond      r < L - 1 with link[r], C_r and N_r+1 participating, r or r + 1 moved:   w_bond (d(C_r, N_r+1) - b0)^2
+ *     ca        the same r (link[r], r or r + 1 moved) with the CA of both participating:  w_ca (d(CA_r, CA_r+1) - a0)^2
+ *     clash     unordered atom pairs (p of residue a, q of residue b), a != b, at least one of a, b moved, a and b not bonded neighbours by link (b == a + 1 with
+ *               link[a] or a == b + 1 with link[b]), both atoms participating:          w_clash max(clash_d - d, 0)^2
+ *     tether    participating atoms of moved residues:                                  w_tether |x - x0|^2
+ *               A pair with d^2 < 1e-12 contributes no force (the rule of abopt_guide_positions); its energy is counted.
+ *   iteration   a Jacobi update: every force is formed from the positions before the iteration.  For a moved residue a with its participating atoms P_a (n_a):
+ *               f_p = -dE/dx_p;  c = mean of x_p;  F = sum f_p;  tau = sum (x_p - c) x f_p;  I = sum |x_p - c|^2;
+ *               D = step F / n_a, scaled down to length max_shift if longer;  w = step tau / I (0 if I < 1e-12), scaled down to length max_angle if longer;
+ *               x_p <- c + Rot(w)(x_p - c) + D,  Rot(w) v = v + (sin t / t) w x v + ((1 - cos t) / t^2) w x (w x v), t = |w| (the limits 1 and 1/2 for t^2 < 1e-12).
+ *               Residues that are not moved never change.  iters = 0 copies the input.
+ *   energy [G*S,2,4] fp32: bond, ca, clash, tether on the input and on the output positions.
+ *   refusal on the device: a candidate with more moved residues than min(max_moved, L) is copied unchanged and its eight energies are NaN.
+ * Every branch point (the max(., 0), the two caps) is continuous, so the device is held to a float64 statement of the above by a tolerance, not bit for bit, as
+ * abopt_guide_positions is.  All sums are fp32 in a fixed order on coordinates relative to the candidate's first participating atom (lowest residue, then
+ * slot), so an input far from the origin loses nothing; a moved residue is kept as its centre and its atoms' offsets from it -- a rotation acts on the offsets,
+ * a shift on the centre (the mean of c + Rot(w)(x_p - c) + D is c + D).  Repeated calls agree bit for bit, and a group's result is that of a call on the group
+ * alone.  Residue pairs are pruned by bounding spheres; the prune is conservative in fp32 and a pruned pair would have added exactly +0.
+ * One stream-ordered launch, one workgroup per candidate, all iterations inside it; no float atomic, no memset node, no workspace, nothing allocated, no host
+ * synchronisation: capturable into a hipGraph.  L >= 1, G S <= 2^31 - 1, G <= 65535, G = 0 or S = 0 is a no-op; every value or pointer check precedes the
+ * launch (ABOPT_EINVAL). */
+int abopt_relax_max_moved(void);
+int abopt_relax_grouped(const float* pos_in, float* pos_out, const uint8_t* mask, int mask_shared, const uint8_t* move, const uint8_t* link,
+                        int G, int S, int L, int A, int max_moved, float w_bond, float w_ca, float w_clash, float w_tether, float clash_d, float step,
+                        float max_shift, float max_angle, int iters, float* energy, abopt_stream stream);
 
 /* ---- Measurement hook (bench.py's roofline leg).  When enabled, every launch of the IPA-core kernel is bracketed
  * by hipEvents on the stream it is launched on; abopt_prof_collect synchronises those events and returns the number
