@@ -44,6 +44,18 @@ __device__ __forceinline__ float wave_sum(float v) {
     v += ABOPT_DPP_ROR(v, 8); v += ABOPT_DPP_ROR(v, 4); v += ABOPT_DPP_ROR(v, 2); v += ABOPT_DPP_ROR(v, 1);
     return v;
 }
+// The xor butterfly (32, 16, ... 1): every lane ends with the same bits.  It adds in another order than wave_sum, so a float result differs in bits, and the
+// candidate scorers (candidate_common.h) pin theirs bit for bit: they keep this one.
+__device__ __forceinline__ float wave_sum_butterfly(float v) {
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) v = v + __shfl_xor(v, off, 64);
+    return v;
+}
+__device__ __forceinline__ int wave_sum_butterfly(int v) {
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
+    return v;
+}
 __device__ __forceinline__ float wave_max(float v) {
     auto a = __builtin_amdgcn_permlane32_swap(__float_as_uint(v), __float_as_uint(v), false, false);
     v = fmaxf(__uint_as_float(a[0]), __uint_as_float(a[1]));

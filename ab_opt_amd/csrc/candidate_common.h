@@ -1,8 +1,10 @@
-// What the scorers that compare the two sides of docked candidates share (interface.hip, sasa.hip; DESIGN.md sections 6.3, 6.6): G groups of S candidates of
-// L residues with A atom slots, a `group` row per group that names the residues' sides, a grid of (candidate folded over x and y, slice in z), and the
-// argument checks of their entry points.  sasa.hip compiles under `#pragma clang fp contract(off)` and includes this header BEFORE the pragma: it may take everything here
-// but d2_fma, the only floating-point arithmetic of this file.
+// What the kernels that work on docked candidates share (interface.hip, sasa.hip, guide.hip, relax.hip; DESIGN.md sections 3.12, 6.3, 6.6, 6.8): G groups of S
+// candidates of L residues with A atom slots, a row per group that names the residues' sides or flags them, a grid of (candidate folded over x and y, slice in z),
+// and the argument checks of their entry points.  sasa.hip, guide.hip and relax.hip compile under `#pragma clang fp contract(off)` and include this header BEFORE
+// the pragma.  d2_fma is the only floating-point arithmetic of this file: its fmaf chain is spelled out, so it means the same on either side of the pragma
+// (guide.hip uses it; sasa.hip and relax.hip, whose every step is rounded once, do not).
 #pragma once
+#include <math.h>
 #include <algorithm>
 #include "abopt_common.h"
 
@@ -15,11 +17,14 @@ constexpr int kGridX = 1 << 22;            // workgroups along x: the rest folds
 
 // ---------------------------------------------------------------- device side
 // The ONE fused distance: fmaf(dz, dz, fmaf(dy, dy, dx dx)) with every step rounded once, spelled so that the compiler contracts nothing differently in
-// different places.  (x - y)^2 == (y - x)^2, so d2(p, q) == d2(q, p) bit for bit.
+// different places.  (x - y)^2 == (y - x)^2, so d2(p, q) == d2(q, p) bit for bit.  The three-argument form takes the differences.
+__device__ __forceinline__ float d2_fma(float dx, float dy, float dz) { return fmaf(dz, dz, fmaf(dy, dy, __fmul_rn(dx, dx))); }
 __device__ __forceinline__ float d2_fma(float ax, float ay, float az, float bx, float by, float bz) {
-    const float dx = __fsub_rn(ax, bx), dy = __fsub_rn(ay, by), dz = __fsub_rn(az, bz);
-    return fmaf(dz, dz, fmaf(dy, dy, __fmul_rn(dx, dx)));
+    return d2_fma(__fsub_rn(ax, bx), __fsub_rn(ay, by), __fsub_rn(az, bz));
 }
+
+// false for a NaN and for +-inf: a comparison, no arithmetic
+__device__ __forceinline__ bool finite_f32(float x) { return fabsf(x) < INFINITY; }
 
 // index of the workgroup in a grid folded by fold_grid: the caller returns if its candidate (or unit) lies beyond the last one, in the grid's last row
 __device__ __forceinline__ int64_t folded_block() { return (int64_t)blockIdx.y * gridDim.x + blockIdx.x; }
@@ -96,6 +101,12 @@ inline int check_candidate_dims(const char* name, int G, int S, int L, int A) {
 // after the G == 0 || S == 0 no-op of the caller: a group is a row of some grid
 inline int check_group_count(const char* name, int G) {
     ABOPT_CHECK_ARG(G <= kMaxGroups, "%s: G=%d groups exceed one launch (max %d)", name, G, kMaxGroups);
+    return ABOPT_OK;
+}
+
+// each of the n named scalars is finite and >= 0
+inline int check_nonnegative(const char* name, const char* const* names, const float* v, int n) {
+    for (int k = 0; k < n; ++k) ABOPT_CHECK_ARG(isfinite(v[k]) && v[k] >= 0.f, "%s: %s must be finite and >= 0 (got %g)", name, names[k], (double)v[k]);
     return ABOPT_OK;
 }
 

@@ -4,11 +4,11 @@
 // One workgroup owns a sample, so nobody else reads the sample's centroid or its rows while they are written; every sum is taken in a fixed order (lanes stride
 // the rows, a butterfly over the wave, the four waves in ascending order): no float atomic, no workspace, and a repeated call gives the same bits.
 #include <math.h>
-#include <algorithm>
 #include "abopt_common.h"
+#include "candidate_common.h"
 #include "kernels.h"
 
-// The squared distances are spelled as an fmaf chain, d2 = fmaf(dz, dz, fmaf(dy, dy, dx dx)), as in interface.hip, and everything else -- the differences, the
+// The squared distances are d2_fma of candidate_common.h (an fmaf chain; included before the pragma), as in interface.hip, and everything else -- the differences, the
 // force sums, p + shift, (p - mean) / scale -- as plain operators under contract(off), as in sasa.hip: hipcc would otherwise contract a * b + c across statements
 // (DESIGN.md section 6.6), and p_norm has to be the rounded difference divided by the scale, bit for bit what denoise_store_position writes.
 #pragma clang fp contract(off)
@@ -20,19 +20,6 @@ constexpr int GD_SEG = 256;                // rows of a repeller tile that one w
 constexpr int GD_TILE = GD_WAVES * GD_SEG; // rows per repeller tile: 16 KB of LDS whatever L is
 constexpr int GD_K = 4;                    // moved rows a wave carries through the tiles at a time
 constexpr int GD_PASS = GD_WAVES * GD_K;   // consecutive rows dealt to the waves per pass
-constexpr int GD_GRID_X = 1 << 22;         // workgroups along x: the rest folds into y
-
-__device__ __forceinline__ float gd_wave_sum(float v) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v = v + __shfl_xor(v, off, 64);          // a butterfly: every lane ends with the same bits
-    return v;
-}
-__device__ __forceinline__ int gd_wave_sum(int v) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-    return v;
-}
-__device__ __forceinline__ float gd_d2(float dx, float dy, float dz) { return fmaf(dz, dz, fmaf(dy, dy, dx * dx)); }
 
 // Grid: the sample folded over x and y; 4 waves.
 //   phase A   thread t strides the rows t, t + 256, ...: coordinate sums (relative to position_mean, so that the magnitudes stay small) and counts of the moved
@@ -52,7 +39,7 @@ __global__ __launch_bounds__(256) void guide_positions_kernel(float* __restrict_
     __shared__ float red[GD_WAVES][6];
     __shared__ int redn[GD_WAVES][2];
     __shared__ int cnt[GD_WAVES];
-    const int64_t c = (int64_t)blockIdx.y * gridDim.x + blockIdx.x;
+    const int64_t c = folded_block();
     if (c >= N) return;                                                         // the last row of a folded grid; block-uniform
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
     float* p = p_all + c * L * 3;
@@ -72,9 +59,9 @@ __global__ __launch_bounds__(256) void guide_positions_kernel(float* __restrict_
         if (g) { sm0 = sm0 + x; sm1 = sm1 + y; sm2 = sm2 + z; ++nm; }
         else   { sh0 = sh0 + x; sh1 = sh1 + y; sh2 = sh2 + z; ++nh; }
     }
-    sm0 = gd_wave_sum(sm0); sm1 = gd_wave_sum(sm1); sm2 = gd_wave_sum(sm2);
-    sh0 = gd_wave_sum(sh0); sh1 = gd_wave_sum(sh1); sh2 = gd_wave_sum(sh2);
-    nm = gd_wave_sum(nm); nh = gd_wave_sum(nh);
+    sm0 = wave_sum_butterfly(sm0); sm1 = wave_sum_butterfly(sm1); sm2 = wave_sum_butterfly(sm2);
+    sh0 = wave_sum_butterfly(sh0); sh1 = wave_sum_butterfly(sh1); sh2 = wave_sum_butterfly(sh2);
+    nm = wave_sum_butterfly(nm); nh = wave_sum_butterfly(nh);
     if (lane == 0) {
         red[wave][0] = sm0; red[wave][1] = sm1; red[wave][2] = sm2; red[wave][3] = sh0; red[wave][4] = sh1; red[wave][5] = sh2;
         redn[wave][0] = nm; redn[wave][1] = nh;
@@ -92,7 +79,7 @@ __global__ __launch_bounds__(256) void guide_positions_kernel(float* __restrict_
     if (nh > 0) {
         const float fm = (float)nm, fh = (float)nh;
         const float dx = sh0 / fh - sm0 / fm, dy = sh1 / fh - sm1 / fm, dz = sh2 / fh - sm2 / fm;
-        const float D = sqrtf(gd_d2(dx, dy, dz));
+        const float D = sqrtf(d2_fma(dx, dy, dz));
         if (D > 0.f) {
             const float g = w_att * fmaxf(D - r_att, 0.f) / D;
             ax = g * dx; ay = g * dy; az = g * dz;
@@ -144,7 +131,7 @@ __global__ __launch_bounds__(256) void guide_positions_kernel(float* __restrict_
                     for (int k = 0; k < GD_K; ++k) {
                         if (!((mine >> k) & 1u)) continue;
                         const float dx = px[k] - q.x, dy = py[k] - q.y, dz = pz[k] - q.z;
-                        const float d2 = gd_d2(dx, dy, dz);
+                        const float d2 = d2_fma(dx, dy, dz);
                         if (d2 < 1e-12f) continue;                              // a coincident pair has no direction: it contributes 0
                         const float d = sqrtf(d2);
                         const float s = fmaxf(r_rep - d, 0.f) / d;
@@ -156,7 +143,7 @@ __global__ __launch_bounds__(256) void guide_positions_kernel(float* __restrict_
 #pragma unroll
         for (int k = 0; k < GD_K; ++k) {
             if (!((mine >> k) & 1u)) continue;                                  // wave-uniform
-            const float sx = gd_wave_sum(fx[k]), sy = gd_wave_sum(fy[k]), sz = gd_wave_sum(fz[k]);
+            const float sx = wave_sum_butterfly(fx[k]), sy = wave_sum_butterfly(fy[k]), sz = wave_sum_butterfly(fz[k]);
             if (lane != 0) continue;
             float dx = ax + w_rep * sx, dy = ay + w_rep * sy, dz = az + w_rep * sz;
             // the cap in double: the capped shift is max_shift / |shift| times the shift with ONE fp32 rounding per component, so its length stays
@@ -187,8 +174,7 @@ extern "C" int abopt_guide_positions(float* p, float* p_norm, const uint8_t* mas
                     "guide_positions: N=%d samples are not whole groups of role_shared=%d", N, role_shared);
     const float sc[6] = {w_att, r_att, w_rep, r_rep, max_shift, position_scale};
     static const char* const names[6] = {"w_att", "r_att", "w_rep", "r_rep", "max_shift", "position_scale"};
-    for (int k = 0; k < 6; ++k)
-        ABOPT_CHECK_ARG(isfinite(sc[k]) && sc[k] >= 0.f, "guide_positions: %s must be finite and >= 0 (got %g)", names[k], (double)sc[k]);
+    if (const int rc = check_nonnegative("guide_positions", names, sc, 6)) return rc;
     ABOPT_CHECK_ARG(w_att <= 1.f, "guide_positions: w_att must be <= 1, the pull may not overshoot (got %g)", (double)w_att);
     ABOPT_CHECK_ARG(max_shift > 0.f, "guide_positions: max_shift must be > 0 (got %g)", (double)max_shift);
     ABOPT_CHECK_ARG(position_scale > 0.f, "guide_positions: position_scale must be > 0 (got %g)", (double)position_scale);
@@ -196,9 +182,8 @@ extern "C" int abopt_guide_positions(float* p, float* p_norm, const uint8_t* mas
     ABOPT_CHECK_ARG(isfinite(position_mean[0]) && isfinite(position_mean[1]) && isfinite(position_mean[2]), "guide_positions: position_mean must be finite");
     if (N == 0 || L == 0) return ABOPT_OK;
     if (w_att == 0.f && w_rep == 0.f) return ABOPT_OK;                          // every shift is 0: nothing is written
-    ABOPT_CHECK_ARG((int64_t)N <= (int64_t)GD_GRID_X * 65535, "guide_positions: N=%d samples exceed one launch", N);
-    const unsigned gx = (unsigned)std::min<int64_t>(N, GD_GRID_X);
-    hipLaunchKernelGGL(guide_positions_kernel, dim3(gx, (unsigned)(((int64_t)N + gx - 1) / gx)), dim3(256), 0, (hipStream_t)stream, p, p_norm, mask_generate,
+    ABOPT_CHECK_ARG((int64_t)N <= (int64_t)kGridX * 65535, "guide_positions: N=%d samples exceed one launch", N);
+    hipLaunchKernelGGL(guide_positions_kernel, fold_grid(N, 1u), dim3(256), 0, (hipStream_t)stream, p, p_norm, mask_generate,
                        mask_res, role, role_shared, N, L, w_att, r_att, w_rep, r_rep, max_shift, position_scale, position_mean[0], position_mean[1],
                        position_mean[2]);
     ABOPT_LAUNCH_CHECK();

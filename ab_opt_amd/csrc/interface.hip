@@ -184,7 +184,7 @@ __global__ __launch_bounds__(256) void interface_pairs_kernel(const float* __res
             if (n2t < IG_T2) break;                                             // the row ended inside this tile; block-uniform
         }
     }
-    for (int off = 32; off > 0; off >>= 1) clash += __shfl_xor(clash, off, 64);
+    clash = wave_sum_butterfly(clash);
     if (lane == 0) {
         if (clash) atomicAdd(&counters[0], clash);
         if (contacts) atomicAdd(&counters[1], contacts);

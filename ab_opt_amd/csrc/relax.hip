@@ -47,22 +47,15 @@ struct RelaxLds {
     }
 };
 
-__device__ __forceinline__ float rx_sum(float v) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v = v + __shfl_xor(v, off, 64);          // a butterfly: every lane ends with the same bits
-    return v;
-}
-__device__ __forceinline__ bool rx_finite(float x) { return fabsf(x) < INFINITY; }  // false for a NaN
-
 // atom t (= residue * A + slot) of the input takes part: its mask byte is set and its coordinates are finite
 __device__ __forceinline__ bool rx_part(const float* pos, const uint8_t* mask, int64_t t) {
-    return mask[t] && rx_finite(pos[t * 3]) && rx_finite(pos[t * 3 + 1]) && rx_finite(pos[t * 3 + 2]);
+    return mask[t] && finite_f32(pos[t * 3]) && finite_f32(pos[t * 3 + 1]) && finite_f32(pos[t * 3 + 2]);
 }
 // ... and where it is, relative to o
 __device__ __forceinline__ bool rx_atom(const float* pos, const uint8_t* mask, int64_t t, float3 o, float3& y) {
     if (!mask[t]) return false;
     const float a = pos[t * 3], b = pos[t * 3 + 1], c = pos[t * 3 + 2];
-    if (!(rx_finite(a) && rx_finite(b) && rx_finite(c))) return false;
+    if (!(finite_f32(a) && finite_f32(b) && finite_f32(c))) return false;
     y = make_float3(a - o.x, b - o.y, c - o.z);
     return true;
 }
@@ -268,8 +261,8 @@ __global__ __launch_bounds__(256) void relax_kernel(const float* pos_all, float*
                     rx_push(s, make_float3(vp.x, vp.y, vp.z), -w2_tether * tx, -w2_tether * ty, -w2_tether * tz);
                 }
             }
-            const float fx = rx_sum(s.fx), fy = rx_sum(s.fy), fz = rx_sum(s.fz), tx = rx_sum(s.tx), ty = rx_sum(s.ty), tz = rx_sum(s.tz);
-            const float eb = rx_sum(s.e_bond), ec = rx_sum(s.e_ca), el = rx_sum(s.e_clash), et = rx_sum(s.e_tether);
+            const float fx = wave_sum_butterfly(s.fx), fy = wave_sum_butterfly(s.fy), fz = wave_sum_butterfly(s.fz), tx = wave_sum_butterfly(s.tx), ty = wave_sum_butterfly(s.ty), tz = wave_sum_butterfly(s.tz);
+            const float eb = wave_sum_butterfly(s.e_bond), ec = wave_sum_butterfly(s.e_ca), el = wave_sum_butterfly(s.e_clash), et = wave_sum_butterfly(s.e_tether);
             if (lane == 0) {
                 const float fn = lds.acc[(size_t)i * 3 + 2].z;
                 lds.acc[(size_t)i * 3] = make_float4(fx, fy, fz, eb);
@@ -345,8 +338,8 @@ __global__ __launch_bounds__(256) void relax_kernel(const float* pos_all, float*
                     wave_lds_sync();
                 }
                 if (!any) continue;                                             // every lane's share is +0
-                const float fx = rx_sum(s.fx), fy = rx_sum(s.fy), fz = rx_sum(s.fz), tx = rx_sum(s.tx), ty = rx_sum(s.ty), tz = rx_sum(s.tz);
-                const float el = rx_sum(s.e_clash);
+                const float fx = wave_sum_butterfly(s.fx), fy = wave_sum_butterfly(s.fy), fz = wave_sum_butterfly(s.fz), tx = wave_sum_butterfly(s.tx), ty = wave_sum_butterfly(s.ty), tz = wave_sum_butterfly(s.tz);
+                const float el = wave_sum_butterfly(s.e_clash);
                 if (lane == 0) {
                     float4 f = lds.acc[(size_t)i * 3], t = lds.acc[(size_t)i * 3 + 1], e = lds.acc[(size_t)i * 3 + 2];
                     f.x = f.x + fx; f.y = f.y + fy; f.z = f.z + fz;
@@ -364,7 +357,7 @@ __global__ __launch_bounds__(256) void relax_kernel(const float* pos_all, float*
                 eb = eb + lds.acc[(size_t)i * 3].w; ec = ec + lds.acc[(size_t)i * 3 + 1].w;
                 el = el + lds.acc[(size_t)i * 3 + 2].x; et = et + lds.acc[(size_t)i * 3 + 2].y;
             }
-            eb = kn.w_bond * rx_sum(eb); ec = kn.w_ca * rx_sum(ec); el = kn.w_clash * rx_sum(el); et = kn.w_tether * rx_sum(et);
+            eb = kn.w_bond * wave_sum_butterfly(eb); ec = kn.w_ca * wave_sum_butterfly(ec); el = kn.w_clash * wave_sum_butterfly(el); et = kn.w_tether * wave_sum_butterfly(et);
             if (lane == 0) {
                 if (k == 0) { energy[0] = eb; energy[1] = ec; energy[2] = el; energy[3] = et; }
                 if (k == kn.iters) { energy[4] = eb; energy[5] = ec; energy[6] = el; energy[7] = et; }
@@ -438,8 +431,7 @@ extern "C" int abopt_relax_grouped(const float* pos_in, float* pos_out, const ui
     ABOPT_CHECK_ARG(A >= 3, "relax_grouped: atom slots 0, 1, 2 are N, CA, C (A >= 3, got %d)", A);
     const float sc[8] = {w_bond, w_ca, w_clash, w_tether, clash_d, step, max_shift, max_angle};
     static const char* const names[8] = {"w_bond", "w_ca", "w_clash", "w_tether", "clash_d", "step", "max_shift", "max_angle"};
-    for (int k = 0; k < 8; ++k)
-        ABOPT_CHECK_ARG(isfinite(sc[k]) && sc[k] >= 0.f, "relax_grouped: %s must be finite and >= 0 (got %g)", names[k], (double)sc[k]);
+    if ((rc = check_nonnegative("relax_grouped", names, sc, 8)) != ABOPT_OK) return rc;
     ABOPT_CHECK_ARG(max_shift > 0.f, "relax_grouped: max_shift must be > 0 (got %g)", (double)max_shift);
     ABOPT_CHECK_ARG(max_angle > 0.f, "relax_grouped: max_angle must be > 0 (got %g)", (double)max_angle);
     ABOPT_CHECK_ARG(iters >= 0 && iters <= RX_MAX_ITERS, "relax_grouped: iters must be 0 .. %d (got %d)", RX_MAX_ITERS, iters);

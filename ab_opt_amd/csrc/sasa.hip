@@ -25,11 +25,10 @@ constexpr float SA_MAX_RADIUS = 16.f;      // a larger van der Waals radius take
 __device__ __forceinline__ float sa_add(float a, float b) { return a + b; }
 __device__ __forceinline__ float sa_sub(float a, float b) { return a - b; }
 __device__ __forceinline__ float sa_mul(float a, float b) { return a * b; }
-__device__ __forceinline__ bool sa_finite(float x) { return fabsf(x) < INFINITY; }            // false for NaN and for +-inf
 
 // the ONE rule of which atoms take part (include/abopt.h): mask byte set, finite coordinates, 0 < r <= 16 (a NaN radius fails both comparisons)
 __device__ __forceinline__ bool sa_takes_part(uint8_t m, float x, float y, float z, float r) {
-    return m && sa_finite(x) && sa_finite(y) && sa_finite(z) && r > 0.f && r <= SA_MAX_RADIUS;
+    return m && finite_f32(x) && finite_f32(y) && finite_f32(z) && r > 0.f && r <= SA_MAX_RADIUS;
 }
 
 // d2 = (dx dx + dy dy) + dz dz, every step rounded once, in this association
