@@ -13,7 +13,7 @@ import torch
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # ABOPT_LIB_PATH: developer override to load a variant build of the same ABI (csrc/Makefile VARIANT=...: A/B of two source trees)
 LIB_PATH = os.environ.get('ABOPT_LIB_PATH') or os.path.join(_HERE, 'libabopt_hip.so')
-ABI_VERSION = 57
+ABI_VERSION = 58
 
 c_f = C.c_void_p        # device float*
 c_i64 = C.c_void_p      # device int64*
@@ -174,6 +174,8 @@ _SIGNATURES = {
     'abopt_guide_positions': (c_int, [c_f, c_f, c_u8, c_u8, c_i32, c_int, c_int, c_int] + [c_float] * 6 + [c_void_p, c_stream]),
     'abopt_relax_max_moved': (c_int, []),
     'abopt_relax_grouped': (c_int, [c_f, c_f, c_u8, c_int, c_u8, c_u8] + [c_int] * 5 + [c_float] * 8 + [c_int, c_f, c_stream]),
+    'abopt_sequence_liabilities_grouped': (c_int, [c_u8, c_u8, c_u8] + [c_int] * 4 + [c_void_p] * 3 + [c_stream]),
+    'abopt_surface_patches_grouped': (c_int, [c_f, c_u8, c_int, c_i32, c_f, c_u8, c_int, c_f, c_float] + [c_int] * 4 + [c_void_p, c_void_p, c_stream]),
     'abopt_prof_enable': (c_int, [c_int]),
     'abopt_prof_spans_reset': (c_int, [c_stream]),
     'abopt_prof_spans': (c_int, [POINTER(c_int), POINTER(c_double)]),
@@ -1022,6 +1024,95 @@ def sasa_grouped(pos, mask, group, radius, probe=1.4, points=128):
     _check(lib().abopt_sasa_grouped(ptr(pos, torch.float32), ptr(mask), int(shared), ptr(group, torch.int32), ptr(radius, torch.float32), ptr(dirs, torch.float32),
                                     n, G, S, L, A, probe, k, ptr(pts), ptr(area), ptr(buf), buf.numel(), stream()))
     return dict(pts=pts, area=area)
+
+
+LIABILITY_RUN_MAX = 16      # the longest hydrophobic-run window
+
+
+def check_run_min(name, v):
+    """int(v): 0 (the hydrophobic-run class is off) or 2 .. 16, or ValueError (the check abopt_sequence_liabilities_grouped makes, ahead of any device work)."""
+    if isinstance(v, bool) or int(v) != v or not (int(v) == 0 or 2 <= int(v) <= LIABILITY_RUN_MAX):
+        raise ValueError(f'{name} must be 0 (off) or an integer in 2 .. {LIABILITY_RUN_MAX} (got {v!r})')
+    return int(v)
+
+
+def sequence_liabilities_grouped(seqs, group_size, rows=None, link=None, run_min=5, want_freq=False):
+    """Sequence liabilities of G*S designs in G groups (include/abopt.h: abopt_sequence_liabilities_grouped).  seqs (G*S, n) as for
+    cluster_sequences_grouped (type k = model.AA_LETTERS[k]; a byte >= 20 is no type); rows (optional, (G, n) bool): the scored positions, None = all; link
+    (optional, (G, n) bool): residue k is peptide-bonded to k + 1 (`sampler.backbone_links`), None = every consecutive pair; run_min: the length of a
+    hydrophobic run, 0 = off, else 2 .. 16.  A motif window exists iff it lies inside the sequence, every step of it is linked and every byte is a type; it
+    counts iff one of its positions is a scored row.
+    -> dict of device tensors: flags (G*S, n) uint8, bit b at a window's anchor = class model.LIABILITY_NAMES[b]; counts (G*S, 12) int32: the windows counted
+    per class (0-6), the flagged positions (7), K + R, D + E, H among the scored rows (8-10), the scored rows that hold a type (11); hyd10 (G*S,) int32: ten
+    times the Kyte-Doolittle hydropathy summed over the scored rows [, freq (G, n) int32 with want_freq: how many of the group's designs carry a flag at each
+    position].  One stream-ordered launch, no host synchronisation, capturable."""
+    name = 'sequence_liabilities_grouped'
+    run = check_run_min(f'{name}: run_min', run_min)
+    if seqs.dim() == 2 and int(group_size) >= 1 and seqs.shape[0] % int(group_size) == 0:
+        want = (seqs.shape[0] // int(group_size), seqs.shape[1])
+        for what, t in (('rows', rows), ('link', link)):
+            if t is not None and tuple(t.shape) != want:
+                raise ValueError(f'{name}: {what} {tuple(t.shape)} must be (G, n) = {want}')
+    seqs, G, S, n = _seq_bytes(name, seqs, group_size)
+    rows, link = _as_flags(rows), _as_flags(link)
+    N, dev = G * S, seqs.device
+    new = torch.empty if N else torch.zeros                          # an empty call launches nothing
+    flags = new(N, n, dtype=torch.uint8, device=dev)
+    counts = new(N, 13, dtype=torch.int32, device=dev)
+    freq = new(G, n, dtype=torch.int32, device=dev) if want_freq else None
+    _check(lib().abopt_sequence_liabilities_grouped(ptr(seqs), ptr(rows, optional=True), ptr(link, optional=True), run, G, S, n, ptr(flags), ptr(counts),
+                                                    ptr(freq, optional=True), stream()))
+    res = dict(flags=flags, counts=counts[:, :12], hyd10=counts[:, 12])
+    if want_freq:
+        res['freq'] = freq
+    return res
+
+
+_PATCH_WEIGHT = {}
+
+
+def default_patch_weight(device='cpu'):
+    """The default hydrophobicity table of `surface_patches_grouped`: the Kyte-Doolittle hydropathy of the twenty types (model.KD_HYDROPATHY, each rounded to fp32
+    once) and 0 for entry 20, which serves every byte >= 20.  -> (21,) fp32 on `device`, cached per device: treat it as read-only."""
+    key = str(torch.device(device))
+    if key not in _PATCH_WEIGHT:
+        from .model import KD_HYDROPATHY
+        _PATCH_WEIGHT[key] = torch.tensor(list(KD_HYDROPATHY) + [0.0], dtype=torch.float64).float().to(device)
+    return _PATCH_WEIGHT[key]
+
+
+def surface_patches_grouped(pos, mask, group, area, seqs, weight=None, radius=10.0):
+    """Exposed hydrophobic patches of G*S candidates in G groups (include/abopt.h: abopt_surface_patches_grouped): per residue of side 1,
+    the sum of weight[type] x exposed area over the side-1 residues whose centre (CB, else CA) lies within `radius` of its own.  pos (G*S,L,A,3), 2 <= A <= 15;
+    mask (G*S,L,A), or (G,L,A) shared by the S candidates of a group; group (G,L) int: only side 1 is scored and contributes; area (G*S,L): the exposed area per
+    residue, e.g. a column of sasa_grouped's area; seqs (G*S,L), or (G,L) shared by the group, any integer dtype (clamped into 0..255; a byte >= 20 reads
+    weight[20]); weight (optional, (21,)): default `default_patch_weight` (Kyte-Doolittle, 0 for entry 20) -- a NaN entry takes that type out; radius in Angstrom.
+    -> dict of device tensors: patch (G*S,L) fp32 and nbr (G*S,L) int32 (the residue itself included; both 0 for a residue that takes no part).  One
+    stream-ordered launch, no host synchronisation, capturable."""
+    name = 'surface_patches_grouped'
+    G, S, L, A, shared = _candidate_args(name, pos, mask, group)
+    if A < 2:
+        raise ValueError(f'{name}: A={A} atoms per residue, the slot 1 is CA (expected 2 .. 15)')
+    N = G * S
+    if tuple(area.shape) != (N, L) or not area.dtype.is_floating_point:
+        raise ValueError(f'{name}: area {tuple(area.shape)} {area.dtype} must be floating point of shape (G*S, L) = {(N, L)}')
+    if seqs.dim() != 2 or seqs.shape[1] != L or seqs.shape[0] not in (N, G) or seqs.dtype.is_floating_point or seqs.dtype.is_complex:
+        raise ValueError(f'{name}: seqs {tuple(seqs.shape)} {seqs.dtype} must be integer of shape (G*S, L) = {(N, L)} or (G, L) = {(G, L)}')
+    if weight is not None and (tuple(weight.shape) != (21,) or not weight.dtype.is_floating_point):
+        raise ValueError(f'{name}: weight {tuple(weight.shape)} {weight.dtype} must be floating point of shape (21,): the twenty types and "no type"')
+    radius = check_distance_cutoff(f'{name}: radius', radius)
+    pos, mask, group, _ = _candidate_tensors(pos, mask, group)
+    dev = pos.device
+    seq_shared = seqs.shape[0] != N or S == 1
+    seqs = (seqs if seqs.dtype == torch.uint8 else seqs.to(torch.uint8) if seqs.dtype == torch.bool else seqs.clamp(0, 255).to(torch.uint8)).contiguous()
+    area = area.float().contiguous()
+    weight = default_patch_weight(dev) if weight is None else weight.to(device=dev, dtype=torch.float32).contiguous()
+    new = torch.empty if N else torch.zeros                          # an empty call launches nothing
+    patch = new(N, L, dtype=torch.float32, device=dev)
+    nbr = new(N, L, dtype=torch.int32, device=dev)
+    _check(lib().abopt_surface_patches_grouped(ptr(pos, torch.float32), ptr(mask), int(shared), ptr(group, torch.int32), ptr(area, torch.float32), ptr(seqs, torch.uint8),
+                                               int(seq_shared), ptr(weight, torch.float32), radius, G, S, L, A, ptr(patch), ptr(nbr), stream()))
+    return dict(patch=patch, nbr=nbr)
 
 
 def check_lddt_cutoff(name, v):

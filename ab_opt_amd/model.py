@@ -70,7 +70,13 @@ def aa_allowed_mask(length, exclude='', at=None, device=None):
     return mask.to(device) if device is not None else mask
 
 
-ROLE_HOTSPOT, ROLE_REPEL = 1, 2          # the bits of a guide_role word (include/abopt.h: abopt_guide_positions)
+# Developability (include/abopt.h: abopt_sequence_liabilities_grouped): the liability classes in the bit order of a flag byte, and the
+# Kyte-Doolittle hydropathy (J. Mol. Biol. 157, 1982) of the twenty types in AA_LETTERS order -- in tenths, the exact integers the kernel sums, and as floats.
+LIABILITY_NAMES = ('n_glyc', 'deamidation', 'isomerisation', 'cleavage', 'cys', 'met', 'hydrophobic_run')
+KD_HYDROPATHY_TENTHS = (18, 25, -35, -35, 28, -4, -32, 45, -39, 38, 19, -35, -16, -35, -45, -8, -7, 42, -9, -13)
+KD_HYDROPATHY = tuple(v / 10.0 for v in KD_HYDROPATHY_TENTHS)
+
+ROLE_HOTSPOT, ROLE_REPEL = 1, 2         # the bits of a guide_role word (include/abopt.h: abopt_guide_positions)
 
 
 def guide_roles(batch_or_length, hotspots=None, repel=None, device=None):

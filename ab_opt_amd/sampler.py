@@ -228,6 +228,98 @@ def surface_summary(sa):
     return dict(sasa_res=cplx, bsa_res=bsa_res, bsa=bsa_res.sum(-1, dtype=torch.float64).float(), sasa=cplx.sum(-1, dtype=torch.float64).float(), pts=sa['pts'])
 
 
+def liability_summary(out):
+    """flags / counts / hyd10 of hip.sequence_liabilities_grouped -> the dict `sequence_liabilities` returns: flags; one count per class under its name of
+    model.LIABILITY_NAMES; flagged, positive (K + R), negative (D + E), his, scored (the scored rows that hold a type) and hyd10, all int32; net_charge =
+    positive - negative (int32); gravy = hyd10 / (10 scored), one float64 division, NaN where nothing is scored.  Pure torch, no host read."""
+    from .model import LIABILITY_NAMES
+    counts = out['counts']
+    res = dict(flags=out['flags'], **{name: counts[..., k] for k, name in enumerate(LIABILITY_NAMES)})
+    res.update(flagged=counts[..., 7], positive=counts[..., 8], negative=counts[..., 9], his=counts[..., 10], scored=counts[..., 11], hyd10=out['hyd10'])
+    res['net_charge'] = counts[..., 8] - counts[..., 9]
+    scored = counts[..., 11].double()
+    res['gravy'] = torch.where(scored > 0, out['hyd10'].double() / (10.0 * scored.clamp_min(1.0)), float('nan'))
+    if 'freq' in out:
+        res['freq'] = out['freq']
+    return res
+
+
+def sequence_liabilities(seqs, rows=None, link=None, run_min=5):
+    """Sequence liabilities of S designed sequences on the device (include/abopt.h: abopt_sequence_liabilities_grouped): N-glycosylation
+    sequons (N, not P, S/T), deamidation (N then G/S), isomerisation (D then G/S), Asp-Pro cleavage, Cys, Met and runs of run_min hydrophobic residues (F, I, L,
+    M, V, W, Y; 0 = off), with the charged residues and the Kyte-Doolittle hydropathy of the scored rows.  seqs (S, n), any integer dtype, type k =
+    model.AA_LETTERS[k]; rows (optional, (n,) bool): the scored positions, e.g. the designed ones -- a motif counts iff one of its residues is a scored row, so a
+    sequon completed beside a framework Asn is a liability of the design; link (optional, (n,) bool, `backbone_links`): a motif does not reach over a chain break.
+    -> the dict of `liability_summary` (each entry (S,), flags (S, n)), on the device, no host read.  Raises on CPU tensors (no fallback)."""
+    from . import hip
+    if seqs.dim() != 2 or seqs.shape[0] < 1 or seqs.shape[1] < 1:
+        raise ValueError(f'sequence_liabilities: expected (S, n) sequences with S, n >= 1, got {tuple(seqs.shape)}')
+    for what, t in (('rows', rows), ('link', link)):
+        if t is not None and tuple(t.shape) != (seqs.shape[1],):
+            raise ValueError(f'sequence_liabilities: {what} {tuple(t.shape)} must be (n,) = {(seqs.shape[1],)}')
+    one = lambda t: None if t is None else t[None]
+    return liability_summary(hip.sequence_liabilities_grouped(seqs, seqs.shape[0], rows=one(rows), link=one(link), run_min=run_min))
+
+
+def patch_summary(patch, nbr, area, group, seqs, weight):
+    """patch / nbr of hip.surface_patches_grouped, the area (N, L) they were formed on, group (G, L), seqs (N or G, L) and weight (21,) -> dict: patch_res, nbr;
+    sap (N,) = sum of max(patch_i, 0) and patch_max (N,) = the largest patch among the residues that take part (NaN if none does), float64 rounded to fp32 once;
+    patch_argmax (N,) int64: its residue, the lowest index on a tie, -1 if nobody takes part; apolar_area / polar_area (N,): the area of the side-1 residues
+    whose weight is positive / not positive (a NaN weight is in neither), float64 sums rounded once.  Pure torch, no host read."""
+    N, L = patch.shape
+    G = group.shape[0]
+    part = nbr > 0                                                                     # a residue that takes part is its own neighbour
+    sap = patch.clamp_min(0.0).sum(-1, dtype=torch.float64).float()
+    masked = torch.where(part, patch, float('-inf'))
+    top = masked.amax(-1, keepdim=True)
+    idx = torch.arange(L, device=patch.device).expand(N, L)
+    arg = torch.where(part & (masked == top), idx, L).amin(-1)                         # argmax does not promise the first maximum
+    none = ~part.any(-1)
+    w = weight.to(patch.device)[seqs.long().clamp(0, 20)]
+    side1 = (group == 1)
+    per = lambda t: t if t.shape[0] == N else t.view(G, 1, L).expand(G, N // G if G else 0, L).reshape(N, L)
+    w, side1 = per(w), per(side1)
+    a64 = area.double()
+    zero = torch.zeros_like(a64)
+    return dict(patch_res=patch, nbr=nbr, sap=sap, patch_max=torch.where(none, float('nan'), top[:, 0]), patch_argmax=torch.where(none, -1, arg),
+                apolar_area=torch.where(side1 & (w > 0), a64, zero).sum(-1).float(), polar_area=torch.where(side1 & (w <= 0), a64, zero).sum(-1).float())
+
+
+def developability(batch, seqs, pos, mask, rows='generated', probe=1.4, points=128, radius=10.0, run_min=5, weight=None):
+    """What a designed antibody is, chemically, and where it lies on the surface: the first scorer that reads a candidate's sequence and
+    its structure together.  batch, pos (G*S, L, A, 3) and mask as for `interface_geometry`; seqs (G*S, L), or (G, L) when the S candidates of a complex share
+    their sequence (the re-docks of one design), type k = model.AA_LETTERS[k].  Three calls in a chain:
+      1. hip.sasa_grouped, antibody (side 1) against antigen (side 2) with `slot_radii` (probe, points as for `buried_surface`);
+      2. hip.surface_patches_grouped of the antibody on its FREE area (column 0, the antigen taken away): an aggregation-prone patch matters on the unbound
+         antibody, in the vial, whether or not the antigen later covers it (radius in Angstrom; weight (21,), default Kyte-Doolittle);
+      3. hip.sequence_liabilities_grouped on `rows` -- 'generated' (generate_flag), 'antibody' (every antibody residue) or a (G, L) mask -- with the links of
+         `backbone_links`, one row of results per row of seqs.
+    -> dict of device tensors: pts, area of (1); the entries of `patch_summary` (patch_res, nbr, sap, patch_max, patch_argmax, apolar_area, polar_area: per
+    candidate); the entries of `liability_summary` (per row of seqs).  The area is that of five backbone + CB slots, so this is a coarse-grained patch score
+    comparable between candidates of one complex, NOT a published SAP value; Kyte-Doolittle, 10 A and run_min = 5 are conventional values, not tuned ones, and
+    their distribution for trained weights is unmeasured.  No host synchronisation.  The screen does not call this: apply it to what optimize_antibody /
+    sample_grouped return."""
+    from . import hip, screen
+    grp = _sides('developability', batch, 'chains')
+    if isinstance(rows, str):
+        if rows == 'generated':
+            scored = batch['generate_flag'].bool()
+        elif rows == 'antibody':
+            scored = screen.chain_groups(batch['fragment_type']) == 1
+        else:
+            raise ValueError(f"developability: rows must be 'generated', 'antibody' or a (G, L) tensor, not {rows!r}")
+    else:
+        scored = rows
+    sa = hip.sasa_grouped(pos, mask, grp, slot_radii(pos.shape[2] if pos.dim() == 4 else 1), probe=probe, points=points)
+    free = sa['area'][..., 0].contiguous()
+    weight = hip.default_patch_weight(pos.device) if weight is None else weight
+    pt = hip.surface_patches_grouped(pos, mask, grp, free, seqs, weight=weight, radius=radius)
+    link =backbone_links(batch['chain_nb'], batch['res_nb'])
+    per_group = seqs.shape[0] // max(1, grp.shape[0])                                  # rows of seqs per complex: S, or 1 when the sequence is shared
+    lb = hip.sequence_liabilities_grouped(seqs, max(1, per_group), rows=scored, link=link, run_min=run_min)
+    return dict(sa, **patch_summary(pt['patch'], pt['nbr'], free, grp, seqs, weight), **liability_summary(lb))
+
+
 def _lddt_group(name, fragment_type, interface, G):
     """group (G, L) of the interface form from fragment_type (G, L) or (L,) (screen.chain_groups), or None."""
     from . import screen

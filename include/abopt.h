@@ -23,7 +23,7 @@
 extern "C" {
 #endif
 
-#define ABOPT_ABI_VERSION 57
+#define ABOPT_ABI_VERSION 58
 
 enum { ABOPT_OK = 0, ABOPT_EINVAL = 1, ABOPT_EHIP = 2, ABOPT_EUNSUPPORTED = 3, ABOPT_EWORKSPACE = 4 };
 
@@ -846,6 +846,53 @@ int abopt_relax_max_moved(void);
 int abopt_relax_grouped(const float* pos_in, float* pos_out, const uint8_t* mask, int mask_shared, const uint8_t* move, const uint8_t* link,
                         int G, int S, int L, int A, int max_moved, float w_bond, float w_ca, float w_clash, float w_tether, float clash_d, float step,
                         float max_shift, float max_angle, int iters, float* energy, abopt_stream stream);
+
+/* ---- Developability (ABI 58; no reference counterpart): what a designed sequence is, chemically, and where it lies on the surface --
+ * the filters every antibody pipeline applies before synthesis.  Residue types are the library's: type k = 'ACDEFGHIKLMNPQRSTVWY'[k]; a byte >= 20 is "no type"
+ * (UNK, padding), as in abopt_sequence_profile_grouped.
+ *
+ * abopt_sequence_liabilities_grouped -- integers only, one launch.  G groups of S designs of n positions:
+ *   seqs [G*S,n] uint8; rows (optional, may be NULL) [G,n] uint8: the scored positions, e.g. the designed ones, NULL = all; link (optional, may be NULL) [G,n]
+ *   uint8: link[k] != 0 means residue k is peptide-bonded to k + 1 (the last entry is ignored), NULL = every consecutive pair is bonded; run_min: 0 = class 6
+ *   off, else 2 .. 16.
+ *   window      the positions k .. k + w - 1 (anchor k, width w).  It EXISTS iff k + w - 1 < n, every step inside it is linked and every byte in it is < 20.
+ *               It COUNTS iff it exists and at least one of its positions is a scored row: a sequon completed by designing its third residue beside a
+ *               framework Asn is a liability of the design.
+ *   classes     bit b of the flag byte at the anchor:  0 n_glyc: w = 3, N, not P, S or T;  1 deamidation: w = 2, N then G or S;  2 isomerisation: w = 2, D
+ *               then G or S;  3 cleavage: w = 2, D then P;  4 cys: w = 1, C;  5 met: w = 1, M;  6 hydrophobic_run: w = run_min, every residue one of
+ *               F, I, L, M, V, W, Y -- EVERY anchor of such a window is flagged, not only the first of a maximal run.
+ *   flags [G*S,n] uint8 (DEVICE, spelled void*): the classes whose window at this anchor counts.
+ *   counts [G*S,13] int32 (DEVICE, spelled void*), per design: 0-6 the windows counted per class; 7 the positions with a non-zero flag; 8 K + R, 9 D + E,
+ *               10 H among the scored rows; 11 the scored rows whose byte is < 20; 12 hyd10: the sum over the scored rows of ten times the Kyte-Doolittle
+ *               hydropathy, an exact integer -- in type order 18, 25, -35, -35, 28, -4, -32, 45, -39, 38, 19, -35, -16, -35, -45, -8, -7, 42, -9, -13; a byte
+ *               >= 20 gives 0.  (hyd10 is column 12 of counts, not an output of its own.)
+ *   freq (optional, may be NULL) [G,n] int32 (DEVICE, spelled void*): how many of the group's S designs carry any flag at position k.
+ * Every output is written whole by plain stores: no atomic, no memset node, nothing to clear (with freq the flags are computed a second time, per group, by
+ * further workgroups of the same launch).  Stream-ordered, capturable into a hipGraph, nothing allocated, no host synchronisation.  S >= 1, n >= 1,
+ * G S n <= 2^31 - 1, G <= 65535, G = 0 is a no-op; a bad value or a NULL seqs / flags / counts: ABOPT_EINVAL with a message, before the launch.
+ *
+ * abopt_surface_patches_grouped -- fp32 in a fixed order, one launch.  G groups of S candidates, conventions of abopt_sasa_grouped:
+ *   pos [G*S,L,A,3] fp32; mask [G*S,L,A], or [G,L,A] shared by the S candidates of a group (mask_shared != 0); group [G,L] int32: only side 1 is scored and only
+ *   side 1 contributes (a caller scoring the antigen swaps the sides); area [G*S,L] fp32: the exposed area per residue, contiguous -- a column of
+ *   abopt_sasa_grouped's area; seqs [G*S,L] uint8, or [G,L] shared by the group (seq_shared != 0: the re-docks of one design share their sequence);
+ *   weight [21] fp32 (DEVICE): the hydrophobicity per type, entry 20 serves every byte >= 20; radius fp32 in Angstrom, finite and >= 0.
+ *   centre      of a residue: its atom slot 4 (CB) if A >= 5 and that slot is masked in, else slot 1 (CA); so 2 <= A <= 15.
+ *   taking part a residue takes part iff its group is 1, its centre's mask byte is set, its centre's three coordinates are finite, its area is finite and >= 0
+ *               and its weight is finite.
+ *   arithmetic  h_j = weight[t_j] area_j: one fp32 multiply, rounded once, fused into nothing.  d2 = fmaf(dz, dz, fmaf(dy, dy, dx dx)) on the differences
+ *               dx = c_ix - c_jx (dy, dz likewise), every step rounded once.  T = radius radius, rounded once.  j is a NEIGHBOUR of i iff both take part and
+ *               d2 <= T; a residue is its own neighbour.
+ *   patch [G*S,L] fp32 (DEVICE, spelled void*): for a residue that takes part acc = 0.0f, then acc = acc + h_j over its neighbours j in ascending j; 0 for
+ *               any other residue.
+ *   nbr [G*S,L] int32 (DEVICE, spelled void*): the number of neighbours; 0 for a residue that takes no part.
+ * Every verdict is a pure function of the inputs; there is no prune.  A lane owns a target residue and adds by itself: no reduction, no atomic, so no order but
+ * the definition's exists and a group's result is that of a call on the group alone.  Stream-ordered, capturable into a hipGraph, nothing allocated, no
+ * workspace, no host synchronisation; the outputs are written whole.  L >= 1, 2 <= A <= 15, G S <= 2^31 - 1, G <= 65535, G = 0 or S = 0 is a no-op; every
+ * value or pointer check precedes the launch (ABOPT_EINVAL). */
+int abopt_sequence_liabilities_grouped(const uint8_t* seqs, const uint8_t* rows, const uint8_t* link, int run_min, int G, int S, int n, void* flags,
+                                       void* counts, void* freq, abopt_stream stream);
+int abopt_surface_patches_grouped(const float* pos, const uint8_t* mask, int mask_shared, const int32_t* group, const float* area, const uint8_t* seqs,
+                                  int seq_shared, const float* weight, float radius, int G, int S, int L, int A, void* patch, void* nbr, abopt_stream stream);
 
 /* ---- Measurement hook (bench.py's roofline leg).  When enabled, every launch of the IPA-core kernel is bracketed
  * by hipEvents on the stream it is launched on; abopt_prof_collect synchronises those events and returns the number
