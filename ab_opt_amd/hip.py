@@ -13,7 +13,7 @@ import torch
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # ABOPT_LIB_PATH: developer override to load a variant build of the same ABI (csrc/Makefile VARIANT=...: A/B of two source trees)
 LIB_PATH = os.environ.get('ABOPT_LIB_PATH') or os.path.join(_HERE, 'libabopt_hip.so')
-ABI_VERSION = 58
+ABI_VERSION = 59
 
 c_f = C.c_void_p        # device float*
 c_i64 = C.c_void_p      # device int64*
@@ -176,6 +176,7 @@ _SIGNATURES = {
     'abopt_relax_grouped': (c_int, [c_f, c_f, c_u8, c_int, c_u8, c_u8] + [c_int] * 5 + [c_float] * 8 + [c_int, c_f, c_stream]),
     'abopt_sequence_liabilities_grouped': (c_int, [c_u8, c_u8, c_u8] + [c_int] * 4 + [c_void_p] * 3 + [c_stream]),
     'abopt_surface_patches_grouped': (c_int, [c_f, c_u8, c_int, c_i32, c_f, c_u8, c_int, c_f, c_float] + [c_int] * 4 + [c_void_p, c_void_p, c_stream]),
+    'abopt_interface_energy_grouped': (c_int, [c_f, c_u8, c_int, c_i32, c_u8, c_int, c_u8, c_f, c_f] + [c_int] * 4 + [c_float] * 6 + [c_void_p, c_void_p, c_stream]),
     'abopt_prof_enable': (c_int, [c_int]),
     'abopt_prof_spans_reset': (c_int, [c_stream]),
     'abopt_prof_spans': (c_int, [POINTER(c_int), POINTER(c_double)]),
@@ -1113,6 +1114,82 @@ def surface_patches_grouped(pos, mask, group, area, seqs, weight=None, radius=10
     _check(lib().abopt_surface_patches_grouped(ptr(pos, torch.float32), ptr(mask), int(shared), ptr(group, torch.int32), ptr(area, torch.float32), ptr(seqs, torch.uint8),
                                                int(seq_shared), ptr(weight, torch.float32), radius, G, S, L, A, ptr(patch), ptr(nbr), stream()))
     return dict(patch=patch, nbr=nbr)
+
+
+_RESIDUE_CHARGE = {}
+
+
+def default_residue_charge(device='cpu'):
+    """The default charge table of `interface_energy_grouped`: model.RESIDUE_CHARGE (K, R = +1; D, E = -1; everything else and entry 20 are 0).
+    -> (21,) fp32 on `device`, cached per device: treat it as read-only."""
+    key = str(torch.device(device))
+    if key not in _RESIDUE_CHARGE:
+        from .model import RESIDUE_CHARGE
+        _RESIDUE_CHARGE[key] = torch.tensor(RESIDUE_CHARGE, dtype=torch.float32).to(device)
+    return _RESIDUE_CHARGE[key]
+
+
+def check_interface_energy(hb_cutoff=-0.5, elec_cutoff=15.0, salt_cutoff=7.0, pair_cutoff=8.0, eps=4.0, d_min=3.0):
+    """The knobs of the interface energy (include/abopt.h: abopt_interface_energy_grouped) as a dict of floats under their own names, or
+    ValueError naming the argument: hb_cutoff finite and <= 0 (kcal/mol), the three cutoffs finite and >= 0 (Angstrom), eps and d_min finite and > 0.  The
+    defaults are conventional values (DSSP's -0.5 kcal/mol; 15, 7 and 8 A; eps = 4 r; a floor of 3 A), NOT tuned ones.  No device is needed."""
+    import math
+    out = {}
+    f = float(hb_cutoff)
+    if not math.isfinite(f) or f > 0.0:
+        raise ValueError(f'hb_cutoff must be finite and <= 0 (got {hb_cutoff!r})')
+    out['hb_cutoff'] = f
+    for name, v in (('elec_cutoff', elec_cutoff), ('salt_cutoff', salt_cutoff), ('pair_cutoff', pair_cutoff), ('eps', eps), ('d_min', d_min)):
+        f = float(v)
+        if not math.isfinite(f) or f < 0.0:
+            raise ValueError(f'{name} must be finite and >= 0 (got {v!r})')
+        if name in ('eps', 'd_min') and f == 0.0:
+            raise ValueError(f'{name} must be > 0')
+        out[name] = f
+    return out
+
+
+def interface_energy_grouped(pos, mask, group, seqs, charge=None, pair_table=None, link=None, **knobs):
+    """Interface energetics of G*S candidates in G groups (include/abopt.h: abopt_interface_energy_grouped): per residue of either side,
+    over its partners on the other side, backbone hydrogen bonds (the DSSP rule), a Coulomb term between charged centres (CB, else CA) with the dielectric eps r,
+    and a caller's pair table within pair_cutoff.  pos (G*S,L,A,3), 4 <= A <= 15, slots 0 .. 4 = N, CA, C, O, CB; mask (G*S,L,A), or (G,L,A) shared by the S
+    candidates of a group; group (G,L) int: 1 and 2 name the two sides; seqs (G*S,L), or (G,L) shared by the group, any integer dtype (clamped into 0..255; a
+    byte >= 20 reads entry 20 of both tables); charge (optional, (21,)): default `default_residue_charge` -- a NaN entry takes that type out; pair_table
+    (optional, (21,21)): None = the pair term is off (model.hydrophobic_contact_table() is a placeholder, no statistical potential is shipped); link (optional,
+    (G,L) bool, `sampler.backbone_links`): residue r is peptide-bonded to r + 1, None = every consecutive pair.  knobs: those of `check_interface_energy`,
+    conventional values, not tuned ones.
+    -> dict of device tensors: energy (G*S,L,3) fp32 (hb, elec, pair; kcal/mol-like) and count (G*S,L,5) int32 (bonds as donor, as acceptor, salt bridges,
+    like-charge pairs, partners within pair_cutoff); zeros for a residue on no side.  A pair's energy is given in full to both residues: per-candidate totals sum
+    one side (`sampler.energy_summary`).  One stream-ordered launch, no host synchronisation, capturable."""
+    name = 'interface_energy_grouped'
+    kn = check_interface_energy(**knobs)
+    G, S, L, A, shared = _candidate_args(name, pos, mask, group)
+    if A < 4:
+        raise ValueError(f'{name}: A={A} atoms per residue, the slots 0 .. 3 are N, CA, C, O (expected 4 .. 15)')
+    N = G * S
+    if seqs.dim() != 2 or seqs.shape[1] != L or seqs.shape[0] not in (N, G) or seqs.dtype.is_floating_point or seqs.dtype.is_complex:
+        raise ValueError(f'{name}: seqs {tuple(seqs.shape)} {seqs.dtype} must be integer of shape (G*S, L) = {(N, L)} or (G, L) = {(G, L)}')
+    if charge is not None and (tuple(charge.shape) != (21,) or not charge.dtype.is_floating_point):
+        raise ValueError(f'{name}: charge {tuple(charge.shape)} {charge.dtype} must be floating point of shape (21,): the twenty types and "no type"')
+    if pair_table is not None and (tuple(pair_table.shape) != (21, 21) or not pair_table.dtype.is_floating_point):
+        raise ValueError(f'{name}: pair_table {tuple(pair_table.shape)} {pair_table.dtype} must be floating point of shape (21, 21)')
+    if link is not None and tuple(link.shape) != (G, L):
+        raise ValueError(f'{name}: link {tuple(link.shape)} must be (G, L) = {(G, L)}')
+    pos, mask, group, link = _candidate_tensors(pos, mask, group, link)
+    dev = pos.device
+    seq_shared = seqs.shape[0] != N or S == 1
+    seqs = (seqs if seqs.dtype == torch.uint8 else seqs.to(torch.uint8) if seqs.dtype == torch.bool else seqs.clamp(0, 255).to(torch.uint8)).contiguous()
+    charge = default_residue_charge(dev) if charge is None else charge.to(device=dev, dtype=torch.float32).contiguous()
+    if pair_table is not None:
+        pair_table = pair_table.to(device=dev, dtype=torch.float32).contiguous()
+    new = torch.empty if N else torch.zeros                          # an empty call launches nothing
+    energy = new(N, L, 3, dtype=torch.float32, device=dev)
+    count = new(N, L, 5, dtype=torch.int32, device=dev)
+    _check(lib().abopt_interface_energy_grouped(ptr(pos, torch.float32), ptr(mask), int(shared), ptr(group, torch.int32), ptr(seqs, torch.uint8), int(seq_shared),
+                                                ptr(link, optional=True), ptr(charge, torch.float32), ptr(pair_table, torch.float32, optional=True), G, S, L, A,
+                                                kn['hb_cutoff'], kn['elec_cutoff'], kn['salt_cutoff'], kn['pair_cutoff'], kn['eps'], kn['d_min'], ptr(energy),
+                                                ptr(count), stream()))
+    return dict(energy=energy, count=count)
 
 
 def check_lddt_cutoff(name, v):

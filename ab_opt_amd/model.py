@@ -76,7 +76,20 @@ LIABILITY_NAMES = ('n_glyc', 'deamidation', 'isomerisation', 'cleavage', 'cys', 
 KD_HYDROPATHY_TENTHS = (18, 25, -35, -35, 28, -4, -32, 45, -39, 38, 19, -35, -16, -35, -45, -8, -7, 42, -9, -13)
 KD_HYDROPATHY = tuple(v / 10.0 for v in KD_HYDROPATHY_TENTHS)
 
-ROLE_HOTSPOT, ROLE_REPEL = 1, 2         # the bits of a guide_role word (include/abopt.h: abopt_guide_positions)
+# Interface energetics (include/abopt.h: abopt_interface_energy_grouped): the formal charge of each type in AA_LETTERS order plus entry
+# 20 ("no type"): K, R = +1, D, E = -1, everything else 0 (His is taken as neutral) -- the conventional value at neutral pH, not a tuned one.
+RESIDUE_CHARGE = tuple(1.0 if c in 'KR' else -1.0 if c in 'DE' else 0.0 for c in AA_LETTERS) + (0.0,)
+
+
+def hydrophobic_contact_table():
+    """A PLACEHOLDER pair table for hip.interface_energy_grouped, (21, 21) fp32 on the CPU: -1 where both types are among F, I, L, M, V, W, Y, else 0 (entry 20,
+    "no type", is 0 throughout).  It counts hydrophobic contacts with a minus sign; it is NOT a statistical contact potential -- none is shipped, a caller who
+    has one passes it as pair_table."""
+    h = torch.tensor([1.0 if c in 'FILMVWY' else 0.0 for c in AA_LETTERS] + [0.0])
+    return 0.0 - h[:, None] * h[None, :]
+
+
+ROLE_HOTSPOT, ROLE_REPEL = 1, 2        # the bits of a guide_role word (include/abopt.h: abopt_guide_positions)
 
 
 def guide_roles(batch_or_length, hotspots=None, repel=None, device=None):

@@ -320,6 +320,39 @@ def developability(batch, seqs, pos, mask, rows='generated', probe=1.4, points=1
     return dict(sa, **patch_summary(pt['patch'], pt['nbr'], free, grp, seqs, weight), **liability_summary(lb))
 
 
+def energy_summary(out, group):
+    """energy / count of hip.interface_energy_grouped and the group (G, L) they were formed on -> dict: per candidate (N,), each pair counted ONCE (the kernel
+    gives a pair's energy to both of its residues, so everything is summed over side 1): hbonds (donor + acceptor), salt_bridges, like_pairs, pair_contacts,
+    int32; e_hb, e_elec, e_pair and their sum e_total, float64 sums over side 1 rounded to fp32 once.  freq (G, L) int32: in how many of a group's candidates each
+    residue, of either side, holds a hydrogen bond or a salt bridge.  energy_res (N, L, 3) and count_res (N, L, 5): the per-residue arrays.  Pure torch, no host
+    read."""
+    energy, count = out['energy'], out['count']
+    N, L = count.shape[:2]
+    G = group.shape[0]
+    S = N // G if G else 0
+    side1 = (group == 1).view(G, 1, L).expand(G, S, L).reshape(N, L)
+    c1 = torch.where(side1[..., None], count, 0).sum(1, dtype=torch.int32)
+    e1 = torch.where(side1[..., None], energy.double(), 0.0).sum(1)
+    held = (count[..., 0] + count[..., 1] + count[..., 2]) > 0
+    return dict(hbonds=c1[:, 0] + c1[:, 1], salt_bridges=c1[:, 2], like_pairs=c1[:, 3], pair_contacts=c1[:, 4], e_hb=e1[:, 0].float(), e_elec=e1[:, 1].float(),
+                e_pair=e1[:, 2].float(), e_total=e1.sum(-1).float(), freq=held.view(G, S, L).sum(1, dtype=torch.int32), energy_res=energy, count_res=count)
+
+
+def interface_energy(batch, seqs, pos, mask, groups='chains', charge=None, pair_table=None, **knobs):
+    """Interface energetics of candidate structures of the complexes of `batch` (hip.interface_energy_grouped): whether the contacts
+    across an interface are backbone hydrogen bonds and salt bridges or like charges pressed together.  batch, pos (G*S, L, A, 3), mask and groups as for
+    `interface_geometry` (A >= 4); seqs (G*S, L), or (G, L) when the candidates of a complex share their sequence, type k = model.AA_LETTERS[k]; charge (21,),
+    default model.RESIDUE_CHARGE; pair_table (21, 21), default None = off; the links are those of `backbone_links`; knobs: hb_cutoff, elec_cutoff, salt_cutoff,
+    pair_cutoff, eps, d_min of hip.check_interface_energy.
+    -> the dict of `energy_summary`, on the device, no host synchronisation.  A score on five backbone + CB slots: no side chains, no water, no screening --
+    comparable between candidates of one complex, NOT a binding free energy; the constants are conventional values, not tuned ones, and their distribution for
+    trained weights is unmeasured.  The screen does not call this: apply it to what optimize_antibody / sample_grouped return."""
+    from . import hip
+    grp = _sides('interface_energy', batch, groups)
+    out = hip.interface_energy_grouped(pos, mask, grp, seqs, charge=charge, pair_table=pair_table, link=backbone_links(batch['chain_nb'], batch['res_nb']), **knobs)
+    return energy_summary(out, grp)
+
+
 def _lddt_group(name, fragment_type, interface, G):
     """group (G, L) of the interface form from fragment_type (G, L) or (L,) (screen.chain_groups), or None."""
     from . import screen

@@ -23,7 +23,7 @@
 extern "C" {
 #endif
 
-#define ABOPT_ABI_VERSION 58
+#define ABOPT_ABI_VERSION 59
 
 enum { ABOPT_OK = 0, ABOPT_EINVAL = 1, ABOPT_EHIP = 2, ABOPT_EUNSUPPORTED = 3, ABOPT_EWORKSPACE = 4 };
 
@@ -893,6 +893,50 @@ int abopt_sequence_liabilities_grouped(const uint8_t* seqs, const uint8_t* rows,
                                        void* counts, void* freq, abopt_stream stream);
 int abopt_surface_patches_grouped(const float* pos, const uint8_t* mask, int mask_shared, const int32_t* group, const float* area, const uint8_t* seqs,
                                   int seq_shared, const float* weight, float radius, int G, int S, int L, int A, void* patch, void* nbr, abopt_stream stream);
+
+/* ---- Interface energetics (ABI 59; no reference counterpart: the reference ranks its relaxed poses by Rosetta's dG_separated): what
+ * the contacts across an interface are, chemically -- backbone hydrogen bonds, charge pairs and a caller's residue-pair table --, per residue.  A small
+ * energy-LIKE score on the five backbone + CB slots, comparable between candidates of one complex and nothing more; every constant is a conventional value,
+ * not a tuned one.  G groups of S candidates, conventions of abopt_interface_geometry_grouped and abopt_surface_patches_grouped:
+ *   pos [G*S,L,A,3] fp32, 4 <= A <= 15, atom slots 0 .. 4 = N, CA, C, O, CB; mask [G*S,L,A], or [G,L,A] shared by the S candidates of a group (mask_shared != 0);
+ *   group [G,L] int32: 1 and 2 name the two sides, any other value is on no side; seqs [G*S,L] uint8, or [G,L] shared by the group (seq_shared != 0), type k =
+ *   'ACDEFGHIKLMNPQRSTVWY'[k], a byte >= 20 reads entry 20 of every table; link (optional, may be NULL) [G,L] uint8: link[r] != 0 means residue r is
+ *   peptide-bonded to r + 1 (the last entry is ignored), NULL = every consecutive pair is bonded; charge [21] fp32 (DEVICE); pair_table (optional, may be NULL)
+ *   [21,21] fp32 (DEVICE), NULL = the pair term is off.
+ *   scalars     fp32: hb_cutoff finite and <= 0 (kcal/mol; conventionally -0.5); elec_cutoff, salt_cutoff, pair_cutoff finite and >= 0 (Angstrom;
+ *               conventionally 15, 7, 8); eps and d_min finite and > 0 (conventionally 4 and 3 A).  Each cutoff and d_min is squared once in fp32.
+ *   taking part an atom takes part iff its mask byte is set and its three coordinates are finite.  A term that needs an atom that takes no part is SKIPPED for
+ *               that pair; it never becomes NaN.  This is the one rule; everything below builds on it.
+ *   centre      of a residue: its CB (slot 4) if A >= 5 and that atom takes part, else its CA if that takes part; otherwise the residue has no centre.
+ *   pairs       ordered pairs (owner i, partner j) with group[i] + group[j] == 3, both in {1, 2}.  A pair of bonded neighbours (j == i + 1 with link[i], or
+ *               j == i - 1 with link[j]) is skipped for every term.
+ *   arithmetic  fp32, every step rounded once, nothing fused: d2(a, b) = (dx dx + dy dy) + dz dz on dx = a_x - b_x (dy, dz likewise), in this association;
+ *               distances are sqrt(d2); divisions and square roots are correctly rounded.
+ *   amide H     residue r has one iff r >= 1, step r - 1 is linked, the type of r is not P (12), N of r and C, O of r - 1 take part (r - 1 need not be on a
+ *               side) and len = sqrt(ux ux + uy uy + uz uz) > 0 for u = C_{r-1} - O_{r-1} (same association).  Then H = N_r + u / len per coordinate.
+ *   1. hbond    (Kabsch & Sander 1983, the DSSP rule) donor d with an H and acceptor a with C and O taking part, both CA taking part and
+ *               d2(CA_d, CA_a) < 81 (DSSP's 9 A pre-filter is part of the definition):
+ *               E = 27.888 (((1 / r_ON + 1 / r_CH) - 1 / r_OH) - 1 / r_CN), r_XY = |X_a - Y_d|; if any of the four distances is < 0.5 A, E = -9.9; otherwise
+ *               E = -9.9 where E < -9.9.  A bond EXISTS iff E < hb_cutoff.  For each partner j the owner is examined as donor to j, then as acceptor from j;
+ *               each existing bond adds E to the owner's hb energy and 1 to its donor / acceptor count.
+ *   2. charges  q = charge[type]; a NaN entry reads as 0.  With both centres, q_i != 0, q_j != 0 and d2 <= elec_cutoff^2 (d2 between the centres):
+ *               E = (332.0637 (q_i q_j)) / (eps max(d2, d_min^2)) -- Coulomb with the dielectric eps r, no exponential screening -- is added to the owner's
+ *               elec energy.  Such a pair with d2 <= salt_cutoff^2 is a SALT BRIDGE if q_i q_j < 0 and a LIKE-CHARGE PAIR if q_i q_j > 0.
+ *   3. pairs    with both centres and d2 <= pair_cutoff^2 the partner is counted (column 4, with or without a table) and, with pair_table given,
+ *               pair_table[t_i][t_j] -- the row is the owner's, the table need not be symmetric -- is added to the owner's pair energy; a NaN entry adds nothing.
+ *   energy [G*S,L,3] fp32 (DEVICE, spelled void*): hb, elec, pair.  Each starts at 0.0f and takes its terms over the partners j in ascending j, within a j the
+ *               donor term before the acceptor term: acc = acc + E, rounded once.  Every pair's energy is attributed in full to BOTH of its residues, so a
+ *               per-candidate total sums one side only.
+ *   count [G*S,L,5] int32 (DEVICE, spelled void*): bonds as donor, bonds as acceptor, salt bridges, like-charge pairs, partners within pair_cutoff.
+ *   A residue on no side gets zeros in both.
+ * Every verdict is a pure function of the inputs; there is no prune beyond the definition's own tests.  A lane owns a residue and adds by itself: no reduction,
+ * no atomic, so no order but the definition's exists and a group's result is that of a call on the group alone.  One stream-ordered launch, capturable into a
+ * hipGraph, nothing allocated, no workspace, no host synchronisation; the outputs are written whole by plain stores.  L >= 1, G S <= 2^31 - 1, G <= 65535,
+ * G = 0 or S = 0 is a no-op; every value or pointer check precedes the launch (ABOPT_EINVAL). */
+int abopt_interface_energy_grouped(const float* pos, const uint8_t* mask, int mask_shared, const int32_t* group, const uint8_t* seqs, int seq_shared,
+                                   const uint8_t* link, const float* charge, const float* pair_table, int G, int S, int L, int A, float hb_cutoff,
+                                   float elec_cutoff, float salt_cutoff, float pair_cutoff, float eps, float d_min, void* energy, void* count,
+                                   abopt_stream stream);
 
 /* ---- Measurement hook (bench.py's roofline leg).  When enabled, every launch of the IPA-core kernel is bracketed
  * by hipEvents on the stream it is launched on; abopt_prof_collect synchronises those events and returns the number
