@@ -3,6 +3,7 @@
 // and the argument checks of their entry points.  sasa.hip, guide.hip, relax.hip, develop.hip and interface_energy.hip compile under `#pragma clang fp contract(off)` and include this header BEFORE
 // the pragma.  d2_fma is the only floating-point arithmetic of this file: its fmaf chain is spelled out, so it means the same on either side of the pragma
 // (guide.hip and develop.hip use it; sasa.hip, relax.hip and interface_energy.hip, whose every step is rounded once, do not).
+// similarity.hip (section 6.11), which compares rows of two panels and has no groups, takes the folded grid and d2_fma from here.
 #pragma once
 #include <math.h>
 #include <algorithm>

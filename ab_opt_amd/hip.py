@@ -177,6 +177,8 @@ _SIGNATURES = {
     'abopt_sequence_liabilities_grouped': (c_int, [c_u8, c_u8, c_u8] + [c_int] * 4 + [c_void_p] * 3 + [c_stream]),
     'abopt_surface_patches_grouped': (c_int, [c_f, c_u8, c_int, c_i32, c_f, c_u8, c_int, c_f, c_float] + [c_int] * 4 + [c_void_p, c_void_p, c_stream]),
     'abopt_interface_energy_grouped': (c_int, [c_f, c_u8, c_int, c_i32, c_u8, c_int, c_u8, c_f, c_f] + [c_int] * 4 + [c_float] * 6 + [c_void_p, c_void_p, c_stream]),
+    'abopt_align_sequences': (c_int, [c_u8, c_u8, c_u8, c_u8, c_i32] + [c_int] * 7 + [c_void_p] * 3 + [c_stream]),
+    'abopt_gapped_rmsd': (c_int, [c_f, c_u8, c_f, c_u8] + [c_int] * 4 + [c_void_p, c_void_p, c_stream]),
     'abopt_prof_enable': (c_int, [c_int]),
     'abopt_prof_spans_reset': (c_int, [c_stream]),
     'abopt_prof_spans': (c_int, [POINTER(c_int), POINTER(c_double)]),
@@ -1190,6 +1192,104 @@ def interface_energy_grouped(pos, mask, group, seqs, charge=None, pair_table=Non
                                                 kn['hb_cutoff'], kn['elec_cutoff'], kn['salt_cutoff'], kn['pair_cutoff'], kn['eps'], kn['d_min'], ptr(energy),
                                                 ptr(count), stream()))
     return dict(energy=energy, count=count)
+
+
+SIMILARITY_MAX_LEN = 256    # elements of a row of align_sequences / gapped_rmsd
+SIMILARITY_MAX_TABLE = 32   # rows of a substitution table
+
+
+def check_gaps(name, gap_open, gap_extend):
+    """(int(gap_open), int(gap_extend)), or ValueError unless both are integers with -32767 <= gap_open <= gap_extend <= 0 (the check abopt_align_sequences
+    makes, ahead of any device work; the alignment's statement equals the enumeration of all alignments only with gap_open <= gap_extend)."""
+    for what, v in (('gap_open', gap_open), ('gap_extend', gap_extend)):
+        if isinstance(v, bool) or int(v) != v:
+            raise ValueError(f'{name}: {what} must be an integer (got {v!r}); scale the table and the gaps together, e.g. by 2 for halves')
+    o, e = int(gap_open), int(gap_extend)
+    if not -32767 <= o <= e <= 0:
+        raise ValueError(f'{name}: expected -32767 <= gap_open <= gap_extend <= 0 (got gap_open={o}, gap_extend={e})')
+    return o, e
+
+
+def _similarity_rows(name, what, t, mask, floating):
+    """One side of a similarity call, checked without a device: t (rows, n) integer, or (rows, n, 3) floating point with `floating`; 1 <= n <= 256; mask None or
+    (rows, n).  -> (rows, n), or ValueError."""
+    want = 3 if floating else 2
+    kind = 'floating point (rows, n, 3)' if floating else 'integer (rows, n)'
+    ok = t.dim() == want and (not floating or t.shape[2] == 3) and (t.dtype.is_floating_point if floating else not (t.dtype.is_floating_point or t.dtype.is_complex))
+    if not ok:
+        raise ValueError(f'{name}: {what} {tuple(t.shape)} {t.dtype} must be {kind}')
+    rows, n = t.shape[0], t.shape[1]
+    if not 1 <= n <= SIMILARITY_MAX_LEN:
+        raise ValueError(f'{name}: {what} has {n} elements per row, expected 1 .. {SIMILARITY_MAX_LEN}')
+    if mask is not None and tuple(mask.shape) != (rows, n):
+        raise ValueError(f'{name}: the mask of {what} {tuple(mask.shape)} must be (rows, n) = {(rows, n)}')
+    return rows, n
+
+
+def _similarity_device(name, q, r):
+    """Both sides on one HIP device, or ValueError: the last refusal, before anything is allocated."""
+    if not (q.is_cuda and r.is_cuda):
+        raise ValueError(f'{name}: the kernels run on a HIP device only; got a CPU tensor (there is no CPU path)')
+    if q.device != r.device:
+        raise ValueError(f'{name}: queries on {q.device} and references on {r.device} must share a device')
+    ptr(q, strided=True)                                             # the current device is the tensors'
+    return q.device
+
+
+def _bytes(t):
+    """integer residue types as contiguous uint8, clamped into 0..255 on the device like _seq_bytes"""
+    return (t if t.dtype == torch.uint8 else t.to(torch.uint8) if t.dtype == torch.bool else t.clamp(0, 255).to(torch.uint8)).contiguous()
+
+
+def align_sequences(q, r, table, gap_open, gap_extend, qmask=None, rmask=None):
+    """Global alignment of every query row with every reference row: substitution table, affine gaps, end gaps free (include/abopt.h: abopt_align_sequences;
+    DESIGN.md section 6.11).  q (Q, na) and r (R, nb), any integer dtype (clamped into 0..255), na, nb <= 256; qmask / rmask (optional, (Q, na) / (R, nb) bool):
+    a row's sequence is its mask-true bytes in order, None = all; table (T, T) integer, 1 <= T <= 32, row = the query's byte, a byte >= T reads row or column
+    T - 1, entries within +-32767 (`model.identity_table`, `model.substitution_table`); gap_open <= gap_extend <= 0, integers: a gap run of k columns inside
+    the alignment costs gap_open + (k - 1) gap_extend, one that touches either end nothing.
+    -> dict of device tensors (Q, R) int32: score (the maximum), matches (the most among the alignments of that score), columns (the fewest among those);
+    100 matches / columns is the reference's seqid, up to its choice among co-optimal alignments.  One stream-ordered launch, no host synchronisation,
+    capturable."""
+    name = 'align_sequences'
+    Q, na = _similarity_rows(name, 'q', q, qmask, False)
+    R, nb = _similarity_rows(name, 'r', r, rmask, False)
+    if table.dim() != 2 or table.shape[0] != table.shape[1] or not 1 <= table.shape[0] <= SIMILARITY_MAX_TABLE or table.dtype.is_floating_point or \
+            table.dtype.is_complex:
+        raise ValueError(f'{name}: table {tuple(table.shape)} {table.dtype} must be integer of shape (T, T), 1 <= T <= {SIMILARITY_MAX_TABLE}')
+    o, e = check_gaps(name, gap_open, gap_extend)
+    if Q * R > 0x7fffffff:
+        raise ValueError(f'{name}: {Q} x {R} pairs exceed 2^31 - 1')
+    dev = _similarity_device(name, q, r)
+    q, r, qmask, rmask = _bytes(q), _bytes(r), _as_flags(qmask), _as_flags(rmask)
+    table = table.to(device=dev, dtype=torch.int32).contiguous()
+    new = torch.empty if Q * R else torch.zeros                      # an empty call launches nothing
+    out = {k: new(Q, R, dtype=torch.int32, device=dev) for k in ('score', 'matches', 'columns')}
+    _check(lib().abopt_align_sequences(ptr(q, torch.uint8), ptr(qmask, optional=True), ptr(r, torch.uint8), ptr(rmask, optional=True), ptr(table, torch.int32),
+                                       table.shape[0], o, e, Q, R, na, nb, ptr(out['score']), ptr(out['matches']), ptr(out['columns']), stream()))
+    return out
+
+
+def gapped_rmsd(qca, rca, qmask=None, rmask=None):
+    """The reference's gapped CA RMSD (tools/eval/similarity.py: reslist_rmsd) of every query row against every reference row, without superposition
+    (include/abopt.h: abopt_gapped_rmsd).  qca (Q, na, 3) and rca (R, nb, 3) floating point, na, nb <= 256; qmask / rmask (optional,
+    (Q, na) / (R, nb) bool): a row's residues are its mask-true ones in order, None = all.  The shorter list is placed in the longer, order kept, its last two
+    residues adjacent (the reference's boundary), and the sum of squared CA deviations is minimised.
+    -> dict of device tensors (Q, R): sd fp32 (the minimum; -1 if either side is empty), m int32 (the shorter length; 0 then), rmsd fp32 = sqrt(sd / m), -1
+    where m is 0.  One launch and a few torch operations, stream-ordered, no host synchronisation, capturable."""
+    name = 'gapped_rmsd'
+    Q, na = _similarity_rows(name, 'qca', qca, qmask, True)
+    R, nb = _similarity_rows(name, 'rca', rca, rmask, True)
+    if Q * R > 0x7fffffff:
+        raise ValueError(f'{name}: {Q} x {R} pairs exceed 2^31 - 1')
+    dev = _similarity_device(name, qca, rca)
+    qca, rca, qmask, rmask = qca.float().contiguous(), rca.float().contiguous(), _as_flags(qmask), _as_flags(rmask)
+    new = torch.empty if Q * R else torch.zeros                      # an empty call launches nothing
+    sd = new(Q, R, dtype=torch.float32, device=dev)
+    m = new(Q, R, dtype=torch.int32, device=dev)
+    _check(lib().abopt_gapped_rmsd(ptr(qca, torch.float32), ptr(qmask, optional=True), ptr(rca, torch.float32), ptr(rmask, optional=True), Q, R, na, nb, ptr(sd),
+                                   ptr(m), stream()))
+    rmsd = torch.where(m > 0, torch.sqrt(sd / m.clamp(min=1).float()), torch.full_like(sd, -1.0))
+    return dict(sd=sd, m=m, rmsd=rmsd)
 
 
 def check_lddt_cutoff(name, v):

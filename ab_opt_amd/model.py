@@ -89,6 +89,50 @@ def hydrophobic_contact_table():
     return 0.0 - h[:, None] * h[None, :]
 
 
+def identity_table(match=2, mismatch=-2):
+    """The simplest substitution table of hip.align_sequences (DESIGN.md section 6.11), (21, 21) int32 on the CPU: `match` on the diagonal, `mismatch` elsewhere;
+    entry 20 serves every byte >= 20 ("no type"), which therefore scores `match` against itself -- whether two bytes MATCH is decided on the raw bytes."""
+    for what, v in (('match', match), ('mismatch', mismatch)):
+        if isinstance(v, bool) or int(v) != v or abs(int(v)) > 32767:
+            raise ValueError(f'identity_table: {what} must be an integer within +-32767 (got {v!r})')
+    t = torch.full((21, 21), int(mismatch), dtype=torch.int32)
+    t.fill_diagonal_(int(match))
+    return t
+
+
+def substitution_table(letters, matrix, scale=2):
+    """A caller's substitution matrix as a table of hip.align_sequences, (21, 21) int32 on the CPU: reordered from the caller's alphabet `letters` (a string, one
+    letter per row and column of `matrix`; case is ignored) into AA_LETTERS order, multiplied by `scale`, which must make every entry an integer (ValueError
+    otherwise: the kernel is integer-only, so halves are carried by scale = 2 and the gaps are scaled with them).  A type the alphabet lacks, and entry 20
+    ("no type") unless the alphabet has 'X', gets the minimum of the entries taken, in its whole row and column.  No matrix is shipped.  The reference's
+    alignment (BLOSUM62, gaps -10 / -0.5) is, with Biopython installed,
+        m = Bio.Align.substitution_matrices.load('BLOSUM62')
+        table = substitution_table(m.alphabet, numpy.array(m), scale=2)        # half units
+        hip.align_sequences(q, r, table, gap_open=-20, gap_extend=-1)          # the reference's -10 / -0.5 in the same units"""
+    letters = [c.upper() for c in letters]
+    m = torch.as_tensor(matrix, dtype=torch.float64)
+    if len(set(letters)) != len(letters) or any(len(c) != 1 for c in letters):
+        raise ValueError(f'substitution_table: the alphabet {"".join(letters)!r} repeats a letter')
+    if tuple(m.shape) != (len(letters), len(letters)):
+        raise ValueError(f'substitution_table: matrix {tuple(m.shape)} does not fit the alphabet of {len(letters)} letters')
+    s = m * float(scale)
+    if not torch.isfinite(s).all() or not torch.equal(s, s.round()):
+        raise ValueError(f'substitution_table: scale={scale!r} does not make every entry an integer')
+    if s.abs().max() > 32767:
+        raise ValueError('substitution_table: an entry exceeds +-32767 after scaling')
+    src = [letters.index(c) if c in letters else -1 for c in AA_LETTERS + 'X']
+    have = [k for k in src if k >= 0]
+    if not have:
+        raise ValueError(f'substitution_table: the alphabet {"".join(letters)!r} holds none of {AA_LETTERS}')
+    low = s[have][:, have].min()
+    t = torch.full((21, 21), float(low), dtype=torch.float64)
+    for i, a in enumerate(src):
+        for j, b in enumerate(src):
+            if a >= 0 and b >= 0:
+                t[i, j] = s[a, b]
+    return t.to(torch.int32)
+
+
 ROLE_HOTSPOT, ROLE_REPEL = 1, 2        # the bits of a guide_role word (include/abopt.h: abopt_guide_positions)
 
 

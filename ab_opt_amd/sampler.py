@@ -353,6 +353,77 @@ def interface_energy(batch, seqs, pos, mask, groups='chains', charge=None, pair_
     return energy_summary(out, grp)
 
 
+def _front_rows(name, flags, *tensors):
+    """The kernels of `similarity` take rows of at most 256 elements.  flags (N, L) bool and tensors (N, L, ...): returned as they are when L <= 256; else each
+    row's flagged elements are moved to the front, in order, and the rows cut to 256 -- which costs one host read, to refuse a row with more than 256 of them."""
+    from . import hip
+    W = hip.SIMILARITY_MAX_LEN
+    if flags.shape[1] <= W:
+        return (flags,) + tensors
+    if int(flags.sum(1).max()) > W:
+        raise ValueError(f'{name}: a row selects more than {W} residues')
+    order = torch.sort((~flags).to(torch.uint8), dim=1, stable=True)[1][:, :W]
+    take = lambda t: torch.gather(t, 1, order.view(order.shape + (1,) * (t.dim() - 2)).expand(order.shape + t.shape[2:]))
+    return (take(flags),) + tuple(take(t) for t in tensors)
+
+
+def similarity(batch, seqs, pos, mask, rows='generated', ref_seqs=None, ref_ca=None, ref_mask=None, table=None, gap_open=-20, gap_extend=-1):
+    """How close candidates are to reference sequences and loops of ANY length: the `seqid` and `rmsd` of the reference's eval stage
+    (tools/eval/similarity.py), by hip.align_sequences and hip.gapped_rmsd.  batch: G complexes; seqs (G*S, L), type k = model.AA_LETTERS[k]; pos (G*S, L, A, 3)
+    with CA in slot 1 and mask (G*S, L, A): S candidates of each, candidate c belongs to complex c // S.  rows: the compared residues of a candidate --
+    'generated' (generate_flag), 'antibody' (every antibody residue) or a (G, L) mask; a residue whose CA is masked out is left out of the rmsd.
+    Without references every candidate is compared with the NATIVE residues of its own complex on the same rows (batch['aa'], batch['pos_heavyatom']): the
+    reference's two eval numbers, every entry (G*S,) -- the launch compares every candidate with every complex's natives and keeps its own, G times the pairs
+    kept.  With ref_seqs (R, nb) and / or ref_ca (R, nb, 3), and ref_mask (R, nb) (None = all), every candidate is compared with every reference: every entry
+    (G*S, R) -- a panel of known binders, germlines, the designs themselves.  table: default model.identity_table(); the default gaps are the reference's
+    -10 / -0.5 in the half units of model.substitution_table(..., scale=2) (no BLOSUM62 is shipped).
+    -> dict of device tensors: seqid fp32 (100 matches / columns, -1 at 0 columns), score, matches, columns int32 [with sequences]; rmsd, sd fp32 and m int32
+    [with coordinates].  End gaps are free, so sequences whose best overlap scores below 0 are not paired at all (score 0, seqid 0).  No superposition: the
+    rmsd is that of the frames pos is given in.  Rows wider than 256 cost one host read, otherwise none.  The screen does not call this: apply it to what
+    optimize_antibody / sample_grouped return."""
+    from . import hip, screen
+    from .model import identity_table
+    name = 'similarity'
+    G, L = batch['aa'].shape
+    if isinstance(rows, str):
+        if rows == 'generated':
+            scored = batch['generate_flag'].bool()
+        elif rows == 'antibody':
+            scored = screen.chain_groups(batch['fragment_type']) == 1
+        else:
+            raise ValueError(f"{name}: rows must be 'generated', 'antibody' or a (G, L) tensor, not {rows!r}")
+    else:
+        scored = rows.bool()
+    if seqs.dim() != 2 or pos.dim() != 4 or mask.dim() != 3 or tuple(scored.shape) != (G, L) or seqs.shape[1] != L or tuple(pos.shape[1:]) != (L, pos.shape[2], 3) \
+            or pos.shape[2] < 2 or tuple(mask.shape) != tuple(pos.shape[:3]) or seqs.shape[0] != pos.shape[0] or (seqs.shape[0] % G if G else seqs.shape[0]):
+        raise ValueError(f'{name}: expected seqs (G*S, L), pos (G*S, L, A >= 2, 3), mask (G*S, L, A) and rows (G, L) with G = {G}, L = {L}; got '
+                         f'{tuple(seqs.shape)}, {tuple(pos.shape)}, {tuple(mask.shape)} and {tuple(scored.shape)}')
+    N = seqs.shape[0]
+    S = N // G if G else 0
+    own = ref_seqs is None and ref_ca is None
+    crow = scored.repeat_interleave(S, 0) if S != 1 else scored
+    cflag, cseq, cca, cok = _front_rows(name, crow, seqs, pos[:, :, 1], mask[:, :, 1].bool())
+    if own:
+        rflag, ref_seqs, ref_ca, rok = _front_rows(name, scored, batch['aa'], batch['pos_heavyatom'][:, :, 1], batch['mask_heavyatom'][:, :, 1].bool())
+        ref_ca_mask = rflag & rok
+    else:
+        rflag = ref_mask
+        ref_ca_mask = ref_mask
+    out = {}
+    if ref_seqs is not None:
+        al = hip.align_sequences(cseq, ref_seqs, identity_table() if table is None else table, gap_open, gap_extend, qmask=cflag, rmask=rflag)
+        cols = al['columns']
+        out.update(al, seqid=torch.where(cols > 0, 100.0 * al['matches'].float() / cols.clamp(min=1).float(), torch.full_like(cols, -1, dtype=torch.float32)))
+    if ref_ca is not None:
+        out.update(hip.gapped_rmsd(cca, ref_ca, qmask=cflag & cok, rmask=ref_ca_mask))
+    if own and G:                                                   # a candidate's own complex is column c // S
+        col = (torch.arange(N, device=seqs.device) // S)[:, None]
+        out = {k: v.gather(1, col)[:, 0] for k, v in out.items()}
+    elif own:
+        out = {k: v.reshape(0) for k, v in out.items()}
+    return out
+
+
 def _lddt_group(name, fragment_type, interface, G):
     """group (G, L) of the interface form from fragment_type (G, L) or (L,) (screen.chain_groups), or None."""
     from . import screen

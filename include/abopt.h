@@ -938,6 +938,52 @@ int abopt_interface_energy_grouped(const float* pos, const uint8_t* mask, int ma
                                    float elec_cutoff, float salt_cutoff, float pair_cutoff, float eps, float d_min, void* energy, void* count,
                                    abopt_stream stream);
 
+/* ---- Similarity to reference sequences and loops: the `seqid` and `rmsd` of the reference's eval stage (tools/eval/similarity.py)
+ * for sequences and residue lists of DIFFERENT lengths.  Both entries compare every one of Q query rows with every one of R reference rows.
+ * ABOPT_ABI_VERSION stays 59: the two entries are additions, no existing signature moves, and a library built before them is still caught, because binding
+ * the signature table fails on the missing symbol.
+ *   rows        a row has na (query) or nb (reference) elements and a mask of one byte per element, NULL = all true; a row's SEQUENCE is its mask-true
+ *               elements in order -- masks need not be prefixes, and a row may be empty.
+ *
+ * abopt_align_sequences -- integers only.  Global alignment with a substitution table and affine gaps, end gaps free.
+ *   q [Q,na] uint8, qmask (may be NULL) [Q,na] uint8; r [R,nb] uint8, rmask (may be NULL) [R,nb] uint8; table [T,T] int32 (DEVICE), 1 <= T <= 32, row = the
+ *   query's byte, column = the reference's, a byte >= T reads row or column T - 1; an entry beyond +-32767 is read as +-32767; gap_open and gap_extend with
+ *   -32767 <= gap_open <= gap_extend <= 0.
+ *   alignment   a sequence of columns, each a pair (a_i, b_j), a gap against b_j or a_i against a gap, that spells a (the query's sequence) and b in order.
+ *   gap run     a maximal run of consecutive columns with the gap on the SAME side.  A run that touches either end of the alignment costs nothing; any
+ *               other run of k columns costs gap_open + (k - 1) gap_extend.  (A run of one side directly after a run of the other is a run of its own: behind
+ *               a leading run it does not touch the end, so it is paid.)
+ *   pair        scores table[a_i][b_j] and is a MATCH iff the two raw bytes are equal (also when both are >= T).
+ *   score, matches, columns [Q,R] int32 (DEVICE, spelled void*): score is the maximum over all alignments; matches the largest number of matches among the
+ *               alignments of that score; columns the smallest number of columns among those.  All three are additive along an alignment, so a three-state
+ *               Gotoh recurrence that carries (score, matches, -columns) and takes the lexicographic maximum computes them; the result depends on no
+ *               traceback order.  With gap_open <= gap_extend it equals the enumeration of every alignment
+ *               (tests/test_similarity.py::test_alignment_statement_equals_brute_force).  If either sequence is empty: 0, 0, max(len a, len b).
+ *   seqid       100 matches / columns is the identity over the alignment's columns that the reference reports.  UNVERIFIED against it: Biopython's first
+ *               alignment may be another co-optimal one, so the identity can differ on ties (Biopython is not a dependency and nothing here was compared
+ *               with it).  The score has no such ambiguity.
+ *
+ * abopt_gapped_rmsd -- fp32 in a fixed order.  The reference's reslist_rmsd as written: CA deviations minimised over gapped placements, no superposition.
+ *   qca [Q,na,3] fp32, qmask (may be NULL) [Q,na]; rca [R,nb,3] fp32, rmask (may be NULL) [R,nb].
+ *   lists       s is the shorter sequence (M residues) and l the longer (N); with equal lengths the query is s.  d(i, j) = fmaf(dz, dz, fmaf(dy, dy, dx dx))
+ *               on dx = s_ix - l_jx (dy, dz likewise), every step rounded once.
+ *   recurrence  SD[M-1][j] = d(M-1, j);  for i < M - 1 and j <= N - M + i:  SD[i][j] = min(d(i, j) + SD[i+1][j+1], SD[i][j+1]), where SD[i][N-M+i+1] reads
+ *               +inf -- so the boundary diagonal is built by the same addition, d + SD[i+1][j+1], and the order of additions is fixed.  One fp32 add and one
+ *               min per cell.
+ *   sd [Q,R] fp32 (DEVICE, spelled void*): min over j <= N - M of SD[0][j];  m [Q,R] int32 (DEVICE, spelled void*): M.  If either sequence is empty: sd = -1
+ *               and m = 0.  The caller's rmsd is sqrt(sd / m).
+ *   ADJACENT LAST PAIR  the last row is d itself, not its running minimum, so the result is the minimum over the order-preserving placements of s in l in
+ *               which the LAST TWO residues of s are adjacent in l (for M >= 2), not over all of them.  That is the reference's number and is kept on
+ *               purpose (tests/test_similarity.py::test_rmsd_statement_is_the_adjacent_last_minimum).
+ *   Coordinates are expected to be finite; a NaN is dropped or kept by a min as fminf does.
+ * Both: one launch, a wave per pair, four pairs per workgroup; no atomic, no workspace, nothing allocated, no host synchronisation, capturable into a hipGraph;
+ * the outputs are written whole by plain stores and a pair's result is that of a call on the pair alone.  Q, R >= 0, na, nb >= 1, Q R <= 2^31 - 1
+ * (ABOPT_EINVAL); na, nb <= 256 (beyond: ABOPT_EUNSUPPORTED); Q = 0 or R = 0 is a no-op; every check precedes the launch. */
+int abopt_align_sequences(const uint8_t* q, const uint8_t* qmask, const uint8_t* r, const uint8_t* rmask, const int32_t* table, int T, int gap_open,
+                          int gap_extend, int Q, int R, int na, int nb, void* score, void* matches, void* columns, abopt_stream stream);
+int abopt_gapped_rmsd(const float* qca, const uint8_t* qmask, const float* rca, const uint8_t* rmask, int Q, int R, int na, int nb, void* sd, void* m,
+                      abopt_stream stream);
+
 /* ---- Measurement hook (bench.py's roofline leg).  When enabled, every launch of the IPA-core kernel is bracketed
  * by hipEvents on the stream it is launched on; abopt_prof_collect synchronises those events and returns the number
  * of launches and their summed duration since the last enable.  Process-global, off by default, not for concurrent
