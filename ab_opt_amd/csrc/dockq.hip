@@ -266,7 +266,7 @@ extern "C" int abopt_dockq_lite_grouped(const float* model_pos, const uint8_t* m
 extern "C" int abopt_dockq_lite(const float* model_pos, const uint8_t* model_mask, int model_mask_shared, const float* native_pos,
                                 const uint8_t* native_mask, const int32_t* group, int S, int L, int A, float* out,
                                 void* ws, size_t ws_bytes, abopt_stream stream) {
-    ABOPT_CHECK_ARG(S >= 0 && L >= 1 && A >= 2, "dockq_lite: bad dims S=%d L=%d A=%d", S, L, A);
+    ABOPT_CHECK_ARG(S >= 0 && L >= 1 && A >= 2 && (int64_t)L * L <= 0x7fffffff, "dockq_lite: bad dims S=%d L=%d A=%d", S, L, A);
     if (S == 0) return ABOPT_OK;
     ABOPT_CHECK_ARG(model_pos && model_mask && native_pos && native_mask && group && out && ws, "dockq_lite: NULL argument");
     if (ws_bytes < abopt_dockq_workspace_bytes(L)) { set_error("dockq_lite: workspace too small (%zu bytes given)", ws_bytes); return ABOPT_EWORKSPACE; }

@@ -553,20 +553,19 @@ class _LoopGraph:
         run(1)                                                          # warm: kernel attributes, host-side caches, cdf tables
         torch.cuda.synchronize(self.res_feat.device)
         self.graph = torch.cuda.CUDAGraph()
-        before = set(hip.Workspace._bufs)
         hip.prof_enable(hip.GRAPH_CAPTURE_EVENTS)                       # normally off: the measurement hook's event pairs stay out of the graph
         if hip.GRAPH_CAPTURE_SPANS:
             hip.lib().abopt_prof_enable(3)               # span slots for the dominant kernel's launches, baked into the captured nodes
         try:
-            with torch.cuda.graph(self.graph):
+            # the scratch slab the capture allocates on the capturing stream lives in this graph's pool: this graph keeps it, it serves no other stream user,
+            # and the capture uses no slab that an earlier capture left under the capturing stream's key (hip.Workspace.private says why)
+            with hip.Workspace.private() as self.keep, torch.cuda.graph(self.graph):
                 self.out = run(spec.stop_after)
         finally:
             if hip.GRAPH_CAPTURE_EVENTS:
                 hip.lib().abopt_prof_enable(2)           # stop bracketing launches, keep the pairs the graph re-records
             if hip.GRAPH_CAPTURE_SPANS:
                 hip.lib().abopt_prof_enable(4)
-        # the scratch slab the capture allocated on the capturing stream lives in this graph's pool: it must not serve another stream user
-        self.keep = [hip.Workspace._bufs.pop(k) for k in set(hip.Workspace._bufs) - before]
         self.info = dict(dpm.last_run_info)
         self._pf_src = None                                             # (weakref to the caller's pair_feat, its _version) of the last copy
 

@@ -4,6 +4,7 @@ PyTorch is used only as the owner of device memory and streams: every call passe
 `tensor.data_ptr()` and `torch.cuda.current_stream().cuda_stream`.  There is no fallback:
 if the library is missing or a tensor is not on a HIP device, these functions raise.
 """
+import contextlib
 import ctypes as C
 from ctypes import POINTER, c_char_p, c_double, c_float, c_int, c_int64, c_longlong, c_size_t, c_uint64, c_void_p
 import os
@@ -263,6 +264,28 @@ class Workspace:
             buf = torch.empty(int(nbytes), dtype=torch.uint8, device=device)
             cls._bufs[key] = buf
         return buf
+
+    @classmethod
+    @contextlib.contextmanager
+    def private(cls):
+        """`with Workspace.private() as keep:` around a stream capture.  Inside, no buffer from before is visible, so every buffer the recorded launches use is
+        allocated inside the capture, from the graph's own pool; on exit those buffers are in the list `keep` -- whoever holds the graph holds it, for as long --
+        and the buffers from before are back, untouched.
+        Why hiding and not only "keep the keys that are new": torch records every capture on ONE stream (torch.cuda.graph.default_capture_stream), so the key of
+        that stream is usually there already, left by an earlier capture, and its buffer lives in that earlier graph's pool.  A capture that finds it large
+        enough records launches that point into a foreign pool; one that finds it too small replaces it, the replacement is then nobody's, and the next
+        capture that needs more drops it in turn.  Either way a live graph ends up pointing at a freed block of a pool whose graph is gone, and
+        torch.cuda.graph.__enter__ calls torch.cuda.empty_cache(), which gives the free blocks of such pools back to the device: the next replay of that graph
+        then writes into memory that is unmapped or somebody else's."""
+        held = dict(cls._bufs)
+        cls._bufs.clear()
+        keep = []
+        try:
+            yield keep
+        finally:
+            keep.extend(cls._bufs.values())
+            cls._bufs.clear()
+            cls._bufs.update(held)
 
 
 def device_info():
@@ -1582,13 +1605,42 @@ def reconstruct_backbone_partially(pos_ctx, R_new, t_new, aa, chain_nb, res_nb, 
     return pos_new, mask_new
 
 
+def _dockq_args(name, model_pos, model_mask, native_pos, native_mask, group):
+    """The shape contract of hip.dockq_lite_grouped (hip.dockq_lite checks the same with G = 1, in its own words), checked without a device: the candidate side is _candidate_args (model_pos (G*S, L, A, 3) in whole groups of
+    the G rows of group (G, L), model_mask (G*S, L, A) or (G, L, A)); the native side is native_pos (G, L, A, 3) and native_mask (G, L, A) with G >= 1; the CA
+    is atom slot 1, so A >= 2.  -> (G, S, L, A, shared: the mask is per native), or ValueError."""
+    G, S, L, A, shared = _candidate_args(name, model_pos, model_mask, group)
+    if G < 1 or tuple(native_pos.shape) != (G, L, A, 3) or tuple(native_mask.shape) != (G, L, A):
+        raise ValueError(f'{name}: native_pos {tuple(native_pos.shape)} and native_mask {tuple(native_mask.shape)} are not (G, L, A, 3) and (G, L, A) '
+                         f'with G >= 1 for the (G, L, A) = {(G, L, A)} of the candidates and group')
+    if A < 2:
+        raise ValueError(f'{name}: A={A} atoms per residue, expected 2 .. 15 (the CA is atom slot 1)')
+    return G, S, L, A, shared
+
+
 def dockq_lite(model_pos, model_mask, native_pos, native_mask, group, check=True):
     """DockQ of S candidates against one native (include/abopt.h: abopt_dockq_lite) -> (S, 4) = fnat, irms, Lrms, DockQ.
     model_pos (S,L,A,3); model_mask (S,L,A) or (L,A) shared; native_pos (L,A,3); native_mask (L,A); group (L,) int {0,1,2}.
     check=True (one device read-back) raises, like the reference's asserts (DockQ.py:150-188), when a candidate has no CA atom
-    common to model and native in its interface, receptor or ligand; check=False leaves the kernel's -1 markers in place."""
-    S, L, A, _ = model_pos.shape
-    shared = model_mask.dim() == 2
+    common to model and native in its interface, receptor or ligand; check=False leaves the kernel's -1 markers in place.
+    A wrong shape of any of the five tensors is a ValueError before any device call: what _dockq_args checks, with G = 1 and the shapes named as given;
+    2 <= A <= 15; a three-dimensional model_mask has one row per candidate (a (1,L,A) mask with S > 1 is refused, not taken as shared)."""
+    name = 'dockq_lite'
+    shapes = [tuple(t.shape) for t in (model_pos, model_mask, native_pos, native_mask, group)]
+    if [len(s) for s in shapes] not in ([4, 3, 3, 2, 1], [4, 2, 3, 2, 1]):
+        raise ValueError(f'{name}: expected model_pos (S, L, A, 3), model_mask (S, L, A) or (L, A), native_pos (L, A, 3), native_mask (L, A) and group (L,), got '
+                         f'{shapes[0]}, {shapes[1]}, {shapes[2]}, {shapes[3]} and {shapes[4]}')
+    S, A, L = shapes[0][0], shapes[0][2], shapes[4][0]
+    if L < 1 or shapes[0][1:] != (L, A, 3):
+        raise ValueError(f'{name}: model_pos {shapes[0]} is not (S, L, A, 3) with the L = {L} of group {shapes[4]}')
+    if not 2 <= A <= 15:
+        raise ValueError(f'{name}: A={A} atoms per residue, expected 2 .. 15 (the CA is atom slot 1)')
+    shared = len(shapes[1]) == 2
+    if shapes[1] != ((L, A) if shared else (S, L, A)):
+        raise ValueError(f'{name}: model_mask {shapes[1]} is neither per candidate {(S, L, A)} nor shared {(L, A)}')
+    if shapes[2] != (L, A, 3) or shapes[3] != (L, A):
+        raise ValueError(f'{name}: native_pos {shapes[2]} and native_mask {shapes[3]} are not {(L, A, 3)} and {(L, A)}')
+    ptr(model_pos, strided=True)                                       # a CPU tensor is refused before anything is allocated
     model_pos, model_mask, native_pos, native_mask = _contig(model_pos.float(), model_mask, native_pos.float(), native_mask)
     group = group.to(torch.int32).contiguous()
     out = torch.empty(S, 4, dtype=torch.float32, device=model_pos.device)
@@ -1606,15 +1658,10 @@ def dockq_lite_grouped(model_pos, model_mask, native_pos, native_mask, group, ch
     """DockQ of G*S candidates against G natives in one launch (include/abopt.h: abopt_dockq_lite_grouped) -> (G*S, 4) = fnat, irms, Lrms, DockQ;
     candidate c is scored against native c // S, and every row equals dockq_lite on its group alone, bit for bit.
     model_pos (G*S,L,A,3); model_mask (G*S,L,A), or (G,L,A) shared by the S candidates of a native; native_pos (G,L,A,3); native_mask (G,L,A);
-    group (G,L) int {0,1,2}.  check: as dockq_lite."""
-    G, L, A, _ = native_pos.shape
-    N = model_pos.shape[0]
-    if G == 0 or N % G or tuple(model_pos.shape[1:]) != (L, A, 3):
-        raise ValueError(f'dockq_lite_grouped: {tuple(model_pos.shape)} candidates do not split into groups of the {G} natives {tuple(native_pos.shape)}')
-    S = N // G
-    shared = model_mask.shape[0] != N or S == 1
-    if tuple(model_mask.shape) != ((G if shared else N), L, A):
-        raise ValueError(f'dockq_lite_grouped: model_mask {tuple(model_mask.shape)} is neither per candidate nor per native')
+    group (G,L) int {0,1,2}.  check: as dockq_lite.  A wrong shape of any of the five tensors is a ValueError before any device call (_dockq_args)."""
+    G, S, L, A, shared = _dockq_args('dockq_lite_grouped', model_pos, model_mask, native_pos, native_mask, group)
+    N = G * S
+    ptr(model_pos, strided=True)                                       # a CPU tensor is refused before anything is allocated
     model_pos, model_mask, native_pos, native_mask = _contig(model_pos.float(), model_mask, native_pos.float(), native_mask)
     group = group.to(torch.int32).contiguous()
     out = torch.empty(N, 4, dtype=torch.float32, device=model_pos.device)

@@ -617,12 +617,10 @@ class GraphedTrainStep:
                 self._one_step()
         torch.cuda.current_stream(dev).wait_stream(side)
         torch.cuda.synchronize(dev)
-        before = set(hip.Workspace._bufs)
         self.graph = torch.cuda.CUDAGraph()
         optimizer.zero_grad(set_to_none=True)
-        with torch.cuda.graph(self.graph):
+        with hip.Workspace.private() as self.keep, torch.cuda.graph(self.graph):         # scratch slabs owned by this graph's pool, and no one else's
             self.losses = self._one_step()
-        self.keep = [hip.Workspace._bufs.pop(k) for k in set(hip.Workspace._bufs) - before]     # scratch slabs owned by this graph's pool
 
     def _set_seed(self, dpm):
         self.seed_dev.copy_(torch.tensor([dpm._new_seed(), 0], dtype=torch.int64))

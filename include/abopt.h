@@ -404,7 +404,8 @@ int abopt_add_noise(const int64_t* t, const float* alpha_bars, const float* fwd_
  * all heavy atoms, 5 A for Fnat, 10 A for the interface) and superimposes CA atoms twice (interface -> iRMS; receptor -> LRMS).
  * Structures are tensors with the batch's residue indexing: pos [L,A,3] Angstrom, mask [L,A], group [L] (0 = not in the file,
  * 1 / 2 = the two chains); atom slot 1 = CA.  model_pos [S,L,A,3]; model_mask [S,L,A], or [L,A] with model_mask_shared = 1.
- * out [S,4] = (fnat, irms, Lrms, DockQ).  ws: abopt_dockq_workspace_bytes(L).
+ * out [S,4] = (fnat, irms, Lrms, DockQ).  ws: abopt_dockq_workspace_bytes(L).  S >= 0, L >= 1 with L * L <= INT_MAX (the contact table is
+ * indexed with an int; L = 46341 is refused with ABOPT_EINVAL, as by the grouped entry), A >= 2.
  * A candidate whose interface, receptor or ligand has NO CA atom present in both model and native has no superposition: its irms /
  * Lrms (and DockQ) come back as -1 (the reference asserts on such inputs); with 1 or 2 common atoms the fit is degenerate but defined. */
 size_t abopt_dockq_workspace_bytes(int L);
