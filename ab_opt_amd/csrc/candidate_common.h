@@ -3,7 +3,8 @@
 // and the argument checks of their entry points.  sasa.hip, guide.hip, relax.hip, develop.hip and interface_energy.hip compile under `#pragma clang fp contract(off)` and include this header BEFORE
 // the pragma.  d2_fma is the only floating-point arithmetic of this file: its fmaf chain is spelled out, so it means the same on either side of the pragma
 // (guide.hip and develop.hip use it; sasa.hip, relax.hip and interface_energy.hip, whose every step is rounded once, do not).
-// similarity.hip (section 6.11), which compares rows of two panels and has no groups, takes the folded grid and d2_fma from here.
+// similarity.hip (section 6.11) and superpose.hip (section 6.12), which compare rows of two panels and have no groups, take the folded grid and compact_ranks
+// from here (similarity.hip d2_fma too).
 #pragma once
 #include <math.h>
 #include <algorithm>
@@ -77,6 +78,22 @@ __device__ __forceinline__ int slice_ranks(int L, Pred pred, int slice, int slic
     cur = 0;
     if (lo < hi) take(L, pred, cur, lo, nullptr, false);
     return hi - lo;
+}
+
+// Wave-uniform: the elements k < n of a row with mask[k] != 0 (mask == NULL: all), in order, are numbered 0 .. len - 1 and put(rank, k) is called for each by the
+// lane that holds it.  -> len.  The ranks come from a ballot prefix per 64 elements.
+template <class Put>
+__device__ __forceinline__ int compact_ranks(const uint8_t* __restrict__ mask, int n, Put put) {
+    const int lane = threadIdx.x & 63;
+    int len = 0;
+    for (int k0 = 0; k0 < n; k0 += 64) {
+        const int k = k0 + lane;
+        const bool f = k < n && (mask == nullptr || mask[k] != 0);
+        const unsigned long long b = __ballot(f);
+        if (f) put(len + __popcll(b & ((1ull << lane) - 1ull)), k);
+        len += __popcll(b);
+    }
+    return len;
 }
 
 // ---------------------------------------------------------------- host side

@@ -6,10 +6,12 @@
 //   greedy     the alive structure with the most alive neighbours (ties: lowest index) becomes a centre, its alive neighbours its members
 // Two launches: pose_adjacency_kernel writes the neighbour relation as a bit matrix (and every row's population), greedy_cluster_kernel walks it.
 // Designed sequences are clustered by the same walk over the Hamming relation of seq_adjacency_kernel, and sequence_profile_kernel counts a group's
-// per-position composition (abopt_cluster_sequences_grouped, abopt_sequence_profile_grouped).
+// per-position composition (abopt_cluster_sequences_grouped, abopt_sequence_profile_grouped).  Loop shapes are clustered by the walk
+// over a third relation, the RMSD after best-fit superposition of shape_adjacency_kernel (abopt_cluster_shapes_grouped).
 #include <math.h>
 #include "abopt_common.h"
 #include "kernels.h"
+#include "superpose.h"
 
 namespace abopt {
 
@@ -265,6 +267,48 @@ __global__ __launch_bounds__(256) void seq_adjacency_kernel(const uint8_t* __res
     }
 }
 
+// ---- Shape clustering: the same greedy walk over a third relation, the RMSD AFTER best-fit superposition on all n points.
+//   distance   ss(a, b) = min over proper rotations and translations of sum_k |R a_k + t - b_k|^2, by superpose_pair (superpose.h) in double
+//   neighbours ss(a, b) <= cutoff^2 n; the diagonal is always set
+constexpr int SH_MAXLEN = 256;             // points of a structure: the row length abopt_superposed_rmsd takes
+
+struct RowPoint {                          // the k-th point of a structure in global memory, as double
+    const float* row;
+    __device__ __forceinline__ void operator()(int k, double p[3]) const { p[0] = (double)row[3 * k]; p[1] = (double)row[3 * k + 1]; p[2] = (double)row[3 * k + 2]; }
+};
+
+constexpr int SH_ROWS = 4;                 // rows of a workgroup: one per wave
+
+// The shape twin of pose_adjacency_kernel: the same outputs (bit rows through __ballot, lane j = column 64 cb + j, row populations, every word written once by
+// lane 0).  A lane computes its pair from start to finish with superpose_pair and shares nothing, so nothing is staged and a workgroup gains nothing from many
+// rows: grid (4-row tile, group), a wave per row -- S / 4 workgroups, where the 64-row tile of the pose kernel would leave three quarters of the CUs idle at
+// S = 4096 and one wave per SIMD at S = 16384.  The rows come straight from global memory (a wave's 64 columns are 64 runs of 12 n bytes that the tile's 4 waves
+// read together, out of the caches; three passes over them).  The greedy kernel needs a relation that is symmetric bit for bit and a best fit is not symmetric
+// in floating point, so the pair (a, b) is ALWAYS evaluated as (x = row min(a, b), y = row max(a, b)): the lanes that own (a, b) and (b, a) run the same
+// instructions on the same values.  A structure holding a NaN has ss = NaN against everything, which is no neighbour; its diagonal bit is set like every other.
+__global__ __launch_bounds__(SH_ROWS * 64) void shape_adjacency_kernel(const float* __restrict__ x_all, unsigned long long* __restrict__ bits_all,
+                                                                       int32_t* __restrict__ pop_all, float* __restrict__ rmsd_all, int S, int n, double thr) {
+    const int g = blockIdx.y, tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+    const int W = (S + 63) >> 6, n3 = n * 3, r = blockIdx.x * SH_ROWS + wave;
+    if (r >= S) return;                                                         // wave-uniform; this kernel has no barrier
+    const float* x = x_all + (int64_t)g * S * n3;
+    int pop = 0;
+    for (int cb = 0; cb < W; ++cb) {
+        const int col = cb * 64 + lane;
+        const bool valid = col < S;
+        const int c = min(col, S - 1);                                          // columns past S read the last structure and are masked below
+        const int lo = min(r, c), hi = max(r, c);
+        const RowPoint a{x + (int64_t)lo * n3}, b{x + (int64_t)hi * n3};
+        double rot[9], tr[3];
+        const double ss = superpose_pair(n, n, a, b, a, b, rot, tr);
+        const unsigned long long word = __ballot(valid && (ss <= thr || col == r));
+        if (lane == 0) bits_all[((int64_t)g * S + r) * W + cb] = word;
+        pop += __popcll(word);
+        if (rmsd_all && valid) rmsd_all[((int64_t)g * S + r) * S + col] = col == r ? 0.f : superposed_rmsd_of(ss, n);
+    }
+    if (lane == 0) pop_all[(int64_t)g * S + r] = pop;
+}
+
 constexpr int PF_TILE = 64;                // positions a workgroup owns
 constexpr int PF_BINS = 21;                // the 20 residue types + everything else
 
@@ -298,7 +342,7 @@ static int greedy_prepare(int S, size_t* lds) {
     return ensure_dynamic_lds((const void*)greedy_cluster_kernel, *lds, g_cluster_lds);
 }
 
-// ... and its launch on a neighbour relation (bit matrix + populations) some adjacency kernel has written to the workspace: both entries end here
+// ... and its launch on a neighbour relation (bit matrix + populations) some adjacency kernel has written to the workspace: all three entries end here
 static int greedy_launch(const unsigned long long* bits, const int32_t* pop, void* label, void* centre, void* size, void* count, int G, int S, int max_clusters,
                          size_t lds, hipStream_t st) {
     hipLaunchKernelGGL(greedy_cluster_kernel, dim3((unsigned)G), dim3(CL_THREADS), lds, st, bits, pop, (int32_t*)label, (int32_t*)centre, (int32_t*)size,
@@ -338,6 +382,31 @@ extern "C" int abopt_cluster_poses_grouped(const float* structs, int G, int S, i
     int rc = greedy_prepare(S, &lds);
     if (rc != ABOPT_OK) return rc;
     hipLaunchKernelGGL(pose_adjacency_kernel, dim3((unsigned)W, (unsigned)G), dim3(256), 0, st, structs, bits, pop, rmsd, S, n, thr);
+    ABOPT_LAUNCH_CHECK();
+    return greedy_launch(bits, pop, label, centre, size, count, G, S, max_clusters, lds, st);
+}
+
+extern "C" int abopt_cluster_shapes_grouped(const float* structs, int G, int S, int n, float cutoff, int max_clusters, void* ws, size_t ws_bytes,
+                                            void* label, void* centre, void* size, void* count, float* rmsd, abopt_stream stream) {
+    ABOPT_CHECK_ARG(G >= 0 && S >= 1 && n >= 3 && max_clusters >= 0 && (int64_t)G * S <= 0x7fffffff,
+                    "cluster_shapes_grouped: bad dims G=%d S=%d n=%d max_clusters=%d (a best fit takes n >= 3 points)", G, S, n, max_clusters);
+    if (S > CL_MAX_S) { set_error("cluster_shapes_grouped: S=%d structures per group exceed the greedy kernel's LDS state (max %d)", S, CL_MAX_S); return ABOPT_EUNSUPPORTED; }
+    if (n > SH_MAXLEN) { set_error("cluster_shapes_grouped: n=%d points per structure exceed the maximum of %d", n, SH_MAXLEN); return ABOPT_EUNSUPPORTED; }
+    ABOPT_CHECK_ARG(isfinite(cutoff) && cutoff >= 0.f, "cluster_shapes_grouped: the cutoff must be finite and >= 0 (got %g)", (double)cutoff);
+    if (G == 0) return ABOPT_OK;
+    ABOPT_CHECK_ARG(G <= 65535, "cluster_shapes_grouped: G=%d groups exceed one launch (max 65535)", G);
+    ABOPT_CHECK_ARG(structs && ws && label && centre && size && count, "cluster_shapes_grouped: NULL argument");
+    ABOPT_CHECK_ARG(((uintptr_t)ws & 7) == 0, "cluster_shapes_grouped: the workspace must be 8-byte aligned");
+    if (ws_bytes < abopt_cluster_ws_bytes(G, S)) { set_error("cluster_shapes_grouped: workspace too small (%zu bytes given)", ws_bytes); return ABOPT_EWORKSPACE; }
+    hipStream_t st = (hipStream_t)stream;
+    const int W = (S + 63) / 64;
+    unsigned long long* bits = (unsigned long long*)ws;
+    int32_t* pop = (int32_t*)(bits + (size_t)G * S * W);
+    const double thr = (double)cutoff * (double)cutoff * (double)n;             // finite for every finite cutoff: a huge one makes every finite pair a neighbour
+    size_t lds;
+    int rc = greedy_prepare(S, &lds);
+    if (rc != ABOPT_OK) return rc;
+    hipLaunchKernelGGL(shape_adjacency_kernel, dim3((unsigned)((S + SH_ROWS - 1) / SH_ROWS), (unsigned)G), dim3(SH_ROWS * 64), 0, st, structs, bits, pop, rmsd, S, n, thr);
     ABOPT_LAUNCH_CHECK();
     return greedy_launch(bits, pop, label, centre, size, count, G, S, max_clusters, lds, st);
 }

@@ -6,6 +6,7 @@
 // the batch; one launch scores all S candidates of a complex.  Latency-bound (a few hundred KB): one workgroup per candidate.
 #include "abopt_common.h"
 #include "kernels.h"
+#include "superpose.h"                     // jacobi4_max_eigvec: Horn's unit quaternion of the best rotation
 
 namespace abopt {
 
@@ -50,29 +51,6 @@ __device__ __forceinline__ double block_sum(double v, double* red) {          //
     if (lane == 0) red[wave] = v;
     __syncthreads();
     return red[0] + red[1] + red[2] + red[3];
-}
-
-// Largest-eigenvalue eigenvector of the symmetric 4x4 matrix N (cyclic Jacobi, double): Horn's unit quaternion of the best rotation.
-__device__ void jacobi4_max_eigvec(double N[4][4], double q[4]) {
-    double V[4][4] = {{1, 0, 0, 0}, {0, 1, 0, 0}, {0, 0, 1, 0}, {0, 0, 0, 1}};
-    for (int sweep = 0; sweep < 16; ++sweep) {
-        double off = 0;
-        for (int i = 0; i < 4; ++i) for (int j = i + 1; j < 4; ++j) off += N[i][j] * N[i][j];
-        if (off < 1e-30) break;
-        for (int p = 0; p < 3; ++p)
-            for (int r = p + 1; r < 4; ++r) {
-                if (fabs(N[p][r]) < 1e-300) continue;
-                const double theta = (N[r][r] - N[p][p]) / (2.0 * N[p][r]);
-                const double tt = (theta >= 0 ? 1.0 : -1.0) / (fabs(theta) + sqrt(theta * theta + 1.0));
-                const double c = 1.0 / sqrt(tt * tt + 1.0), s = tt * c;
-                for (int k = 0; k < 4; ++k) { const double a = N[k][p], b = N[k][r]; N[k][p] = c * a - s * b; N[k][r] = s * a + c * b; }
-                for (int k = 0; k < 4; ++k) { const double a = N[p][k], b = N[r][k]; N[p][k] = c * a - s * b; N[r][k] = s * a + c * b; }
-                for (int k = 0; k < 4; ++k) { const double a = V[k][p], b = V[k][r]; V[k][p] = c * a - s * b; V[k][r] = s * a + c * b; }
-            }
-    }
-    int best = 0;
-    for (int i = 1; i < 4; ++i) if (N[i][i] > N[best][best]) best = i;
-    for (int k = 0; k < 4; ++k) q[k] = V[k][best];
 }
 
 // Best rotation R (row-major) and centroids moving the model CA atoms selected by `fit` onto the native ones (SVDSuperimposer), then

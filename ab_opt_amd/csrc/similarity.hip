@@ -27,22 +27,6 @@ constexpr long long SM_NEG = -(1ll << 62); // "no such alignment": far below eve
 
 __device__ __forceinline__ long long sm_max(long long a, long long b) { return a > b ? a : b; }
 
-// Wave-uniform: the elements k < n of a row with mask[k] != 0 (mask == NULL: all), in order, are numbered 0 .. len - 1 and put(rank, k) is called for each by the
-// lane that holds it.  -> len.  The ranks come from a ballot prefix per 64 elements.
-template <class Put>
-__device__ __forceinline__ int sm_compact(const uint8_t* __restrict__ mask, int n, Put put) {
-    const int lane = threadIdx.x & 63;
-    int len = 0;
-    for (int k0 = 0; k0 < n; k0 += 64) {
-        const int k = k0 + lane;
-        const bool f = k < n && (mask == nullptr || mask[k] != 0);
-        const unsigned long long b = __ballot(f);
-        if (f) put(len + __popcll(b & ((1ull << lane) - 1ull)), k);
-        len += __popcll(b);
-    }
-    return len;
-}
-
 // ---------------------------------------------------------------- sequence alignment
 // Grid folded over x and y, four waves, a wave per pair (query row q, reference row r).  The table is staged once per workgroup as int16 (entries are clamped
 // into -32767 .. 32767), the two compacted sequences per wave.  The query runs down the rows (1 .. n) and the reference along the columns (1 .. m) of the Gotoh
@@ -71,8 +55,8 @@ __global__ __launch_bounds__(SM_WAVES * 64) void align_sequences_kernel(const ui
     wave_lds_sync();
     const uint8_t* qrow = q_all + qi * na;
     const uint8_t* rrow = r_all + ri * nb;
-    const int n = sm_compact(qmask_all ? qmask_all + qi * na : nullptr, na, [&](int rank, int k) { a[rank] = qrow[k]; });
-    const int m = sm_compact(rmask_all ? rmask_all + ri * nb : nullptr, nb, [&](int rank, int k) { b[rank] = rrow[k]; });
+    const int n = compact_ranks(qmask_all ? qmask_all + qi * na : nullptr, na, [&](int rank, int k) { a[rank] = qrow[k]; });
+    const int m = compact_ranks(rmask_all ? rmask_all + ri * nb : nullptr, nb, [&](int rank, int k) { b[rank] = rrow[k]; });
     wave_lds_sync();
     long long best = -(long long)(n + m);                                       // nothing aligned: every residue against a free gap
     if (n > 0 && m > 0) {
@@ -155,9 +139,9 @@ __global__ __launch_bounds__(SM_WAVES * 64) void gapped_rmsd_kernel(const float*
     const float* rrow = rca_all + ri * nb * 3;
     float (*ca_q)[SM_MAXLEN] = ca[wave][0];
     float (*ca_r)[SM_MAXLEN] = ca[wave][1];
-    const int nq = sm_compact(qmask_all ? qmask_all + qi * na : nullptr, na, [&](int rank, int k) {
+    const int nq = compact_ranks(qmask_all ? qmask_all + qi * na : nullptr, na, [&](int rank, int k) {
         ca_q[0][rank] = qrow[3 * k]; ca_q[1][rank] = qrow[3 * k + 1]; ca_q[2][rank] = qrow[3 * k + 2]; });
-    const int nr = sm_compact(rmask_all ? rmask_all + ri * nb : nullptr, nb, [&](int rank, int k) {
+    const int nr = compact_ranks(rmask_all ? rmask_all + ri * nb : nullptr, nb, [&](int rank, int k) {
         ca_r[0][rank] = rrow[3 * k]; ca_r[1][rank] = rrow[3 * k + 1]; ca_r[2][rank] = rrow[3 * k + 2]; });
     wave_lds_sync();
     if (nq == 0 || nr == 0) {

@@ -165,6 +165,7 @@ _SIGNATURES = {
     'abopt_cluster_poses_grouped': (c_int, [c_f, c_int, c_int, c_int, c_float, c_int, c_void_p, c_size_t] + [c_void_p] * 4 + [c_f, c_stream]),
     'abopt_cluster_sequences_grouped': (c_int, [c_u8, c_int, c_int, c_int, c_int, c_int, c_void_p, c_size_t] + [c_void_p] * 5 + [c_stream]),
     'abopt_sequence_profile_grouped': (c_int, [c_u8, c_int, c_int, c_int, c_void_p, c_stream]),
+    'abopt_cluster_shapes_grouped': (c_int, [c_f, c_int, c_int, c_int, c_float, c_int, c_void_p, c_size_t] + [c_void_p] * 4 + [c_f, c_stream]),
     'abopt_interface_geometry_ws_bytes': (c_size_t, [c_int, c_int, c_int]),
     'abopt_interface_geometry_grouped': (c_int, [c_f, c_u8, c_int, c_i32, c_u8] + [c_int] * 4 + [c_float] * 3 + [c_void_p] * 3 + [c_size_t, c_stream]),
     'abopt_lddt_ws_bytes': (c_size_t, [c_int, c_int, c_int]),
@@ -180,6 +181,7 @@ _SIGNATURES = {
     'abopt_interface_energy_grouped': (c_int, [c_f, c_u8, c_int, c_i32, c_u8, c_int, c_u8, c_f, c_f] + [c_int] * 4 + [c_float] * 6 + [c_void_p, c_void_p, c_stream]),
     'abopt_align_sequences': (c_int, [c_u8, c_u8, c_u8, c_u8, c_i32] + [c_int] * 7 + [c_void_p] * 3 + [c_stream]),
     'abopt_gapped_rmsd': (c_int, [c_f, c_u8, c_f, c_u8] + [c_int] * 4 + [c_void_p, c_void_p, c_stream]),
+    'abopt_superposed_rmsd': (c_int, [c_f, c_u8, c_u8, c_f, c_u8, c_u8] + [c_int] * 4 + [c_void_p] * 5 + [c_stream]),
     'abopt_prof_enable': (c_int, [c_int]),
     'abopt_prof_spans_reset': (c_int, [c_stream]),
     'abopt_prof_spans': (c_int, [POINTER(c_int), POINTER(c_double)]),
@@ -813,6 +815,34 @@ def cluster_poses_grouped(structs, group_size, cutoff, max_clusters=0, want_rmsd
     return out
 
 
+def cluster_shapes_grouped(structs, group_size, cutoff, max_clusters=0, want_rmsd=False):
+    """`cluster_poses_grouped` with every pair of structures SUPERPOSED before the distance is taken: clusters by shape, whatever frame each structure lives in
+    (include/abopt.h: abopt_cluster_shapes_grouped).  structs (G*S, n, 3) with 3 <= n <= 256 -- below three points no rotation is
+    determined and the call refuses --; cutoff in Angstrom (RMSD after the best proper rotation and translation, all n points fitted and measured); max_clusters
+    0 = no cap.  -> the dict of `cluster_poses_grouped`; rmsd (G, S, S) is symmetric bit for bit, 0 on the diagonal, and equals `superposed_rmsd` on rows
+    (min, max) bit for bit.  Two stream-ordered launches, no host synchronisation."""
+    structs = structs.contiguous().float()
+    S, M = int(group_size), int(max_clusters)
+    if structs.dim() != 3 or S < 1 or structs.shape[0] % S or structs.shape[2] != 3:
+        raise ValueError(f'cluster_shapes_grouped: {tuple(structs.shape)} structures are not whole groups of {S} >= 1 structures (n, 3)')
+    B, n, _ = structs.shape
+    if not 3 <= n <= SIMILARITY_MAX_LEN:
+        raise ValueError(f'cluster_shapes_grouped: structures have {n} points, expected 3 .. {SIMILARITY_MAX_LEN} (a best fit takes three)')
+    if M < 0:
+        raise ValueError(f'cluster_shapes_grouped: max_clusters must be >= 0 (0 = no cap), got {max_clusters!r}')
+    cutoff = check_cluster_cutoff('cluster_shapes_grouped: cutoff', cutoff)
+    ptr(structs)                                                    # a CPU tensor is refused here, before anything is allocated
+    G, dev = B // S, structs.device
+    i32 = dict(dtype=torch.int32, device=dev)
+    out = dict(label=torch.empty(B, **i32), centre=torch.empty(G, S, **i32), size=torch.empty(G, S, **i32), count=torch.empty(G, **i32))
+    if want_rmsd:
+        out['rmsd'] = torch.empty(G, S, S, dtype=torch.float32, device=dev)
+    buf = Workspace.get(max(8, lib().abopt_cluster_ws_bytes(G, S)), dev)
+    _check(lib().abopt_cluster_shapes_grouped(ptr(structs), G, S, n, cutoff, M, ptr(buf), buf.numel(), ptr(out['label']), ptr(out['centre']), ptr(out['size']),
+                                              ptr(out['count']), ptr(out.get('rmsd'), optional=True), stream()))
+    return out
+
+
 def check_max_mismatch(name, m):
     """int(m), or ValueError for a negative one (the check abopt_cluster_sequences_grouped makes, ahead of any device work)."""
     if isinstance(m, bool) or int(m) != m or int(m) < 0:
@@ -1313,6 +1343,35 @@ def gapped_rmsd(qca, rca, qmask=None, rmask=None):
                                    ptr(m), stream()))
     rmsd = torch.where(m > 0, torch.sqrt(sd / m.clamp(min=1).float()), torch.full_like(sd, -1.0))
     return dict(sd=sd, m=m, rmsd=rmsd)
+
+
+def superposed_rmsd(q, r, qfit=None, rfit=None, qscore=None, rscore=None, want_transform=False):
+    """RMSD after best-fit superposition of every query row onto every reference row (include/abopt.h: abopt_superposed_rmsd).
+    q (Q, na, 3) and r (R, nb, 3) floating point, na, nb <= 256; qfit / rfit (optional, (Q, na) / (R, nb) bool): the points the rotation and translation are
+    fitted on, None = all; qscore / rscore (optional): the points the deviation is measured on, None = that row's fit points.  Points pair by rank: the k-th
+    true element of a query row with the k-th true element of a reference row.  The query is the mobile side; proper rotations only.
+    -> dict of device tensors (Q, R): rmsd fp32, n_fit and n_score int32 [, rot (Q, R, 3, 3) and trans (Q, R, 3) fp32 with want_transform: r ~ rot q + trans].
+    A pair whose fit counts or score counts differ, with fewer than 3 fit points or no score point is NOT scored: rmsd -1, n_fit = n_score = 0, rot the
+    identity, trans 0.  One stream-ordered launch, no host synchronisation, capturable."""
+    name = 'superposed_rmsd'
+    Q, na = _similarity_rows(name, 'q', q, qfit, True)
+    R, nb = _similarity_rows(name, 'r', r, rfit, True)
+    for what, m, want in (('qscore', qscore, (Q, na)), ('rscore', rscore, (R, nb))):
+        if m is not None and tuple(m.shape) != want:
+            raise ValueError(f'{name}: {what} {tuple(m.shape)} must be (rows, n) = {want}')
+    if Q * R > 0x7fffffff:
+        raise ValueError(f'{name}: {Q} x {R} pairs exceed 2^31 - 1')
+    dev = _similarity_device(name, q, r)
+    q, r = q.float().contiguous(), r.float().contiguous()
+    qfit, rfit, qscore, rscore = _as_flags(qfit), _as_flags(rfit), _as_flags(qscore), _as_flags(rscore)
+    new = torch.empty if Q * R else torch.zeros                      # an empty call launches nothing
+    out = dict(rmsd=new(Q, R, dtype=torch.float32, device=dev), n_fit=new(Q, R, dtype=torch.int32, device=dev), n_score=new(Q, R, dtype=torch.int32, device=dev))
+    if want_transform:
+        out.update(rot=new(Q, R, 3, 3, dtype=torch.float32, device=dev), trans=new(Q, R, 3, dtype=torch.float32, device=dev))
+    _check(lib().abopt_superposed_rmsd(ptr(q, torch.float32), ptr(qfit, optional=True), ptr(qscore, optional=True), ptr(r, torch.float32), ptr(rfit, optional=True),
+                                       ptr(rscore, optional=True), Q, R, na, nb, ptr(out['rmsd']), ptr(out['n_fit']), ptr(out['n_score']),
+                                       ptr(out.get('rot'), optional=True), ptr(out.get('trans'), optional=True), stream()))
+    return out
 
 
 def check_lddt_cutoff(name, v):

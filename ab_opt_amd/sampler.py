@@ -82,6 +82,22 @@ def cluster_poses(ca, cutoff, max_clusters=None):
     return dict(label=out['label'].long(), centre=out['centre'][0, :C].long(), size=out['size'][0, :C].long())
 
 
+def cluster_shapes(ca, cutoff, max_clusters=None):
+    """`cluster_poses` with every pair of structures superposed before the distance is taken (include/abopt.h:
+    abopt_cluster_shapes_grouped): loops are grouped by conformation, whatever frame each lives in -- the designs of several docked poses pooled.  ca (P, n, 3)
+    with 3 <= n <= 256; cutoff in Angstrom: a and b are neighbours iff their RMSD after the best proper rotation and translation, over all n points, is
+    <= cutoff.  The greedy walk, max_clusters and the result are those of `cluster_poses`.  Costs one host read (C).  Raises on CPU tensors (no fallback)."""
+    from . import hip
+    cutoff = hip.check_cluster_cutoff('cluster_shapes: cutoff', cutoff)
+    if max_clusters is not None and int(max_clusters) < 1:
+        raise ValueError(f'cluster_shapes: max_clusters must be >= 1 or None (got {max_clusters!r})')
+    if ca.dim() != 3 or ca.shape[0] < 1 or not 3 <= ca.shape[1] <= hip.SIMILARITY_MAX_LEN or ca.shape[2] != 3:
+        raise ValueError(f'cluster_shapes: expected (P, n, 3) structures with P >= 1 and 3 <= n <= {hip.SIMILARITY_MAX_LEN}, got {tuple(ca.shape)}')
+    out = hip.cluster_shapes_grouped(ca, ca.shape[0], cutoff, int(max_clusters or 0))
+    C = int(out['count'][0])
+    return dict(label=out['label'].long(), centre=out['centre'][0, :C].long(), size=out['size'][0, :C].long())
+
+
 def cluster_sequences(seqs, max_mismatch, max_clusters=None):
     """Greedy clustering of S designed sequences on the device (include/abopt.h: abopt_cluster_sequences_grouped): the single-group form
     of `cluster_poses` on the sequence side.  seqs (S, n), any integer dtype, one residue type per entry; a and b are neighbours iff they differ at no more
@@ -421,6 +437,69 @@ def similarity(batch, seqs, pos, mask, rows='generated', ref_seqs=None, ref_ca=N
         out = {k: v.gather(1, col)[:, 0] for k, v in out.items()}
     elif own:
         out = {k: v.reshape(0) for k, v in out.items()}
+    return out
+
+
+def _residue_set(name, what, batch, sel):
+    """(G, L) bool: 'generated' (generate_flag), 'context' (the antibody residues that are not generated), 'antibody' (screen.chain_groups == 1) or a (G, L) mask"""
+    from . import screen
+    if isinstance(sel, str):
+        gen = batch['generate_flag'].bool()
+        if sel == 'generated':
+            return gen
+        if sel == 'antibody':
+            return screen.chain_groups(batch['fragment_type']) == 1
+        if sel == 'context':
+            return (screen.chain_groups(batch['fragment_type']) == 1) & ~gen
+        raise ValueError(f"{name}: {what} must be 'generated', 'context', 'antibody' or a (G, L) tensor, not {sel!r}")
+    return sel.bool()
+
+
+def superposed_rmsd(batch, pos, mask, fit='generated', score=None, ref_ca=None, ref_fit=None, ref_score=None, want_transform=False):
+    """CA RMSD of candidates AFTER best-fit superposition, fitted on one residue set and measured on another (hip.superposed_rmsd).
+    batch: G complexes; pos (G*S, L, A, 3) with CA in slot 1 and mask (G*S, L, A): S candidates of each, candidate c belongs to complex c // S.  fit / score:
+    'generated' (generate_flag), 'context' (the antibody residues that are not generated), 'antibody' (every antibody residue) or a (G, L) mask; score=None
+    means the fit set.  A residue whose CA is masked out leaves both sets.
+    Without references every candidate is compared with the NATIVE of its own complex on the same rows (batch['pos_heavyatom'], batch['mask_heavyatom']; a
+    residue whose native CA is missing leaves both sets too): every entry (G*S,).  fit='context', score='generated' is the framework-aligned CDR RMSD of loop
+    modelling; fit='generated' is the loop's own shape deviation.  The launch compares every candidate with every complex's native and keeps its own, G times
+    the pairs kept.  With ref_ca (R, nb, 3), ref_fit and ref_score (R, nb) (None = all / = ref_fit) every candidate is compared with every reference: every
+    entry (G*S, R) -- a known binder's loop, canonical-class representatives, the designs themselves.  Points pair by rank, so the sets of a candidate and of
+    a reference must be equally large: a pair whose counts differ, with fewer than 3 fit residues or no score residue has rmsd -1 and counts 0.
+    -> dict of device tensors: rmsd fp32, n_fit, n_score int32 [, rot (..., 3, 3) and trans (..., 3) with want_transform: reference ~ rot candidate + trans].
+    Rows wider than 256 cost one host read, otherwise none (a row may select at most 256 residues, fit and score together).  The screen does not call this:
+    apply it to what optimize_antibody / sample_grouped return."""
+    from . import hip
+    name = 'superposed_rmsd'
+    G, L = batch['aa'].shape
+    fsel = _residue_set(name, 'fit', batch, fit)
+    ssel = fsel if score is None else _residue_set(name, 'score', batch, score)
+    if pos.dim() != 4 or mask.dim() != 3 or tuple(fsel.shape) != (G, L) or tuple(ssel.shape) != (G, L) or tuple(pos.shape[1:]) != (L, pos.shape[2], 3) \
+            or pos.shape[2] < 2 or tuple(mask.shape) != tuple(pos.shape[:3]) or (pos.shape[0] % G if G else pos.shape[0]):
+        raise ValueError(f'{name}: expected pos (G*S, L, A >= 2, 3), mask (G*S, L, A) and fit / score (G, L) with G = {G}, L = {L}; got '
+                         f'{tuple(pos.shape)}, {tuple(mask.shape)}, {tuple(fsel.shape)} and {tuple(ssel.shape)}')
+    own = ref_ca is None
+    if own and (ref_fit is not None or ref_score is not None):
+        raise ValueError(f'{name}: ref_fit / ref_score select residues of ref_ca, which is None')
+    N = pos.shape[0]
+    S = N // G if G else 0
+    per = (lambda t: t.repeat_interleave(S, 0)) if S != 1 else (lambda t: t)
+    cok = mask[:, :, 1].bool()
+    if own:
+        nok = batch['mask_heavyatom'][:, :, 1].bool()
+        cok = cok & per(nok)
+    cfit, cscore = per(fsel) & cok, per(ssel) & cok
+    _, cfit, cscore, cca = _front_rows(name, cfit | cscore, cfit, cscore, pos[:, :, 1])
+    if own:
+        rfit, rscore = fsel & nok, ssel & nok
+        _, ref_fit, ref_score, ref_ca = _front_rows(name, rfit | rscore, rfit, rscore, batch['pos_heavyatom'][:, :, 1])
+    out = hip.superposed_rmsd(cca, ref_ca, qfit=cfit, rfit=ref_fit, qscore=None if score is None else cscore,
+                              rscore=ref_score if (not own or score is not None) else None, want_transform=want_transform)
+    if own and G:                                                   # a candidate's own complex is column c // S
+        rows = torch.arange(N, device=pos.device)
+        out = {k: v[rows, rows // S] for k, v in out.items()}
+    elif own:
+        out = {k: v.reshape((0,) + tuple(v.shape[2:])) for k, v in out.items()}
     return out
 
 

@@ -691,6 +691,23 @@ int abopt_cluster_sequences_grouped(const uint8_t* seqs, int G, int S, int n, in
                                     void* label, void* centre, void* size, void* count, void* dist, abopt_stream stream);
 int abopt_sequence_profile_grouped(const uint8_t* seqs, int G, int S, int n, void* counts, abopt_stream stream);
 
+/* ---- Shape clustering (ABI 59, an addition): abopt_cluster_poses_grouped with the structures SUPERPOSED before the distance is taken --
+ * designed loops that live in different docked frames, pooled and grouped by conformation rather than by where the docking put them.  Nothing in the reference
+ * is matched; per group of S structures [n,3], all n points being fitted and measured:
+ *   distance    ss(a, b) = sum_k |R (x_k - cx) - (y_k - cy)|^2 with x = the structure of the LOWER index of the two, y = the other, cx, cy their centroids and R
+ *               the best proper rotation of x onto y (Horn's quaternion form, a cyclic Jacobi solve, all in double: the pair function of
+ *               abopt_superposed_rmsd below, one lane per pair).  Evaluating (a, b) and (b, a) as the same ordered pair makes the relation symmetric bit for bit.
+ *   neighbours  a ~ b iff ss(a, b) <= (double) cutoff^2 n, and a ~ a always (a structure holding a NaN is a neighbour of itself alone)
+ *   greedy      exactly as abopt_cluster_poses_grouped (the same kernel walks the relation)
+ *   structs, label, centre, size, count, ws: as for abopt_cluster_poses_grouped.  rmsd (optional, [G,S,S] fp32): (float) sqrt(ss / n) of every pair, 0 on the
+ *   diagonal, symmetric bit for bit, and equal bit for bit to abopt_superposed_rmsd on rows (min(a, b), max(a, b)) of the same structures with NULL masks.
+ * Two stream-ordered launches, nothing allocated, no host synchronisation.  1 <= S <= 16384 (beyond: ABOPT_EUNSUPPORTED), G S <= 2^31 - 1, G <= 65535, G = 0
+ * is a no-op, cutoff finite and >= 0.  3 <= n <= 256: below 3 points no rotation is determined and the call REFUSES (ABOPT_EINVAL) rather than report the
+ * distance of an arbitrary optimal one; beyond 256: ABOPT_EUNSUPPORTED.  Every check precedes the first launch.  Collinear structures are compared as
+ * abopt_superposed_rmsd compares them (score == fit: the distance is unique).  A group's result is bit-identical to a call on that group alone. */
+int abopt_cluster_shapes_grouped(const float* structs, int G, int S, int n, float cutoff, int max_clusters, void* ws, size_t ws_bytes,
+                                 void* label, void* centre, void* size, void* count, float* rmsd, abopt_stream stream);
+
 /* ---- Interface geometry (ABI 48): the physical sanity check of a docked pose that every structure-generation pipeline reports -- steric clashes across the
  * interface, the size of the interface in contacts, broken peptide bonds -- and, per group, how often each residue is contacted across the group's candidates
  * (for the D re-docks of a design: the consensus epitope).  Nothing in the reference is matched (its relax stage is its only physical check); the definition is
@@ -984,6 +1001,32 @@ int abopt_align_sequences(const uint8_t* q, const uint8_t* qmask, const uint8_t*
                           int gap_extend, int Q, int R, int na, int nb, void* score, void* matches, void* columns, abopt_stream stream);
 int abopt_gapped_rmsd(const float* qca, const uint8_t* qmask, const float* rca, const uint8_t* rmask, int Q, int R, int na, int nb, void* sd, void* m,
                       abopt_stream stream);
+
+/* ---- RMSD after superposition (ABI 59, an addition): every one of Q query rows against every one of R reference rows, fitted on one
+ * subset of the paired points and measured on another.  "Is this the same loop shape" for designs that live in different frames; fit on the framework and
+ * score on the CDR for the loop-modelling number; a panel of known loops against every design.  Nothing in the reference is matched (its eval stage takes its
+ * RMSD without superposition, abopt_gapped_rmsd above); the definition is this library's own.
+ *   q [Q,na,3] fp32, r [R,nb,3] fp32; qfit, qscore [Q,na] and rfit, rscore [R,nb]: one byte per element.  qfit / rfit NULL = all true; qscore / rscore NULL =
+ *   the same as that row's fit mask.  Masks need not be prefixes.
+ *   pairing     by RANK: the k-th fit-true element of the query row pairs with the k-th fit-true element of the reference row; the score elements likewise.
+ *               The query x is the mobile side, the reference y the target.
+ *   fit         cx, cy = the means of the n_f fit points; S[a][b] = sum (x_a - cx_a)(y_b - cy_b) over the fit pairs; R = the rotation of the unit quaternion
+ *               that is the largest-eigenvalue eigenvector of Horn's 4x4 key matrix of S (a cyclic Jacobi solve of at most 16 sweeps): a proper rotation, never
+ *               a reflection.  All in double from the fp32 inputs, summed in index order by ONE lane per pair: a pair's result is a pure function of its two
+ *               point lists and is that of a call on the pair alone, bit for bit.
+ *   residuals   ss = sum |R (x - cx) - (y - cy)|^2 over the n_s score pairs, in double, with the rotation applied.
+ *   rmsd [Q,R] fp32 = (float) sqrt(ss / n_s); n_fit, n_score [Q,R] int32 (DEVICE, spelled void*): n_f and n_s of the pair.
+ *   rot (may be NULL) [Q,R,3,3] fp32 row-major and trans (may be NULL) [Q,R,3] fp32: R and t = cy - R cx, so that y ~ R x + t.
+ *   NOT SCORED  a pair whose two fit counts differ, or whose two score counts differ, or with n_f < 3 (no rotation is determined), or with n_s = 0:
+ *               rmsd = -1, n_fit = n_score = 0, rot = the identity, trans = 0.
+ *   COLLINEAR   with n_f >= 3 collinear fit points the two largest eigenvalues coincide and the result is that of SOME optimal rotation (whatever turn about the
+ *               line the sweeps leave).  With score == fit the rmsd is unique all the same; rot, trans and an rmsd over other points are not.
+ *   Coordinates are expected to be finite; a NaN in a scored pair's points gives rmsd = NaN (the solve ends whatever the data).
+ * One launch, 16 x 16 pairs per workgroup, a lane per pair; no atomic, no workspace, nothing allocated, no host synchronisation, capturable into a hipGraph; the
+ * outputs are written whole by plain stores.  Q, R >= 0, na, nb >= 1, Q R <= 2^31 - 1 (ABOPT_EINVAL); na, nb <= 256 (beyond: ABOPT_EUNSUPPORTED, nothing
+ * launched); Q = 0 or R = 0 is a no-op; every check precedes the launch. */
+int abopt_superposed_rmsd(const float* q, const uint8_t* qfit, const uint8_t* qscore, const float* r, const uint8_t* rfit, const uint8_t* rscore, int Q, int R,
+                          int na, int nb, void* rmsd, void* n_fit, void* n_score, void* rot, void* trans, abopt_stream stream);
 
 /* ---- Measurement hook (bench.py's roofline leg).  When enabled, every launch of the IPA-core kernel is bracketed
  * by hipEvents on the stream it is launched on; abopt_prof_collect synchronises those events and returns the number
