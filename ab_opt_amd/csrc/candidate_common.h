@@ -1,8 +1,8 @@
-// What the kernels that work on docked candidates share (interface.hip, sasa.hip, guide.hip, relax.hip, develop.hip, interface_energy.hip; DESIGN.md sections 3.12, 6.3, 6.6, 6.8, 6.9, 6.10): G groups of S
+// What the kernels that work on docked candidates share (interface.hip, sasa.hip, guide.hip, relax.hip, develop.hip, interface_energy.hip, backbone.hip; DESIGN.md sections 3.12, 6.3, 6.6, 6.8, 6.9, 6.10, 6.13): G groups of S
 // candidates of L residues with A atom slots, a row per group that names the residues' sides or flags them, a grid of (candidate folded over x and y, slice in z),
-// and the argument checks of their entry points.  sasa.hip, guide.hip, relax.hip, develop.hip and interface_energy.hip compile under `#pragma clang fp contract(off)` and include this header BEFORE
+// and the argument checks of their entry points.  sasa.hip, guide.hip, relax.hip, develop.hip, interface_energy.hip and backbone.hip compile under `#pragma clang fp contract(off)` and include this header BEFORE
 // the pragma.  d2_fma is the only floating-point arithmetic of this file: its fmaf chain is spelled out, so it means the same on either side of the pragma
-// (guide.hip and develop.hip use it; sasa.hip, relax.hip and interface_energy.hip, whose every step is rounded once, do not).
+// (guide.hip and develop.hip use it; sasa.hip, relax.hip, interface_energy.hip and backbone.hip, whose every step is rounded once, do not).
 // similarity.hip (section 6.11) and superpose.hip (section 6.12), which compare rows of two panels and have no groups, take the folded grid and compact_ranks
 // from here (similarity.hip d2_fma too).
 #pragma once

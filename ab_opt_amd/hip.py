@@ -179,6 +179,8 @@ _SIGNATURES = {
     'abopt_sequence_liabilities_grouped': (c_int, [c_u8, c_u8, c_u8] + [c_int] * 4 + [c_void_p] * 3 + [c_stream]),
     'abopt_surface_patches_grouped': (c_int, [c_f, c_u8, c_int, c_i32, c_f, c_u8, c_int, c_f, c_float] + [c_int] * 4 + [c_void_p, c_void_p, c_stream]),
     'abopt_interface_energy_grouped': (c_int, [c_f, c_u8, c_int, c_i32, c_u8, c_int, c_u8, c_f, c_f] + [c_int] * 4 + [c_float] * 6 + [c_void_p, c_void_p, c_stream]),
+    'abopt_backbone_max_rows': (c_int, []),
+    'abopt_backbone_conformation_grouped': (c_int, [c_f, c_u8, c_int, c_u8, c_u8, c_int, c_u8, c_f] + [c_int] * 5 + [c_float] + [c_void_p] * 8 + [c_stream]),
     'abopt_align_sequences': (c_int, [c_u8, c_u8, c_u8, c_u8, c_i32] + [c_int] * 7 + [c_void_p] * 3 + [c_stream]),
     'abopt_gapped_rmsd': (c_int, [c_f, c_u8, c_f, c_u8] + [c_int] * 4 + [c_void_p, c_void_p, c_stream]),
     'abopt_superposed_rmsd': (c_int, [c_f, c_u8, c_u8, c_f, c_u8, c_u8] + [c_int] * 4 + [c_void_p] * 5 + [c_stream]),
@@ -1245,6 +1247,113 @@ def interface_energy_grouped(pos, mask, group, seqs, charge=None, pair_table=Non
                                                 kn['hb_cutoff'], kn['elec_cutoff'], kn['salt_cutoff'], kn['pair_cutoff'], kn['eps'], kn['d_min'], ptr(energy),
                                                 ptr(count), stream()))
     return dict(energy=energy, count=count)
+
+
+BACKBONE_MAX_ROWS = 512     # residues of one candidate at most (abopt_backbone_max_rows(): the hydrogen-bond relation lives in a workgroup's LDS)
+BACKBONE_MAX_REGIONS = 8    # rows of a Ramachandran table
+BACKBONE_COUNTS = ('part', 'phipsi') + tuple(f'region{k}' for k in range(8)) + ('outliers', 'outliers_gly', 'omega', 'cis', 'cis_nonpro', 'twisted', 'H', 'E',
+                                                                                   'G', 'I', 'T', 'C', 'hb_donor', 'hb_acceptor')
+
+
+def rama_regions(table=None):
+    """A Ramachandran table in degrees -> the (K, 8) fp32 tensor (on the CPU) that `backbone_conformation_grouped` takes: per row cos, sin of phi_lo, phi_hi,
+    psi_lo, psi_hi, computed in float64 and rounded once.  table: K <= 8 rows (phi_lo, phi_hi, psi_lo, psi_hi), each arc running counter-clockwise from lo to hi
+    (angles are taken modulo 360); None = model.RAMA_REGIONS, this library's coarse three boxes (see there: not a published contour).  ValueError for an arc of
+    0 degrees or of >= 180 degrees (the two half-plane tests of the definition describe an arc only below 180), for a non-finite bound and for K > 8.  No
+    device is needed."""
+    import math
+    if table is None:
+        from .model import RAMA_REGIONS as table
+    rows = [tuple(float(v) for v in row) for row in table]
+    if len(rows) > BACKBONE_MAX_REGIONS or any(len(row) != 4 for row in rows):
+        raise ValueError(f'rama_regions: expected at most {BACKBONE_MAX_REGIONS} rows of (phi_lo, phi_hi, psi_lo, psi_hi), got {len(rows)} rows')
+    out = torch.zeros(len(rows), 8, dtype=torch.float64)
+    for k, row in enumerate(rows):
+        if not all(math.isfinite(v) for v in row):
+            raise ValueError(f'rama_regions: row {k} holds a non-finite bound: {row}')
+        for name, lo, hi in (('phi', row[0], row[1]), ('psi', row[2], row[3])):
+            width = (hi - lo) % 360.0
+            if not 0.0 < width < 180.0:
+                raise ValueError(f'rama_regions: row {k}: the {name} arc {lo} .. {hi} is {width} degrees wide, expected 0 < width < 180')
+        for c, v in enumerate(row):
+            out[k, 2 * c], out[k, 2 * c + 1] = math.cos(math.radians(v)), math.sin(math.radians(v))
+    return out.float()
+
+
+def check_backbone_conformation(L=1, A=4, regions=None, hb_cutoff=-0.5):
+    """The values `backbone_conformation_grouped` checks besides its shapes, without a device: L <= BACKBONE_MAX_ROWS, 4 <= A <= 15, regions None or a (K, 8)
+    floating-point tensor with K <= 8, hb_cutoff finite and <= 0 (kcal/mol; DSSP's -0.5 is the conventional value, not a tuned one).
+    -> dict(K, hb_cutoff), or ValueError naming the argument."""
+    import math
+    if not 1 <= int(L) <= BACKBONE_MAX_ROWS:
+        raise ValueError(f'L={L} residues, expected 1 .. {BACKBONE_MAX_ROWS} (the hydrogen-bond relation of a candidate lives in the LDS of one workgroup)')
+    if not 4 <= int(A) <= 15:
+        raise ValueError(f'A={A} atoms per residue, the slots 0 .. 3 are N, CA, C, O (expected 4 .. 15)')
+    K = 0
+    if regions is not None:
+        if regions.dim() != 2 or regions.shape[1] != 8 or regions.shape[0] > BACKBONE_MAX_REGIONS or not regions.dtype.is_floating_point:
+            raise ValueError(f'regions {tuple(regions.shape)} {regions.dtype} must be floating point of shape (K, 8) with K <= {BACKBONE_MAX_REGIONS} '
+                             f'(hip.rama_regions makes one)')
+        K = regions.shape[0]
+    f = float(hb_cutoff)
+    if not math.isfinite(f) or f > 0.0:
+        raise ValueError(f'hb_cutoff must be finite and <= 0 (got {hb_cutoff!r})')
+    return dict(K=K, hb_cutoff=f)
+
+
+def backbone_conformation_grouped(pos, mask, rows, seqs=None, link=None, regions=None, hb_cutoff=-0.5):
+    """Backbone conformation of G*S candidates in G groups (include/abopt.h: abopt_backbone_conformation_grouped): per scored residue
+    phi, psi, omega as (cos, sin), the peptide bond's length and two angle cosines, a Ramachandran class, and DSSP-LIKE states from Kabsch & Sander's hydrogen-bond
+    patterns within the candidate (NOT DSSP: no ladders or sheets, no B / E distinction, no bends, no helix trimming); per candidate 24 counts.
+    pos (G*S,L,A,3), 4 <= A <= 15, slots 0 .. 3 = N, CA, C, O, L <= 512; mask (G*S,L,A), or (G,L,A) shared by the S candidates of a group; rows (G,L) flags: the
+    scored residues (every residue is a neighbour and a hydrogen-bond partner all the same); seqs (optional; (G*S,L), or (G,L) shared by the group, any integer
+    dtype, clamped into 0..255): only Pro (12) and Gly (5) matter, None = no residue is either; link (optional, (G,L) bool, `sampler.backbone_links`): residue
+    r is peptide-bonded to r + 1, None = every consecutive pair; regions (optional, (K,8), `rama_regions`): None = rama_regions() of model.RAMA_REGIONS, a
+    (0,8) tensor = no region, every residue with phi and psi an outlier; hb_cutoff in kcal/mol.
+    -> dict of device tensors: torsion (G*S,L,6) fp32 (cos, sin of phi, psi, omega; 0 where undefined), have (G*S,L) uint8 (bits 0 .. 2 phi, psi, omega; 3 .. 5
+    the entries of bond), bond (G*S,L,3) fp32 (|C - N'|, cos CA-C-N', cos C-N'-CA' of the step r -> r + 1), rama (G*S,L) uint8 (region, K = outlier, 255 = none),
+    ss (G*S,L) uint8 (bits: helix_4, helix_3, helix_5, parallel bridge, antiparallel bridge, inside a turn), state (G*S,L) uint8 (index into model.SS_LETTERS,
+    255 = not scored), partner (G*S,L,2) int32 (lowest parallel / antiparallel bridge partner or -1), count (G*S,24) int32 (columns: BACKBONE_COUNTS).  One
+    stream-ordered launch, no host synchronisation, capturable."""
+    name = 'backbone_conformation_grouped'
+    G, S, L, A, shared = _candidate_args(name, pos, mask, rows)
+    try:
+        kn = check_backbone_conformation(L, A, regions, hb_cutoff)
+    except ValueError as e:
+        raise ValueError(f'{name}: {e}') from None
+    N = G * S
+    if seqs is not None and (seqs.dim() != 2 or seqs.shape[1] != L or seqs.shape[0] not in (N, G) or seqs.dtype.is_floating_point or seqs.dtype.is_complex):
+        raise ValueError(f'{name}: seqs {tuple(seqs.shape)} {seqs.dtype} must be integer of shape (G*S, L) = {(N, L)} or (G, L) = {(G, L)}')
+    if link is not None and tuple(link.shape) != (G, L):
+        raise ValueError(f'{name}: link {tuple(link.shape)} must be (G, L) = {(G, L)}')
+    pos, mask, _, link = _candidate_tensors(pos, mask, None, link)
+    dev = pos.device
+    rows = _as_flags(rows)
+    seq_shared = seqs is not None and (seqs.shape[0] != N or S == 1)
+    if seqs is not None:
+        seqs = (seqs if seqs.dtype == torch.uint8 else seqs.to(torch.uint8) if seqs.dtype == torch.bool else seqs.clamp(0, 255).to(torch.uint8)).contiguous()
+    regions = (_rama_default(dev) if regions is None else regions.to(device=dev, dtype=torch.float32).contiguous())
+    K = regions.shape[0]
+    new = torch.empty if N else torch.zeros                          # an empty call launches nothing
+    u8, i32, f32 = (dict(dtype=t, device=dev) for t in (torch.uint8, torch.int32, torch.float32))
+    out = dict(torsion=new(N, L, 6, **f32), have=new(N, L, **u8), bond=new(N, L, 3, **f32), rama=new(N, L, **u8), ss=new(N, L, **u8), state=new(N, L, **u8),
+               partner=new(N, L, 2, **i32), count=new(N, len(BACKBONE_COUNTS), **i32))
+    _check(lib().abopt_backbone_conformation_grouped(ptr(pos, torch.float32), ptr(mask), int(shared), ptr(rows), ptr(seqs, torch.uint8, optional=True),
+                                                     int(seq_shared), ptr(link, optional=True), ptr(regions, torch.float32), K,
+                                                     G, S, L, A, kn['hb_cutoff'], *(ptr(out[k]) for k in ('torsion', 'have', 'bond', 'rama', 'ss', 'state',
+                                                                                                          'partner', 'count')), stream()))
+    return out
+
+
+_RAMA_DEFAULT = {}
+
+
+def _rama_default(device):
+    """rama_regions() on `device`, cached per device: treat it as read-only"""
+    key = str(torch.device(device))
+    if key not in _RAMA_DEFAULT:
+        _RAMA_DEFAULT[key] = rama_regions().to(device)
+    return _RAMA_DEFAULT[key]
 
 
 SIMILARITY_MAX_LEN = 256    # elements of a row of align_sequences / gapped_rmsd

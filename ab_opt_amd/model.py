@@ -89,6 +89,20 @@ def hydrophobic_contact_table():
     return 0.0 - h[:, None] * h[None, :]
 
 
+# Backbone conformation (include/abopt.h: abopt_backbone_conformation_grouped).  SS_LETTERS[k] names code k of `state`, in the order of
+# the reduction H > E > G > I > T > C: helix_4, a bridge of either kind, helix_3, helix_5, inside an n-turn, none of these.  The states are DSSP-LIKE, from
+# Kabsch & Sander's patterns on single hydrogen bonds; they are NOT DSSP's (no ladders or sheets, no B / E distinction, no bends, no helix trimming).
+SS_LETTERS = 'HEGITC'
+RAMA_REGIONS = ((-160.0, -20.0, -120.0, 50.0), (-180.0, -45.0, 90.0, -170.0), (20.0, 120.0, -30.0, 100.0))
+"""RAMA_REGIONS: a COARSE default table for hip.rama_regions, three boxes (phi_lo, phi_hi, psi_lo, psi_hi) in degrees, each arc counter-clockwise from lo to hi:
+    0  alpha-R  phi -160 ..  -20, psi -120 ..   50
+    1  beta     phi -180 ..  -45, psi   90 .. -170  (the psi arc runs through 180 and is 100 degrees wide)
+    2  alpha-L  phi   20 ..  120, psi  -30 ..  100
+The three boxes are disjoint.  These bounds are THIS LIBRARY'S CONVENTION -- rectangles drawn generously around the three classical basins --, not a published
+contour: they are not MolProbity's or any other validation tool's regions, "outlier" here means "in none of these three boxes", and no fraction of outliers
+computed with them is comparable with such a tool's."""
+
+
 def identity_table(match=2, mismatch=-2):
     """The simplest substitution table of hip.align_sequences (DESIGN.md section 6.11), (21, 21) int32 on the CPU: `match` on the diagonal, `mismatch` elsewhere;
     entry 20 serves every byte >= 20 ("no type"), which therefore scores `match` against itself -- whether two bytes MATCH is decided on the raw bytes."""

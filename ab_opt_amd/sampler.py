@@ -369,6 +369,57 @@ def interface_energy(batch, seqs, pos, mask, groups='chains', charge=None, pair_
     return energy_summary(out, grp)
 
 
+def conformation_summary(out, groups=1):
+    """The dict of hip.backbone_conformation_grouped -> it, plus per candidate (N,): scored (int32, the scored rows that take part), helix (H + G + I), strand
+    (E) and coil (T + C) as float64 shares of `scored` (NaN where nothing is scored), outliers, cis, cis_nonpro, twisted, hbonds (those whose donor is a scored
+    row) as int32; and freq (G, L) int32: in how many of the N / G candidates of each of G = `groups` groups a residue is H or E (with the default every
+    candidate is of one group).  Pure torch, no host read."""
+    from .hip import BACKBONE_COUNTS
+    col = {name: k for k, name in enumerate(BACKBONE_COUNTS)}
+    n = out['count']
+    scored = n[:, col['part']]
+    share = lambda v: torch.where(scored > 0, v.double() / scored.clamp_min(1).double(), float('nan'))
+    res = dict(out, scored=scored, helix=share(n[:, col['H']] + n[:, col['G']] + n[:, col['I']]), strand=share(n[:, col['E']]),
+               coil=share(n[:, col['T']] + n[:, col['C']]), outliers=n[:, col['outliers']], cis=n[:, col['cis']], cis_nonpro=n[:, col['cis_nonpro']],
+               twisted=n[:, col['twisted']], hbonds=n[:, col['hb_donor']])
+    N, L = out['state'].shape
+    G = int(groups)
+    if G < 0 or (N % G if G else N):
+        raise ValueError(f'conformation_summary: {N} candidates are not whole groups of {groups} groups')
+    res['freq'] = (out['state'] <= 1).view(G, N // G if G else 0, L).sum(1, dtype=torch.int32)      # H or E
+    return res
+
+
+def backbone_conformation(batch, pos, mask, rows='generated', seqs=None, regions=None, hb_cutoff=-0.5):
+    """Whether the backbones of candidate structures of the complexes of `batch` are plausible polypeptides (hip.backbone_conformation_grouped; DESIGN.md
+    section 6.13): Ramachandran classes, cis / twisted peptides, the peptide bond's geometry and DSSP-LIKE states (NOT DSSP: no ladders or sheets, no B / E
+    distinction, no bends, no helix trimming).  batch, pos (G*S, L, A, 3), mask as for `interface_geometry` (A >= 4, L <= 512); rows: 'generated'
+    (generate_flag), 'antibody' (every antibody residue) or a (G, L) mask -- the scored residues; every real residue is a hydrogen-bond partner; seqs (G*S, L) or
+    (G, L), type k = model.AA_LETTERS[k] (None: no residue is Pro or Gly); the links are those of `backbone_links`; regions: a table of hip.rama_regions, default
+    model.RAMA_REGIONS -- this library's coarse three boxes, not a published contour.
+    -> the dict of `conformation_summary` with freq (G, L) int32 -- in how many of a group's candidates a residue is H or E -- and phi, psi, omega (G*S, L) in
+    degrees, NaN where undefined: torch.atan2 of the kernel's (sin, cos), a convenience that is NOT pinned bitwise (the kernel's cos and sin are).  On the
+    device, no host synchronisation.  The default hb_cutoff and regions are conventional values, not tuned ones; what trained weights give is unmeasured.  The
+    screen does not call this: apply it to what optimize_antibody / sample_grouped return."""
+    from . import hip, screen
+    if isinstance(rows, str):
+        if rows == 'generated':
+            scored = batch['generate_flag'].bool()
+        elif rows == 'antibody':
+            scored = screen.chain_groups(batch['fragment_type']) == 1
+        else:
+            raise ValueError(f"backbone_conformation: rows must be 'generated', 'antibody' or a (G, L) tensor, not {rows!r}")
+    else:
+        scored = rows
+    out = hip.backbone_conformation_grouped(pos, mask, scored, seqs=seqs, link=backbone_links(batch['chain_nb'], batch['res_nb']), regions=regions,
+                                            hb_cutoff=hb_cutoff)
+    res = conformation_summary(out, groups=scored.shape[0])
+    t, have = out['torsion'], out['have']
+    for k, name in enumerate(('phi', 'psi', 'omega')):
+        res[name] = torch.where((have & (1 << k)) != 0, torch.rad2deg(torch.atan2(t[..., 2 * k + 1], t[..., 2 * k])), float('nan'))
+    return res
+
+
 def _front_rows(name, flags, *tensors):
     """The kernels of `similarity` take rows of at most 256 elements.  flags (N, L) bool and tensors (N, L, ...): returned as they are when L <= 256; else each
     row's flagged elements are moved to the front, in order, and the rows cut to 256 -- which costs one host read, to refuse a row with more than 256 of them."""

@@ -956,6 +956,64 @@ int abopt_interface_energy_grouped(const float* pos, const uint8_t* mask, int ma
                                    float elec_cutoff, float salt_cutoff, float pair_cutoff, float eps, float d_min, void* energy, void* count,
                                    abopt_stream stream);
 
+/* ---- Backbone conformation (ABI 59, an addition: no existing signature moves): whether a candidate's backbone is a plausible
+ * polypeptide BETWEEN its residues -- torsions, the peptide bond's geometry, a Ramachandran class, cis / twisted peptides and DSSP-LIKE states from
+ * Kabsch & Sander's hydrogen-bond patterns within the candidate.  This is NOT DSSP: there are no ladders or sheets, no B / E distinction, no bends and no helix
+ * trimming.  Nothing in the reference is matched; the definition is this library's own.  G groups of S candidates, conventions of
+ * abopt_interface_energy_grouped:
+ *   pos [G*S,L,A,3] fp32, 4 <= A <= 15, atom slots 0 .. 3 = N, CA, C, O; mask [G*S,L,A], or [G,L,A] shared by the S candidates of a group (mask_shared != 0);
+ *   rows [G,L] uint8 flags: the SCORED residues; seqs (optional, may be NULL) [G*S,L] uint8, or [G,L] shared by the group (seq_shared != 0), type k =
+ *   'ACDEFGHIKLMNPQRSTVWY'[k]: Pro = 12, Gly = 5, a byte >= 20 is no type, NULL = no residue is Pro or Gly; link (optional, may be NULL) [G,L] uint8:
+ *   link[r] != 0 means STEP r -- residue r is peptide-bonded to r + 1 -- is linked (the last entry is ignored: there is no step L - 1, nor a step -1),
+ *   NULL = every step 0 .. L - 2 is linked; regions [K,8] fp32 (DEVICE; may be NULL with K = 0), 0 <= K <= 8; hb_cutoff fp32, finite and <= 0
+ *   (kcal/mol; conventionally -0.5).
+ *   taking part an atom takes part iff its mask byte is set and its three coordinates are finite (the one rule of abopt_interface_energy_grouped).  A RESIDUE
+ *               takes part iff one of its slots 0 .. 3 does.  A quantity that needs an atom that takes no part is UNDEFINED for that residue; nothing becomes
+ *               NaN.  Every residue that takes part is a neighbour and a hydrogen-bond partner whether or not it is a scored row; only scored rows are
+ *               counted, and a row that is not scored gets torsion = bond = 0, have = ss = 0, rama = state = 255, partner = -1.
+ *   arithmetic  fp32, every step rounded once, nothing fused; divisions and square roots correctly rounded.  a - b per coordinate;
+ *               a . b = (ax bx + ay by) + az bz; a x b = (ay bz - az by, az bx - ax bz, ax by - ay bx); d2(a, b) = (a - b) . (a - b), which is the d2 of
+ *               abopt_interface_energy_grouped.
+ *   torsion     of four points p0 .. p3: b1 = p1 - p0, b2 = p2 - p1, b3 = p3 - p2; n1 = b1 x b2, n2 = b2 x b3; x = n1 . n2; y = sqrt(b2 . b2) (b1 . n2);
+ *               rho = sqrt(x x + y y); cos = x / rho, sin = y / rho (IUPAC sign: a trans peptide has cos = -1).  Undefined unless 0 < rho < inf.
+ *               phi_r = (C_{r-1}, N, CA, C) needs step r - 1 linked; psi_r = (N, CA, C, N_{r+1}) and omega_r = (CA, C, N_{r+1}, CA_{r+1}) need step r linked;
+ *               omega belongs to r.
+ *   torsion [G*S,L,6] fp32 (DEVICE, spelled void*): cos phi, sin phi, cos psi, sin psi, cos omega, sin omega; an undefined pair is 0.0f, 0.0f.
+ *   have [G*S,L] uint8: bit 0 phi, 1 psi, 2 omega, 3 .. 5 the three entries of bond, set where defined.
+ *   bond [G*S,L,3] fp32 (DEVICE, spelled void*) of a linked step r: |C - N_{r+1}| = sqrt(d2(C, N_{r+1})), defined iff it is < inf;
+ *               cos(CA-C-N_{r+1}) and cos(C-N_{r+1}-CA_{r+1}), the cosine at vertex v of a, b being ((a - v) . (b - v)) / (sqrt((a - v) . (a - v))
+ *               sqrt((b - v) . (b - v))), defined iff 0 < that denominator < inf.  Undefined entries are 0.0f.
+ *   rama [G*S,L] uint8: a region is cos, sin of phi_lo, of phi_hi, of psi_lo, of psi_hi (8 floats): a box of two counter-clockwise arcs, each strictly
+ *               narrower than 180 degrees.  theta lies in [lo, hi] iff sin theta cos lo - cos theta sin lo >= 0 and cos theta sin hi - sin theta cos hi >= 0
+ *               (two products and a difference each, on the cos and sin of `torsion`).  A scored row with phi and psi gets the lowest k whose two arcs hold
+ *               them, K if none does (an outlier); 255 otherwise.
+ *   peptide     of a scored row with omega: cis iff cos omega > 0; twisted iff |sin omega| > 0.5; cis is counted once more where r + 1 is not Pro.
+ *   hbond       amide H and E exactly as in abopt_interface_energy_grouped (H = N_r + u / |u|, u = C_{r-1} - O_{r-1}; none for Pro, r = 0, an unlinked
+ *               step r - 1, a missing N, C_{r-1}, O_{r-1} or |u| = 0; E = 27.888 (((1 / r_ON + 1 / r_CH) - 1 / r_OH) - 1 / r_CN), -9.9 if a distance is
+ *               below 0.5 A, else max(E, -9.9)).  hb(a -> d), acceptor a and donor d of ONE candidate, exists iff a != d, they are not linked neighbours
+ *               (d == a + 1 with step a linked, or a == d + 1 with step d linked), d has an H, C and O of a and both CA take part,
+ *               d2(CA_d, CA_a) < 81 (part of the definition) and E < hb_cutoff.  Hbond(i, j) = hb(acceptor i -> donor j); false outside 0 .. L - 1.
+ *   patterns    n-turn at i, n in {3, 4, 5}: Hbond(i, i + n) with every step i .. i + n - 1 linked.  helix_n on the residues i .. i + n - 1 iff there are
+ *               n-turns at i - 1 and at i.  r is INSIDE a turn iff there is an n-turn at some i with i < r < i + n.  bridge(i, j) needs |i - j| >= 3 and the
+ *               steps i - 1, i, j - 1, j linked; parallel: [Hbond(i-1, j) and Hbond(j, i+1)] or [Hbond(j-1, i) and Hbond(i, j+1)]; antiparallel:
+ *               [Hbond(i, j) and Hbond(j, i)] or [Hbond(i-1, j+1) and Hbond(j-1, i+1)].  j need not be a scored row.
+ *   ss [G*S,L] uint8 of a scored row that takes part: bit 0 helix_4, 1 helix_3, 2 helix_5, 3 a parallel bridge, 4 an antiparallel bridge, 5 inside a turn.
+ *   state [G*S,L] uint8 of such a row: 0 H (helix_4), else 1 E (a bridge), else 2 G (helix_3), else 3 I (helix_5), else 4 T (inside a turn), else 5 C;
+ *               255 for any other row.
+ *   partner [G*S,L,2] int32 (DEVICE, spelled void*): the lowest j with a parallel, with an antiparallel bridge(r, j); -1 if none.
+ *   count [G*S,24] int32 (DEVICE, spelled void*), over the scored rows: 0 rows that take part; 1 rows with phi and psi; 2 .. 9 rows of region 0 .. 7;
+ *               10 outliers; 11 outliers that are Gly; 12 rows with omega; 13 cis; 14 cis with r + 1 not Pro; 15 twisted; 16 .. 21 rows of state H, E, G,
+ *               I, T, C; 22 hydrogen bonds whose donor is a scored row; 23 those whose acceptor is one.
+ * Every output is a pure function of the candidate; the counts are integers, so no order of summation exists, and a group's result is that of a call on the
+ * group alone.  One stream-ordered launch, a workgroup per candidate, capturable into a hipGraph, nothing allocated, no workspace, no global atomic, no host
+ * synchronisation; the outputs are written whole by plain stores.  L >= 1, G S <= 2^31 - 1, G <= 65535, G = 0 or S = 0 is a no-op; every value or pointer
+ * check precedes the launch (ABOPT_EINVAL).  The relation hb lives in the workgroup's LDS: L <= abopt_backbone_max_rows() = 512, beyond that
+ * ABOPT_EUNSUPPORTED and nothing is launched. */
+int abopt_backbone_max_rows(void);
+int abopt_backbone_conformation_grouped(const float* pos, const uint8_t* mask, int mask_shared, const uint8_t* rows, const uint8_t* seqs, int seq_shared,
+                                        const uint8_t* link, const float* regions, int K, int G, int S, int L, int A, float hb_cutoff, void* torsion,
+                                        void* have, void* bond, void* rama, void* ss, void* state, void* partner, void* count, abopt_stream stream);
+
 /* ---- Similarity to reference sequences and loops: the `seqid` and `rmsd` of the reference's eval stage (tools/eval/similarity.py)
  * for sequences and residue lists of DIFFERENT lengths.  Both entries compare every one of Q query rows with every one of R reference rows.
  * ABOPT_ABI_VERSION stays 59: the two entries are additions, no existing signature moves, and a library built before them is still caught, because binding
