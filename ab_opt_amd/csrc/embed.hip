@@ -42,7 +42,11 @@ __device__ __forceinline__ V3 xyz(f32x4 a) { return v3(a[0], a[1], a[2]); }
 __device__ __forceinline__ float gauss_d2(float dx, float dy, float dz) { return __builtin_fmaf(dz, dz, __builtin_fmaf(dy, dy, dx * dx)) * 0.01f; }
 __device__ __forceinline__ float gauss_exp(float c, float dd) { return __builtin_amdgcn_exp2f(-1.4426950408889634f * c * dd); }
 
-// geometry.py:336-362: signed dihedral of p0-p1-p2-p3, NaN -> 0 -- the reference's arithmetic op for op (IEEE divisions by the norms, acos, sign).
+// geometry.py:336-362: signed dihedral of p0-p1-p2-p3, NaN -> 0.  Sign and the NaN rule follow the reference's arithmetic (IEEE divisions by the norms); the
+// magnitude does not go through acos of the normals' cosine, which amplifies the cosine's rounding by 1 / sin(theta) (400 x beside the reference's clamp of the
+// cosine at +-0.999999: 1.2e-4 on sin(3 theta) of a pair embedding's angle, tests/test_encode_edges.py), but through
+// atan2(|u1 x u2|, u1 . u2) with |u1 x u2| = |v0| |v0 . (v1 x v2)|, good to a few ulp of pi at every angle; the clamp of the cosine is a clamp of the angle
+// to [acos(0.999999), pi - acos(0.999999)].
 // Round 6: hipcc turned parts of this into v_pk_*_f32 instructions, and those return wrong lanes 48-63 while another wave of the SIMD runs 16x16x32 f16 / bf16 MFMAs (the
 // pair embedding beside this library's denoiser in a second process: 1-3 % of its small launches wrong) -- the library is built without packed-FP32 instructions since
 // (csrc/Makefile: NOPK; tests: test_pair_embedding_repeats_beside_a_second_process, test_no_packed_fp32_instructions_in_the_library).
@@ -53,10 +57,12 @@ __device__ __forceinline__ float dihedral_from_four_points(V3 p0, V3 p1, V3 p2, 
     const V3 n1 = v3(u1.x / l1, u1.y / l1, u1.z / l1), n2 = v3(u2.x / l2, u2.y / l2, u2.z / l2);
     const float sd = dot3(cross3(v1, v2), v0);
     const float sgn = (sd > 0.f) ? 1.f : ((sd < 0.f) ? -1.f : 0.f);
-    float c = dot3(n1, n2);
-    c = fminf(fmaxf(c, -0.999999f), 0.999999f);
-    const float d = sgn * acosf(c);
-    return (d != d) ? 0.f : d;
+    const float c = dot3(n1, n2);
+    if (c != c) return 0.f;                                                             // a zero normal: acos(NaN) -> NaN -> 0 in the reference
+    constexpr float T0 = 1.4142137e-3f, PI_ = 3.14159265358979f;                      // acos(0.999999)
+    float th = atan2f(norm3(v0) * fabsf(sd), dot3(u1, u2));
+    th = fminf(fmaxf(th, T0), PI_ - T0);
+    return sgn * th;
 }
 
 // ------------------------------------------------------------------------------------------------ per-residue pack

@@ -124,8 +124,9 @@ def _backbone_dihedrals(pos, chain_nb, res_nb, mask):
     return torch.stack([omega, phi, psi], dim=-1) * m, m
 
 
-def residue_embedding(mod, aa, res_nb, chain_nb, pos_atoms, mask_atoms, fragment_type, hotspot=None, structure_mask=None, sequence_mask=None):
-    """ResidueEmbedding.forward (residue.py:26-92) on the parameters of `mod` (an ab_opt_amd.embed.ResidueEmbedding), plain torch ops."""
+def residue_features(mod, aa, res_nb, chain_nb, pos_atoms, mask_atoms, fragment_type, hotspot=None, structure_mask=None, sequence_mask=None):
+    """The input of ResidueEmbedding's MLP (residue.py:33-88) -> (features (N, L, in_dim), the dihedral block's mask m (N, L, 3), the rolled
+    structure mask (N, L) or None)."""
     N, L = aa.size()
     A = mod.max_num_atoms
     mres = mask_atoms[:, :, ATOM_CA]
@@ -143,6 +144,7 @@ def residue_embedding(mod, aa, res_nb, chain_nb, pos_atoms, mask_atoms, fragment
         f_crd = f_crd * structure_mask[:, :, None]
     dih, mdih = _backbone_dihedrals(pos, chain_nb, res_nb, mres)
     f_dih = (mod.dihed_embed(dih[:, :, :, None]) * mdih[:, :, :, None]).reshape(N, L, -1)
+    dm = None
     if structure_mask is not None:
         dm = structure_mask & torch.roll(structure_mask, 1, 1) & torch.roll(structure_mask, -1, 1)
         f_dih = f_dih * dm[:, :, None]
@@ -150,7 +152,13 @@ def residue_embedding(mod, aa, res_nb, chain_nb, pos_atoms, mask_atoms, fragment
     if mod.hotspot_embed is not None:
         hs = hotspot if hotspot is not None else torch.zeros_like(aa)
         feats.append(mod.hotspot_embed(hs))
-    return mod.mlp(torch.cat(feats, dim=-1)) * mres[:, :, None]
+    return torch.cat(feats, dim=-1), mdih, dm
+
+
+def residue_embedding(mod, aa, res_nb, chain_nb, pos_atoms, mask_atoms, fragment_type, hotspot=None, structure_mask=None, sequence_mask=None):
+    """ResidueEmbedding.forward (residue.py:26-92) on the parameters of `mod` (an ab_opt_amd.embed.ResidueEmbedding), plain torch ops."""
+    x, _, _ = residue_features(mod, aa, res_nb, chain_nb, pos_atoms, mask_atoms, fragment_type, hotspot, structure_mask, sequence_mask)
+    return mod.mlp(x) * mask_atoms[:, :, ATOM_CA][:, :, None]
 
 
 def pair_embedding(mod, aa, res_nb, chain_nb, pos_atoms, mask_atoms, structure_mask=None, sequence_mask=None):
