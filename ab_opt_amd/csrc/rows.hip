@@ -291,6 +291,14 @@ int launch_dpm_losses(const float* R_pred, const float* R_0, const float* p_pred
 // part[n] = {err_n, m0_n, sum of the sample's smooth-l1 terms, their count}; glogit [N, nb] = softmax - onehot (to be scaled by
 // m0_n / (sum m0 + 1e-10)); gp [N, L, 3] = d(sum of smooth-l1 terms) / d p_pred (to be scaled by 1 / total count).  pred_x0 = 0: pred_p0 =
 // gen ? a_n p0 - b_n p_pred : p0 (transition.py:52-60) and there is no dist loss (gp is zeroed).
+// The sums of the dist loss run over up to L terms per residue and L^2 / 256 per thread: they are kept in double (in float, adding term by term, the loss of L = 5118
+// came out 1.7e-6 off and d p_pred 2e-6 of its maximum off, 30 x and 20 x what a float32 tree sum reaches), the results are rounded to float once.
+// LDS: the static part below (its size is the kernel's .group_segment_fixed_size: the struct's alignment is that of al_s, so nothing is padded between the two),
+// then 32 bytes per residue of dynamic LDS.  Both count against the 160 KB of a workgroup: L <= ABDOCK_MAX_L = 5118 (5119 would need 163 856 bytes).
+struct alignas(16) AbdockStatic { double sum[4]; float cnt[4]; };          // the four waves' partial sums and counts
+constexpr size_t ABDOCK_LDS_PER_ROW = 32, LDS_PER_WORKGROUP = 160 * 1024;
+constexpr int ABDOCK_MAX_L = (int)((LDS_PER_WORKGROUP - sizeof(AbdockStatic)) / ABDOCK_LDS_PER_ROW);
+static_assert(sizeof(AbdockStatic) == 48 && ABDOCK_MAX_L == 5118, "LDS budget of abdock_losses_kernel");
 __global__ __launch_bounds__(256) void abdock_losses_kernel(const float* __restrict__ prmsd_logits, const float* __restrict__ p_pred, const float* __restrict__ p0n,
                                                             const float* __restrict__ coef_a, const float* __restrict__ coef_b, const uint8_t* __restrict__ gen,
                                                             const uint8_t* __restrict__ mres, const float* __restrict__ offsets, int nb, int L, float scale,
@@ -298,8 +306,7 @@ __global__ __launch_bounds__(256) void abdock_losses_kernel(const float* __restr
     extern __shared__ __attribute__((aligned(16))) float al_s[];           // [L][4] p_pred (x, y, z, gen & mres flags) | [L][4] p_true
     float* pp = al_s;
     float* pt = al_s + 4 * L;
-    __shared__ float red[2][4];
-    __shared__ float s_rmsd;
+    __shared__ AbdockStatic sm;
     const int n = blockIdx.x, tid = threadIdx.x;
     const int64_t base = (int64_t)n * L;
     const float ca = pred_x0 ? 0.f : coef_a[n], cb = pred_x0 ? 0.f : coef_b[n];
@@ -317,13 +324,12 @@ __global__ __launch_bounds__(256) void abdock_losses_kernel(const float* __restr
         if (g) cnt += 1.f;
     }
     sq = wave_sum(sq); cnt = wave_sum(cnt);
-    if ((tid & 63) == 0) { red[0][tid >> 6] = sq; red[1][tid >> 6] = cnt; }
-    __syncthreads();
-    if (tid == 0) s_rmsd = sqrtf(((red[0][0] + red[0][1]) + (red[0][2] + red[0][3])) / ((red[1][0] + red[1][1]) + (red[1][2] + red[1][3])));
-    __syncthreads();
+    if ((tid & 63) == 0) { sm.sum[tid >> 6] = sq; sm.cnt[tid >> 6] = cnt; }
+    __syncthreads();                                                       // (also: pp / pt are complete)
     // ---- prmsd cross entropy (wave 0): nb <= 64 bins, one lane per bin
     if (tid < 64) {
-        const float rm = s_rmsd;
+        const float s0 = (float)sm.sum[0], s1 = (float)sm.sum[1], s2 = (float)sm.sum[2], s3 = (float)sm.sum[3];
+        const float rm = sqrtf(((s0 + s1) + (s2 + s3)) / ((sm.cnt[0] + sm.cnt[1]) + (sm.cnt[2] + sm.cnt[3])));
         const float x = (tid < nb) ? prmsd_logits[(int64_t)n * nb + tid] : -INFINITY;
         const float dist = (tid < nb) ? fabsf(rm - offsets[tid]) : INFINITY;
         // argmin with the lowest index on ties (torch.argmin)
@@ -333,6 +339,9 @@ __global__ __launch_bounds__(256) void abdock_losses_kernel(const float* __restr
             const float ob = __shfl_xor(best, o); const int oi = __shfl_xor(bi, o);
             if (ob < best || (ob == best && oi < bi)) { best = ob; bi = oi; }
         }
+        // a NaN rmsd (no generated residue) compares false everywhere: no lane exchanges and every lane keeps its own index.  Lane 0's is the 0 torch.argmin
+        // gives; with an ordinary rmsd all lanes agree already
+        bi = __shfl(bi, 0);
         const float mx = wave_max(x);
         const float e = (tid < nb) ? expf(x - mx) : 0.f;
         const float se = wave_sum(e);
@@ -342,9 +351,10 @@ __global__ __launch_bounds__(256) void abdock_losses_kernel(const float* __restr
         if (tid == 0) { part[n * 4 + 0] = -(xb - lse); part[n * 4 + 1] = gen[base] ? 1.f : 0.f; }      // (a NaN rmsd -- no generated residue -- selects bin 0, as argmin does)
     }
     // ---- dist loss: thread k owns residue k: its row terms (i = k) and its column terms (j = k)
-    float lsum = 0.f, lcnt = 0.f;
+    double lsum = 0.0;
+    float lcnt = 0.f;
     for (int k = tid; k < L; k += 256) {
-        float gx = 0.f, gy = 0.f, gz = 0.f;
+        double gx = 0.0, gy = 0.0, gz = 0.0;
         if (pred_x0) {
             const float kx = pp[4 * k], ky = pp[4 * k + 1], kz = pp[4 * k + 2], tx = pt[4 * k], ty = pt[4 * k + 1], tz = pt[4 * k + 2];
             const int fk = (int)pp[4 * k + 3];
@@ -358,35 +368,37 @@ __global__ __launch_bounds__(256) void abdock_losses_kernel(const float* __restr
                 const float dp = sqrtf(dx * dx + dy * dy + dz * dz), dt = sqrtf(ex * ex + ey * ey + ez * ez);
                 const float x = dp - dt, ax = fabsf(x);
                 const float sl = ax < 1.f ? 0.5f * x * x : ax - 0.5f, ds = ax < 1.f ? x : (x > 0.f ? 1.f : -1.f);
-                if (as_row) { lsum += sl; lcnt += 1.f; }
+                if (as_row) { lsum += (double)sl; lcnt += 1.f; }
                 const float w = (dp > 0.f ? ds / dp : 0.f) * ((as_row ? 1.f : 0.f) + (as_col ? 1.f : 0.f));      // cdist backward: zero at zero distance
-                gx += w * dx; gy += w * dy; gz += w * dz;
+                gx += (double)(w * dx); gy += (double)(w * dy); gz += (double)(w * dz);
             }
         }
-        gp[(base + k) * 3] = gx; gp[(base + k) * 3 + 1] = gy; gp[(base + k) * 3 + 2] = gz;
+        gp[(base + k) * 3] = (float)gx; gp[(base + k) * 3 + 1] = (float)gy; gp[(base + k) * 3 + 2] = (float)gz;
     }
     __syncthreads();
-    lsum = wave_sum(lsum); lcnt = wave_sum(lcnt);
-    if ((tid & 63) == 0) { red[0][tid >> 6] = lsum; red[1][tid >> 6] = lcnt; }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) lsum += __shfl_xor(lsum, o);
+    lcnt = wave_sum(lcnt);
+    if ((tid & 63) == 0) { sm.sum[tid >> 6] = lsum; sm.cnt[tid >> 6] = lcnt; }
     __syncthreads();
-    if (tid == 0) { part[n * 4 + 2] = (red[0][0] + red[0][1]) + (red[0][2] + red[0][3]); part[n * 4 + 3] = (red[1][0] + red[1][1]) + (red[1][2] + red[1][3]); }
+    if (tid == 0) { part[n * 4 + 2] = (float)((sm.sum[0] + sm.sum[1]) + (sm.sum[2] + sm.sum[3])); part[n * 4 + 3] = (sm.cnt[0] + sm.cnt[1]) + (sm.cnt[2] + sm.cnt[3]); }
 }
 
 int launch_abdock_losses(const float* prmsd_logits, const float* p_pred, const float* p0n, const float* coef_a, const float* coef_b, const uint8_t* gen,
                          const uint8_t* mres, const float* offsets, int nb, int N, int L, float scale, int pred_x0, float* part, float* glogit, float* gp,
                          hipStream_t st) {
     if (N == 0) return ABOPT_OK;
-    ABOPT_CHECK_ARG(nb >= 1 && nb <= 64 && L >= 1 && (size_t)L * 32 <= 160 * 1024, "abdock_losses: num_bins=%d (1..64), L=%d (at most 5120)", nb, L);
+    ABOPT_CHECK_ARG(nb >= 1 && nb <= 64 && L >= 1 && L <= ABDOCK_MAX_L, "abdock_losses: num_bins=%d (1..64), L=%d (at most %d)", nb, L, ABDOCK_MAX_L);
     static LdsConfig lds_cfg;
-    if (int rc = ensure_dynamic_lds(reinterpret_cast<const void*>(abdock_losses_kernel), (size_t)L * 32, lds_cfg)) return rc;
-    hipLaunchKernelGGL(abdock_losses_kernel, dim3(N), dim3(256), (size_t)L * 32, st, prmsd_logits, p_pred, p0n, coef_a, coef_b, gen, mres, offsets, nb, L, scale, pred_x0,
+    if (int rc = ensure_dynamic_lds(reinterpret_cast<const void*>(abdock_losses_kernel), (size_t)L * ABDOCK_LDS_PER_ROW, lds_cfg)) return rc;
+    hipLaunchKernelGGL(abdock_losses_kernel, dim3(N), dim3(256), (size_t)L * ABDOCK_LDS_PER_ROW, st, prmsd_logits, p_pred, p0n, coef_a, coef_b, gen, mres, offsets, nb, L, scale, pred_x0,
                        part, glogit, gp);
     ABOPT_LAUNCH_CHECK();
     return ABOPT_OK;
 }
 
 // LayerNorm of the reference's own definition over rows of `cols` (<= 256) values (D/modules/common/layers.py:146-155: biased variance,
-// sqrt(var + eps)); forward keeps xhat = (x - mean) / sd and 1 / sd for the backward:
+// sqrt(var + eps)), the mean taken in two steps (below); forward keeps xhat = (x - mean) / sd and 1 / sd for the backward:
 //   dx = (g dy - mean(g dy) - xhat mean(g dy xhat)) / sd;   d gamma = sum_rows dy xhat, d beta = sum_rows dy (left to abopt_colsum on dyx / dy).
 // One wave per row.
 __global__ __launch_bounds__(256) void row_layer_norm_kernel(const float* __restrict__ x, const float* __restrict__ gamma, const float* __restrict__ beta, int cols,
@@ -397,10 +409,16 @@ __global__ __launch_bounds__(256) void row_layer_norm_kernel(const float* __rest
     float v[4], s = 0.f;
 #pragma unroll
     for (int q = 0; q < 4; ++q) { const int c = lane + 64 * q; v[q] = c < cols ? x[r * cols + c] : 0.f; s += v[q]; }
+    // The float mean of a row that lies far from zero is off by up to half an ulp of the MEAN (5e-4 at 1e4), and x - mean carries that into every output of the row.
+    // x - mean itself is exact there, so the rest of the mean is the mean of the differences: subtracted too, the centred values are good to their own ulp.
     const float mean = wave_sum(s) / (float)cols;
+    float s1 = 0.f;
+#pragma unroll
+    for (int q = 0; q < 4; ++q) { const int c = lane + 64 * q; v[q] = c < cols ? v[q] - mean : 0.f; s1 += v[q]; }
+    const float rest = wave_sum(s1) / (float)cols;
     float s2 = 0.f;
 #pragma unroll
-    for (int q = 0; q < 4; ++q) { const int c = lane + 64 * q; v[q] = c < cols ? v[q] - mean : 0.f; s2 += v[q] * v[q]; }
+    for (int q = 0; q < 4; ++q) { const int c = lane + 64 * q; v[q] = c < cols ? v[q] - rest : 0.f; s2 += v[q] * v[q]; }
     const float sd = sqrtf(wave_sum(s2) / (float)cols + eps);
 #pragma unroll
     for (int q = 0; q < 4; ++q) {
@@ -503,3 +521,5 @@ int launch_query_row_list(const uint8_t* mask_generate, int N, int L, int32_t* r
 }
 
 }  // namespace abopt
+
+extern "C" int abopt_abdock_losses_max_length(void) { return abopt::ABDOCK_MAX_L; }

@@ -146,6 +146,7 @@ _SIGNATURES = {
     'abopt_pair_embed_backward_workspace_bytes': (c_size_t, [c_int, c_int, c_int]),
     'abopt_pair_embed_backward': (c_int, [POINTER(EncodeInputs), POINTER(PairEmbedWeights)] + [c_f] * 6 + [c_void_p, c_size_t, c_stream]),
     'abopt_dpm_losses': (c_int, [c_f] * 5 + [c_i64, c_i64, c_f, c_u8, c_int, c_int] + [c_f] * 4 + [c_stream]),
+    'abopt_abdock_losses_max_length': (c_int, []),
     'abopt_abdock_losses': (c_int, [c_f] * 5 + [c_u8, c_u8, c_f, c_int, c_int, c_int, c_float, c_int, c_f, c_f, c_f, c_stream]),
     'abopt_layer_norm_forward': (c_int, [c_f, c_f, c_f, c_int, c_float, c_int64, c_f, c_f, c_f, c_stream]),
     'abopt_layer_norm_backward': (c_int, [c_f] * 4 + [c_int, c_int64, c_f, c_f, c_stream]),

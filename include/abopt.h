@@ -557,7 +557,11 @@ int abopt_dpm_losses(const float* R_pred, const float* R_0, const float* p_pred,
  *           m0_n = mask_generate[n, 0]; pred_p0 = p_pred (pred_x0 = 1) or gen ? coef_a[n] p0 - coef_b[n] p_pred : p0 (pred_x0 = 0, transition.py:52-60);
  *   dist  = mean smooth_l1(cdist(p_pred) - cdist(p0)) over the pairs mask_generate_i & mask_res_i & mask_res_j (pred_x0 = 1 only).
  * sample_parts [N,4] = {CE_n, m0_n, sum of the sample's smooth-l1 terms, their count}; dprmsd_logits [N,num_bins] = softmax - onehot (scale by
- * m0_n / (sum m0 + 1e-10)); dp_pred [N,L,3] = d(sum of smooth-l1 terms)/d p_pred (scale by 1 / total count; zeros when pred_x0 = 0). */
+ * m0_n / (sum m0 + 1e-10)); dp_pred [N,L,3] = d(sum of smooth-l1 terms)/d p_pred (scale by 1 / total count; zeros when pred_x0 = 0).  A sample without a
+ * generated residue has rmsd = 0 / 0 = NaN and takes bin 0, as torch.argmin does.  1 <= num_bins <= 64.  A sample's positions live in the workgroup's LDS, 32 bytes
+ * per residue beside the kernel's 48 bytes of static LDS: L <= abopt_abdock_losses_max_length() = 5118 = (163840 - 48) / 32; a longer L is refused
+ * (ABOPT_EINVAL) before any HIP call, the outputs untouched.  (The entry is an addition: ABOPT_ABI_VERSION stays 59.) */
+int abopt_abdock_losses_max_length(void);
 int abopt_abdock_losses(const float* prmsd_logits, const float* p_pred, const float* p0_norm, const float* coef_a, const float* coef_b,
                         const uint8_t* mask_generate, const uint8_t* mask_res, const float* bin_offsets, int num_bins, int N, int L, float position_scale,
                         int pred_x0, float* sample_parts, float* dprmsd_logits, float* dp_pred, abopt_stream stream);
