@@ -185,6 +185,8 @@ _SIGNATURES = {
     'abopt_align_sequences': (c_int, [c_u8, c_u8, c_u8, c_u8, c_i32] + [c_int] * 7 + [c_void_p] * 3 + [c_stream]),
     'abopt_gapped_rmsd': (c_int, [c_f, c_u8, c_f, c_u8] + [c_int] * 4 + [c_void_p, c_void_p, c_stream]),
     'abopt_superposed_rmsd': (c_int, [c_f, c_u8, c_u8, c_f, c_u8, c_u8] + [c_int] * 4 + [c_void_p] * 5 + [c_stream]),
+    'abopt_align_traceback': (c_int, [c_u8, c_u8, c_u8, c_u8, c_i32] + [c_int] * 3 + [c_i32] + [c_int] * 5 + [c_void_p] * 6 + [c_stream]),
+    'abopt_superposed_rmsd_mapped': (c_int, [c_f, c_f, c_void_p, c_i32, c_int] + [c_u8] * 4 + [c_int] * 4 + [c_void_p] * 5 + [c_stream]),
     'abopt_prof_enable': (c_int, [c_int]),
     'abopt_prof_spans_reset': (c_int, [c_stream]),
     'abopt_prof_spans': (c_int, [POINTER(c_int), POINTER(c_double)]),
@@ -1481,6 +1483,96 @@ def superposed_rmsd(q, r, qfit=None, rfit=None, qscore=None, rscore=None, want_t
     _check(lib().abopt_superposed_rmsd(ptr(q, torch.float32), ptr(qfit, optional=True), ptr(qscore, optional=True), ptr(r, torch.float32), ptr(rfit, optional=True),
                                        ptr(rscore, optional=True), Q, R, na, nb, ptr(out['rmsd']), ptr(out['n_fit']), ptr(out['n_score']),
                                        ptr(out.get('rot'), optional=True), ptr(out.get('trans'), optional=True), stream()))
+    return out
+
+
+def _pair_list(name, pairs, Q, R):
+    """The optional (P, 2) list of (query row, reference row), checked without a device -> the number of pairs of the call.  The VALUES are not read here (that
+    would synchronise): the kernels treat a pair outside the panels as documented."""
+    if pairs is None:
+        if Q * R > 0x7fffffff:
+            raise ValueError(f'{name}: {Q} x {R} pairs exceed 2^31 - 1')
+        return Q * R
+    if pairs.dim() != 2 or pairs.shape[1] != 2 or pairs.dtype.is_floating_point or pairs.dtype.is_complex or pairs.dtype == torch.bool:
+        raise ValueError(f'{name}: pairs {tuple(pairs.shape)} {pairs.dtype} must be integer of shape (P, 2): (query row, reference row)')
+    if pairs.shape[0] > 0x7fffffff:
+        raise ValueError(f'{name}: {pairs.shape[0]} pairs exceed 2^31 - 1')
+    return pairs.shape[0]
+
+
+def align_traceback(q, r, table, gap_open, gap_extend, qmask=None, rmask=None, pairs=None, want_ops=True, want_rmap=False):
+    """THE alignment of chosen pairs of rows -- which element is paired with which (include/abopt.h: abopt_align_traceback).  The
+    arguments of `align_sequences`, plus pairs (optional, (P, 2) integer: query row, reference row; None = all Q R pairs, row-major).  Among the alignments with
+    the best (score, matches, -columns), the one that is least when read from its last column to its first, a pair before a query residue against a gap before
+    a gap against a reference residue.
+    -> dict of device tensors over the P pairs: score, matches, columns (P) int32, equal to `align_sequences`; qmap (P, na) int16: for element k of the query
+    row the element of the reference row it is paired with, -1 if masked out, against a gap or in a free overhang [, ops (P, na + nb) uint8 with want_ops: 1 a
+    pair, 2 a query residue against a gap, 3 a gap against a reference residue, 0 beyond `columns`; rmap (P, nb) int16 with want_rmap: the inverse of qmap].
+    A pair outside the panels: 0, 0, 0, ops 0, maps -1.  Score everything with `align_sequences`, choose, and trace the chosen: the maps of 10^6 pairs of rows
+    of 256 are 0.5 GB.  One stream-ordered launch, no host synchronisation, capturable."""
+    name = 'align_traceback'
+    Q, na = _similarity_rows(name, 'q', q, qmask, False)
+    R, nb = _similarity_rows(name, 'r', r, rmask, False)
+    if table.dim() != 2 or table.shape[0] != table.shape[1] or not 1 <= table.shape[0] <= SIMILARITY_MAX_TABLE or table.dtype.is_floating_point or \
+            table.dtype.is_complex:
+        raise ValueError(f'{name}: table {tuple(table.shape)} {table.dtype} must be integer of shape (T, T), 1 <= T <= {SIMILARITY_MAX_TABLE}')
+    o, e = check_gaps(name, gap_open, gap_extend)
+    P = _pair_list(name, pairs, Q, R)
+    dev = _similarity_device(name, q, r)
+    if pairs is not None and pairs.device != dev:
+        raise ValueError(f'{name}: pairs on {pairs.device} must be on {dev}')
+    q, r, qmask, rmask = _bytes(q), _bytes(r), _as_flags(qmask), _as_flags(rmask)
+    table = table.to(device=dev, dtype=torch.int32).contiguous()
+    plist = None if pairs is None else pairs.to(torch.int32).contiguous()
+    new = torch.empty if P else torch.zeros                          # an empty call launches nothing
+    out = {k: new(P, dtype=torch.int32, device=dev) for k in ('score', 'matches', 'columns')}
+    out['qmap'] = new(P, na, dtype=torch.int16, device=dev)
+    if want_ops:
+        out['ops'] = new(P, na + nb, dtype=torch.uint8, device=dev)
+    if want_rmap:
+        out['rmap'] = new(P, nb, dtype=torch.int16, device=dev)
+    if pairs is None or P:                                           # an empty list has no address: NULL would mean "all pairs"
+        _check(lib().abopt_align_traceback(ptr(q, torch.uint8), ptr(qmask, optional=True), ptr(r, torch.uint8), ptr(rmask, optional=True), ptr(table, torch.int32),
+                                           table.shape[0], o, e, ptr(plist, optional=True), P, Q, R, na, nb, ptr(out['score']), ptr(out['matches']),
+                                           ptr(out['columns']), ptr(out.get('ops'), optional=True), ptr(out['qmap']), ptr(out.get('rmap'), optional=True), stream()))
+    return out
+
+
+def superposed_rmsd_mapped(q, r, qmap, pairs=None, qfit=None, rfit=None, qscore=None, rscore=None, want_transform=False):
+    """`superposed_rmsd` on the pairs a map names, so that rows of different lengths superpose (include/abopt.h: abopt_superposed_rmsd_mapped; DESIGN.md section
+    6.14).  q (Q, na, 3), r (R, nb, 3) floating point; qmap (P, na) integer: for pair p, element k of the query row is paired with element qmap[p, k] of the
+    reference row, anything outside [0, nb) = unpaired (`align_traceback`'s qmap, or a caller's own pairing -- it need not be monotone); pairs (optional, (P, 2):
+    query row, reference row; None = all Q R, row-major); qfit / rfit: a pair is fitted on iff both its elements are true (None = all); qscore / rscore: measured
+    on likewise (None = that side's fit mask).
+    -> dict of device tensors over the P pairs: rmsd fp32, n_fit, n_score int32 [, rot (P, 3, 3), trans (P, 3) with want_transform].  Fewer than 3 fit pairs, no
+    score pair or a pair outside the panels: -1, 0, 0, the identity, 0.  Equal bit for bit to `superposed_rmsd` on the same pairs gathered into rows of equal
+    count.  One stream-ordered launch, no host synchronisation, capturable."""
+    name = 'superposed_rmsd_mapped'
+    Q, na = _similarity_rows(name, 'q', q, qfit, True)
+    R, nb = _similarity_rows(name, 'r', r, rfit, True)
+    for what, m, want in (('qscore', qscore, (Q, na)), ('rscore', rscore, (R, nb))):
+        if m is not None and tuple(m.shape) != want:
+            raise ValueError(f'{name}: {what} {tuple(m.shape)} must be (rows, n) = {want}')
+    P = _pair_list(name, pairs, Q, R)
+    if qmap.dim() != 2 or tuple(qmap.shape) != (P, na) or qmap.dtype.is_floating_point or qmap.dtype.is_complex or qmap.dtype == torch.bool:
+        raise ValueError(f'{name}: qmap {tuple(qmap.shape)} {qmap.dtype} must be integer of shape (P, na) = {(P, na)}')
+    dev = _similarity_device(name, q, r)
+    for what, t in (('qmap', qmap), ('pairs', pairs)):
+        if t is not None and t.device != dev:
+            raise ValueError(f'{name}: {what} on {t.device} must be on {dev}')
+    q, r = q.float().contiguous(), r.float().contiguous()
+    qmap = (qmap if qmap.dtype == torch.int16 else qmap.clamp(-1, SIMILARITY_MAX_LEN).to(torch.int16)).contiguous()
+    plist = None if pairs is None else pairs.to(torch.int32).contiguous()
+    qfit, rfit, qscore, rscore = _as_flags(qfit), _as_flags(rfit), _as_flags(qscore), _as_flags(rscore)
+    new = torch.empty if P else torch.zeros                          # an empty call launches nothing
+    out = dict(rmsd=new(P, dtype=torch.float32, device=dev), n_fit=new(P, dtype=torch.int32, device=dev), n_score=new(P, dtype=torch.int32, device=dev))
+    if want_transform:
+        out.update(rot=new(P, 3, 3, dtype=torch.float32, device=dev), trans=new(P, 3, dtype=torch.float32, device=dev))
+    if pairs is None or P:                                           # an empty list has no address: NULL would mean "all pairs"
+        _check(lib().abopt_superposed_rmsd_mapped(ptr(q, torch.float32), ptr(r, torch.float32), ptr(qmap), ptr(plist, optional=True), P, ptr(qfit, optional=True),
+                                                  ptr(qscore, optional=True), ptr(rfit, optional=True), ptr(rscore, optional=True), Q, R, na, nb, ptr(out['rmsd']),
+                                                  ptr(out['n_fit']), ptr(out['n_score']), ptr(out.get('rot'), optional=True), ptr(out.get('trans'), optional=True),
+                                                  stream()))
     return out
 
 

@@ -147,6 +147,27 @@ def substitution_table(letters, matrix, scale=2):
     return t.to(torch.int32)
 
 
+def alignment_strings(ops, q_row, r_row, qmask=None, rmask=None):
+    """The two gapped strings of one alignment, on the host.  ops: one row of hip.align_traceback's `ops` (1 a pair, 2 a query residue
+    against a gap, 3 a gap against a reference residue, 0 = beyond the alignment); q_row (na,) and r_row (nb,): the two rows of residue types the pair was traced
+    on, type k = AA_LETTERS[k], anything else 'X'; qmask / rmask: their masks (None = all).  -> (query string, reference string), equally long, '-' for a gap.
+    ValueError unless ops spells exactly the mask-true residues of both rows."""
+    def seq(row, mask):
+        row = [int(v) for v in torch.as_tensor(row).reshape(-1).tolist()]
+        keep = [True] * len(row) if mask is None else [bool(v) for v in torch.as_tensor(mask).reshape(-1).tolist()]
+        if len(keep) != len(row):
+            raise ValueError(f'alignment_strings: a mask of {len(keep)} elements on a row of {len(row)}')
+        return [AA_LETTERS[v] if 0 <= v < len(AA_LETTERS) else 'X' for v, k in zip(row, keep) if k]
+    a, b = seq(q_row, qmask), seq(r_row, rmask)
+    word = [int(v) for v in torch.as_tensor(ops).reshape(-1).tolist()]
+    while word and word[-1] == 0:
+        word.pop()
+    if any(v not in (1, 2, 3) for v in word) or sum(v != 3 for v in word) != len(a) or sum(v != 2 for v in word) != len(b):
+        raise ValueError(f'alignment_strings: ops does not spell the {len(a)} query and {len(b)} reference residues')
+    ia, ib = iter(a), iter(b)
+    return ''.join(next(ia) if v != 3 else '-' for v in word), ''.join(next(ib) if v != 2 else '-' for v in word)
+
+
 ROLE_HOTSPOT, ROLE_REPEL = 1, 2        # the bits of a guide_role word (include/abopt.h: abopt_guide_positions)
 
 

@@ -491,6 +491,67 @@ def similarity(batch, seqs, pos, mask, rows='generated', ref_seqs=None, ref_ca=N
     return out
 
 
+def aligned_rmsd(batch, seqs, pos, mask, rows='generated', ref_seqs=None, ref_ca=None, ref_mask=None, table=None, gap_open=-20, gap_extend=-1,
+                 want_transform=False):
+    """How close in SHAPE candidates are to loops of another length, in any frame: the sequences are aligned, the alignment is traced
+    (hip.align_traceback) and the CA atoms are superposed on the aligned pairs and measured on them (hip.superposed_rmsd_mapped) -- the twin of `similarity`,
+    whose rmsd depends on the frame.  batch, seqs (G*S, L), pos (G*S, L, A, 3), mask (G*S, L, A) and rows as for `similarity`; a residue whose CA is masked out
+    leaves the rows, on either side.
+    Without references every candidate is compared with the NATIVE residues of its own complex on the same rows: every entry (G*S, ...) -- G*S pairs are
+    traced, not G*S x G.  With ref_seqs (R, nb), ref_ca (R, nb, 3) (both) and ref_mask (R, nb) (None = all) every candidate is compared with every reference:
+    every entry (G*S, R, ...).  table and gaps as for `similarity`.
+    -> dict of device tensors: seqid fp32 (100 matches / columns of THE alignment, -1 at 0 columns), score, matches, columns int32, n_pairs int32 (the aligned
+    pairs), rmsd fp32 (-1 with fewer than 3 pairs), qmap (..., L') int16 and ops (..., L' + nb) uint8 as hip.align_traceback returns them [, rot (..., 3, 3)
+    and trans (..., 3) with want_transform: reference ~ rot candidate + trans].  L' = L and qmap indexes residues; rows wider than 256 are packed to the front
+    first (one host read) and qmap indexes the packed rows.  The screen does not call this: apply it to what optimize_antibody / sample_grouped return."""
+    from . import hip, screen
+    from .model import identity_table
+    name = 'aligned_rmsd'
+    G, L = batch['aa'].shape
+    if isinstance(rows, str):
+        if rows == 'generated':
+            scored = batch['generate_flag'].bool()
+        elif rows == 'antibody':
+            scored = screen.chain_groups(batch['fragment_type']) == 1
+        else:
+            raise ValueError(f"{name}: rows must be 'generated', 'antibody' or a (G, L) tensor, not {rows!r}")
+    else:
+        scored = rows.bool()
+    if seqs.dim() != 2 or pos.dim() != 4 or mask.dim() != 3 or tuple(scored.shape) != (G, L) or seqs.shape[1] != L or tuple(pos.shape[1:]) != (L, pos.shape[2], 3) \
+            or pos.shape[2] < 2 or tuple(mask.shape) != tuple(pos.shape[:3]) or seqs.shape[0] != pos.shape[0] or (seqs.shape[0] % G if G else seqs.shape[0]):
+        raise ValueError(f'{name}: expected seqs (G*S, L), pos (G*S, L, A >= 2, 3), mask (G*S, L, A) and rows (G, L) with G = {G}, L = {L}; got '
+                         f'{tuple(seqs.shape)}, {tuple(pos.shape)}, {tuple(mask.shape)} and {tuple(scored.shape)}')
+    own = ref_seqs is None and ref_ca is None
+    if not own and (ref_seqs is None or ref_ca is None):
+        raise ValueError(f'{name}: references need both ref_seqs (R, nb) and ref_ca (R, nb, 3)')
+    if own and ref_mask is not None:
+        raise ValueError(f'{name}: ref_mask selects residues of the references, which are None')
+    if not own and (ref_seqs.dim() != 2 or ref_ca.dim() != 3 or tuple(ref_ca.shape) != tuple(ref_seqs.shape) + (3,)):
+        raise ValueError(f'{name}: expected ref_seqs (R, nb) and ref_ca (R, nb, 3); got {tuple(ref_seqs.shape)} and {tuple(ref_ca.shape)}')
+    N = seqs.shape[0]
+    S = N // G if G else 0
+    crow = scored.repeat_interleave(S, 0) if S != 1 else scored
+    cflag, cseq, cca = _front_rows(name, crow & mask[:, :, 1].bool(), seqs, pos[:, :, 1])
+    pairs = None
+    if own:
+        rflag, ref_seqs, ref_ca = _front_rows(name, scored & batch['mask_heavyatom'][:, :, 1].bool(), batch['aa'], batch['pos_heavyatom'][:, :, 1])
+        c = torch.arange(N, device=seqs.device)
+        pairs = torch.stack([c, c // max(S, 1)], 1).to(torch.int32)         # a candidate's own complex is c // S
+    else:
+        rflag = ref_mask
+    tb = hip.align_traceback(cseq, ref_seqs, identity_table() if table is None else table, gap_open, gap_extend, qmask=cflag, rmask=rflag, pairs=pairs)
+    sr = hip.superposed_rmsd_mapped(cca, ref_ca, tb['qmap'], pairs=pairs, want_transform=want_transform)
+    cols = tb['columns']
+    out = dict(seqid=torch.where(cols > 0, 100.0 * tb['matches'].float() / cols.clamp(min=1).float(), torch.full_like(cols, -1, dtype=torch.float32)),
+               score=tb['score'], matches=tb['matches'], columns=cols, n_pairs=(tb['qmap'] >= 0).sum(1).to(torch.int32), rmsd=sr['rmsd'], qmap=tb['qmap'],
+               ops=tb['ops'])
+    if want_transform:
+        out.update(rot=sr['rot'], trans=sr['trans'])
+    if not own:
+        out = {k: v.reshape((N, ref_seqs.shape[0]) + tuple(v.shape[1:])) for k, v in out.items()}
+    return out
+
+
 def _residue_set(name, what, batch, sel):
     """(G, L) bool: 'generated' (generate_flag), 'context' (the antibody residues that are not generated), 'antibody' (screen.chain_groups == 1) or a (G, L) mask"""
     from . import screen

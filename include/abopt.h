@@ -1090,6 +1090,45 @@ int abopt_gapped_rmsd(const float* qca, const uint8_t* qmask, const float* rca, 
 int abopt_superposed_rmsd(const float* q, const uint8_t* qfit, const uint8_t* qscore, const float* r, const uint8_t* rfit, const uint8_t* rscore, int Q, int R,
                           int na, int nb, void* rmsd, void* n_fit, void* n_score, void* rot, void* trans, abopt_stream stream);
 
+/* ---- The alignment itself, and superposition on its pairs (ABI 59, additions).
+ *
+ * abopt_align_traceback -- integers only.  The rows, masks, table, gaps and prices of abopt_align_sequences above, for P chosen pairs of rows.
+ *   pairs       (may be NULL) [P,2] int32 (DEVICE): (query row, reference row) of pair p, in any order, repeats allowed.  NULL: all Q R pairs, row-major, and P
+ *               is ignored.  The intended use: score everything with abopt_align_sequences, choose, trace the chosen pairs only -- tracing 10^6 pairs of
+ *               rows of 256 writes 0.5 GB of maps.  A pair outside [0, Q) x [0, R) reads nothing and writes score 0, matches 0, columns 0, ops 0, maps -1.
+ *   word        an alignment of a (the query's sequence, n residues) and b (m residues) is a word over three letters: P, a pair; A, a residue of a against a
+ *               gap; B, a gap against a residue of b.  It spells both sequences and is priced as above (gap runs, free ends, a match iff the raw bytes are equal).
+ *   THE ALIGNMENT  among the words that attain the lexicographic maximum of (score, matches, -columns): the word that is lexicographically least when read
+ *               from its LAST column to its first, with P < A < B.  This names one alignment whatever computes it (tests/alignment_trace_statement.py
+ *               enumerates the words; the kernel walks the Gotoh tables backwards over SETS of states, closing each set under the ties X = H and Y = H and
+ *               writing the least letter any state can write over a tight edge -- a single-state walk with a fixed preference is wrong on ties).
+ *               If either sequence is empty: the word is all A or all B.  If nothing is worth pairing: B^m A^n.
+ *   score, matches, columns [P] int32 (DEVICE, spelled void*): equal to abopt_align_sequences on the same pair, exactly; 100 matches / columns is the seqid of
+ *               THE alignment.
+ *   ops         (may be NULL) [P, na + nb] uint8: column c < columns of the alignment, left to right: 1 = P, 2 = A, 3 = B; 0 beyond.
+ *   qmap        (may be NULL) [P, na] int16: for ELEMENT k of the query row (an index into the row, not a rank: masks that are no prefixes map directly) the
+ *               element index of the reference row it is paired with; -1 if the element is masked out, against a gap or in a free overhang.
+ *   rmap        (may be NULL) [P, nb] int16: the inverse.
+ * One launch, a wave per pair, 4, 2 or 1 pairs per workgroup (na round8(nb) bytes of LDS per pair, at most 64 KiB); no atomic, no workspace, nothing allocated,
+ * no host synchronisation, capturable; every output written whole by plain stores; the walk takes `columns` steps whatever the bytes.  Checks: dims (P >= 0
+ * with pairs), na, nb <= 256 (beyond: ABOPT_EUNSUPPORTED), T and the gaps, the no-op (P = 0 with pairs, Q R = 0 without), pointers.
+ *
+ * abopt_superposed_rmsd_mapped -- abopt_superposed_rmsd on the pairs a map names, so that rows of DIFFERENT lengths superpose.
+ *   q [Q,na,3], r [R,nb,3] fp32; qmap [P,na] int16 (DEVICE, spelled void*, read only); pairs as above; qfit, qscore [Q,na] and rfit, rscore [R,nb] bytes.
+ *   fit pairs   of pair p: the (k, j = qmap[p][k]) in ascending k with 0 <= j < nb, qfit true at k and rfit true at j (NULL = all).  The score pairs likewise
+ *               from the score masks; a NULL score mask on a side is that side's fit mask.  A j outside [0, nb) means "unpaired" and is never dereferenced.
+ *               The map need not come from abopt_align_traceback, nor be monotone: a caller's own pairing is legal.
+ *   rmsd, n_fit, n_score [P]; rot (may be NULL) [P,3,3], trans (may be NULL) [P,3]: as abopt_superposed_rmsd defines them, by the same pair function on the
+ *               same two point lists -- so the result equals abopt_superposed_rmsd on the pairs gathered into rows of equal count, bit for bit.
+ *   NOT SCORED  fewer than 3 fit pairs, no score pair, or a pair outside the panels: rmsd = -1, n_fit = n_score = 0, rot = the identity, trans = 0.
+ * One launch, a lane per pair, rows read straight from memory; no atomic, no workspace, capturable.  Checks as above. */
+int abopt_align_traceback(const uint8_t* q, const uint8_t* qmask, const uint8_t* r, const uint8_t* rmask, const int32_t* table, int T, int gap_open,
+                          int gap_extend, const int32_t* pairs, int P, int Q, int R, int na, int nb, void* score, void* matches, void* columns, void* ops,
+                          void* qmap, void* rmap, abopt_stream stream);
+int abopt_superposed_rmsd_mapped(const float* q, const float* r, void* qmap, const int32_t* pairs, int P, const uint8_t* qfit, const uint8_t* qscore,
+                                 const uint8_t* rfit, const uint8_t* rscore, int Q, int R, int na, int nb, void* rmsd, void* n_fit, void* n_score, void* rot,
+                                 void* trans, abopt_stream stream);
+
 /* ---- Measurement hook (bench.py's roofline leg).  When enabled, every launch of the IPA-core kernel is bracketed
  * by hipEvents on the stream it is launched on; abopt_prof_collect synchronises those events and returns the number
  * of launches and their summed duration since the last enable.  Process-global, off by default, not for concurrent
